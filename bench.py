@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: fused depth -> world point-cloud throughput on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]            (N=1)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]            (N=1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times exactly K steps and prints the line; its roofline object carries only the timed region's
+own figures.  --full adds everything else below (sustained and per-kernel roofline figures, the cached-input regime, the other
+regimes, end_to_end, cpu_baseline).  --dump-outputs DIR writes the cloud of the last timed step as DIR/xyz.npy (single process;
+a fixed seeded sample of rows when the cloud is larger than DUMP_ROWS), so that two builds can be compared output for output.
 
 Workload (BASELINE.json configs[1], "C2"): KITTI-sized 1280x384 uint8 depth, 100 frames per GPU, synthetic (seed 1234),
 resident in HBM.  One STEP = one pass of the hot path over one batch of FRESH frames = the library's fused unproject + SE(3)
@@ -16,7 +21,7 @@ For N > 1 the step additionally assembles the fused world cloud on every rank (t
 timed, checked bit for bit and printed under "assemble"; the headline step is the fastest).  Weak scaling: every rank owns
 100 frames; `value` = UNIQUE fused points of all ranks / max-over-ranks time.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (with --full; a plain run has the *_timed_region figures of roofline only):
   roofline     -- the step against the HBM roof.  `frac` = algorithmic bytes (13 B/point) / sustained median step duration
                   (HIP events on the launch stream, >= 4000 launches, fresh rasters, sweep + fused kernel) / 8 TB/s;
                   frac_timed_region = the same over the K timed steps; frac_kernel_only = the fused kernel alone (events
@@ -150,6 +155,31 @@ def kernel_only_ms(torch, stream, ctx, sweep, fuse_unstaged, groups=5, per=60):
         ctx.set_tuning("fuse_prefetch", 0)
 
 
+def settle(torch, launch, seconds=0.25, per=50):
+    """Back-to-back launches for `seconds` of wall time before the warm-up steps, `per` at a time between synchronisations.
+    An idle GPU takes its first ~50 ms of load to settle (profiles/r03_clock_ramp.log); the sustained measurement of --full
+    covers that too, and without this a short --warmup would time a ramping GPU."""
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < seconds:
+        for _ in range(per):
+            launch()
+        torch.cuda.synchronize()
+
+
+DUMP_ROWS = 1 << 21          # --dump-outputs writes at most this many xyz rows: 25 MB as f32, 50 MB as f64
+
+
+def dump_outputs(torch, xyz, out_dir):
+    """--dump-outputs: the cloud `xyz` (n x 3 on the device) as out_dir/xyz.npy -- whole when n <= DUMP_ROWS, else the rows at
+    a fixed sample of indices (seed 0, sorted, duplicates dropped), the same for every run with the same arguments."""
+    n = xyz.shape[0]
+    if n > DUMP_ROWS:
+        rows = np.unique(np.random.default_rng(0).integers(0, n, size=DUMP_ROWS))
+        xyz = xyz.index_select(0, torch.from_numpy(rows).to(xyz.device))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "xyz.npy"), xyz.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -163,16 +193,27 @@ def main():
     ap.add_argument("--inputs", default="fresh", choices=["fresh", "cached"],
                     help="fresh (default): the step rotates through %d resident rasters, none of which is in the Infinity Cache when "
                          "its launch starts; cached: ONE raster re-read every step (rounds 1-4's headline regime)" % RASTER_COPIES)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the sustained and per-kernel roofline figures, the "
+                         "cached-input regime, and for N=1 the other regimes, end_to_end and cpu_baseline (the --no-* flags below "
+                         "skip parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the cloud of the last one as DIR/xyz.npy (single process; a fixed seeded "
+                         "sample of %d rows when it is larger)" % DUMP_ROWS)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full, N=1: skip the cpu_baseline object")
     ap.add_argument("--no-regimes", action="store_true",
-                    help="N=1: skip the child process that measures the launch in the other input regimes (tools/bench_regimes.py); "
-                         "rocprofv3 --pmc passes use this flag (a profiled process must not start another program)")
-    ap.add_argument("--no-end-to-end", action="store_true", help="N=1: skip the end_to_end object (tools/bench_e2e.py)")
+                    help="--full, N=1: skip the child process that measures the launch in the other input regimes "
+                         "(tools/bench_regimes.py); rocprofv3 --pmc passes use this flag (a profiled process must not start another program)")
+    ap.add_argument("--no-end-to-end", action="store_true", help="--full, N=1: skip the end_to_end object (tools/bench_e2e.py)")
     ap.add_argument("--out-dtype", default="float32", choices=["float32", "float64"])
     ap.add_argument("--workload", default="fuse", choices=["fuse", "apply", "icp", "voxel", "c5", "regimes", "e2e"],
                     help="fuse (default, the headline C2 line); the others print one JSON line for a secondary kernel on one GPU "
                          "(tools/bench_secondary.py, bench_regimes.py, bench_e2e.py)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs and a.workload != "fuse":
+        ap.error("--dump-outputs writes the headline (fuse) workload's cloud")
     env_world = int(os.environ.get("WORLD_SIZE", "1"))
     if a.workload in ("apply", "icp", "voxel", "c5"):
         S = importlib.import_module("bench_secondary")
@@ -182,8 +223,8 @@ def main():
     if a.workload == "e2e":
         return importlib.import_module("bench_e2e").e2e_host(a)
 
-    # N = 1: the other regimes of the launch and the end-to-end legs, by child processes BEFORE this one touches the GPU
-    default_job = env_world == 1 and a.gpus == 1 and a.out_dtype == "float32" and a.frames == FRAMES_PER_GPU
+    # N = 1, --full: the other regimes of the launch and the end-to-end legs, by child processes BEFORE this one touches the GPU
+    default_job = a.full and env_world == 1 and a.gpus == 1 and a.out_dtype == "float32" and a.frames == FRAMES_PER_GPU
     other = run_child("regimes") if default_job and not a.no_regimes else None
     e2e = importlib.import_module("bench_e2e").end_to_end_children() if default_job and not a.no_end_to_end else None
     A = importlib.import_module("bench_assemble")
@@ -206,6 +247,8 @@ def main():
     dev = torch.device("cuda", dev_index)
     # R3D_BENCH_FORCE_COLLECTIVES=1 runs the N>1 code path even with one rank: a rehearsal of the RCCL calls on a 1-GPU box
     use_dist = world > 1 or os.environ.get("R3D_BENCH_FORCE_COLLECTIVES", "0") not in ("", "0")
+    if use_dist and a.dump_outputs:
+        sys.exit("bench.py --dump-outputs is for single-process runs")
     if use_dist:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29533")
@@ -266,12 +309,13 @@ def main():
         dist.all_reduce(tm, op=dist.ReduceOp.MAX)
         return float(tm.item())
 
-    # the step's duration sustained (also the clock ramp), the fused kernel alone, and the cached-input regime beside them
     bytes_per_launch = n_local * (1 + 3 * (4 if a.out_dtype == "float32" else 8))
-    step_ms, step_mean_ms, step_n = sustained_ms(torch, stream, fuse)
-    k_only_ms = kernel_only_ms(torch, stream, ctx, lambda: L.check(ctx.lib.r3d_cache_prefetch(ctx.handle, rasters[turn["i"] % n_copies].data_ptr(), n_local)), fuse)
-    cached_ms, _, cached_n = sustained_ms(torch, stream, lambda: r3d.fuse_frames_device(
-        ctx, cam, base.data_ptr(), np.uint8, F, table.data_ptr(), shard.data_ptr(), out_np), min_launches=1000, min_ms=50.0)
+    if a.full:
+        # the step's duration sustained, the fused kernel alone, and the cached-input regime beside them
+        step_ms, step_mean_ms, step_n = sustained_ms(torch, stream, fuse)
+        k_only_ms = kernel_only_ms(torch, stream, ctx, lambda: L.check(ctx.lib.r3d_cache_prefetch(ctx.handle, rasters[turn["i"] % n_copies].data_ptr(), n_local)), fuse)
+        cached_ms, _, cached_n = sustained_ms(torch, stream, lambda: r3d.fuse_frames_device(
+            ctx, cam, base.data_ptr(), np.uint8, F, table.data_ptr(), shard.data_ptr(), out_np), min_launches=1000, min_ms=50.0)
     kernel_label = "fuse_lane_kernel<u8,f32,pose>" if a.out_dtype == "float32" else "fuse_pair_kernel<u8,f64,pose>"
 
     def frac_of(ms, nbytes=bytes_per_launch):
@@ -282,14 +326,16 @@ def main():
     def make_line(mode, elapsed, region_ms):
         """`region_ms`: HIP-event duration of one step inside the timed region (first start to last end / K)."""
         total_pts = world * n_local * a.steps
-        ach = bytes_per_launch / (step_ms * 1e-3) / 1e9
-        traffic, traffic_source = pmc_traffic(F, a.out_dtype, regime=a.inputs)
         sweeps = region.get("sweeps")            # staging sweeps the library enqueued inside the timed region (counted, not guessed)
-        sweep_ms = max(step_ms - k_only_ms, 0.0) if a.inputs == "fresh" else 0.0
-        kernels = [{"name": kernel_label, "ms": round(step_ms - sweep_ms, 5), "launches_per_step": 1}]
-        if a.inputs == "fresh":
-            kernels.insert(0, {"name": "cache_touch_kernel", "ms": round(sweep_ms, 5), "launches_per_step": 1})
-        after_h2d = (other or {}).get("after_h2d_upload", {}).get("auto_frac")
+        # what the timed region itself shows; --full adds the measurements of their own below
+        roofline = {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "kernel_ms_timed_region": round(region_ms, 5) if region_ms else None,
+                    "frac_timed_region": frac_of(region_ms) if region_ms else None,
+                    "staging_sweeps_in_timed_region": sweeps,
+                    "algorithmic_bytes_per_launch": bytes_per_launch,
+                    "timing": "*_timed_region: events around the %d timed steps (inside the wall-clock bracket of ms_per_step); "
+                              "the sustained and per-kernel figures are measured by --full" % a.steps,
+                    "kernel_ms_timed_region_over_ms_per_step": round(region_ms / (elapsed / a.steps * 1e3), 4) if region_ms else None}
         line = {
             "metric": "Mpoints/s fused (1280x384 depth, N frames)",
             "value": round(total_pts / elapsed / 1e6, 2),
@@ -311,35 +357,40 @@ def main():
                        "inputs": a.inputs, "frames_per_gpu": F, "points_per_step": world * n_local,
                        "step": A.step_text(mode), "assemble": mode, "assemble_choice": a.assemble,
                        "parallelism": "frames sharded, %d rank(s), one process per GPU" % world},
-            # the two regimes side by side, as scalars: fresh rasters every step (a pipeline) / one raster re-read (rounds 1-4)
-            "value_fresh_inputs": round(n_local / step_ms / 1e3, 1) if a.inputs == "fresh" else (other or {}).get("auto_Mpoints_s"),
-            "value_cached_inputs": round(n_local / cached_ms / 1e3, 1),
-            "roofline": {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": frac_of(step_ms), "traffic": traffic, "traffic_source": traffic_source,
-                         "frac_of_measured_copy": round(ach / HBM_COPY_GBS, 4),
-                         "kernel": kernel_label + (" behind the library's cache_touch_kernel sweep of its raster" if a.inputs == "fresh" else ""),
-                         "kernel_ms": round(step_ms, 5), "kernel_mean_ms": round(step_mean_ms, 5), "launches": step_n,
-                         "frac_mean": frac_of(step_mean_ms),
-                         "kernel_ms_timed_region": round(region_ms, 5) if region_ms else None,
-                         "frac_timed_region": frac_of(region_ms) if region_ms else None,
-                         "kernel_only_ms": round(k_only_ms, 5), "frac_kernel_only": frac_of(k_only_ms),
-                         "frac_fresh_inputs": frac_of(step_ms) if a.inputs == "fresh" else (other or {}).get("auto_frac"),
-                         "frac_cached_inputs": frac_of(cached_ms), "cached_inputs_ms": round(cached_ms, 5),
-                         "frac_after_h2d": after_h2d,
-                         # what HBM itself moves per second: with fresh inputs every algorithmic byte crosses it (read by the sweep,
-                         # written by the kernel); with cached inputs only the 12 B/point of xyz do
-                         "frac_hbm_side": frac_of(step_ms) if a.inputs == "fresh" else frac_of(step_ms, n_local * xyz_bytes),
-                         "frac_hbm_side_cached_inputs": frac_of(cached_ms, n_local * xyz_bytes),
-                         "kernels": kernels, "staging_sweeps_in_timed_region": sweeps,
-                         "algorithmic_bytes_per_launch": bytes_per_launch,
-                         "timing": "frac / kernel_ms: sustained MEDIAN of %d steps in groups of 100 between HIP events on the launch stream, "
-                                   "before the timed region; *_timed_region: events around the %d timed steps (inside the wall-clock "
-                                   "bracket of ms_per_step); kernel_only: events between the sweep and the fused kernel" % (step_n, a.steps),
-                         "kernel_ms_timed_region_over_ms_per_step": round(region_ms / (elapsed / a.steps * 1e3), 4) if region_ms else None,
-                         "other_regimes": other},
+            "roofline": roofline,
             "gpu_ms_per_step": round(region_ms, 5) if region_ms else None,
-            "kernel_only_Mpoints_s_per_gpu": round(n_local / k_only_ms / 1e3, 1),
         }
+        if a.full:
+            ach = bytes_per_launch / (step_ms * 1e-3) / 1e9
+            traffic, traffic_source = pmc_traffic(F, a.out_dtype, regime=a.inputs)
+            sweep_ms = max(step_ms - k_only_ms, 0.0) if a.inputs == "fresh" else 0.0
+            kernels = [{"name": kernel_label, "ms": round(step_ms - sweep_ms, 5), "launches_per_step": 1}]
+            if a.inputs == "fresh":
+                kernels.insert(0, {"name": "cache_touch_kernel", "ms": round(sweep_ms, 5), "launches_per_step": 1})
+            after_h2d = (other or {}).get("after_h2d_upload", {}).get("auto_frac")
+            # the two regimes side by side, as scalars: fresh rasters every step (a pipeline) / one raster re-read (rounds 1-4)
+            line["value_fresh_inputs"] = round(n_local / step_ms / 1e3, 1) if a.inputs == "fresh" else (other or {}).get("auto_Mpoints_s")
+            line["value_cached_inputs"] = round(n_local / cached_ms / 1e3, 1)
+            roofline.update({"achieved": round(ach, 1), "frac": frac_of(step_ms), "traffic": traffic, "traffic_source": traffic_source,
+                             "frac_of_measured_copy": round(ach / HBM_COPY_GBS, 4),
+                             "kernel": kernel_label + (" behind the library's cache_touch_kernel sweep of its raster" if a.inputs == "fresh" else ""),
+                             "kernel_ms": round(step_ms, 5), "kernel_mean_ms": round(step_mean_ms, 5), "launches": step_n,
+                             "frac_mean": frac_of(step_mean_ms),
+                             "kernel_only_ms": round(k_only_ms, 5), "frac_kernel_only": frac_of(k_only_ms),
+                             "frac_fresh_inputs": frac_of(step_ms) if a.inputs == "fresh" else (other or {}).get("auto_frac"),
+                             "frac_cached_inputs": frac_of(cached_ms), "cached_inputs_ms": round(cached_ms, 5),
+                             "frac_after_h2d": after_h2d,
+                             # what HBM itself moves per second: with fresh inputs every algorithmic byte crosses it (read by the
+                             # sweep, written by the kernel); with cached inputs only the 12 B/point of xyz do
+                             "frac_hbm_side": frac_of(step_ms) if a.inputs == "fresh" else frac_of(step_ms, n_local * xyz_bytes),
+                             "frac_hbm_side_cached_inputs": frac_of(cached_ms, n_local * xyz_bytes),
+                             "kernels": kernels,
+                             "timing": "frac / kernel_ms: sustained MEDIAN of %d steps in groups of 100 between HIP events on the launch "
+                                       "stream, before the timed region; *_timed_region: events around the %d timed steps (inside the "
+                                       "wall-clock bracket of ms_per_step); kernel_only: events between the sweep and the fused kernel"
+                                       % (step_n, a.steps),
+                             "other_regimes": other})
+            line["kernel_only_Mpoints_s_per_gpu"] = round(n_local / k_only_ms / 1e3, 1)
         if use_dist:
             line["transport"] = asm.note
             line["assemble"] = asm.results
@@ -370,6 +421,8 @@ def main():
         region["sweeps"] = ctx.get_tuning("fuse_sweeps") - s0
         return max_over_ranks(sec), ev0.elapsed_time(ev1) / max(a.steps, 1)   # this rank's stream: first start to last end
 
+    settle(torch, fuse)
+    turn["i"] = 0                  # with the same arguments, every run's timed steps read the same rasters in the same order
     mode, asm = "none", None
     if use_dist:
         B = types.SimpleNamespace(torch=torch, dist=dist, r3d=r3d, ctx=ctx, cam=cam, stream=stream, dev=dev, dev_index=dev_index,
@@ -392,10 +445,12 @@ def main():
         elapsed, region_ms = headline(asm.make_step(mode) if use_dist else fuse)
     if asm is not None:
         asm.disarm()
+    if a.dump_outputs:
+        dump_outputs(torch, shard, a.dump_outputs)
 
     if rank == 0:
         line = make_line(mode, elapsed, region_ms)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(3)
         if e2e is not None:
             line["end_to_end"] = e2e

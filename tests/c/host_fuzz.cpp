@@ -16,6 +16,13 @@
 
 #include "r3d.h"
 
+// scratch files go to $TMPDIR (default /tmp): the suite points it at the test's own directory, so runs by different users
+// on one machine never meet
+static std::string scratch(const std::string& name) {
+  const char* d = getenv("TMPDIR");
+  return std::string(d && *d ? d : "/tmp") + "/" + name;
+}
+
 static char g_err[512];
 void r3d_set_error(const char* fmt, ...) {
   va_list ap;
@@ -110,7 +117,7 @@ int main(int argc, char** argv) {
     for (int n_files : {7, 60}) {
       std::vector<std::string> names;
       std::vector<const char*> paths;
-      for (int k = 0; k < n_files; ++k) names.push_back("/tmp/r3d_fuzz_batch_" + std::to_string(k) + ".txt");
+      for (int k = 0; k < n_files; ++k) names.push_back(scratch("r3d_fuzz_batch_" + std::to_string(k) + ".txt"));
       for (auto& s_ : names) paths.push_back(s_.c_str());
       const int64_t per = n / n_files;
       if (r3d_write_xyz_txt_batch(paths.data(), n_files, v.data(), R3D_F64, per, nullptr, 0) != R3D_OK) return 28;
@@ -132,14 +139,14 @@ int main(int argc, char** argv) {
   }
   std::vector<unsigned char> rgb(v.size());
   for (auto& c : rgb) c = (unsigned char)rng();
-  if (r3d_write_ply_rgb("/tmp/r3d_fuzz_rgb.ply", vf.data(), R3D_F32, rgb.data(), n) != R3D_OK) return 1;
+  if (r3d_write_ply_rgb(scratch("r3d_fuzz_rgb.ply").c_str(), vf.data(), R3D_F32, rgb.data(), n) != R3D_OK) return 1;
   std::vector<uint32_t> rgba((size_t)n);
   for (auto& c : rgba) c = (uint32_t)rng() & 0x00ffffffu;
-  if (r3d_write_ply_rgba("/tmp/r3d_fuzz_rgba.ply", vf.data(), R3D_F32, rgba.data(), n) != R3D_OK) return 1;
-  if (r3d_write_ply("/tmp/r3d_fuzz.ply", vf.data(), R3D_F32, n) != R3D_OK) return 1;
+  if (r3d_write_ply_rgba(scratch("r3d_fuzz_rgba.ply").c_str(), vf.data(), R3D_F32, rgba.data(), n) != R3D_OK) return 1;
+  if (r3d_write_ply(scratch("r3d_fuzz.ply").c_str(), vf.data(), R3D_F32, n) != R3D_OK) return 1;
   std::vector<uint16_t> zraw((size_t)n);
   for (auto& z : zraw) z = (uint16_t)rng();
-  if (r3d_write_xyz_txt("/tmp/r3d_fuzz.txt", vf.data(), R3D_F32, n, zraw.data(), R3D_DEPTH_U16, 0) != R3D_OK) return 1;
+  if (r3d_write_xyz_txt(scratch("r3d_fuzz.txt").c_str(), vf.data(), R3D_F32, n, zraw.data(), R3D_DEPTH_U16, 0) != R3D_OK) return 1;
   // the text parser: round trip of the txt just formatted (bit for bit), then random byte damage and truncation
   {
     int64_t np_ = 0, bad_line = 0;
@@ -185,10 +192,11 @@ int main(int argc, char** argv) {
       const int flips = 1 + (int)(rng() % 8);
       for (int j = 0; j < flips; ++j) bad[rng() % bad.size()] = (unsigned char)rng();
       if (trial % 7 == 0) bad.resize(rng() % bad.size());
-      FILE* g = fopen("/tmp/r3d_fuzz.png", "wb");
+      const std::string path_ = scratch("r3d_fuzz.png");
+      FILE* g = fopen(path_.c_str(), "wb");
       fwrite(bad.data(), 1, bad.size(), g);
       fclose(g);
-      const char* p[1] = {"/tmp/r3d_fuzz.png"};
+      const char* p[1] = {path_.c_str()};
       int hh = 0, ww = 0, bb = 0;
       if (r3d_png_gray_info(p[0], &hh, &ww, &bb) == R3D_OK && hh == h && ww == w && bb == bits)
         survived += r3d_png_gray_decode_batch(p, 1, out.data(), h, w, bits) == R3D_OK;
@@ -216,10 +224,11 @@ int main(int argc, char** argv) {
         std::vector<unsigned char> bad = png2;
         for (int j = 0; j < 1 + (int)(rng() % 6); ++j) bad[rng() % bad.size()] = (unsigned char)rng();
         if (trial % 5 == 0) bad.resize(rng() % bad.size());
-        FILE* g = fopen("/tmp/r3d_fuzz_c.png", "wb");
+        const std::string path_ = scratch("r3d_fuzz_c.png");
+        FILE* g = fopen(path_.c_str(), "wb");
         fwrite(bad.data(), 1, bad.size(), g);
         fclose(g);
-        const char* p[1] = {"/tmp/r3d_fuzz_c.png"};
+        const char* p[1] = {path_.c_str()};
         int hh = 0, ww = 0;
         if (r3d_png_rgb_info(p[0], &hh, &ww, &ch2) == R3D_OK && hh == h2 && ww == w2) (void)r3d_png_rgb_decode_batch(p, 1, rgb_out.data(), h2, w2);
       }
@@ -243,10 +252,11 @@ int main(int argc, char** argv) {
         std::vector<unsigned char> bad = png2;
         for (int j = 0; j < 1 + (int)(rng() % 6); ++j) bad[rng() % bad.size()] = (unsigned char)rng();
         if (trial % 5 == 0) bad.resize(rng() % bad.size());
-        FILE* g = fopen("/tmp/r3d_fuzz_g8.png", "wb");
+        const std::string path_ = scratch("r3d_fuzz_g8.png");
+        FILE* g = fopen(path_.c_str(), "wb");
         fwrite(bad.data(), 1, bad.size(), g);
         fclose(g);
-        const char* p[1] = {"/tmp/r3d_fuzz_g8.png"};
+        const char* p[1] = {path_.c_str()};
         int hh = 0, ww = 0;
         if (r3d_png_gray8_info(p[0], &hh, &ww) == R3D_OK && hh == h2 && ww == w2) (void)r3d_png_gray8_decode_batch(p, 1, g8.data(), h2, w2, trial & 1);
       }
@@ -280,10 +290,11 @@ int main(int argc, char** argv) {
       // half of the trials aim at the headers (the first 700 bytes hold the tables and the frame / scan headers)
       for (int j = 0; j < flips; ++j) bad[(trial & 1) ? rng() % std::min<size_t>(bad.size(), 700) : rng() % bad.size()] = (unsigned char)rng();
       if (trial % 6 == 0) bad.resize(rng() % bad.size());
-      FILE* g = fopen("/tmp/r3d_fuzz.jpg", "wb");
+      const std::string path_ = scratch("r3d_fuzz.jpg");
+      FILE* g = fopen(path_.c_str(), "wb");
       fwrite(bad.data(), 1, bad.size(), g);
       fclose(g);
-      const char* p[1] = {"/tmp/r3d_fuzz.jpg"};
+      const char* p[1] = {path_.c_str()};
       int hh = 0, ww = 0;
       if (r3d_jpeg_gray_info(p[0], &hh, &ww) == R3D_OK && hh > 0 && ww > 0 && (int64_t)hh * ww <= (int64_t)1 << 22) {
         std::vector<unsigned char> yy((size_t)hh * ww);

@@ -29,7 +29,7 @@ def test_headline_line_is_complete_and_self_consistent():
     launch differ by several per cent from run to run (round 3: 0.0980 / 0.0994 / 0.1057 ms on three boxes), and a perf wobble
     must never fail the gate the parity tests sit behind.  Rates are checked for being rates (positive, below the physical
     peak); how large they are is on the JSON line for the reader, not for an assert."""
-    d = run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5"])          # the driver's command shape
+    d = run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])          # the driver's command shape, everything measured
     for k in REQUIRED + ["cpu_baseline", "end_to_end"]:
         assert k in d, k
     assert d["metric"].startswith("Mpoints/s fused (1280x384 depth") and d["unit"] == "Mpoints/s"
@@ -117,11 +117,51 @@ def test_headline_line_is_complete_and_self_consistent():
     assert drop["cpu_reference_s_per_frame"] == f2f["s_per_frame"]
 
 
+def test_plain_run_times_the_steps_asked_for_and_dumps_the_last_steps_cloud(tmp_path):
+    """The driver's command without --full: the headline keys, EXACTLY --steps timed steps (the library's own sweep counter),
+    none of the figures --full measures, and --dump-outputs: the cloud of the last timed step (raster (W + K - 1) mod 16 of the
+    seeded rotation) at the bench's fixed sample of rows, bit for bit the library's fuse of that raster; a cloud no larger
+    than the sample is written whole, in the requested precision."""
+    import importlib
+    import numpy as np
+    from helpers import PKG
+    r3d = importlib.import_module(PKG)
+    d = run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", str(tmp_path / "c2")])
+    for k in REQUIRED + ["gpu_ms_per_step"]:
+        assert k in d, k
+    for k in ("cpu_baseline", "end_to_end", "value_cached_inputs", "value_fresh_inputs", "kernel_only_Mpoints_s_per_gpu"):
+        assert k not in d, k
+    rf = d["roofline"]
+    assert "frac" not in rf and "other_regimes" not in rf and rf["staging_sweeps_in_timed_region"] == 20
+    assert d["steps"] == 20 and d["warmup"] == 5 and d["config"]["inputs"] == "fresh"
+    assert abs(d["value"] - 100 * 384 * 1280 / d["ms_per_step"] / 1e3) / d["value"] < 1e-3
+    assert 0 < rf["kernel_ms_timed_region"] <= d["ms_per_step"] and d["gpu_ms_per_step"] == rf["kernel_ms_timed_region"]
+    assert abs(rf["frac_timed_region"] - rf["algorithmic_bytes_per_launch"] / (rf["kernel_ms_timed_region"] * 1e-3) / 1e9 / 8000.0) < 1e-3
+    n = 100 * 384 * 1280
+    rows = np.unique(np.random.default_rng(0).integers(0, n, size=1 << 21))
+    got = np.load(tmp_path / "c2" / "xyz.npy")
+    assert got.dtype == np.float32 and got.shape == (len(rows), 3)
+    rng = np.random.default_rng(1234)
+    base = rng.integers(1, 256, size=(100, 384, 1280), dtype=np.uint8)
+    q, t = rng.normal(size=(100, 4)), rng.normal(size=(100, 3)) * 10
+    want = r3d.fuse_frames(base + np.uint8(17 * ((5 + 20 - 1) % 16)), q, t, out_dtype=np.float32)     # u8 wraps, as in the bench
+    assert np.array_equal(got, want[rows])
+    del base, want
+    run_bench(["--gpus", "1", "--steps", "3", "--warmup", "0", "--frames", "4", "--inputs", "cached", "--out-dtype", "float64",
+               "--dump-outputs", str(tmp_path / "f64")])
+    got = np.load(tmp_path / "f64" / "xyz.npy")
+    rng = np.random.default_rng(1234)
+    base = rng.integers(1, 256, size=(4, 384, 1280), dtype=np.uint8)
+    q, t = rng.normal(size=(4, 4)), rng.normal(size=(4, 3)) * 10
+    assert got.dtype == np.float64 and np.array_equal(got, r3d.fuse_frames(base, q, t, out_dtype=np.float64))
+
+
 def test_cached_inputs_regime_is_still_a_flag_away():
     """`--inputs cached` = rounds 1-4's headline regime (ONE raster re-read every step, served by the Infinity Cache): the
     line says which regime it ran, no sweep is in its steps (the library's own counter), and the HBM-side fraction counts
     the 12 B/point of xyz only."""
-    d = run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--inputs", "cached", "--no-regimes", "--no-end-to-end", "--no-cpu-baseline"])
+    d = run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--inputs", "cached", "--full", "--no-regimes", "--no-end-to-end",
+                   "--no-cpu-baseline"])
     rf = d["roofline"]
     assert d["config"]["inputs"] == "cached" and "SAME raster" in d["config"]["workload"]
     assert [k["name"] for k in rf["kernels"]] == ["fuse_lane_kernel<u8,f32,pose>"] and rf["staging_sweeps_in_timed_region"] == 0

@@ -36,7 +36,7 @@ def test_host_code_is_clean_under_asan_ubsan(tmp_path, golden_dir):
                           str(tmp_path / "a.png"), str(tmp_path / "s420.jpg"), str(tmp_path / "s444.jpg"), str(tmp_path / "grey.jpg"),
                           str(tmp_path / "s422.jpg"), str(tmp_path / "tiny.jpg")],
                          capture_output=True, text=True,
-                         timeout=600, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+                         timeout=600, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", TMPDIR=str(tmp_path)))
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]
     assert "host fuzz OK" in run.stdout and "corrupted JPEG trials" in run.stdout
 
@@ -66,5 +66,5 @@ def test_host_pools_are_race_free_under_tsan(tmp_path, golden_dir):
               + rng.normal(0, 10, (61, 83, 3))).clip(0, 255).astype(np.uint8)
     Image.fromarray(smooth, "RGB").save(tmp_path / "s420.jpg", quality=85, subsampling=2)
     run = subprocess.run([exe, os.path.join(golden_dir, "scene3", "depth", "000.png"), str(tmp_path / "s420.jpg")],
-                         capture_output=True, text=True, timeout=900)
+                         capture_output=True, text=True, timeout=900, env=dict(os.environ, TMPDIR=str(tmp_path)))
     assert run.returncode == 0 and "host fuzz OK" in run.stdout and "ThreadSanitizer" not in run.stderr, run.stdout[-1000:] + run.stderr[-3000:]

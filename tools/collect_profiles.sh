@@ -7,7 +7,7 @@ R=${1:-r05}
 OUT=gpurun_out/prof_$R
 mkdir -p $OUT
 export TMPDIR=/tmp
-BENCH="python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline"
+BENCH="python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline"
 # a profiled process must not start another program (the profiler's preload has initialised the GPU): every pass runs the
 # bench with --no-regimes / --no-end-to-end, and the other regimes of the launch are profiled as their own direct command
 BENCH_PMC="$BENCH --no-regimes --no-end-to-end"

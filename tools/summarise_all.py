@@ -123,7 +123,7 @@ def main():
     def frac(ns):
         return round(alg / ns / 1e3 / 8.0, 4)
 
-    summary = {"round": a.round, "command": "python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-regimes --no-end-to-end",
+    summary = {"round": a.round, "command": "python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-regimes --no-end-to-end",
                "rocprof_kernel_stats": {"name": row["Name"], "calls": int(row["Calls"]), "average_ns": float(row["AverageNs"]),
                                         "min_ns": int(row["MinNs"]), "max_ns": int(row["MaxNs"])},
                "rocprof_kernel_trace": {"n": len(d), "median_ns": statistics.median(d), "last_half_mean_ns": statistics.mean(d[len(d) // 2:]),
@@ -202,7 +202,7 @@ def main():
                "of_which_staging_sweep_read_bytes": rd_t,
                "raw_KiB": {"FETCH_SIZE": fetch[kf], "WRITE_SIZE": write[kf], "sweep_FETCH_SIZE": fetch[kt[0]] if kt else None},
                "collected": "round %s, rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes; per step = sweep + fused kernel" % a.round,
-               "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of `bench.py --gpus 1 --steps 20 --warmup 5`"},
+               "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of `bench.py --gpus 1 --steps 20 --warmup 5 --full`"},
               open(os.path.join(dst, "pmc_fuse_latest.json"), "w"), indent=1)
     # ---- every kernel
     stats = one(os.path.join(src, "all", "**", "*_kernel_stats.csv"))
