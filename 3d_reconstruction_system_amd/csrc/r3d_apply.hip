@@ -236,6 +236,12 @@ int apply_common(r3d_ctx* ctx, const void* d_xyz_in, int in_dtype, int64_t n_poi
   if (n_points == 0) return R3D_OK;
   R3D_REQUIRE(d_xyz_in && d_xyz_out, "NULL device pointer");
   R3D_REQUIRE(d_xyz_in == d_xyz_out ? in_dtype == out_dtype : true, "in-place apply needs equal dtypes");
+  {  // a partial overlap would make the result depend on which tile's stores land before which tile's loads
+    const uintptr_t in0 = (uintptr_t)d_xyz_in, out0 = (uintptr_t)d_xyz_out;
+    const uintptr_t in1 = in0 + (size_t)n_points * 3 * r3d_xyz_size(in_dtype);
+    const uintptr_t out1 = out0 + (size_t)n_points * 3 * r3d_xyz_size(out_dtype);
+    R3D_REQUIRE(in0 == out0 || in1 <= out0 || out1 <= in0, "input and output ranges overlap without being the same range");
+  }
   r3d_wrote(ctx, d_xyz_out, (size_t)n_points * 3 * r3d_xyz_size(out_dtype));   // an ICP loop working on these points is over
   ApplyArgs a;
   a.in = d_xyz_in;

@@ -178,7 +178,8 @@ int r3d_project3d_grad_f32(r3d_ctx* ctx, const float* d_grad_pix, const float* d
 
 /* ---- a4 on an existing cloud: p_world = Rinv . (p_cam - t), the evaluation order of point_camera()
  * (camera_to_world.py:57-59) and of the fused kernel, so fuse_frames(depth) == se3_apply(unproject(depth))
- * bit for bit.  h_pose is ALWAYS a host pointer: 12 doubles [Rinv row-major (9), t (3)].  In-place allowed. */
+ * bit for bit.  h_pose is ALWAYS a host pointer: 12 doubles [Rinv row-major (9), t (3)].  In-place allowed
+ * (d_xyz_out == d_xyz_in, equal dtypes); any other overlap of the input and output ranges -> R3D_ERR_INVALID. */
 int r3d_se3_apply(r3d_ctx* ctx, const void* d_xyz_in, int in_dtype, int64_t n_points, const double* h_pose,
                   void* d_xyz_out, int out_dtype);
 int r3d_se3_apply_host(r3d_ctx* ctx, const void* h_xyz_in, int in_dtype, int64_t n_points, const double* h_pose,
@@ -186,7 +187,8 @@ int r3d_se3_apply_host(r3d_ctx* ctx, const void* h_xyz_in, int in_dtype, int64_t
 
 /* ---- a7: p' = (T . [x,y,z,1]^T)[0:3] for a general row-major 4x4.
  * Replaces local_world(flag=True)/point_camera (transfer_T_icp.py:71-97, 10-12).
- * h_T is ALWAYS a host pointer (16 doubles); in-place (d_xyz_out == d_xyz_in) is allowed. */
+ * h_T is ALWAYS a host pointer (16 doubles); in-place (d_xyz_out == d_xyz_in, equal dtypes) is allowed; any other
+ * overlap of the input and output ranges -> R3D_ERR_INVALID. */
 int r3d_apply_T(r3d_ctx* ctx, const void* d_xyz_in, int in_dtype, int64_t n_points, const double* h_T,
                 void* d_xyz_out, int out_dtype);
 int r3d_apply_T_host(r3d_ctx* ctx, const void* h_xyz_in, int in_dtype, int64_t n_points, const double* h_T,
