@@ -144,6 +144,13 @@ SIGNATURES = {
     "r3d_voxelset_union": (_i, [_vp, _vp]),
     "r3d_voxelset_stats": (_i, [_vp, _vp, _vp, _vp]),
     "r3d_voxelset_codes": (_i, [_vp, _vp, _i64, _vp]),
+    "r3d_voxelgrid_create": (_i, [_vp, _d, _i64, _i, _pvp]),
+    "r3d_voxelgrid_destroy": (_i, [_vp]),
+    "r3d_voxelgrid_clear": (_i, [_vp]),
+    "r3d_voxelgrid_insert": (_i, [_vp, _vp, _vp, _i64]),
+    "r3d_voxelgrid_insert_host": (_i, [_vp, _vp, _vp, _i64]),
+    "r3d_voxelgrid_stats": (_i, [_vp, _vp, _vp, _vp]),
+    "r3d_voxelgrid_extract": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "r3d_sort_u64": (_i, [_vp, _vp, _i64, _i]),
     "r3d_octree_format_bt": (_i, [_vp, _i64, _d, _vp, _sz, _psz, _vp]),
     "r3d_octree_write_bt": (_i, [C.c_char_p, _vp, _i64, _d, _vp]),

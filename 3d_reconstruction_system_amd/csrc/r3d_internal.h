@@ -136,6 +136,10 @@ int r3d_voxelset_device_view(r3d_voxelset* vs, r3d_ctx** ctx, double* factor, ui
 bool r3d_voxelset_sort_feasible(const r3d_voxelset* vs, int64_t n_points, bool forced);
 int r3d_voxelset_sample(r3d_voxelset* vs, const float* d_xyz, int64_t n_points, int64_t n_insert, double cas_base_ps, bool* sort_out);
 int r3d_voxelset_insert_path(r3d_voxelset* vs, const float* d_xyz, int64_t n_points, int path);
+// A table of packed keys (kEmpty = free) holding `n` keys -> their ascending Morton codes in scratch slot 1 (slot 2 is the sort's
+// spare, d_counters[3] the compaction cursor); asynchronous.  Shared by the voxel set and the voxel grid (r3d_voxelgrid.hip).
+int r3d_voxel_table_sorted_codes(r3d_ctx* ctx, const uint64_t* d_table, uint64_t capacity, unsigned long long* d_counters,
+                                 int64_t n, uint64_t** d_list_out);
 
 // Device -> pageable host memory through pinned staging chunks (r3d_hostpipe.hip); synchronous.
 int r3d_download_pageable(r3d_ctx* ctx, void* h_dst, const void* d_src, size_t bytes);

@@ -1765,20 +1765,30 @@ static int codes_to_device_list(r3d_voxelset* vs, uint64_t** d_list_out, int64_t
     return R3D_ERR_NOMEM;
   }
   if (n == 0) return R3D_OK;
+  return r3d_voxel_table_sorted_codes(vs->ctx, vs->d_table, vs->capacity, vs->d_counters, n, d_list_out);
+}
+
+}  // extern "C"
+
+int r3d_voxel_table_sorted_codes(r3d_ctx* ctx, const uint64_t* d_table, uint64_t capacity, unsigned long long* d_counters,
+                                 int64_t n, uint64_t** d_list_out) {
   void *d_list = nullptr, *d_tmp = nullptr;
-  if ((rc = r3d_scratch(vs->ctx, 1, (size_t)n * sizeof(uint64_t), &d_list))) return rc;
-  if ((rc = r3d_scratch(vs->ctx, 2, (size_t)n * sizeof(uint64_t), &d_tmp))) return rc;
-  R3D_HIP(hipMemsetAsync(vs->d_counters + 3, 0, sizeof(unsigned long long), vs->ctx->stream));
-  int blocks = vs->ctx->num_cus * 8;
-  const uint64_t need = (vs->capacity + kCompactSlots - 1) / kCompactSlots;
+  int rc = r3d_scratch(ctx, 1, (size_t)n * sizeof(uint64_t), &d_list);
+  if (rc) return rc;
+  if ((rc = r3d_scratch(ctx, 2, (size_t)n * sizeof(uint64_t), &d_tmp))) return rc;
+  R3D_HIP(hipMemsetAsync(d_counters + 3, 0, sizeof(unsigned long long), ctx->stream));
+  int blocks = ctx->num_cus * 8;
+  const uint64_t need = (capacity + kCompactSlots - 1) / kCompactSlots;
   if ((uint64_t)blocks > need) blocks = (int)need;
-  hipLaunchKernelGGL(voxel_compact_kernel, dim3(blocks), dim3(kThreads), 0, vs->ctx->stream, vs->d_table, vs->capacity,
-                     static_cast<uint64_t*>(d_list), vs->d_counters);
+  hipLaunchKernelGGL(voxel_compact_kernel, dim3(blocks), dim3(kThreads), 0, ctx->stream, d_table, capacity,
+                     static_cast<uint64_t*>(d_list), d_counters);
   R3D_HIP(hipGetLastError());
-  if ((rc = r3d_radix_sort_u64(vs->ctx, static_cast<uint64_t*>(d_list), static_cast<uint64_t*>(d_tmp), n, 48))) return rc;
+  if ((rc = r3d_radix_sort_u64(ctx, static_cast<uint64_t*>(d_list), static_cast<uint64_t*>(d_tmp), n, 48))) return rc;
   *d_list_out = static_cast<uint64_t*>(d_list);
   return R3D_OK;
 }
+
+extern "C" {
 
 // Config 5 (frames sharded, ONE map): every rank voxelises its own shard of the world cloud into its own HBM hash set --
 // 12 B/point never leave the GPU -- then the ranks exchange only their DISTINCT codes (8 B/voxel, unequal shards) and

@@ -70,6 +70,21 @@ __device__ __forceinline__ bool voxel_key(float x, float y, float z, double fact
   return true;
 }
 
+// The same key, and the products u = factor * (double)x it is the floor of (the voxel grid, r3d_voxelgrid.hip, keeps the
+// fraction u - floor(u) of every point).  Accepts and rejects exactly the points voxel_key does.
+__device__ __forceinline__ bool voxel_key_u(float x, float y, float z, double factor, uint64_t* key, double u[3]) {
+  u[0] = factor * (double)x;
+  u[1] = factor * (double)y;
+  u[2] = factor * (double)z;
+  const double dx = floor(u[0]), dy = floor(u[1]), dz = floor(u[2]);
+  const bool ok = dx >= -(double)kTreeMaxVal && dx < (double)kTreeMaxVal && dy >= -(double)kTreeMaxVal &&
+                  dy < (double)kTreeMaxVal && dz >= -(double)kTreeMaxVal && dz < (double)kTreeMaxVal;
+  if (!ok) return false;
+  const uint32_t ix = (uint32_t)((int)dx + kTreeMaxVal), iy = (uint32_t)((int)dy + kTreeMaxVal), iz = (uint32_t)((int)dz + kTreeMaxVal);
+  *key = (uint64_t)(ix | (iy << 16)) | ((uint64_t)iz << 32);
+  return true;
+}
+
 // the value the previous lane of the wave holds (lane 0: its own), by DPP wave_shr:1 -- one VALU move per 32 bits instead of a
 // ds_bpermute round trip through the LDS crossbar (__shfl_up compiles to two of those for a 64-bit value)
 __device__ __forceinline__ uint64_t prev_lane_u64(uint64_t v) {

@@ -6,6 +6,7 @@ through the third-party python-octomap binding (octomap/txt_transfer_octomap.py:
 `OcTree` below offers that same small surface; points are buffered on the host and inserted in bulk by the
 HIP hash-set kernel, the pruned octree is serialised by the library's host code.
 """
+import collections
 import ctypes as C
 import os
 
@@ -98,6 +99,130 @@ def voxelize(xyz, resolution=0.1, ctx=None):
         finally:
             vs.close()
         cap *= 4
+
+
+VOXELGRID_RGB = 1
+
+DownSampled = collections.namedtuple("DownSampled", ["xyz", "rgba", "counts", "codes"])
+DownSampled.__doc__ = ("One row per occupied voxel in ascending Morton order: centroid xyz [M,3] float32, mean colour rgba [M] "
+                       "uint32 (None without colour), point counts [M] uint32, Morton codes [M] uint64.")
+
+
+def _cloud_f32(xyz):
+    xyz = np.ascontiguousarray(xyz, dtype=np.float32)
+    if xyz.ndim != 2 or xyz.shape[1] != 3:
+        raise ValueError("cloud must be [N,3]")
+    return xyz
+
+
+def _colour_words(rgba, n):
+    rgba = np.asarray(rgba)
+    if rgba.dtype != np.uint32 or rgba.ndim != 1 or rgba.shape[0] != n:
+        raise ValueError("rgba must be [N] uint32 colour words (r | g << 8 | b << 16), one per point: got %s %s for %d points"
+                         % (rgba.dtype, rgba.shape, n))
+    return np.ascontiguousarray(rgba)
+
+
+class VoxelGrid:
+    """HBM-resident voxel-grid downsampler (r3d_voxelgrid): insert points (any number of calls), extract one row per occupied
+    voxel -- centroid, count, Morton code and, with colour=True, the mean colour word.  The voxels are VoxelSet's; every output
+    bit is independent of how the points were split into inserts."""
+
+    def __init__(self, resolution=0.1, capacity=1 << 20, colour=False, ctx=None):
+        if not float(resolution) > 0.0:
+            raise ValueError("resolution must be positive")
+        if int(capacity) < 0:
+            raise ValueError("capacity must be >= 0")
+        self.handle = None
+        self.ctx = ctx or default_context()
+        self.resolution = float(resolution)
+        self.colour = bool(colour)
+        h = C.c_void_p()
+        L.check(self.ctx.lib.r3d_voxelgrid_create(self.ctx.handle, self.resolution, int(capacity),
+                                                  VOXELGRID_RGB if self.colour else 0, C.byref(h)))
+        self.handle = h.value
+        self.ctx.adopt(self)
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.r3d_voxelgrid_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def clear(self):
+        L.check(self.ctx.lib.r3d_voxelgrid_clear(self.handle))
+
+    def _check_colour(self, given):
+        if given and not self.colour:
+            raise ValueError("rgba given to a VoxelGrid made without colour")
+        if self.colour and not given:
+            raise ValueError("a VoxelGrid made with colour=True needs rgba for every point")
+
+    def insert(self, xyz, rgba=None):
+        """Host arrays: xyz [N,3] (float32; other float types are converted), rgba [N] uint32 or None."""
+        xyz = _cloud_f32(xyz)
+        self._check_colour(rgba is not None)
+        rgba = None if rgba is None else _colour_words(rgba, xyz.shape[0])
+        L.check(self.ctx.lib.r3d_voxelgrid_insert_host(self.handle, xyz.ctypes.data, None if rgba is None else rgba.ctypes.data,
+                                                       xyz.shape[0]))
+
+    def insert_device(self, d_xyz, n, d_rgba=None):
+        """Device pointers (ints): n float32 xyz rows and, for a colour grid, n uint32 colour words; asynchronous."""
+        self._check_colour(d_rgba is not None)
+        L.check(self.ctx.lib.r3d_voxelgrid_insert(self.handle, d_xyz, d_rgba, int(n)))
+
+    def stats(self):
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        L.check(self.ctx.lib.r3d_voxelgrid_stats(self.handle, C.byref(a), C.byref(b), C.byref(c)))
+        return {"voxels": a.value, "ignored_points": b.value, "overflow": c.value}
+
+    def extract_device(self, d_xyz_out=None, d_rgba_out=None, d_count_out=None, d_codes_out=None, cap=0):
+        """Rows into caller device buffers (pointers or None) of `cap` rows each; returns the number of voxels.  All None:
+        only the count."""
+        n = C.c_int64()
+        L.check(self.ctx.lib.r3d_voxelgrid_extract(self.handle, d_xyz_out, d_rgba_out, d_count_out, d_codes_out, int(cap),
+                                                   C.byref(n)))
+        return n.value
+
+    def extract(self):
+        """DownSampled(xyz [M,3] float32, rgba [M] uint32 | None, counts [M] uint32, codes [M] uint64) on the host."""
+        m = self.extract_device()
+        if m == 0:
+            return DownSampled(np.zeros((0, 3), np.float32), np.zeros(0, np.uint32) if self.colour else None,
+                               np.zeros(0, np.uint32), np.zeros(0, np.uint64))
+        d_xyz, d_cnt, d_codes = self.ctx.alloc(m * 12), self.ctx.alloc(m * 4), self.ctx.alloc(m * 8)
+        d_rgba = self.ctx.alloc(m * 4) if self.colour else None
+        try:
+            self.extract_device(d_xyz.ptr, d_rgba.ptr if d_rgba else None, d_cnt.ptr, d_codes.ptr, m)
+            xyz = d_xyz.download(np.float32, 3 * m).reshape(-1, 3)
+            rgba = d_rgba.download(np.uint32, m) if d_rgba else None
+            counts, codes = d_cnt.download(np.uint32, m), d_codes.download(np.uint64, m)
+        finally:
+            for b in (d_xyz, d_cnt, d_codes, d_rgba):
+                if b is not None:
+                    b.free()
+        return DownSampled(xyz, rgba, counts, codes)
+
+
+def voxel_down_sample(xyz, voxel_size, rgba=None, ctx=None):
+    """One-shot voxel-grid downsampling of a host cloud: DownSampled rows, one per occupied voxel (ascending Morton code).
+    The table is sized from N (2 slots per point), so it cannot overflow.  Points without a voxel key (non-finite, outside
+    +-32768 voxels) are ignored."""
+    xyz = _cloud_f32(xyz)
+    if not float(voxel_size) > 0.0:
+        raise ValueError("voxel_size must be positive")
+    rgba = None if rgba is None else _colour_words(rgba, xyz.shape[0])
+    vg = VoxelGrid(voxel_size, max(1 << 10, 2 * xyz.shape[0]), rgba is not None, ctx)
+    try:
+        vg.insert(xyz, rgba)
+        return vg.extract()
+    finally:
+        vg.close()
 
 
 class OcTree:

@@ -474,6 +474,32 @@ int r3d_voxelset_insert_codes(r3d_voxelset* vs, const uint64_t* d_codes, int64_t
  * `comm` must live on the set's context (one stream orders the set's kernels and the exchange).  If ANY rank's set has
  * overflowed, every rank takes part in the first exchange and then returns R3D_ERR_NOMEM: no rank is left waiting. */
 int r3d_voxelset_union(r3d_voxelset* vs, struct r3d_comm* comm);
+
+/* ---- voxel-grid downsampling: one output point per occupied voxel (Open3D's voxel_down_sample).  A device-resident
+ * accumulator bound to one ctx: points are inserted, possibly over many calls, then extracted as one row per occupied voxel
+ * in ascending 48-bit Morton order.  The voxel of a point is the voxel set's (same key rule, same ignored points), so the
+ * extracted codes equal r3d_voxelset_codes of the same cloud and go straight to r3d_octree_write_bt.  Per voxel: the code, the
+ * exact point count, the centroid (f32, from exact fixed-point sums: within ulp_f32 + res * 2^-28 of the exact mean) and,
+ * with R3D_VOXELGRID_RGB, the mean colour word (r | g << 8 | b << 16, as r3d_fuse_frames_rgb writes; each channel
+ * floor((2 S + n) / (2 n))).  Every output bit is independent of launch geometry and of how the points were split into
+ * inserts and in which order.  `capacity` = table slots (rounded up to a power of two; >= 2x the expected voxels).  A full
+ * table counts the points that found no slot (n_overflow) and extract then returns R3D_ERR_NOMEM until r3d_voxelgrid_clear.
+ * A voxel of more than 2^32 - 1 points makes extract return R3D_ERR_INVALID with nothing written. */
+typedef struct r3d_voxelgrid r3d_voxelgrid;
+#define R3D_VOXELGRID_RGB 1 /* the grid also accumulates colour words */
+int r3d_voxelgrid_create(r3d_ctx* ctx, double resolution, int64_t capacity, int flags, r3d_voxelgrid** vg_out);
+int r3d_voxelgrid_destroy(r3d_voxelgrid* vg);
+int r3d_voxelgrid_clear(r3d_voxelgrid* vg);
+/* asynchronous on the ctx stream; d_rgba NULL = no colour (must be NULL iff the grid was created without R3D_VOXELGRID_RGB);
+ * the alpha byte of an input word is not read */
+int r3d_voxelgrid_insert(r3d_voxelgrid* vg, const float* d_xyz, const uint32_t* d_rgba, int64_t n_points);
+int r3d_voxelgrid_insert_host(r3d_voxelgrid* vg, const float* h_xyz, const uint32_t* h_rgba, int64_t n_points);
+/* synchronises; any pointer may be NULL.  n_ignored as r3d_voxelset_stats; n_overflow = points that found no slot */
+int r3d_voxelgrid_stats(r3d_voxelgrid* vg, int64_t* n_voxels, int64_t* n_ignored, int64_t* n_overflow);
+/* synchronises; device outputs ([cap][3] f32, [cap] u32, [cap] u32, [cap] u64), any of them may be NULL; all NULL = only
+ * report *n_out.  cap < voxels -> R3D_ERR_INVALID, nothing written, *n_out set; overlapping output ranges -> R3D_ERR_INVALID. */
+int r3d_voxelgrid_extract(r3d_voxelgrid* vg, float* d_xyz_out, uint32_t* d_rgba_out, uint32_t* d_count_out,
+                          uint64_t* d_codes_out, int64_t cap, int64_t* n_out);
 /* In-place ascending sort of 64-bit keys in HBM by their low key_bits bits (stable LSD radix sort, 8-bit digits;
  * asynchronous on the ctx stream).  Building block of r3d_voxelset_codes, exported for tests and reuse. */
 int r3d_sort_u64(r3d_ctx* ctx, uint64_t* d_keys, int64_t n_keys, int key_bits);
