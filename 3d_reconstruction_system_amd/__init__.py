@@ -20,6 +20,8 @@ from .fusion import (REF_INTRINSICS, unproject, fuse_frames, fuse_frames_rgb, se
 from .poses import (scipy_transfer, get_r, pose_table, pose_to_T, read_pose_file, get_T, write_T,  # noqa: F401
                     str_tofloat)
 from .voxelmap import VoxelGrid, DownSampled, voxel_down_sample  # noqa: F401
+from .outliers import (knn, remove_statistical_outlier, remove_radius_outlier, StatisticalOutliers,  # noqa: F401
+                       RadiusOutliers)
 from . import cloud_io, device_text  # noqa: F401
 
 __version__ = "0.2.0"

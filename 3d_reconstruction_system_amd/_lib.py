@@ -151,6 +151,11 @@ SIGNATURES = {
     "r3d_voxelgrid_insert_host": (_i, [_vp, _vp, _vp, _i64]),
     "r3d_voxelgrid_stats": (_i, [_vp, _vp, _vp, _vp]),
     "r3d_voxelgrid_extract": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "r3d_nn_index_knn_self": (_i, [_vp, _i, _vp, _vp]),
+    "r3d_outlier_statistical": (_i, [_vp, _i, _d, _vp, _vp, _vp, _vp]),
+    "r3d_outlier_radius": (_i, [_vp, _d, _i64, _vp, _vp, _vp]),
+    "r3d_select_rows": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "r3d_nn_index_knn_stats": (_i, [_vp, _vp]),
     "r3d_sort_u64": (_i, [_vp, _vp, _i64, _i]),
     "r3d_octree_format_bt": (_i, [_vp, _i64, _d, _vp, _sz, _psz, _vp]),
     "r3d_octree_write_bt": (_i, [C.c_char_p, _vp, _i64, _d, _vp]),

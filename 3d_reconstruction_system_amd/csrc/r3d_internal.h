@@ -150,8 +150,8 @@ int r3d_radix_sort_u64(r3d_ctx* ctx, uint64_t* d_keys, uint64_t* d_tmp, int64_t 
 constexpr int kSortTile = 4096;   // keys per workgroup of every sort kernel
 int r3d_radix_sort_workspace(r3d_ctx* ctx, int64_t n, uint32_t** hist_out, int* n_blocks_out);
 static inline int r3d_sort_stride(int n_blocks) { return (n_blocks + 7) & ~7; }   // counters per histogram row (32-byte aligned rows)
-// hist[bin][tile] (256 rows of `stride` counters) -> exclusive prefixes over the tiles, in place; totals[bin] = the bin's count
-void r3d_sort_launch_scan(r3d_ctx* ctx, uint32_t* hist, int n_blocks, int stride, uint32_t* totals);
+// hist[bin][tile] (n_bins rows of `stride` counters) -> exclusive prefixes over the tiles, in place; totals[bin] = the bin's count
+void r3d_sort_launch_scan(r3d_ctx* ctx, uint32_t* hist, int n_blocks, int stride, uint32_t* totals, int n_bins = 256);
 
 // r3d_nnindex.hip: the index's own copy of the target cloud (original order), its size and its context
 int r3d_nn_index_target(r3d_nn_index* index, const float** d_tgt, int64_t* n_tgt, r3d_ctx** ctx);

@@ -175,9 +175,10 @@ int r3d_radix_sort_workspace(r3d_ctx* ctx, int64_t n, uint32_t** hist_out, int* 
   return R3D_OK;
 }
 
-// hist[bin][tile] -> exclusive prefixes over the tiles in place + the 256 bin totals (for radix passes built outside this file)
-void r3d_sort_launch_scan(r3d_ctx* ctx, uint32_t* hist, int n_blocks, int stride, uint32_t* totals) {
-  hipLaunchKernelGGL(digit_scan_kernel, dim3(kBins), dim3(kThreads), 0, ctx->stream, hist, n_blocks, stride, totals);
+// hist[bin][tile] -> exclusive prefixes over the tiles in place + the bin totals (for radix passes built outside this file,
+// and with n_bins = 1 for the row selection of r3d_knn.hip)
+void r3d_sort_launch_scan(r3d_ctx* ctx, uint32_t* hist, int n_blocks, int stride, uint32_t* totals, int n_bins) {
+  hipLaunchKernelGGL(digit_scan_kernel, dim3(n_bins), dim3(kThreads), 0, ctx->stream, hist, n_blocks, stride, totals);
 }
 
 int r3d_radix_sort_u64(r3d_ctx* ctx, uint64_t* d_keys, uint64_t* d_tmp, int64_t n, int bits, int first_bit, uint64_t** d_result,

@@ -130,6 +130,17 @@ class NNIndex:
                                                 1 if presorted else 0, C.byref(swept) if want_stats else None))
         return swept.value
 
+    def knn_self(self, k, d_idx_ptr, d_d2_ptr=None):
+        """The k (1..32) nearest other points of every indexed point: [n][k] uint32 rows and float32 d2 (d_d2_ptr may be None)
+        in the cloud's original row order, ascending (d2, row); missing neighbours are (0xffffffff, +inf).  Asynchronous."""
+        L.check(self.ctx.lib.r3d_nn_index_knn_self(self.handle, int(k), d_idx_ptr, d_d2_ptr))
+
+    def knn_pairs(self):
+        """Pair evaluations (lane-pairs) of the last knn_self / outlier call on this index (synchronous)."""
+        v = C.c_int64()
+        L.check(self.ctx.lib.r3d_nn_index_knn_stats(self.handle, C.byref(v)))
+        return v.value
+
     def rebuild(self, d_tgt_ptr, n_tgt):
         """Index another cloud of at most the size this one was created with, reusing the allocations."""
         L.check(self.ctx.lib.r3d_nn_index_rebuild(self.handle, d_tgt_ptr, int(n_tgt)))

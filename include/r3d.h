@@ -500,6 +500,31 @@ int r3d_voxelgrid_stats(r3d_voxelgrid* vg, int64_t* n_voxels, int64_t* n_ignored
  * report *n_out.  cap < voxels -> R3D_ERR_INVALID, nothing written, *n_out set; overlapping output ranges -> R3D_ERR_INVALID. */
 int r3d_voxelgrid_extract(r3d_voxelgrid* vg, float* d_xyz_out, uint32_t* d_rgba_out, uint32_t* d_count_out,
                           uint64_t* d_codes_out, int64_t cap, int64_t* n_out);
+/* ---- k nearest neighbours of an index's own points, and outlier removal over them.  P = the cloud the index was built from
+ * (n rows, original order); d2(i,j) = fmaf(dz,dz, fmaf(dy,dy, dx*dx)), dx = x_i - x_j ..., the index's NN expression.  A pair is a
+ * candidate iff j != i and d2(i,j) is finite: a point with a NaN / inf coordinate has no candidates and is nobody's.  Every
+ * call is deterministic (fixed-order fp64 reductions, no float atomics); invalid arguments return R3D_ERR_INVALID with nothing
+ * written.
+ * r3d_nn_index_knn_self (1 <= k <= 32; asynchronous): row i of d_idx_out [n][k] (u32) / d_d2_out [n][k] (f32, may be NULL)
+ * holds the k candidates j with the smallest (d2(i,j), j), ascending; fewer than k candidates -> the tail is (UINT32_MAX, +inf). */
+int r3d_nn_index_knn_self(r3d_nn_index* index, int k, uint32_t* d_idx_out, float* d_d2_out);
+/* Statistical outlier removal (1 <= k <= 32, std_ratio finite and > 0; synchronises).  Point i is scored iff it has k
+ * candidates; m_i = (sum over its k-list of sqrt((double) d2), ascending, in fp64) / k, unscored: +inf.  Over the V scored
+ * points mu = sum m / V, sigma = sqrt(sum (m - mu)^2 / (V - 1)) (0 when V <= 1), T = mu + std_ratio sigma; d_keep_out[i]
+ * (u8) = m_i <= T.  m_i depends only on the k smallest d2 values: bit-identical under any row permutation.  Optional:
+ * d_score_out [n] f64 = m_i, h_stats_out (host, 4 doubles) = V, mu, sigma, T; h_n_kept = points kept. */
+int r3d_outlier_statistical(r3d_nn_index* index, int k, double std_ratio, uint8_t* d_keep_out, double* d_score_out,
+                            double* h_stats_out, int64_t* h_n_kept);
+/* Radius outlier removal (radius finite and > 0, min_points >= 1; synchronises): r2 = (float)((double) radius * radius),
+ * c_i = #{candidates j : d2(i,j) <= r2}, d_keep_out[i] = c_i >= min_points; d_count_out [n] u32 (may be NULL) =
+ * min(c_i, min_points) (saturated: the search stops early). */
+int r3d_outlier_radius(r3d_nn_index* index, double radius, int64_t min_points, uint8_t* d_keep_out, uint32_t* d_count_out,
+                       int64_t* h_n_kept);
+/* Order-preserving row selection (synchronises): the xyz rows i with d_keep[i] != 0, in their original order, into d_xyz_out
+ * and (optional) their row numbers i into d_rows_out (u32); *h_n_out = rows kept.  The outputs need room for the kept rows
+ * only; an output that overlaps an input or the other output -> R3D_ERR_INVALID. */
+int r3d_select_rows(r3d_ctx* ctx, const float* d_xyz, int64_t n_points, const uint8_t* d_keep, float* d_xyz_out,
+                    uint32_t* d_rows_out, int64_t* h_n_out);
 /* In-place ascending sort of 64-bit keys in HBM by their low key_bits bits (stable LSD radix sort, 8-bit digits;
  * asynchronous on the ctx stream).  Building block of r3d_voxelset_codes, exported for tests and reuse. */
 int r3d_sort_u64(r3d_ctx* ctx, uint64_t* d_keys, int64_t n_keys, int key_bits);

@@ -33,6 +33,9 @@ int r3d_apply_T_many(r3d_ctx* ctx, const void* d_xyz_in, int in_dtype, int64_t n
  * estimator that probes several clouds keeps one index object instead of paying eight hipMalloc / hipFree pairs per probe).
  * Asynchronous. */
 int r3d_nn_index_rebuild(r3d_nn_index* index, const float* d_tgt, int64_t n_tgt);
+/* Pair evaluations of the last r3d_nn_index_knn_self / r3d_outlier_* call on this index: 32-target groups evaluated x 32 x 64
+ * lanes (inactive lanes of a wave included).  Synchronises. */
+int r3d_nn_index_knn_stats(r3d_nn_index* index, int64_t* h_pairs);
 /* Rows d_rows[0], d_rows[1], ... (n_out uint32 row numbers; a number >= n_points yields a NaN row) of a device xyz cloud into
  * d_xyz_out -- e.g. the permutation r3d_nn_index_sort_cloud reports, applied to a second cloud.  Asynchronous. */
 int r3d_gather_rows(r3d_ctx* ctx, const float* d_xyz, int64_t n_points, const uint32_t* d_rows, int64_t n_out, float* d_xyz_out);
