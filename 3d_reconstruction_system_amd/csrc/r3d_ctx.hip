@@ -247,6 +247,7 @@ static int* tuning_slot(r3d_ctx* ctx, const char* key) {
   if (!strcmp(key, "fuse_stage_auto_mb")) return &ctx->fuse_stage_auto_mb;
   if (!strcmp(key, "fuse_resident_mb")) return &ctx->fuse_resident_mb;
   if (!strcmp(key, "fuse_inputs_fresh")) return &ctx->fuse_inputs_fresh;
+  if (!strcmp(key, "fuse_stage_fold")) return &ctx->fuse_stage_fold;
   if (!strcmp(key, "fuse_sweeps")) return &ctx->fuse_sweeps;
   if (!strcmp(key, "nn_variant")) return &ctx->nn_variant;
   if (!strcmp(key, "nn_warm")) return &ctx->nn_warm;

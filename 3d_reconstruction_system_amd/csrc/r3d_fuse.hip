@@ -167,35 +167,101 @@ __device__ __forceinline__ void load_tile_wave(const uint8_t* __restrict__ depth
   }
 }
 
+// ---- staging folded into the fused launch -------------------------------------------------------------------------
+// The first n_stage workgroups of a fused launch read one contiguous slice each of the chunk's depth bytes (whole 16-byte
+// pieces, the cache_touch_kernel loop below) and exit; the others fuse.  n_stage <= num_cus * 8, so every stager is resident
+// from the start and, dispatched first, holds the device while the read-only phase runs; fuse workgroups take the slots the
+// stagers leave.  Nothing waits for anything: a tile fused before its bytes were staged reads them from HBM -- same result.
+struct StageSlices {
+  const uint4* src;   // 16-byte aligned
+  uint64_t n16;       // 16-byte pieces to read
+  uint32_t n_stage;   // stager workgroups at the front of the grid (0: no staging in this launch)
+};
+
+__device__ __forceinline__ uint32_t touch_pieces(const uint4* __restrict__ src, uint64_t lo, uint64_t hi) {
+  uint32_t acc = 0;
+  for (uint64_t base = lo + threadIdx.x; base < hi; base += kThreads * 4) {
+    uint4 q[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint64_t i = base + (uint64_t)k * kThreads;
+      q[k] = src[i < hi ? i : hi - 1];   // clamped: unconditional loads, all four in flight together
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc ^= q[k].x ^ q[k].y ^ q[k].z ^ q[k].w;
+  }
+  return acc;
+}
+
+// ---- f32 xyz: the tile body ----------------------------------------------------------------------------------------
+// In three phases: (1) every load of the lane's kPx pixels -- depth and the u / v table entries -- is issued, (2) one wait,
+// (3) per pixel, compute and store.  gfx9's vmcnt counts stores too, so a load issued after a store makes the wait for
+// its data wait for that store as well: the body of rounds 1-5 (per-pixel predicated blocks, each load -> wait -> compute
+// -> store) kept one 768-B store per wave in flight and a tile was four memory round trips in a row (that body is
+// fuse32_chained in tools/ab_kernels.hip).  Measured per C2 step on fresh rasters (profiles/r06_step_ab_*.log): with the
+// staging folded in (below), 95.9-96.4 us against the chained body's 98.4-101.4 behind its sweep; behind a separate sweep the
+// three-phase body is bimodal (97 or 108 us, depending on the box), so the two go together.  Loads are clamped into the
+// frame, so they run unconditionally; whole tiles (workgroup-uniform) store without a predicate, ragged ones predicate the
+// stores only.  v stays a vector load per pixel: a tile of a 1280-wide frame lies on two rows, but fetching v[j0], v[j0 + 1]
+// by scalar loads and selecting per lane made the step 3-13 us SLOWER (ab_kernels var3 vs var1).
+template <bool POSE, bool RAGGED>
+__device__ __forceinline__ void store_tile(float* __restrict__ out, const FuseDims& dm, const Pose& P, uint64_t fbase,
+                                           const uint32_t p[kPx], const double z[kPx], const double ui[kPx],
+                                           const double vj[kPx]) {
+#pragma unroll
+  for (int r = 0; r < kPx; ++r) {
+    double w[3];
+    point<POSE>(z[r], ui[r], vj[r], P, w);
+    if (!RAGGED || p[r] < dm.hw) store_x3_nt(out + (fbase + p[r]) * 3, f32x3{(float)w[0], (float)w[1], (float)w[2]});
+  }
+}
+
 template <typename DT, bool POSE, bool WAVE>
 __global__ __launch_bounds__(kThreads) void fuse_lane_kernel(const DT* __restrict__ depth, float* __restrict__ out,
                                                              const double* __restrict__ u, const double* __restrict__ v,
-                                                             const double* __restrict__ pose, const FuseDims dm) {
+                                                             const double* __restrict__ pose, const FuseDims dm,
+                                                             const StageSlices st) {
+  if (blockIdx.x < st.n_stage) {
+    const uint64_t lo = st.n16 * blockIdx.x / st.n_stage, hi = st.n16 * (blockIdx.x + 1) / st.n_stage;
+    const uint32_t acc = touch_pieces(st.src, lo, hi);
+    if (acc == 0x9e3779b9u && st.n16 == ~(uint64_t)0) out[0] = (float)acc;  // never true: keeps the loads, writes nothing
+    return;
+  }
   const uint32_t tid = threadIdx.x;
   const uint32_t first = WAVE ? 256u * (tid >> 6) + (tid & 63u) : tid;  // this lane's pixel of round 0 within the tile
   constexpr uint32_t kRound = WAVE ? 64u : (uint32_t)kThreads;           // pixel step between its rounds
-  for (uint32_t tile = blockIdx.x; tile < dm.total_tiles; tile += gridDim.x) {
+  for (uint32_t tile = blockIdx.x - st.n_stage; tile < dm.total_tiles; tile += gridDim.x - st.n_stage) {
     const uint32_t frame = magic_div(tile, dm.t_magic, dm.t_shift);
     const uint32_t tf = tile - frame * dm.tiles_per_frame;
     Pose P;
     load_pose<POSE>(pose, frame, P);
     const uint64_t fbase = (uint64_t)frame * dm.hw;
+    const uint32_t t0 = tf * kTile;
+    // phase 1: every load
     DT raw[kPx];
     if constexpr (WAVE)
       load_tile_wave<kPx>(depth, dm, fbase, tf, tid, raw);
     else
-      load_tile<DT, kPx, 0, (POSE || sizeof(DT) > 1)>(depth, dm, tile, tid, raw);  // measured per variant, see load_tile
+      load_tile<DT, kPx, 0, true>(depth, dm, tile, tid, raw);
+    uint32_t p[kPx];
+    double z[kPx], ui[kPx], vj[kPx];
 #pragma unroll
     for (int r = 0; r < kPx; ++r) {
-      const uint32_t p = tf * kTile + r * kRound + first;
-      if (p < dm.hw) {
-        const uint32_t j = magic_div(p, dm.w_magic, dm.w_shift);
-        const uint32_t i = p - j * dm.width;
-        double w[3];
-        point<POSE>((double)raw[r] * dm.scale, u[i], v[j], P, w);
-        store_x3_nt(out + (fbase + p) * 3, f32x3{(float)w[0], (float)w[1], (float)w[2]});
-      }
+      p[r] = t0 + r * kRound + first;
+      const uint32_t pc = min(p[r], dm.hw - 1);
+      const uint32_t j = magic_div(pc, dm.w_magic, dm.w_shift);
+      ui[r] = u[pc - j * dm.width];
+      vj[r] = v[j];
     }
+    // phase 2: one wait, for all of them
+    __builtin_amdgcn_s_waitcnt(0);
+#pragma unroll
+    for (int r = 0; r < kPx; ++r) z[r] = (double)raw[r] * dm.scale;
+    // phase 3: compute and store, the stores back to back
+    if (t0 + kTile <= dm.hw)  // whole tile (workgroup-uniform)
+      store_tile<POSE, false>(out, dm, P, fbase, p, z, ui, vj);
+    else
+      store_tile<POSE, true>(out, dm, P, fbase, p, z, ui, vj);
   }
 }
 
@@ -506,15 +572,22 @@ __global__ __launch_bounds__(kThreads) void cache_touch_kernel(const uint4* __re
   if (acc == 0x9e3779b9u && n16 == ~(uint64_t)0) *sink = acc;  // never true: keeps the loads, writes nothing
 }
 
-// whole 16-byte pieces inside [p, p + bytes): the ragged ends share their cache lines with the pieces next to them
-void cache_touch(r3d_ctx* ctx, const void* p, uint64_t bytes) {
+// whole 16-byte pieces inside [p, p + bytes): the ragged ends share their cache lines with the pieces next to them.
+// Workgroups: one per 1024 pieces (one round of four loads per lane), at most num_cus * 8 (all resident at once).
+StageSlices stage_slices(const r3d_ctx* ctx, const void* p, uint64_t bytes) {
   const uintptr_t lo = ((uintptr_t)p + 15) & ~(uintptr_t)15, hi = ((uintptr_t)p + bytes) & ~(uintptr_t)15;
-  if (hi <= lo) return;
+  if (hi <= lo) return StageSlices{nullptr, 0, 0};
   const uint64_t n16 = (hi - lo) / 16;
   uint64_t blocks = (n16 + kThreads * 4 - 1) / (kThreads * 4);
   if (blocks > (uint64_t)ctx->num_cus * 8) blocks = (uint64_t)ctx->num_cus * 8;
-  hipLaunchKernelGGL(cache_touch_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, ctx->stream,
-                     reinterpret_cast<const uint4*>(lo), n16, static_cast<uint32_t*>(nullptr));
+  return StageSlices{reinterpret_cast<const uint4*>(lo), n16, (uint32_t)blocks};
+}
+
+void cache_touch(r3d_ctx* ctx, const void* p, uint64_t bytes) {
+  const StageSlices st = stage_slices(ctx, p, bytes);
+  if (!st.n_stage) return;
+  hipLaunchKernelGGL(cache_touch_kernel, dim3(st.n_stage), dim3(kThreads), 0, ctx->stream, st.src, st.n16,
+                     static_cast<uint32_t*>(nullptr));
 }
 
 struct FusePtrs {
@@ -527,8 +600,10 @@ struct FusePtrs {
   uint32_t* rgba;
 };
 
+// st.n_stage > 0 only for the f32 lane kernel: the grid is then n_stage stagers + `blocks` fuse workgroups
 template <typename DT, bool POSE>
-void launch_typed(const FusePtrs& p, const FuseDims& dm, int out_dtype, int blocks, bool wave, hipStream_t s) {
+void launch_typed(const FusePtrs& p, const FuseDims& dm, int out_dtype, int blocks, bool wave, const StageSlices& st,
+                  hipStream_t s) {
   const DT* d = static_cast<const DT*>(p.depth);
   if (out_dtype == R3D_F64) {
     hipLaunchKernelGGL((fuse_pair_kernel<DT, POSE>), dim3(blocks), dim3(kThreads), 0, s, d, static_cast<double*>(p.out), p.u,
@@ -539,22 +614,23 @@ void launch_typed(const FusePtrs& p, const FuseDims& dm, int out_dtype, int bloc
   } else {
     if constexpr (std::is_same<DT, uint8_t>::value && !POSE) {
       if (wave) {
-        hipLaunchKernelGGL((fuse_lane_kernel<DT, POSE, true>), dim3(blocks), dim3(kThreads), 0, s, d, static_cast<float*>(p.out),
-                           p.u, p.v, p.pose, dm);
+        hipLaunchKernelGGL((fuse_lane_kernel<DT, POSE, true>), dim3(blocks + st.n_stage), dim3(kThreads), 0, s, d,
+                           static_cast<float*>(p.out), p.u, p.v, p.pose, dm, st);
         return;
       }
     }
-    hipLaunchKernelGGL((fuse_lane_kernel<DT, POSE, false>), dim3(blocks), dim3(kThreads), 0, s, d, static_cast<float*>(p.out),
-                       p.u, p.v, p.pose, dm);
+    hipLaunchKernelGGL((fuse_lane_kernel<DT, POSE, false>), dim3(blocks + st.n_stage), dim3(kThreads), 0, s, d,
+                       static_cast<float*>(p.out), p.u, p.v, p.pose, dm, st);
   }
 }
 
 template <bool POSE>
-void launch_depth(const FusePtrs& p, const FuseDims& dm, int depth_dtype, int out_dtype, int blocks, bool wave, hipStream_t s) {
+void launch_depth(const FusePtrs& p, const FuseDims& dm, int depth_dtype, int out_dtype, int blocks, bool wave,
+                  const StageSlices& st, hipStream_t s) {
   switch (depth_dtype) {
-    case R3D_DEPTH_U8: launch_typed<uint8_t, POSE>(p, dm, out_dtype, blocks, wave, s); break;
-    case R3D_DEPTH_U16: launch_typed<uint16_t, POSE>(p, dm, out_dtype, blocks, wave, s); break;
-    default: launch_typed<float, POSE>(p, dm, out_dtype, blocks, wave, s); break;
+    case R3D_DEPTH_U8: launch_typed<uint8_t, POSE>(p, dm, out_dtype, blocks, wave, st, s); break;
+    case R3D_DEPTH_U16: launch_typed<uint16_t, POSE>(p, dm, out_dtype, blocks, wave, st, s); break;
+    default: launch_typed<float, POSE>(p, dm, out_dtype, blocks, wave, st, s); break;
   }
 }
 
@@ -671,7 +747,14 @@ int fuse_common(r3d_ctx* ctx, const r3d_camera* cam, const void* d_depth, int de
     dm.total_tiles = (uint32_t)total_tiles;
     dm.rgb_vec_ok = rr && ((uintptr_t)rr % 16 == 0) && (hw % 16 == 0);
     dm.depth_vec_ok = ((uintptr_t)dd % 4 == 0) && ((hw * dsz) % 4 == 0);
-    if (stage_depth) cache_touch(ctx, dd, hw * dsz * (uint64_t)nf);
+    // the f32 lane kernel stages its own depth bytes in its first workgroups (fuse_stage_fold, StageSlices); the other kernels,
+    // and fuse_stage_fold 0, get the separate sweep in front.  Either way the counter counts one staging per staged input.
+    const bool fold = stage_depth && ctx->fuse_stage_fold && !vs && out_dtype == R3D_F32 && !p.rgb && total_tiles < (1u << 30);
+    StageSlices st{nullptr, 0, 0};
+    if (fold)
+      st = stage_slices(ctx, dd, hw * dsz * (uint64_t)nf);
+    else if (stage_depth)
+      cache_touch(ctx, dd, hw * dsz * (uint64_t)nf);
     if (stage_rgb) cache_touch(ctx, rr, hw * 3 * (uint64_t)nf);
     ctx->fuse_sweeps += (int)stage_depth + (int)stage_rgb;
     // measured (profiles/r02_c5_probe.log, r02_ab_kernels.log, r02_all_kernels.json): one tile per workgroup for every kernel
@@ -687,9 +770,9 @@ int fuse_common(r3d_ctx* ctx, const r3d_camera* cam, const void* d_depth, int de
       if (g > total_tiles) g = total_tiles;
       launch_voxel(p, dm, vv, depth_dtype, with_pose, (int)g, ctx->stream);
     } else if (with_pose)
-      launch_depth<true>(p, dm, depth_dtype, out_dtype, (int)blocks, wave, ctx->stream);
+      launch_depth<true>(p, dm, depth_dtype, out_dtype, (int)blocks, wave, st, ctx->stream);
     else
-      launch_depth<false>(p, dm, depth_dtype, out_dtype, (int)blocks, wave, ctx->stream);
+      launch_depth<false>(p, dm, depth_dtype, out_dtype, (int)blocks, wave, st, ctx->stream);
   }
   if (colour_after) {
     const uint64_t n = hw * (uint64_t)n_frames;

@@ -32,6 +32,9 @@ struct r3d_ctx {
   // it writes it from outside the cache (H2D copies, the host pipeline's uploads, collective receives, frees).  This many MB
   // of inputs are presumed to survive in the 256 MiB cache while a launch's write stream passes through it.
   int fuse_resident_mb = 128;
+  // 1: a staged f32 lane launch reads its depth chunk in its own first workgroups (no separate sweep launch); 0: the sweep of
+  // rounds 1-5 in front (A/B, escape hatch)
+  int fuse_stage_fold = 1;
   int fuse_sweeps = 0;        // read-only statistic: staging sweeps the fused launches of this ctx have enqueued so far
   int fuse_inputs_fresh = 0;  // write-only knob: a foreign producer (torch, another library) has rewritten input buffers
   int nn_variant = 0;     // sources per lane (1, 2, 4; 0 = auto)

@@ -83,7 +83,9 @@ int r3d_ctx_stream(r3d_ctx* ctx, void** stream_out);
  * a raster an H2D copy has just written runs at 0.49 of the HBM peak plain, 0.82 staged; staging a cached one costs 8 %).
  * A FOREIGN producer (torch, another library) that rewrites an input buffer in place says so with
  * r3d_ctx_set_tuning(ctx, "fuse_inputs_fresh", 1): an event, not a state -- nothing on the device is presumed cached any more;
- * reading the key back gives the number of ranges on record; "fuse_sweeps" counts the staging sweeps enqueued so far).
+ * reading the key back gives the number of ranges on record; "fuse_sweeps" counts the staging sweeps enqueued so far, one per
+ * staged input chunk).  "fuse_stage_fold" (default 1): a staged launch of the f32-xyz kernel without colour reads its depth
+ * chunk in its own first workgroups instead of a separate sweep launch in front; 0 = the separate sweep (A/B, escape hatch).
  * No knob changes any result bit.  Unknown key -> R3D_ERR_INVALID.  (Kernel A/B variants live in tools/ab_kernels.hip,
  * not in the library.) */
 int r3d_ctx_set_tuning(r3d_ctx* ctx, const char* key, int value);

@@ -413,6 +413,135 @@ __global__ __launch_bounds__(kThreads) void fuse_rgb(const uint8_t* __restrict__
   }
 }
 
+// ---- the library's f32 lane kernel (u8 depth, pose) as it was through round 5: per-pixel predicated blocks, each
+// load -> wait -> compute -> store.  gfx9's vmcnt counts stores, so each block's wait also waits for the previous pixel's
+// store and a wave has one 768-B store in flight at a time.  Kept as the A/B partner of the library's three-phase body.
+struct LibDims {
+  double scale;
+  uint32_t hw, width, tiles_per_frame, n_frames, w_magic, w_shift, t_magic, t_shift, total_tiles;
+};
+
+static void make_magic(uint32_t d, uint32_t* magic, uint32_t* shift) {
+  uint32_t s = 0;
+  while (((uint64_t)1 << s) < d) ++s;
+  *magic = (uint32_t)((((uint64_t)1 << (31 + s)) / d) + 1);
+  *shift = 31 + s;
+}
+
+__device__ __forceinline__ uint32_t magic_div(uint32_t x, uint32_t magic, uint32_t shift) {
+  return (uint32_t)(((uint64_t)x * magic) >> shift);
+}
+
+__device__ __forceinline__ void store_x3_nt(void* dst, f32x3 v) {
+  asm volatile("global_store_dwordx3 %0, %1, off nt\n\ts_nop 1" ::"v"(dst), "v"(v) : "memory");
+}
+
+__global__ __launch_bounds__(kThreads) void fuse32_chained(const uint8_t* __restrict__ depth, float* __restrict__ out,
+                                                           const double* __restrict__ u, const double* __restrict__ v,
+                                                           const double* __restrict__ pose, const LibDims dm) {
+  const uint32_t tid = threadIdx.x;
+  for (uint32_t tile = blockIdx.x; tile < dm.total_tiles; tile += gridDim.x) {
+    const uint32_t frame = magic_div(tile, dm.t_magic, dm.t_shift);
+    const uint32_t tf = tile - frame * dm.tiles_per_frame;
+    Pose P;
+    load_pose(pose, frame, P);
+    const uint64_t fbase = (uint64_t)frame * dm.hw;
+    uint8_t raw[kPx];
+#pragma unroll
+    for (int r = 0; r < kPx; ++r) raw[r] = depth[fbase + min(tf * kTile + r * kThreads + tid, dm.hw - 1)];
+#pragma unroll
+    for (int r = 0; r < kPx; ++r) {
+      const uint32_t p = tf * kTile + r * kThreads + tid;
+      if (p < dm.hw) {
+        const uint32_t j = magic_div(p, dm.w_magic, dm.w_shift);
+        const uint32_t i = p - j * dm.width;
+        double w[3];
+        point((double)raw[r] * dm.scale, u[i], v[j], P, w);
+        store_x3_nt(out + (fbase + p) * 3, f32x3{(float)w[0], (float)w[1], (float)w[2]});
+      }
+    }
+  }
+}
+
+// Body variants of the same kernel for the step A/B (BODY 0 = chained as above, 1 = every load first, one wait, then per pixel
+// compute + store, 2 = every load first, one wait, all four points computed, then the four stores), with (STAGE) or without
+// stager workgroups at the front of the grid.
+__device__ __forceinline__ uint32_t touch_pieces(const uint4* __restrict__ src, uint64_t lo, uint64_t hi) {
+  uint32_t acc = 0;
+  for (uint64_t base = lo + threadIdx.x; base < hi; base += kThreads * 4) {
+    uint4 q[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint64_t i = base + (uint64_t)k * kThreads;
+      q[k] = src[i < hi ? i : hi - 1];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc ^= q[k].x ^ q[k].y ^ q[k].z ^ q[k].w;
+  }
+  return acc;
+}
+
+template <int BODY, bool STAGE>
+__global__ __launch_bounds__(kThreads) void fuse32_var(const uint8_t* __restrict__ depth, float* __restrict__ out,
+                                                       const double* __restrict__ u, const double* __restrict__ v,
+                                                       const double* __restrict__ pose, const LibDims dm, const uint4* stage_src,
+                                                       uint64_t n16, uint32_t n_stage) {
+  if (STAGE && blockIdx.x < n_stage) {
+    const uint64_t lo = n16 * blockIdx.x / n_stage, hi = n16 * (blockIdx.x + 1) / n_stage;
+    const uint32_t acc = touch_pieces(stage_src, lo, hi);
+    if (acc == 0x9e3779b9u && n16 == ~(uint64_t)0) out[0] = (float)acc;
+    return;
+  }
+  const uint32_t tid = threadIdx.x;
+  const uint32_t tile = blockIdx.x - (STAGE ? n_stage : 0);
+  const uint32_t frame = magic_div(tile, dm.t_magic, dm.t_shift);
+  const uint32_t tf = tile - frame * dm.tiles_per_frame;
+  Pose P;
+  load_pose(pose, frame, P);
+  const uint64_t fbase = (uint64_t)frame * dm.hw;
+  uint8_t raw[kPx];
+#pragma unroll
+  for (int r = 0; r < kPx; ++r) raw[r] = depth[fbase + min(tf * kTile + r * kThreads + tid, dm.hw - 1)];
+  if (BODY == 0) {
+#pragma unroll
+    for (int r = 0; r < kPx; ++r) {
+      const uint32_t p = tf * kTile + r * kThreads + tid;
+      if (p < dm.hw) {
+        const uint32_t j = magic_div(p, dm.w_magic, dm.w_shift);
+        const uint32_t i = p - j * dm.width;
+        double w[3];
+        point((double)raw[r] * dm.scale, u[i], v[j], P, w);
+        store_x3_nt(out + (fbase + p) * 3, f32x3{(float)w[0], (float)w[1], (float)w[2]});
+      }
+    }
+    return;
+  }
+  // whole tiles only (C2)
+  double ui[kPx], vj[kPx];
+  const uint32_t j0 = magic_div(tf * kTile, dm.w_magic, dm.w_shift);
+  const double v0 = BODY == 3 ? v[j0] : 0.0, v1 = BODY == 3 ? v[magic_div(tf * kTile + kTile - 1, dm.w_magic, dm.w_shift)] : 0.0;
+#pragma unroll
+  for (int r = 0; r < kPx; ++r) {
+    const uint32_t p = tf * kTile + r * kThreads + tid;
+    const uint32_t j = magic_div(p, dm.w_magic, dm.w_shift);
+    ui[r] = u[p - j * dm.width];
+    vj[r] = BODY == 3 ? (j == j0 ? v0 : v1) : v[j];  // BODY 3: a tile on two rows, v by scalar loads
+  }
+  __builtin_amdgcn_s_waitcnt(0);
+  f32x3 o[kPx];
+#pragma unroll
+  for (int r = 0; r < kPx; ++r) {
+    double w[3];
+    point((double)raw[r] * dm.scale, ui[r], vj[r], P, w);
+    o[r] = f32x3{(float)w[0], (float)w[1], (float)w[2]};
+    if (BODY == 1 || BODY == 3) store_x3_nt(out + (fbase + tf * kTile + r * kThreads + tid) * 3, o[r]);
+  }
+  if (BODY == 2) {
+#pragma unroll
+    for (int r = 0; r < kPx; ++r) store_x3_nt(out + (fbase + tf * kTile + r * kThreads + tid) * 3, o[r]);
+  }
+}
+
 // -------------------------------------------------------------------------------------------------------------------
 template <typename F>
 float time_ms(hipStream_t st, F&& launch, int iters = 200) {
@@ -430,6 +559,127 @@ float time_ms(hipStream_t st, F&& launch, int iters = 200) {
   CK(hipEventDestroy(a));
   CK(hipEventDestroy(b));
   return ms / iters;
+}
+
+// `ab_kernels H W F step`: the C2 step on fresh inputs (16 rotating rasters, staged every launch), interleaved in one process:
+//   parent  = r3d_cache_prefetch sweep + fuse32_chained (the body of rounds 1-5), two launches
+//   fold 0  = the library with fuse_stage_fold 0: its sweep + the three-phase body, two launches
+//   fold 1  = the library default: one launch, stager workgroups first
+// Each round times every candidate over `groups` x 100 launches (HIP events per group); the order rotates per round.
+static int step_ab(r3d_ctx* ctx, r3d_camera* cam, hipStream_t st, int H, int W, int F, const std::vector<uint8_t>& depth,
+                   const double* d_pose, const double* d_u, const double* d_v, int rounds, int groups) {
+  const uint64_t hw = (uint64_t)H * W, n = hw * F;
+  constexpr int kRasters = 16;
+  std::vector<uint8_t*> ras(kRasters);
+  for (int k = 0; k < kRasters; ++k) {
+    CK(hipMalloc(&ras[k], n));
+    std::vector<uint8_t> d2(depth);
+    for (auto& x : d2) x = (uint8_t)(x + 7 * k);
+    CK(hipMemcpy(ras[k], d2.data(), n, hipMemcpyHostToDevice));
+  }
+  float *d_ref, *d_out;
+  CK(hipMalloc(&d_ref, n * 12));
+  CK(hipMalloc(&d_out, n * 12));
+  LibDims dm{1.0, (uint32_t)hw, (uint32_t)W, (uint32_t)((hw + kTile - 1) / kTile), (uint32_t)F, 0, 0, 0, 0, 0};
+  make_magic(dm.width, &dm.w_magic, &dm.w_shift);
+  make_magic(dm.tiles_per_frame, &dm.t_magic, &dm.t_shift);
+  dm.total_tiles = dm.tiles_per_frame * F;
+  RK(r3d_ctx_set_tuning(ctx, "fuse_prefetch", 2));  // stage every launch, as the bench's rotating rasters are
+  const uint32_t n_stage = (uint32_t)std::min<uint64_t>((n / 16 + 1023) / 1024, 2048);  // C2: n % 16 == 0, aligned rasters
+  int turn = 0;
+  struct Cand { const char* name; std::function<void()> fn; };
+  std::vector<Cand> cs = {
+      {"parent: sweep + chained body", [&] {
+         const uint8_t* r = ras[turn++ % kRasters];
+         RK(r3d_cache_prefetch(ctx, r, n));
+         hipLaunchKernelGGL(fuse32_chained, dim3(dm.total_tiles), dim3(kThreads), 0, st, r, d_out, d_u, d_v, d_pose, dm);
+       }},
+      {"sweep + var1 (loads first, per-px store)", [&] {
+         const uint8_t* r = ras[turn++ % kRasters];
+         RK(r3d_cache_prefetch(ctx, r, n));
+         hipLaunchKernelGGL((fuse32_var<1, false>), dim3(dm.total_tiles), dim3(kThreads), 0, st, r, d_out, d_u, d_v, d_pose, dm,
+                            nullptr, 0, 0);
+       }},
+      {"sweep + var3 (var1 + scalar v)", [&] {
+         const uint8_t* r = ras[turn++ % kRasters];
+         RK(r3d_cache_prefetch(ctx, r, n));
+         hipLaunchKernelGGL((fuse32_var<3, false>), dim3(dm.total_tiles), dim3(kThreads), 0, st, r, d_out, d_u, d_v, d_pose, dm,
+                            nullptr, 0, 0);
+       }},
+      {"sweep + var2 (loads first, 4 stores last)", [&] {
+         const uint8_t* r = ras[turn++ % kRasters];
+         RK(r3d_cache_prefetch(ctx, r, n));
+         hipLaunchKernelGGL((fuse32_var<2, false>), dim3(dm.total_tiles), dim3(kThreads), 0, st, r, d_out, d_u, d_v, d_pose, dm,
+                            nullptr, 0, 0);
+       }},
+      {"folded chained body", [&] {
+         const uint8_t* r = ras[turn++ % kRasters];
+         hipLaunchKernelGGL((fuse32_var<0, true>), dim3(dm.total_tiles + n_stage), dim3(kThreads), 0, st, r, d_out, d_u, d_v,
+                            d_pose, dm, reinterpret_cast<const uint4*>(r), n / 16, n_stage);
+       }},
+      {"folded var2", [&] {
+         const uint8_t* r = ras[turn++ % kRasters];
+         hipLaunchKernelGGL((fuse32_var<2, true>), dim3(dm.total_tiles + n_stage), dim3(kThreads), 0, st, r, d_out, d_u, d_v,
+                            d_pose, dm, reinterpret_cast<const uint4*>(r), n / 16, n_stage);
+       }},
+      {"fold 0: sweep + three-phase body", [&] {
+         RK(r3d_ctx_set_tuning(ctx, "fuse_stage_fold", 0));
+         RK(r3d_fuse_frames(ctx, cam, ras[turn++ % kRasters], R3D_DEPTH_U8, F, 1.0, d_pose, d_out, R3D_F32));
+       }},
+      {"fold 1: one launch (default)", [&] {
+         RK(r3d_ctx_set_tuning(ctx, "fuse_stage_fold", 1));
+         RK(r3d_fuse_frames(ctx, cam, ras[turn++ % kRasters], R3D_DEPTH_U8, F, 1.0, d_pose, d_out, R3D_F32));
+       }},
+  };
+  bool ok = true;
+  for (size_t k = 0; k < cs.size(); ++k) {  // bits: every candidate against the library's default on the same raster
+    RK(r3d_ctx_set_tuning(ctx, "fuse_stage_fold", 1));
+    RK(r3d_fuse_frames(ctx, cam, ras[k % kRasters], R3D_DEPTH_U8, F, 1.0, d_pose, d_ref, R3D_F32));
+    CK(hipMemsetAsync(d_out, 0xff, n * 12, st));
+    turn = (int)k;
+    cs[k].fn();
+    CK(hipStreamSynchronize(st));
+    std::vector<uint32_t> a(n * 3), b(n * 3);
+    CK(hipMemcpy(a.data(), d_ref, n * 12, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(b.data(), d_out, n * 12, hipMemcpyDeviceToHost));
+    const bool same = a == b;
+    ok = ok && same;
+    printf("  %-34s %s\n", cs[k].name, same ? "bit-identical" : "MISMATCH");
+  }
+  if (!ok) return 1;
+  hipEvent_t ev[2];
+  CK(hipEventCreate(&ev[0]));
+  CK(hipEventCreate(&ev[1]));
+  std::vector<std::vector<float>> all(cs.size());
+  for (int round = 0; round < rounds; ++round)
+    for (size_t q = 0; q < cs.size(); ++q) {
+      const size_t k = (q + round) % cs.size();
+      for (int i = 0; i < 50; ++i) cs[k].fn();
+      std::vector<float> g;
+      for (int grp = 0; grp < groups; ++grp) {
+        CK(hipEventRecord(ev[0], st));
+        for (int i = 0; i < 100; ++i) cs[k].fn();
+        CK(hipEventRecord(ev[1], st));
+        CK(hipEventSynchronize(ev[1]));
+        float ms = 0;
+        CK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        g.push_back(ms * 1e3f / 100);  // us per step
+      }
+      std::sort(g.begin(), g.end());
+      all[k].insert(all[k].end(), g.begin(), g.end());
+      printf("  round %d  %-34s median %.2f us  (groups %.2f .. %.2f)  %d launches\n", round, cs[k].name, g[g.size() / 2],
+             g.front(), g.back(), groups * 100);
+    }
+  for (size_t k = 0; k < cs.size(); ++k) {
+    auto& a = all[k];
+    std::sort(a.begin(), a.end());
+    printf("STEP %-34s median %.2f us  p10 %.2f  p90 %.2f  min %.2f  max %.2f  (%zu groups of 100)  %.3f of 8 TB/s\n",
+           cs[k].name, a[a.size() / 2], a[a.size() / 10], a[a.size() * 9 / 10], a.front(), a.back(), a.size(),
+           n * 13.0 / (a[a.size() / 2] * 1e-6) / 8e12);
+  }
+  RK(r3d_ctx_set_tuning(ctx, "fuse_stage_fold", 1));
+  RK(r3d_ctx_set_tuning(ctx, "fuse_prefetch", 0));
+  return 0;
 }
 
 int main(int argc, char** argv) {
@@ -485,6 +735,15 @@ int main(int argc, char** argv) {
   int cus = 256;
   const int grid8 = cus * 8;
 
+  if (argc > 4 && !strcmp(argv[4], "step")) {
+    const int rounds = argc > 5 ? atoi(argv[5]) : 6, groups = argc > 6 ? atoi(argv[6]) : 10;
+    printf("== C2 step on fresh inputs, u8 -> f32 xyz + pose, %dx%d x %d frames, %d rounds x %d launches per candidate\n", W, H,
+           F, rounds, groups * 100);
+    const int rc = step_ab(ctx, cam, st, H, W, F, depth, d_pose, d_u, d_v, rounds, groups);
+    r3d_camera_destroy(cam);
+    r3d_ctx_destroy(ctx);
+    return rc;
+  }
   auto same = [&](const void* a, const void* b, size_t bytes, const char* what) {
     std::vector<char> ha(bytes), hb(bytes);
     CK(hipMemcpy(ha.data(), a, bytes, hipMemcpyDeviceToHost));
