@@ -159,6 +159,10 @@ SIGNATURES = {
     "r3d_sort_u64": (_i, [_vp, _vp, _i64, _i]),
     "r3d_octree_format_bt": (_i, [_vp, _i64, _d, _vp, _sz, _psz, _vp]),
     "r3d_octree_write_bt": (_i, [C.c_char_p, _vp, _i64, _d, _vp]),
+    "r3d_octree_records_device": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "r3d_octree_bt_header": (_i, [_i64, _d, _vp, _sz, _psz]),
+    "r3d_voxelset_format_bt": (_i, [_vp, _vp, _sz, _psz, _vp]),
+    "r3d_voxelset_write_bt": (_i, [_vp, C.c_char_p, _vp]),
 }
 
 _lib = None

@@ -255,6 +255,11 @@ static int* tuning_slot(r3d_ctx* ctx, const char* key) {
   if (!strcmp(key, "voxel_dedupe")) return &ctx->voxel_dedupe;
   if (!strcmp(key, "voxel_path")) return &ctx->voxel_path;
   if (!strcmp(key, "voxel_last_path")) return &ctx->voxel_last_path;
+  if (!strcmp(key, "octree_timing")) return &ctx->octree_timing;
+  if (!strcmp(key, "octree_count_us")) return &ctx->octree_us[0];
+  if (!strcmp(key, "octree_scan_us")) return &ctx->octree_us[1];
+  if (!strcmp(key, "octree_own_us")) return &ctx->octree_us[2];
+  if (!strcmp(key, "octree_link_us")) return &ctx->octree_us[3];
   return nullptr;
 }
 

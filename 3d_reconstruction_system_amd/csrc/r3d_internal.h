@@ -50,6 +50,8 @@ struct r3d_ctx {
   int apply_blocks = 0;
   int voxel_path = 0;     // big inserts: 0 auto (a sample of the cloud decides), 1 LDS-set + CAS kernel, 2 sort-merge (r3d_voxel.hip)
   int voxel_last_path = 0; // read-only: the path the last r3d_voxelset_insert took (1 / 2)
+  int octree_timing = 0;  // 1: the device octree serialiser puts HIP events around its four launches and waits for them ...
+  int octree_us[4] = {};  // ... read-only: microseconds of count, scan, own, link of the last such call (r3d_octree.hip)
   int voxel_dedupe = 0;   // 0 auto (on), 1 off, 2 on: per-workgroup LDS dedupe in front of the global hash set; 3: on, with the
                           // flush barrier inside its `if` (A/B against DESIGN 4.5b's finding only)
   // HIP-event stopwatch
@@ -143,6 +145,10 @@ int r3d_voxelset_insert_path(r3d_voxelset* vs, const float* d_xyz, int64_t n_poi
 // spare, d_counters[3] the compaction cursor); asynchronous.  Shared by the voxel set and the voxel grid (r3d_voxelgrid.hip).
 int r3d_voxel_table_sorted_codes(r3d_ctx* ctx, const uint64_t* d_table, uint64_t capacity, unsigned long long* d_counters,
                                  int64_t n, uint64_t** d_list_out);
+
+// The set's distinct voxels as ascending Morton codes in HBM (scratch slot 1 of its context, which is entered; slots 2 and 3 are
+// free again when this returns); an overflowed set -> R3D_ERR_NOMEM as r3d_voxelset_codes reports it.  For r3d_octree.hip.
+int r3d_voxelset_sorted_codes_device(r3d_voxelset* vs, r3d_ctx** ctx, double* resolution, uint64_t** d_list_out, int64_t* n_out);
 
 // Device -> pageable host memory through pinned staging chunks (r3d_hostpipe.hip); synchronous.
 int r3d_download_pageable(r3d_ctx* ctx, void* h_dst, const void* d_src, size_t bytes);

@@ -1457,11 +1457,10 @@ int build_bt(const uint64_t* codes, int64_t n, double res, std::string* out, int
     }
   }
   char head[256];
-  snprintf(head, sizeof(head),
-           "# Octomap OcTree binary file\n# (feel free to add / change comments, but leave the first line as it is!)\n#\n"
-           "id OcTree\nsize %lld\nres %g\ndata\n",
-           (long long)w.n_nodes, res);
-  *out = std::string(head) + w.body;
+  size_t head_bytes = 0;
+  int rc = r3d_octree_bt_header(w.n_nodes, res, head, sizeof(head), &head_bytes);   // the one place the header is spelled (r3d_octree.hip)
+  if (rc) return rc;
+  *out = std::string(head, head_bytes) + w.body;
   *n_nodes = w.n_nodes;
   return R3D_OK;
 }
@@ -1769,6 +1768,15 @@ static int codes_to_device_list(r3d_voxelset* vs, uint64_t** d_list_out, int64_t
 }
 
 }  // extern "C"
+
+int r3d_voxelset_sorted_codes_device(r3d_voxelset* vs, r3d_ctx** ctx, double* resolution, uint64_t** d_list_out, int64_t* n_out) {
+  R3D_REQUIRE(vs != nullptr, "voxel set is NULL");
+  int rc = r3d_ctx_enter(vs->ctx);
+  if (rc) return rc;
+  *ctx = vs->ctx;
+  *resolution = vs->res;
+  return codes_to_device_list(vs, d_list_out, n_out);
+}
 
 int r3d_voxel_table_sorted_codes(r3d_ctx* ctx, const uint64_t* d_table, uint64_t capacity, unsigned long long* d_counters,
                                  int64_t n, uint64_t** d_list_out) {

@@ -4,7 +4,8 @@ through the third-party python-octomap binding (octomap/txt_transfer_octomap.py:
     tree = octomap.OcTree(0.1); tree.updateNode(xyz, True) ...; tree.updateInnerOccupancy(); tree.writeBinary(path)
 
 `OcTree` below offers that same small surface; points are buffered on the host and inserted in bulk by the
-HIP hash-set kernel, the pruned octree is serialised by the library's host code.
+HIP hash-set kernel, and the pruned octree is serialised on the device from the set's sorted codes (csrc/r3d_octree.hip): only the
+finished records cross PCIe.  `format_bt(codes)` is the host serialiser for codes that are already in host memory (no GPU needed).
 """
 import collections
 import ctypes as C
@@ -84,21 +85,64 @@ class VoxelSet:
         L.check(self.ctx.lib.r3d_voxelset_codes(self.handle, out.ctypes.data, out.shape[0], C.byref(n)))
         return out
 
+    def format_bt(self):
+        """(.bt bytes, node count) of the set, serialised on the device; equal to format_bt(self.codes(), resolution)."""
+        lib = self.ctx.lib
+        n, nodes = C.c_size_t(), C.c_int64()
+        L.check(lib.r3d_voxelset_format_bt(self.handle, None, 0, C.byref(n), C.byref(nodes)))
+        buf = C.create_string_buffer(max(n.value, 1))
+        L.check(lib.r3d_voxelset_format_bt(self.handle, buf, n.value, C.byref(n), C.byref(nodes)))
+        return buf.raw[:n.value], nodes.value
 
-def voxelize(xyz, resolution=0.1, ctx=None):
-    """Ascending Morton codes of the voxels hit by an [N,3] cloud; the table is sized from N and regrown on overflow."""
+    def write_bt(self, path):
+        """The set as an OctoMap .bt file, records streamed from the device into the file; returns the node count."""
+        nodes = C.c_int64()
+        L.check(self.ctx.lib.r3d_voxelset_write_bt(self.handle, os.fsencode(path), C.byref(nodes)))
+        return nodes.value
+
+
+def octree_records_device(d_codes, n, ctx=None):
+    """(uint16 records, node count) of the pruned octree over n ascending unique Morton codes at device pointer d_codes."""
+    ctx = ctx or default_context()
+    n_rec, nodes = C.c_int64(), C.c_int64()
+    L.check(ctx.lib.r3d_octree_records_device(ctx.handle, d_codes, int(n), None, 0, C.byref(n_rec), C.byref(nodes)))
+    if n_rec.value == 0:
+        return np.zeros(0, np.uint16), nodes.value
+    d_rec = ctx.alloc(n_rec.value * 2)
+    try:
+        L.check(ctx.lib.r3d_octree_records_device(ctx.handle, d_codes, int(n), d_rec.ptr, n_rec.value, C.byref(n_rec),
+                                                  C.byref(nodes)))
+        return d_rec.download(np.uint16, n_rec.value), nodes.value
+    finally:
+        d_rec.free()
+
+
+def _voxelize_set(xyz, resolution=0.1, ctx=None, capacity=None):
+    """(VoxelSet holding the voxels hit by an [N,3] cloud, its stats); the table is sized from N (or starts at `capacity`
+    slots) and is regrown on overflow."""
     xyz = np.ascontiguousarray(xyz, dtype=np.float32)
-    cap = max(1 << 16, 2 * xyz.shape[0])
+    cap = int(capacity) if capacity else max(1 << 16, 2 * xyz.shape[0])
     while True:
         vs = VoxelSet(resolution, cap, ctx)
         try:
             vs.insert(xyz)
             st = vs.stats()
-            if st["overflow"] == 0:
-                return vs.codes(), st
-        finally:
+        except Exception:
             vs.close()
+            raise
+        if st["overflow"] == 0:
+            return vs, st
+        vs.close()
         cap *= 4
+
+
+def voxelize(xyz, resolution=0.1, ctx=None):
+    """Ascending Morton codes of the voxels hit by an [N,3] cloud; the table is sized from N and regrown on overflow."""
+    vs, st = _voxelize_set(xyz, resolution, ctx)
+    try:
+        return vs.codes(), st
+    finally:
+        vs.close()
 
 
 VOXELGRID_RGB = 1
@@ -228,45 +272,64 @@ def voxel_down_sample(xyz, voxel_size, rgba=None, ctx=None):
 class OcTree:
     """The slice of python-octomap's OcTree the reference scripts use."""
 
+    initial_capacity = None   # table slots of the first attempt (None: sized from the number of points)
+
     def __init__(self, resolution):
         self.resolution = float(resolution)
         self._pending = []
         self._blocks = []
-        self._codes = None
+        self._set = None      # the device set of everything inserted so far (None: stale or empty)
+        self._stats = None
+
+    def _stale(self):
+        if self._set is not None:
+            self._set.close()
+            self._set = None
+        self._stats = None
 
     def updateNode(self, point, occupied=True):
         if not occupied:
             raise NotImplementedError("the reference only inserts hits (updateNode(point, True))")
         self._pending.append((float(point[0]), float(point[1]), float(point[2])))
-        self._codes = None
+        self._stale()
 
     def insertPointCloud(self, xyz):
         self._blocks.append(np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3))
-        self._codes = None
+        self._stale()
 
     def _flush(self):
-        if self._codes is None:
+        """The VoxelSet of the points inserted so far, kept on the device for size() / writeBinary(); None without points."""
+        if self._stats is None:
             blocks = list(self._blocks)
             if self._pending:
                 blocks.append(np.array(self._pending, dtype=np.float64).astype(np.float32))
             pts = np.concatenate(blocks) if blocks else np.zeros((0, 3), np.float32)
             if pts.shape[0]:
-                self._codes, self._stats = voxelize(pts, self.resolution)
+                self._set, self._stats = _voxelize_set(pts, self.resolution, capacity=self.initial_capacity)
             else:
-                self._codes, self._stats = np.zeros(0, np.uint64), {"voxels": 0, "ignored_points": 0, "overflow": 0}
-        return self._codes
+                self._stats = {"voxels": 0, "ignored_points": 0, "overflow": 0}
+        return self._set
 
     def updateInnerOccupancy(self):
         self._flush()
 
     def size(self):
-        return format_bt(self._flush(), self.resolution)[1]
+        vs = self._flush()
+        return vs.format_bt()[1] if vs is not None else 0
 
     def writeBinary(self, filename):
         if isinstance(filename, bytes):
             filename = filename.decode("utf-8")
-        codes = self._flush()
-        nodes = C.c_int64()
-        L.check(L.load().r3d_octree_write_bt(os.fsencode(filename), codes.ctypes.data, codes.shape[0], self.resolution,
-                                             C.byref(nodes)))
+        vs = self._flush()
+        if vs is not None:
+            vs.write_bt(filename)
+        else:   # nothing inserted: the header of an empty tree (no device needed)
+            with open(filename, "wb") as f:
+                f.write(format_bt(np.zeros(0, np.uint64), self.resolution)[0])
         return True
+
+    def __del__(self):
+        try:
+            self._stale()
+        except Exception:
+            pass

@@ -535,6 +535,26 @@ int r3d_octree_format_bt(const uint64_t* h_codes_sorted, int64_t n_codes, double
                          size_t buf_cap, size_t* n_bytes_out, int64_t* n_nodes_out);
 int r3d_octree_write_bt(const char* path, const uint64_t* h_codes_sorted, int64_t n_codes, double resolution,
                         int64_t* n_nodes_out);
+/* The same tree serialised ON THE DEVICE (csrc/r3d_octree.hip): the codes never visit host memory, only the finished records
+ * (2 bytes per inner node) cross PCIe.  Byte-identical to the two host calls above, which stay as the path without a GPU.
+ * r3d_octree_records_device: the uint16 records (depth-first pre-order; child c's field at bits 2c..2c+1: 00 absent, 10 leaf,
+ * 11 inner) of the pruned tree over n_codes ascending unique codes in HBM; *n_nodes_out = the header's `size` (inner nodes +
+ * the leaves the records name).  Two-call protocol (d_records_out == NULL: sizes only); synchronises the ctx stream once for
+ * the sizes, the records themselves are enqueued.  cap_records < records, codes that do not strictly ascend or pass 48 bits,
+ * output overlapping input -> R3D_ERR_INVALID, nothing written.  n_codes == 0 -> 0 records, 0 nodes.  No byte outside
+ * d_records_out[0 .. records) is touched, whatever its alignment.
+ * Tuning key "octree_timing" 1: HIP events around the four launches, read back (microseconds of the last call) through
+ * "octree_count_us", "octree_scan_us", "octree_own_us", "octree_link_us"; such a call waits for its launches. */
+int r3d_octree_records_device(r3d_ctx* ctx, const uint64_t* d_codes_sorted, int64_t n_codes, uint16_t* d_records_out,
+                              int64_t cap_records, int64_t* n_records_out, int64_t* n_nodes_out);
+/* The text header in front of the records, alone (host; h_buf == NULL only reports its length; it is not NUL-terminated).
+ * n_nodes < 0, resolution <= 0 or a buffer that is too small -> R3D_ERR_INVALID. */
+int r3d_octree_bt_header(int64_t n_nodes, double resolution, char* h_buf, size_t buf_cap, size_t* n_bytes_out);
+/* The whole chain on the set's context: sorted codes (device) -> records (device) -> the .bt bytes in a host buffer (two-call
+ * protocol like r3d_octree_format_bt) or, streamed by r3d_write_device_text_files, in a file.  An overflowed set is reported
+ * exactly as r3d_voxelset_codes reports it (R3D_ERR_NOMEM; no file is created). */
+int r3d_voxelset_format_bt(r3d_voxelset* vs, char* h_buf, size_t buf_cap, size_t* n_bytes_out, int64_t* n_nodes_out);
+int r3d_voxelset_write_bt(r3d_voxelset* vs, const char* path, int64_t* n_nodes_out);
 
 #ifdef __cplusplus
 }

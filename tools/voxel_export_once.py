@@ -1,5 +1,11 @@
-"""The f2 export chain on the GPU box: insert -> ascending Morton codes in host memory -> OctoMap .bt, timed stage by stage.
-usage: python tools/voxel_export_once.py [frames]   (C2-like random cloud: ~1 voxel per point, the worst case for every stage)"""
+"""The f2 export chain on the GPU box, old and new side by side in one process, timed stage by stage:
+  host chain    insert -> ascending Morton codes in host memory (codes()) -> r3d_octree_write_bt (host threads) -> file
+  device chain  insert -> VoxelSet.write_bt: sorted codes stay in HBM -> records on the GPU (HIP events around the four launches)
+                -> streamed into the file
+The two files must be equal.  usage: python tools/voxel_export_once.py [frames] [reps] [scan] [--json FILE]
+(default: C2-like random cloud, ~1 voxel per point, the worst case for every stage; `scan`: wavy surfaces under random poses at
+0.02 m, several points per voxel)"""
+import json
 import importlib
 import os
 import sys
@@ -15,27 +21,88 @@ V = importlib.import_module("3d_reconstruction_system_amd.voxelmap")
 import ctypes as C
 L = importlib.import_module("3d_reconstruction_system_amd._lib")
 
-frames = int(sys.argv[1]) if len(sys.argv) > 1 else 100
-H, W = 384, 1280
+args = [a for a in sys.argv[1:] if not a.startswith("--")]
+json_path = sys.argv[sys.argv.index("--json") + 1] if "--json" in sys.argv else None
+if json_path:
+    args.remove(json_path)
+scan = "scan" in args
+args = [a for a in args if a != "scan"]
+frames = int(args[0]) if len(args) > 0 else (32 if scan else 100)
+reps = int(args[1]) if len(args) > 1 else 5
 ctx = R.Context(0)
-rng = np.random.default_rng(1234)
-depth = rng.integers(1, 256, (frames, H, W), dtype=np.uint8)
+if scan:
+    H, W, res, cap = 1080, 1920, 0.02, 1 << 26
+    rng = np.random.default_rng(555)
+    jj, ii = np.mgrid[0:H, 0:W]
+    depth = np.stack([8.0 + 3.0 * np.sin(ii / (90.0 + 7 * (k % 8))) * np.cos(jj / (70.0 + 5 * (k % 8))) + 0.02 * rng.random((H, W))
+                      for k in range(frames)]).astype(np.float32)
+    intr = (960.0, 960.0, 959.5, 539.5)
+else:
+    H, W, res, cap = 384, 1280, 0.1, 1 << 27
+    rng = np.random.default_rng(1234)
+    depth = rng.integers(1, 256, (frames, H, W), dtype=np.uint8)
+    intr = R.REF_INTRINSICS
 q = rng.normal(size=(frames, 4))
 t = rng.normal(size=(frames, 3)) * 10
-world = R.fuse_frames(depth, q, t, out_dtype=np.float32, ctx=ctx)
-n = world.shape[0]
-for rep in range(3):
-    vs = V.VoxelSet(0.1, 1 << 27, ctx)
-    t0 = time.perf_counter(); vs.insert(world); st = vs.stats(); t1 = time.perf_counter()
-    codes = vs.codes(); t2 = time.perf_counter()
-    vs.close()
-    td = tempfile.mkdtemp(dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
-    p = os.path.join(td, "m.bt")
+n = frames * H * W
+cam = ctx.camera(H, W, *intr)
+tab = R.pose_table(q, t)
+d_depth, d_pose, d_xyz = ctx.alloc(depth.nbytes).upload(depth), ctx.alloc(tab.nbytes).upload(tab), ctx.alloc(n * 12)
+R.fuse_frames_device(ctx, cam, d_depth.ptr, depth.dtype.type, frames, d_pose.ptr, d_xyz.ptr, np.float32)
+td = tempfile.mkdtemp(dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
+p_old, p_new = os.path.join(td, "host.bt"), os.path.join(td, "device.bt")
+KEYS = ("octree_count_us", "octree_scan_us", "octree_own_us", "octree_link_us")
+rows = []
+vs = V.VoxelSet(res, cap, ctx)
+vs.insert_device(d_xyz.ptr, n)
+st = vs.stats()
+assert st["overflow"] == 0
+for rep in range(reps + 1):   # old and new alternate; the first pair warms up (allocations, page cache) and is not reported
+    row = {}
+    ctx.sync()
+    t0 = time.perf_counter()
+    codes = vs.codes()
+    t1 = time.perf_counter()
     nodes = C.c_int64()
-    t3 = time.perf_counter()
-    L.check(ctx.lib.r3d_octree_write_bt(os.fsencode(p), codes.ctypes.data, codes.shape[0], C.c_double(0.1), C.byref(nodes)))
-    t4 = time.perf_counter()
-    size = os.path.getsize(p)
-    os.remove(p); os.rmdir(td)
-    print("%d points -> %d voxels: insert from host memory (H2D incl.) %.1f ms | codes() to host, sorted %.1f ms | .bt (%d nodes, %.1f MB) %.0f ms"
-          % (n, codes.shape[0], (t1 - t0) * 1e3, (t2 - t1) * 1e3, nodes.value, size / 1e6, (t4 - t3) * 1e3))
+    L.check(ctx.lib.r3d_octree_write_bt(os.fsencode(p_old), codes.ctypes.data, codes.shape[0], C.c_double(res), C.byref(nodes)))
+    t2 = time.perf_counter()
+    row["host_codes_ms"], row["host_build_write_ms"], row["host_chain_ms"] = (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t2 - t0) * 1e3
+    ctx.set_tuning("octree_timing", 0)
+    ctx.sync()
+    t0 = time.perf_counter()
+    nodes_new = vs.write_bt(p_new)
+    t1 = time.perf_counter()
+    row["device_chain_ms"] = (t1 - t0) * 1e3
+    ctx.set_tuning("octree_timing", 1)        # a second, instrumented run: the four launches alone
+    vs.write_bt(p_new)
+    ctx.set_tuning("octree_timing", 0)
+    for k in KEYS:
+        row[k[7:-3] + "_ms"] = ctx.get_tuning(k) / 1e3
+    row["passes_ms"] = sum(row[k[7:-3] + "_ms"] for k in KEYS)
+    assert nodes_new == nodes.value and open(p_old, "rb").read() == open(p_new, "rb").read(), "the two chains disagree"
+    if rep:
+        rows.append(row)
+size = os.path.getsize(p_new)
+os.remove(p_old); os.remove(p_new); os.rmdir(td)
+vs.close()
+
+
+def stat(key):
+    v = sorted(r[key] for r in rows)
+    return {"median": round(float(np.median(v)), 3), "min": round(v[0], 3), "max": round(v[-1], 3)}
+
+
+summary = {"cloud": "scan" if scan else "c2_worst_case", "points": n, "voxels": int(codes.shape[0]), "nodes": int(nodes.value),
+           "file_bytes": size, "reps": len(rows), "files_equal": True}
+for key in rows[0]:
+    summary[key] = stat(key)
+summary["serialise_speedup_median"] = round(summary["host_build_write_ms"]["median"] / max(summary["passes_ms"]["median"], 1e-6), 1)
+summary["chain_speedup_median"] = round(summary["host_chain_ms"]["median"] / summary["device_chain_ms"]["median"], 2)
+print("%d points -> %d voxels, %d nodes, %.1f MB, %d repetitions (median [min .. max] ms)" % (n, codes.shape[0], nodes.value, size / 1e6, len(rows)))
+for key in rows[0]:
+    print("  %-22s %10.3f [%.3f .. %.3f]" % (key[:-3], summary[key]["median"], summary[key]["min"], summary[key]["max"]))
+print("  host build + write() / device passes = %.1f x; file to file %.2f x" % (summary["serialise_speedup_median"], summary["chain_speedup_median"]))
+print(json.dumps(summary))
+if json_path:
+    with open(json_path, "a") as f:
+        f.write(json.dumps(summary) + "\n")
