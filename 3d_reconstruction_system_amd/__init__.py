@@ -22,6 +22,8 @@ from .poses import (scipy_transfer, get_r, pose_table, pose_to_T, read_pose_file
 from .voxelmap import VoxelGrid, DownSampled, voxel_down_sample  # noqa: F401
 from .outliers import (knn, remove_statistical_outlier, remove_radius_outlier, StatisticalOutliers,  # noqa: F401
                        RadiusOutliers)
+from .normals import (Normals, estimate_normals, estimate_normals_device, estimate_covariances,  # noqa: F401
+                      fused_viewpoints)
 from . import cloud_io, device_text  # noqa: F401
 
 __version__ = "0.2.0"

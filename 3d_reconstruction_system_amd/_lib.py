@@ -154,6 +154,7 @@ SIGNATURES = {
     "r3d_nn_index_knn_self": (_i, [_vp, _i, _vp, _vp]),
     "r3d_outlier_statistical": (_i, [_vp, _i, _d, _vp, _vp, _vp, _vp]),
     "r3d_outlier_radius": (_i, [_vp, _d, _i64, _vp, _vp, _vp]),
+    "r3d_normals_knn": (_i, [_vp, _i, _d, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "r3d_select_rows": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "r3d_nn_index_knn_stats": (_i, [_vp, _vp]),
     "r3d_sort_u64": (_i, [_vp, _vp, _i64, _i]),

@@ -394,6 +394,70 @@ def write_ply_rgb(path, xyz, rgb):
                                   xyz.shape[0]))
 
 
+def write_ply_normals(path, xyz, normals, rgb=None):
+    """Binary little-endian PLY with per-vertex normals: float x y z nx ny nz (+ uchar red green blue when rgb [N,3] uint8 is
+    given) -- what MeshLab's shading and surface reconstruction read.  read_ply_normals reads it back."""
+    xyz = np.ascontiguousarray(xyz, dtype='<f4')
+    normals = np.ascontiguousarray(normals, dtype='<f4')
+    if xyz.ndim != 2 or xyz.shape[1] != 3:
+        raise ValueError("cloud must be [N,3]")
+    if normals.shape != xyz.shape:
+        raise ValueError("normals must be [N,3] like the cloud, got %r for %r" % (normals.shape, xyz.shape))
+    fields = [('x', '<f4'), ('y', '<f4'), ('z', '<f4'), ('nx', '<f4'), ('ny', '<f4'), ('nz', '<f4')]
+    if rgb is not None:
+        rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+        if rgb.shape != xyz.shape:
+            raise ValueError("rgb must be [N,3] uint8 like the cloud, got %r" % (rgb.shape,))
+        fields += [('red', 'u1'), ('green', 'u1'), ('blue', 'u1')]
+    rows = np.empty(xyz.shape[0], dtype=np.dtype(fields))
+    for a, name in enumerate(('x', 'y', 'z')):
+        rows[name] = xyz[:, a]
+        rows['n' + name] = normals[:, a]
+    if rgb is not None:
+        for a, name in enumerate(('red', 'green', 'blue')):
+            rows[name] = rgb[:, a]
+    head = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % xyz.shape[0]
+    head += "".join("property %s %s\n" % ("uchar" if t == 'u1' else "float", name) for name, t in fields) + "end_header\n"
+    with open(path, 'wb') as f:
+        f.write(head.encode('ascii'))
+        f.write(rows.tobytes())
+
+
+def read_ply_normals(path):
+    """(xyz [N,3] float32, normals [N,3] float32) of a binary little-endian PLY whose vertex properties start with float
+    x y z nx ny nz (write_ply_normals' layout, with or without its colour bytes)."""
+    with open(path, 'rb') as f:
+        data = f.read()
+    end = data.find(b'end_header\n')
+    if end < 0 or not data.startswith(b'ply'):
+        raise ValueError("%s: not a PLY file" % path)
+    lines = data[:end].decode('ascii', errors='replace').split('\n')
+    if not any(s.strip() == 'format binary_little_endian 1.0' for s in lines):
+        raise ValueError("%s: not a binary little-endian PLY" % path)
+    n, props, in_vertex = None, [], False
+    sizes = {'float': 4, 'float32': 4, 'uchar': 1, 'uint8': 1, 'double': 8, 'float64': 8, 'int': 4, 'uint': 4, 'short': 2,
+             'ushort': 2, 'char': 1}
+    for s in lines:
+        w = s.split()
+        if w[:1] == ['element']:
+            in_vertex = w[1] == 'vertex'
+            if in_vertex:
+                n = int(w[2])
+        elif w[:1] == ['property'] and in_vertex:
+            if len(w) != 3 or w[1] not in sizes:
+                raise ValueError("%s: unsupported vertex property %r" % (path, s))
+            props.append((w[2], w[1]))
+    if n is None or [p for p in props[:6]] != [(name, 'float') for name in ('x', 'y', 'z', 'nx', 'ny', 'nz')]:
+        raise ValueError("%s: vertex properties must start with float x y z nx ny nz" % path)
+    stride = sum(sizes[t] for _, t in props)
+    start = end + len(b'end_header\n')
+    if len(data) - start < n * stride:
+        raise ValueError("%s: %d vertices of %d bytes announced, file is too short" % (path, n, stride))
+    rows = np.frombuffer(data, dtype=np.uint8, count=n * stride, offset=start).reshape(n, stride)
+    six = np.ascontiguousarray(rows[:, :24]).view('<f4').reshape(n, 6).astype(np.float32)
+    return np.ascontiguousarray(six[:, :3]), np.ascontiguousarray(six[:, 3:])
+
+
 def _parse_rows_native(buf, offset, separator):
     """[N,3] float64 from the text in `buf[offset:]` by the library's threaded parser, or None when a line is not plain
     'x<sep>y<sep>z[...]' in the subset std::from_chars shares with float() -- the caller then parses it Python's way."""

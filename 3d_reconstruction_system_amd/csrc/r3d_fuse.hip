@@ -35,6 +35,7 @@
 #include <type_traits>
 
 #include "r3d_internal.h"
+#include "r3d_magic_div.h"
 #include "r3d_voxel_dev.h"
 
 namespace {
@@ -59,9 +60,8 @@ struct FuseDims {
   uint32_t depth_vec_ok;    // raster: every whole tile starts 4-byte aligned (hw * sizeof(element) % 4 == 0, aligned base)
 };
 
-__device__ __forceinline__ uint32_t magic_div(uint32_t x, uint32_t magic, uint32_t shift) {
-  return (uint32_t)(((uint64_t)x * magic) >> shift);
-}
+using r3d_magic::magic_div;
+using r3d_magic::make_magic;
 
 struct Pose {
   double r[9];
@@ -656,16 +656,6 @@ void launch_voxel(const FusePtrs& p, const FuseDims& dm, const VoxelView& vv, in
     case R3D_DEPTH_U16: launch_voxel_typed<uint16_t>(p, dm, vv, with_pose, blocks, s); break;
     default: launch_voxel_typed<float>(p, dm, vv, with_pose, blocks, s); break;
   }
-}
-
-// Magic number for floor(x / d), exact for every x < 2^31 and d >= 1 (round-up method):
-//   s = ceil(log2 d), m = floor(2^(31+s) / d) + 1 (< 2^32), x / d = (x * m) >> (31 + s).
-// m*d - 2^(31+s) lies in (0, d] <= 2^s, which is the exactness condition for 31-bit x.
-void make_magic(uint32_t d, uint32_t* magic, uint32_t* shift) {
-  uint32_t s = 0;
-  while (((uint64_t)1 << s) < d) ++s;
-  *magic = (uint32_t)((((uint64_t)1 << (31 + s)) / d) + 1);
-  *shift = 31 + s;
 }
 
 int fuse_common(r3d_ctx* ctx, const r3d_camera* cam, const void* d_depth, int depth_dtype, int n_frames,

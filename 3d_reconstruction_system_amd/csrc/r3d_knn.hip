@@ -15,6 +15,9 @@
 //                 instead of O(D^2).  Writes m_i and one (sum m, V) row per workgroup; the lists never leave registers.
 //         kRadius no list: the count of d2 <= r2, self included; the bound is r2 and the workgroup stops once every lane has
 //                 min_points + 1.
+//         kNormals kList's search unchanged; the epilogue walks the slots in order, gathers each neighbour from the original-order
+//                 cloud, accumulates the nine fp64 sums about the query point, solves the 3x3 covariance for its smallest
+//                 eigenvector (cyclic Jacobi, fp64) and orients it: 12 to 44 bytes per point leave, the lists never do.
 //       Unused front slots hold a sentinel below every real entry, so the last slot is always the k-th real one.
 //   sor_mean / sor_dev / sor_threshold / sor_keep: fixed-order fp64 reductions (one row per workgroup, one-wave folds) for
 //       mu, sigma and T, then the mask -- no float atomics, the same bits on every run.
@@ -23,6 +26,7 @@
 #include <cmath>
 
 #include "r3d_internal.h"
+#include "r3d_magic_div.h"
 #include "r3d_nnindex_dev.h"
 #include "r3d_sort_dev.h"
 
@@ -38,7 +42,7 @@ using r3d_nn::P3;
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-enum Mode { kList = 0, kScore = 1, kRadius = 2 };
+enum Mode { kList = 0, kScore = 1, kRadius = 2, kNormals = 3 };
 
 constexpr uint64_t kKeyTail = 0x7f80000000000000ull;  // key of (+inf, row 0): above every candidate, whose d2 is finite
 constexpr int kReduceBlocks = 1024;                    // workgroups of the grid-stride passes (one row / atomic each)
@@ -49,15 +53,23 @@ struct KnnArgs {
   const float *tile_box, *sub_box, *group_box, *super_box;
   int k;
   float r2;               // kRadius: candidates with d2 <= r2 count (FLT_MAX when radius^2 overflows: finite d2 only)
+                          // kNormals: list entries with d2 <= r2 are members (+inf: no radius)
   uint64_t min_points;    // kRadius: min(min_points, n) -- nobody reaches more than n - 1
   uint32_t* idx_out;      // kList: [n][k]
   float* d2_out;          // kList: [n][k] or NULL
   double* score_out;      // kScore: [n] m_i
   double* partials;       // kScore: [blocks][2] (sum of finite m, V)
   uint8_t* keep_out;      // kRadius
-  uint32_t* count_out;    // kRadius: min(c, min_points) or NULL
+  uint32_t* count_out;    // kRadius: min(c, min_points) or NULL; kNormals: c_i or NULL
   unsigned long long* n_kept;   // kRadius
   unsigned long long* groups;   // 32-target groups evaluated, summed over waves
+  // kNormals (behind everything else: the other modes' kernel-argument offsets stay where they were)
+  const float* tgt;       // [n][3] original order: the neighbour gathers
+  float* nrm_out;         // [n][3]
+  float* curv_out;        // [n] or NULL
+  double* cov_out;        // [n][6] or NULL
+  const double* views;    // [n_views][3] or NULL (orient by the largest component)
+  uint32_t n_views, v_magic, v_shift;   // row i belongs to view min(i / points_per_view, n_views - 1): make_magic(points_per_view)
 };
 
 // strict lower bound of the squared distance from a point to a box (lo xyz at b[0..2], hi xyz at b[3..5]); an empty box
@@ -95,14 +107,127 @@ __device__ __forceinline__ double block_sum_f64(double v, double* sh) {
   return t;
 }
 
+// ---- kNormals' epilogue ------------------------------------------------------------------------------------------------------
+// One Jacobi rotation of the symmetric 3x3 (diagonal app, aqq; off-diagonal apq; arp, arq the third row's entries) and of the
+// eigenvector columns p, q; returns false when apq is already negligible next to the diagonal (2^-64 of it).
+__device__ __forceinline__ bool jacobi_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p,
+                                              double& v0q, double& v1p, double& v1q, double& v2p, double& v2q) {
+  if (!(fabs(apq) > 5.421010862427522e-20 * (fabs(app) + fabs(aqq)))) return false;
+  const double theta = (aqq - app) / (2.0 * apq);
+  const double at = fabs(theta);
+  double t = at > 1e150 ? 0.5 / at : 1.0 / (at + sqrt(at * at + 1.0));
+  t = theta < 0.0 ? -t : t;
+  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c, tau = s / (1.0 + c);
+  app -= t * apq;
+  aqq += t * apq;
+  apq = 0.0;
+  const double rp = arp, rq = arq;
+  arp = rp - s * (rq + tau * rp);
+  arq = rq + s * (rp - tau * rq);
+  double p, q;
+  p = v0p, q = v0q, v0p = p - s * (q + tau * p), v0q = q + s * (p - tau * q);
+  p = v1p, q = v1q, v1p = p - s * (q + tau * p), v1q = q + s * (p - tau * q);
+  p = v2p, q = v2q, v2p = p - s * (q + tau * p), v2q = q + s * (p - tau * q);
+  return true;
+}
+
+// Eigenvalues l[0] <= l[1] <= l[2] of the symmetric C (xx, xy, xz, yy, yz, zz) and the unit eigenvector of l[0] (the lowest
+// column on ties), by cyclic Jacobi sweeps in fp64.  Scalars only: nothing here is indexed at run time.
+__device__ __forceinline__ void sym3_smallest(const double C[6], double l[3], double n[3]) {
+  double a00 = C[0], a01 = C[1], a02 = C[2], a11 = C[3], a12 = C[4], a22 = C[5];
+  double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
+  for (int sweep = 0; sweep < 16; ++sweep) {
+    bool any = jacobi_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);
+    any |= jacobi_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);
+    any |= jacobi_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);
+    if (!any) break;
+  }
+  const bool c0 = a00 <= a11 && a00 <= a22, c1 = !c0 && a11 <= a22;
+  l[0] = fmin(a00, fmin(a11, a22));
+  l[2] = fmax(a00, fmax(a11, a22));
+  l[1] = fmax(fmin(a00, a11), fmin(fmax(a00, a11), a22));
+  const double x = c0 ? v00 : c1 ? v01 : v02, y = c0 ? v10 : c1 ? v11 : v12, z = c0 ? v20 : c1 ? v21 : v22;
+  const double len = sqrt(x * x + y * y + z * z);
+  n[0] = x / len;
+  n[1] = y / len;
+  n[2] = z / len;
+}
+
+// The lane's point (row `me`, coordinates sx sy sz, act = all finite) and its finished list -> count, covariance, curvature
+// and oriented normal (include/r3d.h: r3d_normals_knn).  A slot that is no member gathers the lane's own row instead: its
+// e = 0 adds +0.0 to sums that are never -0.0, which changes no bit, and the K loads need no branch between them.
+template <int K>
+__device__ __forceinline__ void normals_epilogue(const KnnArgs& a, const uint64_t (&kl)[K], int front, bool act, uint32_t me,
+                                                 float sx, float sy, float sz) {
+  const P3* __restrict__ tgt = reinterpret_cast<const P3*>(a.tgt);
+  const double px = (double)sx, py = (double)sy, pz = (double)sz;
+  double s1x = 0.0, s1y = 0.0, s1z = 0.0, sxx = 0.0, sxy = 0.0, sxz = 0.0, syy = 0.0, syz = 0.0, szz = 0.0;
+  uint32_t c = 0;
+#pragma unroll
+  for (int t = 0; t < K; ++t) {
+    const uint64_t key = kl[t];
+    const bool in = act && t >= front && key < kKeyTail && __uint_as_float((uint32_t)(key >> 32)) <= a.r2;
+    const P3 q = tgt[in ? (uint32_t)key : me];
+    c += in ? 1u : 0u;
+    const double ex = in ? (double)q.x - px : 0.0, ey = in ? (double)q.y - py : 0.0, ez = in ? (double)q.z - pz : 0.0;
+    s1x += ex;
+    s1y += ey;
+    s1z += ez;
+    sxx += ex * ex;
+    sxy += ex * ey;
+    sxz += ex * ez;
+    syy += ey * ey;
+    syz += ey * ez;
+    szz += ez * ez;
+  }
+  const double m = (double)(c + 1u);   // the point itself is a member with e = 0
+  double C[6] = {(sxx - s1x * s1x / m) / m, (sxy - s1x * s1y / m) / m, (sxz - s1x * s1z / m) / m,
+                 (syy - s1y * s1y / m) / m, (syz - s1y * s1z / m) / m, (szz - s1z * s1z / m) / m};
+  double l[3] = {0.0, 0.0, 0.0}, nv[3] = {0.0, 0.0, 0.0};
+  bool plane = act && c >= 2u;
+  if (plane) {
+    sym3_smallest(C, l, nv);
+    plane = l[1] > 0.0;
+  }
+  float curv = 0.f;
+  if (plane) {
+    bool flip;
+    if (a.views) {
+      const uint32_t v = min(r3d_magic::magic_div(me, a.v_magic, a.v_shift), a.n_views - 1u);
+      const double* __restrict__ vp = a.views + (size_t)v * 3;
+      flip = nv[0] * (vp[0] - px) + nv[1] * (vp[1] - py) + nv[2] * (vp[2] - pz) < 0.0;
+    } else {
+      const double ax = fabs(nv[0]), ay = fabs(nv[1]), az = fabs(nv[2]);
+      flip = (ax >= ay && ax >= az ? nv[0] : ay >= az ? nv[1] : nv[2]) < 0.0;
+    }
+    if (flip) nv[0] = -nv[0], nv[1] = -nv[1], nv[2] = -nv[2];
+    const double l0 = fmax(l[0], 0.0), sum = l0 + l[1] + l[2];
+    curv = sum > 0.0 ? (float)(l0 / sum) : 0.f;
+  } else {
+    nv[0] = nv[1] = nv[2] = 0.0;
+#pragma unroll
+    for (int e = 0; e < 6; ++e) C[e] = 0.0;
+  }
+  P3 out;
+  out.x = (float)nv[0], out.y = (float)nv[1], out.z = (float)nv[2];
+  reinterpret_cast<P3*>(a.nrm_out)[me] = out;
+  if (a.curv_out) a.curv_out[me] = curv;
+  if (a.count_out) a.count_out[me] = c;
+  if (a.cov_out) {
+#pragma unroll
+    for (int e = 0; e < 6; ++e) a.cov_out[(size_t)me * 6 + e] = C[e];
+  }
+}
+
 template <int MODE, int K>
 __global__ __launch_bounds__(kThreads) void knn_kernel(const KnnArgs a) {
-  constexpr int NS = MODE == kList ? K : MODE == kScore ? K + 1 : 1;   // list slots
+  constexpr bool LIST = MODE == kList || MODE == kNormals;               // exact (d2, j) lists in registers
+  constexpr int NS = LIST ? K : MODE == kScore ? K + 1 : 1;   // list slots
   constexpr int kUnrollQ = MODE == kRadius ? kGroup / 4 : 1;
   __shared__ __attribute__((aligned(16))) float tx[kTile];
   __shared__ __attribute__((aligned(16))) float ty[kTile];
   __shared__ __attribute__((aligned(16))) float tz[kTile];
-  __shared__ __attribute__((aligned(16))) uint32_t tw[MODE == kList ? kTile : 4];
+  __shared__ __attribute__((aligned(16))) uint32_t tw[LIST ? kTile : 4];
   __shared__ __attribute__((aligned(16))) float gbox[kTile / kGroup][8];  // lo xyz, hi xyz of every 32-target group (+ pad)
 
   const uint32_t tid = threadIdx.x;
@@ -115,13 +240,13 @@ __global__ __launch_bounds__(kThreads) void knn_kernel(const KnnArgs a) {
   const bool act = ok && (sx - sx == 0.f) && (sy - sy == 0.f) && (sz - sz == 0.f);
 
   float fl[MODE == kScore ? NS : 1];
-  uint64_t kl[MODE == kList ? NS : 1];
+  uint64_t kl[LIST ? NS : 1];
   uint32_t cnt = 0;
   const int front = K - a.k;   // sentinel slots in front of the k (kScore: k + 1) real ones
 #pragma unroll
   for (int t = 0; t < NS; ++t) {
     if (MODE == kScore) fl[t] = t < front ? -1.f : INFINITY;
-    if (MODE == kList) kl[t] = t < front ? 0ull : kKeyTail;
+    if (LIST) kl[t] = t < front ? 0ull : kKeyTail;
   }
   (void)fl;
   (void)kl;
@@ -130,7 +255,7 @@ __global__ __launch_bounds__(kThreads) void knn_kernel(const KnnArgs a) {
   // may a box whose strict lower bound is lb still change this lane's answer?  (NaN bounds never allow a skip)
   auto wants = [&](float lb) -> bool {
     if (!act) return false;
-    if (MODE == kList) return !(lb > __uint_as_float((uint32_t)(kl[NS - 1] >> 32)));
+    if (LIST) return !(lb > __uint_as_float((uint32_t)(kl[NS - 1] >> 32)));
     if (MODE == kScore) return !(lb >= fl[NS - 1]);
     return !(lb > a.r2) && (uint64_t)cnt <= a.min_points;   // cnt holds self: min_points + 1 reached = done
   };
@@ -153,7 +278,7 @@ __global__ __launch_bounds__(kThreads) void knn_kernel(const KnnArgs a) {
       for (uint32_t k = tid; k < kTile; k += kThreads) {
         const float4 q = a.tgt4[t_base + k];
         tx[k] = q.x; ty[k] = q.y; tz[k] = q.z;
-        if (MODE == kList) tw[k] = __float_as_uint(q.w);
+        if (LIST) tw[k] = __float_as_uint(q.w);
       }
       if (tid < (kTile / kGroup) * 6) gbox[tid / 6][tid % 6] = a.group_box[tile * ((kTile / kGroup) * 6) + tid];
       __syncthreads();
@@ -234,6 +359,8 @@ __global__ __launch_bounds__(kThreads) void knn_kernel(const KnnArgs a) {
         }
       }
     }
+  } else if constexpr (MODE == kNormals) {
+    if (ok) normals_epilogue<K>(a, kl, front, act, me, sx, sy, sz);
   } else if (MODE == kScore) {
     // m_i = (sum of sqrt((double) d2) over the k real entries, ascending) / k; slot `front` is self's 0
     double m = INFINITY;
@@ -401,6 +528,7 @@ int knn_launch(r3d_nn_index* ix, KnnArgs& a) {
   a.groups = ix->d_knn_groups;
   R3D_HIP(hipMemsetAsync(ix->d_knn_groups, 0, sizeof(unsigned long long), ctx->stream));
   const dim3 grid((unsigned)(ix->n_tiles * (kTile / kThreads))), block(kThreads);
+  a.tgt = ix->d_tgt;
   if constexpr (MODE == kRadius) hipLaunchKernelGGL((knn_kernel<kRadius, 1>), grid, block, 0, ctx->stream, a);
   else if (a.k <= 8) hipLaunchKernelGGL((knn_kernel<MODE, 8>), grid, block, 0, ctx->stream, a);
   else if (a.k <= 16) hipLaunchKernelGGL((knn_kernel<MODE, 16>), grid, block, 0, ctx->stream, a);
@@ -430,6 +558,51 @@ int r3d_nn_index_knn_self(r3d_nn_index* ix, int k, uint32_t* d_idx_out, float* d
   a.idx_out = d_idx_out;
   a.d2_out = d_d2_out;
   return knn_launch<kList>(ix, a);
+}
+
+int r3d_normals_knn(r3d_nn_index* ix, int k, double radius, const double* h_viewpoints, int64_t n_views, int64_t points_per_view,
+                    float* d_normals_out, float* d_curvature_out, double* d_cov_out, uint32_t* d_count_out) {
+  R3D_REQUIRE(ix != nullptr, "nn index is NULL");
+  R3D_REQUIRE(k >= 3 && k <= 32, "k must be in [3, 32], got %d", k);
+  R3D_REQUIRE(!std::isnan(radius), "radius is NaN");
+  R3D_REQUIRE(n_views >= 0, "n_views must be >= 0, got %lld", (long long)n_views);
+  R3D_REQUIRE(n_views == 0 || (h_viewpoints != nullptr && points_per_view >= 1),
+              "n_views > 0 needs a viewpoint table and points_per_view >= 1");
+  R3D_REQUIRE(d_normals_out != nullptr, "d_normals_out is NULL");
+  const int64_t n = ix->n;
+  const bool divide = n_views > 1 && points_per_view < n;   // otherwise every row belongs to view 0
+  R3D_REQUIRE(!divide || n <= ((int64_t)1 << 31), "per-view orientation needs a cloud of at most 2^31 rows");
+  const struct {
+    const void* p;
+    size_t bytes;
+  } out[4] = {{d_normals_out, (size_t)n * 12}, {d_curvature_out, (size_t)n * 4}, {d_cov_out, (size_t)n * 48}, {d_count_out, (size_t)n * 4}};
+  for (int i = 0; i < 4; ++i) {
+    R3D_REQUIRE(!ranges_overlap(out[i].p, out[i].bytes, ix->d_tgt, (size_t)n * 12), "an output overlaps the index's cloud");
+    for (int j = i + 1; j < 4; ++j) R3D_REQUIRE(!ranges_overlap(out[i].p, out[i].bytes, out[j].p, out[j].bytes), "outputs overlap each other");
+  }
+  r3d_ctx* ctx = ix->ctx;
+  int rc = r3d_ctx_enter(ctx);
+  if (rc) return rc;
+  KnnArgs a = {};
+  if (n_views > 0) {
+    // at most a few thousand rows of 24 bytes: one upload per call into the library's own buffer
+    void* views = nullptr;
+    if ((rc = r3d_scratch(ctx, 5, (size_t)n_views * 24, &views))) return rc;
+    R3D_HIP(hipMemcpyAsync(views, h_viewpoints, (size_t)n_views * 24, hipMemcpyHostToDevice, ctx->stream));
+    a.views = static_cast<const double*>(views);
+    a.n_views = divide ? (uint32_t)std::min<int64_t>(n_views, n) : 1u;
+    r3d_magic::make_magic(divide ? (uint32_t)points_per_view : 1u, &a.v_magic, &a.v_shift);
+  }
+  for (int i = 0; i < 4; ++i)
+    if (out[i].p) r3d_wrote(ctx, out[i].p, out[i].bytes);
+  a.k = k;
+  const float r2 = (float)(radius * radius);
+  a.r2 = radius > 0.0 ? r2 : INFINITY;
+  a.nrm_out = d_normals_out;
+  a.curv_out = d_curvature_out;
+  a.cov_out = d_cov_out;
+  a.count_out = d_count_out;
+  return knn_launch<kNormals>(ix, a);
 }
 
 int r3d_outlier_statistical(r3d_nn_index* ix, int k, double std_ratio, uint8_t* d_keep_out, double* d_score_out,

@@ -135,6 +135,15 @@ class NNIndex:
         in the cloud's original row order, ascending (d2, row); missing neighbours are (0xffffffff, +inf).  Asynchronous."""
         L.check(self.ctx.lib.r3d_nn_index_knn_self(self.handle, int(k), d_idx_ptr, d_d2_ptr))
 
+    def normals_knn(self, k, radius, viewpoints, points_per_view, d_normals_ptr, d_curvature_ptr=None, d_cov_ptr=None,
+                    d_count_ptr=None):
+        """r3d_normals_knn: oriented normals [n][3] float32 of the indexed cloud from the covariance of every point's k (3..32)
+        nearest neighbours (radius <= 0: no cut); viewpoints: None or a C-contiguous [V,3] float64 array.  Optional curvature
+        [n] float32, covariance [n][6] float64, count [n] uint32.  Asynchronous."""
+        n_views = 0 if viewpoints is None else int(viewpoints.shape[0])
+        L.check(self.ctx.lib.r3d_normals_knn(self.handle, int(k), float(radius), viewpoints.ctypes.data if n_views else None,
+                                             n_views, int(points_per_view), d_normals_ptr, d_curvature_ptr, d_cov_ptr, d_count_ptr))
+
     def knn_pairs(self):
         """Pair evaluations (lane-pairs) of the last knn_self / outlier call on this index (synchronous)."""
         v = C.c_int64()
@@ -847,7 +856,8 @@ def icp_point_to_plane(src, tgt, tgt_shape=None, tgt_normals=None, init=None, ma
     Returns (T, info).
 
     tgt is ORGANISED: tgt_shape = (H, W), rows in gentxtcord's raster order (p2c:34-44); its normals come from the raster
-    neighbours on the GPU (or pass tgt_normals for an unorganised target).  Source rows at the camera origin (Z = 0 pixels, which
+    neighbours on the GPU.  An UNORGANISED target (fused, downsampled, filtered): tgt_shape=None and
+    tgt_normals=normals.estimate_normals(tgt, viewpoint=...).normals, from the k nearest neighbours.  Source rows at the camera origin (Z = 0 pixels, which
     the reference emits like any other) and non-finite rows are left out.
     init: 4x4 rough pose (e.g. the relative COLMAP pose with a guessed scale); None = identity.
     Every iteration (all on the GPU, no host round trip inside a block of `check_every`): exact nearest neighbours through the

@@ -522,6 +522,30 @@ int r3d_outlier_statistical(r3d_nn_index* index, int k, double std_ratio, uint8_
  * min(c_i, min_points) (saturated: the search stops early). */
 int r3d_outlier_radius(r3d_nn_index* index, double radius, int64_t min_points, uint8_t* d_keep_out, uint32_t* d_count_out,
                        int64_t* h_n_kept);
+/* Normals of the index's own cloud P (n rows, original order) from the covariance of each point's neighbourhood (3 <= k <= 32).
+ * Asynchronous on the ctx stream; deterministic (the same bits on every run and for every launch geometry).
+ * Neighbourhood: N_i = row i of r3d_nn_index_knn_self(index, k) -- the exact (d2, j) order, ties by row, tails dropped -- cut,
+ *   when radius > 0, at the first entry with d2 > (float)((double) radius * radius) (radius <= 0: no cut).  c_i = |N_i| goes to
+ *   d_count_out [n] u32.
+ * Covariance (fp64, no fused multiply-add, fixed order): e_j = (double) p_j - (double) p_i per component; S1 = sum e_j and
+ *   S2_ab = sum e_j,a * e_j,b for ab in xx, xy, xz, yy, yz, zz, both over N_i in list order starting from 0.0.  The point itself
+ *   is a member with e = 0, so m = c_i + 1 and C_ab = (S2_ab - S1_a * S1_b / m) / m, evaluated as written.  d_cov_out [n][6]
+ *   f64 = the six C_ab in that order.  Differences about the query point keep the sums small whatever the cloud's offset.
+ * Normal: the unit eigenvector of the smallest eigenvalue l0 <= l1 <= l2 of C (cyclic Jacobi rotations in fp64; of equal
+ *   eigenvalues the lowest axis), rounded once to f32 into d_normals_out [n][3].  d_curvature_out [n] f32 =
+ *   (float)(l0 / (l0 + l1 + l2)) with a rounding-negative l0 taken as 0 (surface variation; 0 when the sum is 0).
+ * Sign: with n_views > 0, row i belongs to view v = min(i / points_per_view, n_views - 1) (n_views = 1: one camera for the
+ *   whole cloud; n_views = F, points_per_view = H*W: an r3d_fuse_frames cloud and the frames' camera centres) and the normal is
+ *   negated iff n . (h_viewpoints[v] - p_i) < 0, in fp64 from the fp64 eigenvector.  n_views = 0: negated iff its component of
+ *   largest magnitude (lowest axis on ties) is negative.  The table (host, [n_views][3] f64) is copied before the call returns;
+ *   n_views > 1 with points_per_view < n needs n <= 2^31.
+ * No plane: the zero vector, curvature 0 and a zero covariance are written when p_i has a non-finite coordinate, when c_i < 2,
+ *   or when l1 <= 0 (all members on one line to the last bit, e.g. a cluster of identical points); c_i is written as it is.
+ * d_curvature_out, d_cov_out, d_count_out may be NULL.  k out of range, radius NaN, n_views < 0, n_views > 0 with a NULL table
+ *   or points_per_view < 1, NULL normals, outputs overlapping each other or the index's cloud -> R3D_ERR_INVALID, nothing written. */
+int r3d_normals_knn(r3d_nn_index* index, int k, double radius, const double* h_viewpoints, int64_t n_views,
+                    int64_t points_per_view, float* d_normals_out, float* d_curvature_out, double* d_cov_out,
+                    uint32_t* d_count_out);
 /* Order-preserving row selection (synchronises): the xyz rows i with d_keep[i] != 0, in their original order, into d_xyz_out
  * and (optional) their row numbers i into d_rows_out (u32); *h_n_out = rows kept.  The outputs need room for the kept rows
  * only; an output that overlaps an input or the other output -> R3D_ERR_INVALID. */
