@@ -158,6 +158,7 @@ SIGNATURES = {
     "r3d_select_rows": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "r3d_nn_index_knn_stats": (_i, [_vp, _vp]),
     "r3d_sort_u64": (_i, [_vp, _vp, _i64, _i]),
+    "r3d_sort_u64_bits": (_i, [_vp, _vp, _i64, _i, _i]),
     "r3d_octree_format_bt": (_i, [_vp, _i64, _d, _vp, _sz, _psz, _vp]),
     "r3d_octree_write_bt": (_i, [C.c_char_p, _vp, _i64, _d, _vp]),
     "r3d_octree_records_device": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp]),

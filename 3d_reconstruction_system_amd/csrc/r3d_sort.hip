@@ -163,6 +163,8 @@ __global__ __launch_bounds__(kThreads) void digit_scatter_kernel(const uint64_t*
 // The workspace of a sort of n keys (scratch slot 3): hist[bin][r3d_sort_stride(workgroups)] + the 256 bin totals.  A producer that writes the
 // keys tile by tile (kSortTile keys per workgroup, same tiling as the sort) can fill `hist` for the FIRST digit itself and
 // save the sort its first histogram pass (r3d_voxel.hip's key kernel does).
+// Limit: the bin totals and the tiles' prefixes are uint32, so one sort takes fewer than 2^32 keys; nothing in the library
+// reaches that size, and the check below (tiles < 2^31) does not enforce it.
 int r3d_radix_sort_workspace(r3d_ctx* ctx, int64_t n, uint32_t** hist_out, int* n_blocks_out) {
   const int64_t n_blocks64 = (n + kTile - 1) / kTile;
   R3D_REQUIRE(n_blocks64 < ((int64_t)1 << 31), "too many keys for one sort");
@@ -228,6 +230,19 @@ int r3d_sort_u64(r3d_ctx* ctx, uint64_t* d_keys, int64_t n_keys, int key_bits) {
   void* tmp = nullptr;
   if ((rc = r3d_scratch(ctx, 2, (size_t)n_keys * sizeof(uint64_t), &tmp))) return rc;
   return r3d_radix_sort_u64(ctx, d_keys, static_cast<uint64_t*>(tmp), n_keys, key_bits, 0);
+}
+
+// r3d_internal_api.h: the bit range of r3d_radix_sort_u64 as the NN index uses it, reachable for the tests
+int r3d_sort_u64_bits(r3d_ctx* ctx, uint64_t* d_keys, int64_t n_keys, int first_bit, int end_bit) {
+  int rc = r3d_ctx_enter(ctx);
+  if (rc) return rc;
+  R3D_REQUIRE(n_keys >= 0, "n_keys must be >= 0");
+  R3D_REQUIRE(end_bit >= 1 && end_bit <= 64, "end_bit must be in [1,64]");
+  if (n_keys <= 1) return R3D_OK;
+  R3D_REQUIRE(d_keys != nullptr, "NULL device pointer");
+  void* tmp = nullptr;
+  if ((rc = r3d_scratch(ctx, 2, (size_t)n_keys * sizeof(uint64_t), &tmp))) return rc;
+  return r3d_radix_sort_u64(ctx, d_keys, static_cast<uint64_t*>(tmp), n_keys, end_bit, first_bit);
 }
 
 }  // extern "C"

@@ -19,6 +19,11 @@ extern "C" {
 /* Self-test hook (no GPU needed): floor(x / d) computed with the host-made magic number the kernels use for
  * pixel -> (row, column) and tile -> (frame, tile) splits.  d >= 1, x < 2^31. */
 int r3d_selftest_magic_div(uint32_t d, uint32_t x, uint32_t* q_out);
+/* Test hook: r3d_sort_u64 restricted to a bit range, as the NN index sorts (Morton digits above a row number that already
+ * ascends).  In-place STABLE ascending sort of d_keys by their bits [first_bit, end_bit), the span rounded up to whole 8-bit
+ * digits counted from first_bit (bits >= 64 read as zero): keys that agree on those bits keep their input order.
+ * first_bit < 0 or >= end_bit counts as 0.  end_bit in [1, 64]; asynchronous on the ctx stream. */
+int r3d_sort_u64_bits(r3d_ctx* ctx, uint64_t* d_keys, int64_t n_keys, int first_bit, int end_bit);
 
 
 /* The same with the matrix in HBM (16 doubles, row-major; e.g. the step a device-side ICP solve just wrote). */
