@@ -551,6 +551,40 @@ int r3d_normals_knn(r3d_nn_index* index, int k, double radius, const double* h_v
  * only; an output that overlaps an input or the other output -> R3D_ERR_INVALID. */
 int r3d_select_rows(r3d_ctx* ctx, const float* d_xyz, int64_t n_points, const uint8_t* d_keep, float* d_xyz_out,
                     uint32_t* d_rows_out, int64_t* h_n_out);
+/* ---- RANSAC plane segmentation (csrc/r3d_ransac.hip; NOT IN THE REFERENCE -- what users of this kind of pipeline call Open3D's
+ * segment_plane for; no parity with Open3D is claimed, this text is the specification).  d_xyz [n][3] f32, 3 <= n < 2^32;
+ * thr = distance_threshold, finite and > 0; 1 <= H = n_hypotheses <= 65536; seed: any u64.  Synchronises.  Every output bit is
+ * the same on every run; the counts are integer sums and do not depend on the launch geometry.
+ * Sampler (counter-based; r3d_ransac_rows is the same function on the host, no GPU needed): the rows of hypothesis h are
+ *   r_j(h) = mulhi64(splitmix64(seed + (3h + j + 1) * 0x9E3779B97F4A7C15 mod 2^64), n), j = 0, 1, 2, with
+ *   splitmix64(z): z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; return z ^ z >> 31  (mod 2^64)
+ *   and mulhi64(a, n) = (a * n) >> 64.
+ * Hypothesis: a, b, c = the three rows in fp64; u = b - a, v = c - a, N = u x v = (uy vz - uz vy, uz vx - ux vz, ux vy - uy vx),
+ *   l2 = (Nx Nx + Ny Ny) + Nz Nz, all in fp64 as written, no fused multiply-add.  Valid iff the three rows are pairwise different
+ *   and l2 is finite and > 0 (duplicates, collinear triples and non-finite points are out).  n^ = (float)(N / sqrt(l2)) per
+ *   component; the anchor a^ is the f32 point of row r_0.
+ * Count: e = p_i - a^ per component in f32, s = (n^x ex + n^y ey) + n^z ez in f32, no fused multiply-add;
+ *   c_h = #{i : |s| <= (float) thr}.  NaN compares false: a non-finite point is nobody's inlier.  Invalid hypothesis: c_h = 0.
+ *   d_counts_out [H] u32 (may be NULL) = c_h.
+ * Best hypothesis: the lowest h among those with maximal c_h.  Maximum < 3: there is no plane -- R3D_OK, *n_inliers_out = 0, the
+ *   mask all zero, plane, centroid and eigenvalues NaN (best h, c_best, its rows and the valid count are still reported).
+ * Refit: I0 = the best hypothesis' inliers by the same f32 test, m = |I0|.  With e = (double) p - (double) a^: S1 = sum e and
+ *   S2 = the six sums e_a e_b (xx, xy, xz, yy, yz, zz), fp64, reduced in two fixed-order stages (shuffle tree -> LDS -> one row per
+ *   workgroup -> one fold; no float atomics).  Centroid c = a^ + S1 / m, C = (S2 - S1 S1^T / m) / m evaluated as written.
+ *   n = the unit eigenvector of the smallest eigenvalue l0 <= l1 <= l2 of C (cyclic Jacobi in fp64 on the host; of equal
+ *   eigenvalues the lowest axis), negated iff its component of largest magnitude (lowest axis on ties) is negative;
+ *   d = -((nx cx + ny cy) + nz cz).  l1 <= 0 (the inliers are collinear to the last bit): the hypothesis' own fp64 plane,
+ *   n = N / sqrt(l2) with the same sign rule, c = a, eigenvalues as computed.
+ * Final mask: t = (nx (x - cx) + ny (y - cy)) + nz (z - cz) in fp64 from the f32 point, no fused multiply-add;
+ *   d_inlier_out[i] (u8) = |t| <= thr; *n_inliers_out = their number.
+ * h_result (host, 16 doubles): [0..3] plane a b c d, [4..6] centroid, [7..9] l0 l1 l2, [10] best h, [11] c_best,
+ *   [12..14] the best hypothesis' rows, [15] the number of valid hypotheses.
+ * NULL ctx / d_xyz / d_inlier_out / h_result / n_inliers_out, n < 3 or >= 2^32, H out of range, thr not finite or not > 0,
+ *   outputs overlapping the cloud or each other -> R3D_ERR_INVALID, nothing written to any output. */
+int r3d_segment_plane(r3d_ctx* ctx, const float* d_xyz, int64_t n, double distance_threshold, int n_hypotheses, uint64_t seed,
+                      uint8_t* d_inlier_out, uint32_t* d_counts_out, double* h_result, int64_t* n_inliers_out);
+/* The sampler alone (host): rows[j] = r_j(h) for a cloud of n rows.  NULL rows, n < 1 or n >= 2^32 -> R3D_ERR_INVALID. */
+int r3d_ransac_rows(uint64_t seed, uint64_t h, int64_t n, uint32_t* rows);
 /* In-place ascending sort of 64-bit keys in HBM by their low key_bits bits (stable LSD radix sort, 8-bit digits;
  * asynchronous on the ctx stream).  Building block of r3d_voxelset_codes, exported for tests and reuse. */
 int r3d_sort_u64(r3d_ctx* ctx, uint64_t* d_keys, int64_t n_keys, int key_bits);
