@@ -167,6 +167,13 @@ SIGNATURES = {
     "r3d_octree_bt_header": (_i, [_i64, _d, _vp, _sz, _psz]),
     "r3d_voxelset_format_bt": (_i, [_vp, _vp, _sz, _psz, _vp]),
     "r3d_voxelset_write_bt": (_i, [_vp, C.c_char_p, _vp]),
+    "r3d_tsdf_create": (_i, [_vp, _vp, _d, _i, _i, _i, _d, _pvp]),
+    "r3d_tsdf_destroy": (_i, [_vp]),
+    "r3d_tsdf_reset": (_i, [_vp]),
+    "r3d_tsdf_integrate": (_i, [_vp, _vp, _vp, _i, _i, _d, _vp]),
+    "r3d_tsdf_integrate_host": (_i, [_vp, _vp, _vp, _i, _i, _d, _vp]),
+    "r3d_tsdf_volume": (_i, [_vp, _pvp, _vp]),
+    "r3d_tsdf_extract_points": (_i, [_vp, _d, _vp, _vp, _i64, _vp]),
 }
 
 _lib = None

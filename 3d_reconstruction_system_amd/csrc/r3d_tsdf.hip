@@ -1,0 +1,433 @@
+// Dense TSDF volume for gfx950 (MI355X): integration of depth frames and extraction of the zero level set as oriented points.
+// Semantics: include/r3d.h ("TSDF volume"); every output bit is a short chain of IEEE f32 operations in the order written there
+// (the library builds with -ffp-contract=off; hipcc's f32 division and sqrt are correctly rounded by default).
+//
+//   tsdf_integrate_kernel   one lane = two voxels that follow each other in x (one 16-byte access when nx is even, two 8-byte
+//                           ones otherwise: an odd nx leaves every second row 8-byte aligned only).  The frame loop is INSIDE:
+//                           a lane loads its pair once, applies the chunk's frames from registers in ascending order and stores
+//                           once -- and only if a frame touched it.  The per-frame pose (12 floats) is wave-uniform and comes
+//                           from a small device table through scalar loads; the depth read is a gather, neighbouring lanes
+//                           hitting neighbouring pixels.  No LDS, no atomics.
+//   tsdf_count_kernel       extraction, the shape of r3d_select_rows: surface points per tile of 4096 voxels,
+//   (tile scan)             r3d_sort.hip's digit_scan_kernel over the tile counts,
+//   tsdf_emit_kernel        every tile writes its points at its prefix + an in-block scan: linear voxel order, then x, y, z --
+//                           fixed by construction, no atomics on the output cursor.
+#include "r3d_internal.h"
+#include "r3d_sort_dev.h"
+
+#include <cmath>
+#include <new>
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kChunk = R3D_TSDF_CHUNK;   // frames per launch = rows of one slot of the pose table
+constexpr int kSlots = 4;                // slots of the pose table: a call's chunks ride the ring without waiting for each other
+constexpr int kPer = kSortTile / kThreads;   // consecutive voxels per thread of the extraction kernels
+
+struct TsdfFrame {   // world -> camera, f32: p_cam = R p_w + t
+  float r[9];
+  float t[3];
+  float pad[4];
+};
+static_assert(sizeof(TsdfFrame) == 64, "one pose row is 64 bytes");
+
+struct TsdfGrid {
+  int nx, ny, nz;
+  float ox, oy, oz, vs, tr;
+};
+
+struct TsdfCam {
+  float fx, fy, cx, cy, wf, hf, scale;
+  int width;
+  uint32_t frame_px;   // height * width
+};
+
+__device__ __forceinline__ float centre(float o, int idx, float vs) { return o + ((float)idx + 0.5f) * vs; }
+
+// one frame into one voxel; returns whether the frame touched it
+template <typename D>
+__device__ __forceinline__ bool integrate_one(const TsdfFrame& fr, const TsdfCam& cam, const D* __restrict__ depth, float tr, float cx_,
+                                              float cy_, float cz_, float& tsdf, float& w) {
+  const float px = ((fr.r[0] * cx_ + fr.r[1] * cy_) + fr.r[2] * cz_) + fr.t[0];
+  const float py = ((fr.r[3] * cx_ + fr.r[4] * cy_) + fr.r[5] * cz_) + fr.t[1];
+  const float pz = ((fr.r[6] * cx_ + fr.r[7] * cy_) + fr.r[8] * cz_) + fr.t[2];
+  if (!(pz > 0.0f)) return false;
+  const float u = cam.fx * (px / pz) + cam.cx;
+  const float v = cam.fy * (py / pz) + cam.cy;
+  const float ui = floorf(u + 0.5f), vi = floorf(v + 0.5f);
+  if (!(ui >= 0.0f && ui < cam.wf && vi >= 0.0f && vi < cam.hf)) return false;   // NaN fails every comparison
+  const float d = (float)depth[(uint32_t)(int)vi * (uint32_t)cam.width + (uint32_t)(int)ui] * cam.scale;
+  if (!(d > 0.0f && d < INFINITY)) return false;
+  const float sdf = d - pz;
+  if (sdf < -tr) return false;
+  const float tn = fminf(1.0f, sdf / tr);
+  const float w1 = w + 1.0f;
+  tsdf = (tsdf * w + tn) / w1;
+  w = w1;
+  return true;
+}
+
+// grid: ceil(rows * pairs_per_row / 256) workgroups; lane -> (row, pair) -> voxels x0 = 2 pair and x0 + 1 of row (y, z)
+template <typename D, bool VEC>
+__global__ __launch_bounds__(kThreads) void tsdf_integrate_kernel(float2* __restrict__ vol, TsdfGrid g, TsdfCam cam,
+                                                                  const D* __restrict__ depth, const TsdfFrame* __restrict__ table,
+                                                                  int n_frames, uint32_t pairs_per_row, uint32_t n_pairs) {
+  const uint32_t p = blockIdx.x * (uint32_t)kThreads + threadIdx.x;
+  if (p >= n_pairs) return;
+  const uint32_t row = p / pairs_per_row;
+  const int x0 = (int)(p - row * pairs_per_row) * 2;
+  const int z = (int)(row / (uint32_t)g.ny), y = (int)(row - (uint32_t)z * (uint32_t)g.ny);
+  const bool has_b = x0 + 1 < g.nx;   // (always true when VEC: nx is even)
+  float2* at = vol + ((size_t)row * (size_t)g.nx + (size_t)x0);
+  float2 a, b = float2{0.0f, 0.0f};
+  if (VEC) {
+    const float4 q = *reinterpret_cast<const float4*>(at);
+    a = float2{q.x, q.y};
+    b = float2{q.z, q.w};
+  } else {
+    a = at[0];
+    if (has_b) b = at[1];
+  }
+  const float cxa = centre(g.ox, x0, g.vs), cxb = centre(g.ox, x0 + 1, g.vs);
+  const float cy_ = centre(g.oy, y, g.vs), cz_ = centre(g.oz, z, g.vs);
+  bool ta = false, tb = false;
+  for (int f = 0; f < n_frames; ++f) {
+    const TsdfFrame fr = table[f];   // wave-uniform: scalar loads
+    const D* frame = depth + (size_t)f * cam.frame_px;
+    ta |= integrate_one(fr, cam, frame, g.tr, cxa, cy_, cz_, a.x, a.y);
+    tb |= integrate_one(fr, cam, frame, g.tr, cxb, cy_, cz_, b.x, b.y);
+  }
+  if (VEC) {
+    if (ta || tb) *reinterpret_cast<float4*>(at) = float4{a.x, a.y, b.x, b.y};
+  } else {
+    if (ta) at[0] = a;
+    if (tb && has_b) at[1] = b;
+  }
+}
+
+// ---- extraction ------------------------------------------------------------------------------------------------------------------
+struct Vox {
+  int x, y, z;
+};
+
+__device__ __forceinline__ Vox vox_of(int64_t i, const TsdfGrid& g) {
+  const uint32_t row = (uint32_t)i / (uint32_t)g.nx;   // i < 2^31
+  Vox v;
+  v.x = (int)((uint32_t)i - row * (uint32_t)g.nx);
+  v.z = (int)(row / (uint32_t)g.ny);
+  v.y = (int)(row - (uint32_t)v.z * (uint32_t)g.ny);
+  return v;
+}
+
+__device__ __forceinline__ int64_t step_of(int a, const TsdfGrid& g) { return a == 0 ? 1 : a == 1 ? (int64_t)g.nx : (int64_t)g.nx * g.ny; }
+__device__ __forceinline__ int coord_of(const Vox& v, int a) { return a == 0 ? v.x : a == 1 ? v.y : v.z; }
+__device__ __forceinline__ int dim_of(const TsdfGrid& g, int a) { return a == 0 ? g.nx : a == 1 ? g.ny : g.nz; }
+
+// bit a: the edge from voxel i towards +axis a carries a surface point
+__device__ __forceinline__ uint32_t crossings(const float2* __restrict__ vol, const TsdfGrid& g, int64_t i, float mw) {
+  const float2 A = vol[i];
+  if (!(A.y >= mw)) return 0;
+  const Vox v = vox_of(i, g);
+  uint32_t m = 0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    if (coord_of(v, a) + 1 >= dim_of(g, a)) continue;
+    const float2 B = vol[i + step_of(a, g)];
+    if (B.y >= mw && ((A.x < 0.0f) != (B.x < 0.0f))) m |= 1u << a;
+  }
+  return m;
+}
+
+__global__ __launch_bounds__(kThreads) void tsdf_count_kernel(const float2* __restrict__ vol, TsdfGrid g, int64_t n, float mw,
+                                                              uint32_t* __restrict__ hist) {
+  const int64_t base = (int64_t)blockIdx.x * kSortTile + (int64_t)threadIdx.x * kPer;
+  uint32_t c = 0;
+#pragma unroll 4
+  for (int e = 0; e < kPer; ++e)
+    if (base + e < n) c += (uint32_t)__popc(crossings(vol, g, base + e, mw));
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+  __shared__ uint32_t sh[kThreads / 64];
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) hist[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+}
+
+// the neighbour's tsdf if it is inside the volume and valid, else the voxel's own
+__device__ __forceinline__ float tsdf_or(const float2* __restrict__ vol, int64_t j, bool inside, float mw, float own) {
+  if (!inside) return own;
+  const float2 q = vol[j];
+  return q.y >= mw ? q.x : own;
+}
+
+__device__ __forceinline__ void gradient(const float2* __restrict__ vol, const TsdfGrid& g, int64_t i, const Vox& v, float mw, float (&out)[3]) {
+  const float own = vol[i].x;
+#pragma unroll
+  for (int b = 0; b < 3; ++b) {
+    const int64_t s = step_of(b, g);
+    const int c = coord_of(v, b);
+    out[b] = tsdf_or(vol, i + s, c + 1 < dim_of(g, b), mw, own) - tsdf_or(vol, i - s, c >= 1, mw, own);
+  }
+}
+
+// hist: the tiles' exclusive prefixes (r3d_sort_launch_scan)
+__global__ __launch_bounds__(kThreads) void tsdf_emit_kernel(const float2* __restrict__ vol, TsdfGrid g, int64_t n, float mw,
+                                                             const uint32_t* __restrict__ hist, float* __restrict__ xyz_out,
+                                                             float* __restrict__ normals_out, uint64_t cap) {
+  const int64_t base = (int64_t)blockIdx.x * kSortTile + (int64_t)threadIdx.x * kPer;
+  uint64_t mask = 0;   // 3 bits per voxel, voxel-major: the order of the output
+#pragma unroll 4
+  for (int e = 0; e < kPer; ++e)
+    if (base + e < n) mask |= (uint64_t)crossings(vol, g, base + e, mw) << (3 * e);
+  __shared__ uint64_t wave_total[kThreads / 64];
+  uint64_t at = hist[blockIdx.x] + r3d_sort::block_exclusive_scan_256((uint64_t)__popcll(mask), wave_total);
+  while (mask && at < cap) {
+    const int bit = __ffsll((long long)mask) - 1;
+    mask &= mask - 1;
+    const int e = bit / 3, a = bit - 3 * e;
+    const int64_t i = base + e, j = i + step_of(a, g);
+    const Vox v = vox_of(i, g);
+    Vox w = v;
+    if (a == 0) ++w.x; else if (a == 1) ++w.y; else ++w.z;
+    const float A = vol[i].x, B = vol[j].x;
+    const float r = A / (A - B);
+    float pos[3] = {centre(g.ox, v.x, g.vs), centre(g.oy, v.y, g.vs), centre(g.oz, v.z, g.vs)};
+    const float moved = pos[a] + r * g.vs;
+    if (a == 0) pos[0] = moved; else if (a == 1) pos[1] = moved; else pos[2] = moved;
+    if (xyz_out) {
+      xyz_out[3 * at + 0] = pos[0];
+      xyz_out[3 * at + 1] = pos[1];
+      xyz_out[3 * at + 2] = pos[2];
+    }
+    if (normals_out) {
+      float gv[3], gn[3], m[3];
+      gradient(vol, g, i, v, mw, gv);
+      gradient(vol, g, j, w, mw, gn);
+#pragma unroll
+      for (int b = 0; b < 3; ++b) m[b] = gv[b] + r * (gn[b] - gv[b]);
+      const float len = sqrtf((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]);
+      const bool ok = len > 0.0f;
+#pragma unroll
+      for (int b = 0; b < 3; ++b) normals_out[3 * at + b] = ok ? m[b] / len : 0.0f;
+    }
+    ++at;
+  }
+}
+
+}  // namespace
+
+struct r3d_tsdf {
+  r3d_ctx* ctx = nullptr;
+  int device = 0;   // for destroy, which must not dereference ctx
+  TsdfGrid g = {};
+  int64_t n = 0;    // voxels
+  float2* d_vol = nullptr;
+  TsdfFrame* d_table = nullptr;   // [kSlots][kChunk]
+  TsdfFrame* h_table = nullptr;   // the same, pinned: what the uploads read
+  hipEvent_t ev[kSlots] = {};     // slot s of h_table has been read by its upload
+  unsigned next_slot = 0;
+};
+
+int r3d_tsdf_create(r3d_ctx* ctx, const double* h_origin, double voxel_size, int nx, int ny, int nz, double sdf_trunc, r3d_tsdf** out) {
+  R3D_REQUIRE(out != nullptr, "out is NULL");
+  *out = nullptr;
+  R3D_REQUIRE(ctx != nullptr && h_origin != nullptr, "NULL argument");
+  R3D_REQUIRE(nx >= 1 && ny >= 1 && nz >= 1 && (int64_t)nx * ny < ((int64_t)1 << 31) && (int64_t)nx * ny * nz < ((int64_t)1 << 31),
+              "volume dimensions %d x %d x %d: every one must be >= 1 and their product below 2^31", nx, ny, nz);
+  const float o[3] = {(float)h_origin[0], (float)h_origin[1], (float)h_origin[2]};
+  const float vs = (float)voxel_size, tr = (float)sdf_trunc;
+  R3D_REQUIRE(std::isfinite(o[0]) && std::isfinite(o[1]) && std::isfinite(o[2]), "origin must be finite in f32");
+  R3D_REQUIRE(vs > 0.0f && std::isfinite(vs), "voxel_size must be positive and finite in f32");
+  R3D_REQUIRE(tr > 0.0f && std::isfinite(tr), "sdf_trunc must be positive and finite in f32");
+  int rc = r3d_ctx_enter(ctx);
+  if (rc) return rc;
+  r3d_tsdf* v = new (std::nothrow) r3d_tsdf();
+  if (!v) {
+    r3d_set_error("host allocation failed");
+    return R3D_ERR_NOMEM;
+  }
+  v->ctx = ctx;
+  v->device = ctx->device;
+  v->g = TsdfGrid{nx, ny, nz, o[0], o[1], o[2], vs, tr};
+  v->n = (int64_t)nx * ny * nz;
+  hipError_t e = hipMalloc((void**)&v->d_vol, (size_t)v->n * sizeof(float2));
+  if (e == hipSuccess) e = hipMalloc((void**)&v->d_table, sizeof(TsdfFrame) * kSlots * kChunk);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&v->h_table, sizeof(TsdfFrame) * kSlots * kChunk, hipHostMallocDefault);
+  for (int s = 0; s < kSlots && e == hipSuccess; ++s) e = hipEventCreateWithFlags(&v->ev[s], hipEventDisableTiming);
+  if (e != hipSuccess) {
+    r3d_tsdf_destroy(v);
+    if (e == hipErrorOutOfMemory) {
+      r3d_set_error("a TSDF volume of %d x %d x %d voxels does not fit the device", nx, ny, nz);
+      return R3D_ERR_NOMEM;
+    }
+    return r3d_fail_hip(e, "TSDF volume allocation", __FILE__, __LINE__);
+  }
+  if ((rc = r3d_tsdf_reset(v))) {
+    r3d_tsdf_destroy(v);
+    return rc;
+  }
+  *out = v;
+  return R3D_OK;
+}
+
+int r3d_tsdf_destroy(r3d_tsdf* v) {
+  if (!v) return R3D_OK;
+  (void)hipSetDevice(v->device);
+  (void)hipDeviceSynchronize();
+  if (v->d_vol) (void)hipFree(v->d_vol);
+  if (v->d_table) (void)hipFree(v->d_table);
+  if (v->h_table) (void)hipHostFree(v->h_table);
+  for (int s = 0; s < kSlots; ++s)
+    if (v->ev[s]) (void)hipEventDestroy(v->ev[s]);
+  delete v;
+  return R3D_OK;
+}
+
+int r3d_tsdf_reset(r3d_tsdf* v) {
+  R3D_REQUIRE(v != nullptr, "TSDF volume is NULL");
+  int rc = r3d_ctx_enter(v->ctx);
+  if (rc) return rc;
+  R3D_HIP(hipMemsetAsync(v->d_vol, 0, (size_t)v->n * sizeof(float2), v->ctx->stream));
+  return R3D_OK;
+}
+
+int r3d_tsdf_volume(r3d_tsdf* v, float** d_tsdf_weight_out, int64_t* n_voxels_out) {
+  R3D_REQUIRE(v != nullptr, "TSDF volume is NULL");
+  if (d_tsdf_weight_out) *d_tsdf_weight_out = reinterpret_cast<float*>(v->d_vol);
+  if (n_voxels_out) *n_voxels_out = v->n;
+  return R3D_OK;
+}
+
+namespace {
+
+template <typename D>
+void launch_integrate(r3d_tsdf* v, const TsdfCam& cam, const void* d_depth, const TsdfFrame* table, int n) {
+  const TsdfGrid& g = v->g;
+  const uint32_t ppr = ((uint32_t)g.nx + 1) / 2;
+  const uint32_t n_pairs = ppr * (uint32_t)((int64_t)g.ny * g.nz);   // <= nx ny nz < 2^31
+  const dim3 grid((n_pairs + kThreads - 1) / kThreads), block(kThreads);
+  if (g.nx % 2 == 0)
+    hipLaunchKernelGGL((tsdf_integrate_kernel<D, true>), grid, block, 0, v->ctx->stream, v->d_vol, g, cam, static_cast<const D*>(d_depth),
+                       table, n, ppr, n_pairs);
+  else
+    hipLaunchKernelGGL((tsdf_integrate_kernel<D, false>), grid, block, 0, v->ctx->stream, v->d_vol, g, cam, static_cast<const D*>(d_depth),
+                       table, n, ppr, n_pairs);
+}
+
+int integrate_checks(r3d_tsdf* v, const r3d_camera* cam, const void* depth, int depth_dtype, int n_frames, double depth_scale,
+                     const double* h_pose) {
+  R3D_REQUIRE(v != nullptr, "TSDF volume is NULL");
+  R3D_REQUIRE(cam != nullptr, "camera is NULL");
+  R3D_REQUIRE(cam->ctx == v->ctx, "the camera belongs to another context than the volume");
+  R3D_REQUIRE(depth_dtype >= R3D_DEPTH_U8 && depth_dtype <= R3D_DEPTH_F32, "unknown depth dtype %d", depth_dtype);
+  R3D_REQUIRE(n_frames >= 0, "n_frames must be >= 0");
+  if (n_frames == 0) return R3D_OK;
+  R3D_REQUIRE(depth != nullptr && h_pose != nullptr, "NULL depth or pose pointer");
+  R3D_REQUIRE(cam->width <= (1 << 24) && cam->height <= (1 << 24) && (int64_t)cam->width * cam->height < ((int64_t)1 << 31),
+              "raster of %d x %d pixels is too large for the TSDF projection", cam->height, cam->width);
+  R3D_REQUIRE(std::isfinite((float)depth_scale), "depth_scale must be finite in f32");
+  return R3D_OK;
+}
+
+// the launches of one batch whose rasters are in HBM; asynchronous
+int integrate_device(r3d_tsdf* v, const r3d_camera* cam, const void* d_depth, int depth_dtype, int n_frames, double depth_scale,
+                     const double* h_pose) {
+  r3d_ctx* ctx = v->ctx;
+  TsdfCam c;
+  c.fx = (float)cam->fx, c.fy = (float)cam->fy, c.cx = (float)cam->cx, c.cy = (float)cam->cy;
+  c.wf = (float)cam->width, c.hf = (float)cam->height, c.scale = (float)depth_scale;
+  c.width = cam->width;
+  c.frame_px = (uint32_t)cam->height * (uint32_t)cam->width;
+  const size_t frame_bytes = (size_t)c.frame_px * r3d_depth_size(depth_dtype);
+  for (int lo = 0; lo < n_frames; lo += kChunk) {
+    const int n = n_frames - lo < kChunk ? n_frames - lo : kChunk;
+    const unsigned s = v->next_slot++ % kSlots;
+    R3D_HIP(hipEventSynchronize(v->ev[s]));   // the upload that read this slot of the pinned table last is done (never recorded: returns at once)
+    TsdfFrame* h = v->h_table + (size_t)s * kChunk;
+    for (int f = 0; f < n; ++f) {
+      const double* p = h_pose + (size_t)(lo + f) * 12;
+      for (int k = 0; k < 9; ++k) h[f].r[k] = (float)p[k];
+      for (int k = 0; k < 3; ++k) h[f].t[k] = (float)p[9 + k];
+      for (int k = 0; k < 4; ++k) h[f].pad[k] = 0.0f;
+    }
+    TsdfFrame* d = v->d_table + (size_t)s * kChunk;
+    R3D_HIP(hipMemcpyAsync(d, h, sizeof(TsdfFrame) * n, hipMemcpyHostToDevice, ctx->stream));
+    R3D_HIP(hipEventRecord(v->ev[s], ctx->stream));
+    const void* depth = static_cast<const char*>(d_depth) + (size_t)lo * frame_bytes;
+    if (depth_dtype == R3D_DEPTH_U8) launch_integrate<uint8_t>(v, c, depth, d, n);
+    else if (depth_dtype == R3D_DEPTH_U16) launch_integrate<uint16_t>(v, c, depth, d, n);
+    else launch_integrate<float>(v, c, depth, d, n);
+    R3D_HIP(hipGetLastError());
+  }
+  return R3D_OK;
+}
+
+}  // namespace
+
+int r3d_tsdf_integrate(r3d_tsdf* v, const r3d_camera* cam, const void* d_depth, int depth_dtype, int n_frames, double depth_scale,
+                       const double* h_pose_w2c) {
+  int rc = integrate_checks(v, cam, d_depth, depth_dtype, n_frames, depth_scale, h_pose_w2c);
+  if (rc || n_frames == 0) return rc;
+  if ((rc = r3d_ctx_enter(v->ctx))) return rc;
+  return integrate_device(v, cam, d_depth, depth_dtype, n_frames, depth_scale, h_pose_w2c);
+}
+
+int r3d_tsdf_integrate_host(r3d_tsdf* v, const r3d_camera* cam, const void* h_depth, int depth_dtype, int n_frames, double depth_scale,
+                            const double* h_pose_w2c) {
+  int rc = integrate_checks(v, cam, h_depth, depth_dtype, n_frames, depth_scale, h_pose_w2c);
+  if (rc || n_frames == 0) return rc;
+  r3d_ctx* ctx = v->ctx;
+  if ((rc = r3d_ctx_enter(ctx))) return rc;
+  // the batch goes up in slabs of whole frames through the context's input scratch slot; every slab is one integrate call
+  const size_t frame_bytes = (size_t)cam->height * cam->width * r3d_depth_size(depth_dtype);
+  int slab = (int)(((size_t)256 << 20) / (frame_bytes ? frame_bytes : 1));
+  if (slab < 1) slab = 1;
+  if (slab > n_frames) slab = n_frames;
+  void* d_in = nullptr;
+  if ((rc = r3d_scratch(ctx, 0, (size_t)slab * frame_bytes, &d_in))) return rc;
+  for (int lo = 0; lo < n_frames; lo += slab) {
+    const int n = n_frames - lo < slab ? n_frames - lo : slab;
+    if ((rc = r3d_memcpy_h2d(ctx, d_in, static_cast<const char*>(h_depth) + (size_t)lo * frame_bytes, (size_t)n * frame_bytes))) return rc;
+    if ((rc = integrate_device(v, cam, d_in, depth_dtype, n, depth_scale, h_pose_w2c + (size_t)lo * 12))) return rc;
+    R3D_HIP(hipStreamSynchronize(ctx->stream));   // the next slab overwrites the scratch; the caller's memory is free at return
+  }
+  return R3D_OK;
+}
+
+int r3d_tsdf_extract_points(r3d_tsdf* v, double min_weight, float* d_xyz_out, float* d_normals_out, int64_t cap, int64_t* n_out) {
+  R3D_REQUIRE(v != nullptr, "TSDF volume is NULL");
+  R3D_REQUIRE(n_out != nullptr, "n_out is NULL");
+  const float mw = (float)min_weight;
+  R3D_REQUIRE(mw > 0.0f, "min_weight must be > 0 in f32");
+  R3D_REQUIRE(cap >= 0, "cap must be >= 0");
+  R3D_REQUIRE(cap == 0 || d_xyz_out != nullptr, "d_xyz_out is NULL with cap > 0");
+  r3d_ctx* ctx = v->ctx;
+  int rc = r3d_ctx_enter(ctx);
+  if (rc) return rc;
+  if (3 * v->n >= ((int64_t)1 << 32)) {   // the tile prefixes are 32-bit
+    r3d_set_error("surface extraction takes volumes of fewer than 2^32 / 3 voxels");
+    return R3D_ERR_UNSUPPORTED;
+  }
+  const int tiles = (int)((v->n + kSortTile - 1) / kSortTile), stride = r3d_sort_stride(tiles);
+  void* ws = nullptr;
+  if ((rc = r3d_scratch(ctx, 3, (size_t)stride * 4 + 64, &ws))) return rc;
+  uint32_t* hist = static_cast<uint32_t*>(ws);
+  uint32_t* total = hist + stride;
+  hipStream_t st = ctx->stream;
+  hipLaunchKernelGGL(tsdf_count_kernel, dim3(tiles), dim3(kThreads), 0, st, (const float2*)v->d_vol, v->g, v->n, mw, hist);
+  r3d_sort_launch_scan(ctx, hist, tiles, stride, total, 1);
+  R3D_HIP(hipGetLastError());
+  uint32_t m = 0;
+  R3D_HIP(hipMemcpyAsync(&m, total, sizeof(m), hipMemcpyDeviceToHost, st));
+  R3D_HIP(hipStreamSynchronize(st));
+  *n_out = (int64_t)m;
+  const uint64_t rows = (uint64_t)((int64_t)m < cap ? (int64_t)m : cap);
+  if (rows == 0) return R3D_OK;
+  r3d_wrote(ctx, d_xyz_out, (size_t)rows * 12);
+  if (d_normals_out) r3d_wrote(ctx, d_normals_out, (size_t)rows * 12);
+  hipLaunchKernelGGL(tsdf_emit_kernel, dim3(tiles), dim3(kThreads), 0, st, (const float2*)v->d_vol, v->g, v->n, mw, (const uint32_t*)hist,
+                     d_xyz_out, d_normals_out, rows);
+  R3D_HIP(hipGetLastError());
+  return R3D_OK;
+}

@@ -1,0 +1,92 @@
+#!/usr/bin/env python3
+"""TSDF integration of a drop-in working directory on the MI355X: the frames camera_to_world.py fuses into a cloud are averaged in a
+truncated signed distance volume instead, and the volume's zero level set is written as oriented surface points.
+
+    python integrate_tsdf.py --voxel-size S --trunc T [--origin X Y Z] [--dims NX NY NZ] [--margin M] [--min-weight W]
+
+Run from a directory holding ./camera_pose/image_colmap_simi_2.txt and ./depth/ (the inputs of camera_to_world.py; the same
+environment overrides apply: R3D_FX .. R3D_CY, R3D_POSE_SCALE, R3D_DEVICE).  Writes ./ply/tsdf_surface.ply: binary PLY, float
+x y z nx ny nz, the normals pointing towards the cameras.  Without --origin / --dims the volume is the bounding box of the camera
+centres padded by M on every side (default M = 16 T), cut into voxels of S.  A depth of 0 is "no measurement".
+"""
+import argparse
+import math
+import os
+import sys
+
+if __package__ in (None, ""):
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "transfer"))
+    import _common  # type: ignore
+else:
+    from ..transfer import _common
+
+POSE_FILE = './camera_pose/image_colmap_simi_2.txt'
+OUT_FILE = './ply/tsdf_surface.ply'
+
+
+def parse_args(argv):
+    p = argparse.ArgumentParser(description="Integrate ./depth/ + the pose file into a TSDF volume and write its surface points.")
+    p.add_argument("--voxel-size", type=float, required=True, help="edge of a voxel, in the depth maps' unit")
+    p.add_argument("--trunc", type=float, required=True, help="truncation distance of the signed distance (a few voxels)")
+    p.add_argument("--origin", type=float, nargs=3, metavar=("X", "Y", "Z"), help="corner of voxel (0, 0, 0)")
+    p.add_argument("--dims", type=int, nargs=3, metavar=("NX", "NY", "NZ"), help="voxels per axis")
+    p.add_argument("--margin", type=float, default=None,
+                   help="padding of the camera centres' bounding box when --origin / --dims are not given (default 16 x --trunc)")
+    p.add_argument("--min-weight", type=float, default=1.0, help="frames a voxel needs to count (default 1)")
+    args = p.parse_args(argv)
+    for name in ("voxel_size", "trunc", "min_weight"):
+        v = getattr(args, name)
+        if not (math.isfinite(v) and v > 0.0):
+            p.error("--%s must be finite and positive, got %r" % (name.replace("_", "-"), v))
+    if args.margin is not None and not (math.isfinite(args.margin) and args.margin >= 0.0):
+        p.error("--margin must be finite and >= 0, got %r" % args.margin)
+    if (args.origin is None) != (args.dims is None):
+        p.error("--origin and --dims go together")
+    if args.dims is not None and (min(args.dims) < 1 or args.dims[0] * args.dims[1] * args.dims[2] >= 1 << 31):
+        p.error("--dims must be >= 1 each with a product below 2^31, got %r" % (args.dims,))
+    return args
+
+
+def default_volume(w2c, voxel_size, margin):
+    """(origin, dims): the bounding box of the camera centres -R^T t, padded by margin on every side."""
+    import numpy as np
+    R, t = w2c[:, :9].reshape(-1, 3, 3), w2c[:, 9:]
+    centres = -np.einsum("fba,fb->fa", R, t)
+    lo, hi = centres.min(axis=0) - margin, centres.max(axis=0) + margin
+    dims = [max(1, int(math.ceil((hi[a] - lo[a]) / voxel_size))) for a in range(3)]
+    return lo, dims
+
+
+def main(argv=None):
+    args = parse_args(sys.argv[1:] if argv is None else argv)
+    r3d = _common.package()
+    if not os.path.isfile(POSE_FILE):
+        sys.exit("integrate_tsdf.py: %s not found (run from the data directory)" % POSE_FILE)
+    names, quats, ts = r3d.read_pose_file(POSE_FILE)
+    if not names:
+        sys.exit("integrate_tsdf.py: %s lists no frames" % POSE_FILE)
+    ts = ts * _common.pose_scale()
+    if args.origin is None:
+        margin = 16.0 * args.trunc if args.margin is None else args.margin
+        origin, dims = default_volume(r3d.poses_w2c(quats, ts), args.voxel_size, margin)
+        if dims[0] * dims[1] * dims[2] >= 1 << 31:
+            sys.exit("integrate_tsdf.py: the default volume has %d x %d x %d voxels; choose a larger --voxel-size or give --origin / --dims"
+                     % tuple(dims))
+    else:
+        origin, dims = args.origin, args.dims
+    depths = r3d.cloud_io.read_depth_batch([os.path.join('./depth/', n) for n in names])
+    _common.stamp("read %d frames" % len(names))
+    vol = r3d.TSDFVolume(origin, args.voxel_size, dims, args.trunc, ctx=_common.context())
+    vol.integrate(depths, quats, ts, intrinsics=_common.intrinsics())
+    _common.stamp("integrate")
+    xyz, normals = vol.extract_point_cloud(args.min_weight)
+    vol.close()
+    _common.stamp("extract")
+    os.makedirs(os.path.dirname(OUT_FILE), exist_ok=True)
+    r3d.cloud_io.write_ply_normals(OUT_FILE, xyz, normals)
+    print("origin %.9g %.9g %.9g dims %d %d %d voxel %.9g trunc %.9g frames %d points %d -> %s"
+          % (origin[0], origin[1], origin[2], dims[0], dims[1], dims[2], args.voxel_size, args.trunc, len(names), len(xyz), OUT_FILE))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,156 @@
+"""Dense TSDF volume on the MI355X: depth frames + poses are integrated into a truncated signed distance volume, and its zero
+level set comes back as oriented surface points -- what users of a depth + pose pipeline expect before meshing (Open3D's
+UniformTSDFVolume; no parity with Open3D is claimed).  Where fuse_frames concatenates the frames' points, the volume averages
+overlapping frames.  Semantics: include/r3d.h (r3d_tsdf_*) and DESIGN.md section 4.5i.
+
+The volume takes the inputs camera_to_world.py already has: [F,H,W] depth, one pose-file row per frame, a pinhole camera.  Its
+poses are WORLD -> CAMERA (p_cam = R p_w + t: the pose file's quaternion and t as they stand, poses_w2c), not the inverted table
+fuse_frames takes.  A depth of 0 is "no measurement" here.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import _lib as L
+from .device import default_context, depth_code
+from .fusion import REF_INTRINSICS, _as_batch
+from .poses import _rotation_matrix_xyzw
+
+CHUNK = 32   # R3D_TSDF_CHUNK: frames one integration launch applies inside the kernel
+
+
+def poses_w2c(quats_xyzw, ts):
+    """[F,12] float64 rows = (R row-major, t), world -> camera: the rotation of the pose file's scalar-last quaternion
+    (normalised first) and its t -- the layout r3d_tsdf_integrate reads.  fuse_frames' pose_table holds the inverse rotation."""
+    quats_xyzw = np.asarray(quats_xyzw, dtype=np.float64).reshape(-1, 4)
+    ts = np.asarray(ts, dtype=np.float64).reshape(-1, 3)
+    if len(quats_xyzw) != len(ts):
+        raise ValueError("need one translation per quaternion")
+    table = np.empty((len(ts), 12), dtype=np.float64)
+    for k in range(len(ts)):
+        table[k, :9] = _rotation_matrix_xyzw(quats_xyzw[k]).reshape(9)
+        table[k, 9:] = ts[k]
+    return table
+
+
+def _positive_f32(v, what):
+    try:
+        f = float(v)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be a finite number > 0, got %r" % (what, v))
+    with np.errstate(over="ignore"):
+        f32 = np.float32(f)
+    if isinstance(v, bool) or not (math.isfinite(f) and f32 > 0 and np.isfinite(f32)):
+        raise ValueError("%s must be a finite number > 0 (in float32), got %r" % (what, v))
+    return f
+
+
+def _pose_rows(poses, n_frames):
+    p = np.ascontiguousarray(poses, dtype=np.float64)
+    if p.ndim != 2 or p.shape != (n_frames, 12):
+        raise ValueError("poses_w2c must be [%d,12] float64 rows (R row-major, t), got shape %s" % (n_frames, p.shape))
+    return p
+
+
+class TSDFVolume:
+    """origin [3] (the corner of voxel (0, 0, 0); its centre is origin + voxel_size / 2), voxel_size, dims = (nx, ny, nz),
+    sdf_trunc: the truncation distance.  One float2 {tsdf, weight} per voxel in HBM."""
+
+    def __init__(self, origin, voxel_size, dims, sdf_trunc, ctx=None):
+        o = np.ascontiguousarray(origin, dtype=np.float64)
+        if o.shape != (3,) or not np.isfinite(o.astype(np.float32)).all():
+            raise ValueError("origin must be three finite numbers, got %r" % (origin,))
+        vs, tr = _positive_f32(voxel_size, "voxel_size"), _positive_f32(sdf_trunc, "sdf_trunc")
+        try:
+            nx, ny, nz = [int(d) for d in dims]
+            exact = all(int(d) == d and not isinstance(d, bool) for d in dims)
+        except (TypeError, ValueError):
+            raise ValueError("dims must be three integers >= 1, got %r" % (dims,))
+        if not exact or min(nx, ny, nz) < 1 or nx * ny * nz >= 1 << 31:
+            raise ValueError("dims must be three integers >= 1 with a product below 2^31, got %r" % (dims,))
+        self.ctx = ctx or default_context()
+        self.origin, self.voxel_size, self.sdf_trunc, self.dims = o, vs, tr, (nx, ny, nz)
+        self.n_voxels = nx * ny * nz
+        h = C.c_void_p()
+        L.check(self.ctx.lib.r3d_tsdf_create(self.ctx.handle, o.ctypes.data, vs, nx, ny, nz, tr, C.byref(h)))
+        self.handle = h.value
+        self.ctx.adopt(self)
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.r3d_tsdf_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        """Back to the fresh volume: all zero bytes."""
+        L.check(self.ctx.lib.r3d_tsdf_reset(self.handle))
+
+    def integrate(self, depths, quats_xyzw, ts, intrinsics=REF_INTRINSICS, depth_scale=1.0):
+        """Integrate host rasters [H,W] or [F,H,W] (uint8, uint16 or float32) seen from the pose-file rows (quats_xyzw, ts), in
+        frame order.  Synchronous."""
+        d = _as_batch(depths)
+        f, h, w = d.shape
+        table = poses_w2c(quats_xyzw, ts)
+        if table.shape[0] != f:
+            raise ValueError("%d frames but %d poses" % (f, table.shape[0]))
+        if f * h * w == 0:
+            return
+        cam = self.ctx.camera(h, w, *intrinsics)
+        L.check(self.ctx.lib.r3d_tsdf_integrate_host(self.handle, cam.handle, d.ctypes.data, depth_code(d.dtype), f, float(depth_scale),
+                                                     table.ctypes.data))
+
+    def integrate_device(self, cam, d_depth, depth_dtype, n_frames, poses_w2c, depth_scale=1.0):
+        """The same from rasters in HBM (d_depth: [n_frames][H][W] of depth_dtype at a raw device address; cam: ctx.camera(...));
+        poses_w2c: [n_frames,12] host rows.  Asynchronous on the context's stream."""
+        n_frames = int(n_frames)
+        if n_frames < 0:
+            raise ValueError("n_frames must be >= 0, got %d" % n_frames)
+        table = _pose_rows(poses_w2c, n_frames)
+        L.check(self.ctx.lib.r3d_tsdf_integrate(self.handle, cam.handle, d_depth, depth_code(depth_dtype), n_frames, float(depth_scale),
+                                                table.ctypes.data))
+
+    def device_view(self):
+        """(raw device address of the [n_voxels][2] float32 {tsdf, weight} array, n_voxels)."""
+        p, n = C.c_void_p(), C.c_int64()
+        L.check(self.ctx.lib.r3d_tsdf_volume(self.handle, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def volume(self):
+        """(tsdf, weight): two [nz][ny][nx] float32 arrays."""
+        p, n = self.device_view()
+        raw = np.empty((n, 2), dtype=np.float32)
+        L.check(self.ctx.lib.r3d_download(self.ctx.handle, raw.ctypes.data, p, raw.nbytes))   # synchronous
+        nx, ny, nz = self.dims
+        return np.ascontiguousarray(raw[:, 0]).reshape(nz, ny, nx), np.ascontiguousarray(raw[:, 1]).reshape(nz, ny, nx)
+
+    def extract_points_device(self, min_weight, d_xyz, d_normals, cap):
+        """Surface points into d_xyz / d_normals ([cap][3] float32 device addresses; d_normals may be None); returns the TRUE
+        number of points, of which at most cap rows were written.  Synchronises."""
+        n = C.c_int64()
+        L.check(self.ctx.lib.r3d_tsdf_extract_points(self.handle, _positive_f32(min_weight, "min_weight"), d_xyz, d_normals, int(cap),
+                                                     C.byref(n)))
+        return n.value
+
+    def extract_point_cloud(self, min_weight=1.0):
+        """(xyz [N,3], normals [N,3]) float32: one point per volume edge whose two voxels have at least min_weight frames each and
+        tsdf values of different sign, in linear voxel order (x fastest), per voxel the x, y, z edge; the normals point towards the
+        cameras (zero rows where the gradient vanishes)."""
+        mw = _positive_f32(min_weight, "min_weight")
+        n = self.extract_points_device(mw, None, None, 0)
+        if n == 0:
+            return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32)
+        d_xyz, d_nrm = self.ctx.alloc(n * 12), self.ctx.alloc(n * 12)
+        try:
+            got = self.extract_points_device(mw, d_xyz.ptr, d_nrm.ptr, n)
+            assert got == n, (got, n)
+            return d_xyz.download(np.float32, 3 * n).reshape(n, 3), d_nrm.download(np.float32, 3 * n).reshape(n, 3)
+        finally:
+            d_xyz.free()
+            d_nrm.free()

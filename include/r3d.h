@@ -614,6 +614,54 @@ int r3d_octree_bt_header(int64_t n_nodes, double resolution, char* h_buf, size_t
 int r3d_voxelset_format_bt(r3d_voxelset* vs, char* h_buf, size_t buf_cap, size_t* n_bytes_out, int64_t* n_nodes_out);
 int r3d_voxelset_write_bt(r3d_voxelset* vs, const char* path, int64_t* n_nodes_out);
 
+/* ---- TSDF volume (csrc/r3d_tsdf.hip; NOT IN THE REFERENCE -- what users of a depth + pose pipeline integrate their frames into
+ * before meshing; no parity with Open3D's UniformTSDFVolume is claimed, this text is the specification).  Where r3d_fuse_frames
+ * concatenates the frames' points, noise and all, the volume averages overlapping frames and yields the zero level set as
+ * oriented points.  Every output bit is a chain of IEEE f32 operations in the order written here: no fused multiply-add,
+ * correctly rounded division and square root, independent of launch geometry and of how the frames are split into calls.
+ * Volume: origin[3], voxel_size, sdf_trunc are doubles rounded once to f32 (o, vs, tr; o finite, vs > 0, tr > 0), nx, ny, nz >= 1
+ *   with nx ny nz < 2^31.  Storage: one float2 {tsdf, weight} per voxel at linear index (z ny + y) nx + x; a fresh or reset volume
+ *   is all zero bytes.
+ * Integration of frame f into voxel (x, y, z), frames in ascending f, all f32:
+ *     c  = o + ((float) idx + 0.5f) * vs                                   per axis
+ *     pc = ((R0 c.x + R1 c.y) + R2 c.z) + t                                per row of the pose, rounded to f32 on the host
+ *     skip unless pc.z > 0
+ *     u  = fx (pc.x / pc.z) + cx;  v = fy (pc.y / pc.z) + cy               the camera's intrinsics rounded to f32
+ *     ui = floorf(u + 0.5f);  vi = floorf(v + 0.5f)                        skip unless 0 <= ui < W and 0 <= vi < H (as floats; NaN skips)
+ *     d  = (float) depth[f][vi][ui] * (float) depth_scale                  skip unless d > 0 and d is finite
+ *     sdf = d - pc.z                                                       skip if sdf < -tr
+ *     tn = fminf(1.0f, sdf / tr);  w1 = w + 1.0f;  tsdf = (tsdf * w + tn) / w1;  w = w1
+ *   h_pose_w2c: n_frames x 12 host doubles [R row-major (9), t (3)], WORLD -> CAMERA: p_cam = R p_w + t -- the quaternion's
+ *   rotation and the pose file's t as they stand, BEFORE the inversion r3d_fuse_frames' table takes.  A depth of 0 is "no
+ *   measurement" (the cloud path keeps its Z = 0 pixels).  Rasters of more than 2^24 pixels a side or 2^31 in all: R3D_ERR_INVALID.
+ *   The frames of a call are applied R3D_TSDF_CHUNK per launch, inside the kernel: a batch costs one read and one write of the
+ *   voxels it touches, not one per frame.  r3d_tsdf_integrate is asynchronous (the pose rows are copied before it returns);
+ *   r3d_tsdf_integrate_host uploads the rasters itself and is synchronous.  NULL volume / camera, a camera of another ctx, an
+ *   unknown dtype, n_frames < 0, NULL depth or poses with n_frames > 0 -> R3D_ERR_INVALID, nothing written; n_frames == 0 -> R3D_OK.
+ * Surface points (synchronises): mw = (float) min_weight > 0; a voxel is valid iff w >= mw.  Voxels in linear index order, per
+ *   voxel v the axes a = x, y, z in that order: n = v + e_a; if n is inside the volume, both are valid and (A < 0) != (B < 0) for
+ *   A = tsdf(v), B = tsdf(n), one point: r = A / (A - B), position = the centre c of v with component a replaced by c_a + r * vs.
+ *   Normal: g(q)_b = T(q + e_b) - T(q - e_b), T = that neighbour's tsdf if it is inside the volume and valid, else tsdf(q);
+ *   m = g(v) + r * (g(n) - g(v)) per component, len = sqrtf((m0 m0 + m1 m1) + m2 m2), normal = m / len, or zeros unless len > 0.
+ *   It points from behind the surface to in front of it, i.e. towards the cameras.
+ *   d_xyz_out / d_normals_out: [cap][3] f32 (normals may be NULL; both may with cap == 0).  *n_out = the true number of points,
+ *   always; at most cap rows are written and nothing beyond them; cap < *n_out is not an error.  Volumes of 2^32 / 3 voxels or
+ *   more: R3D_ERR_UNSUPPORTED.
+ * r3d_tsdf_volume: the device view of the float2 array ([n_voxels][2] f32), valid until destroy; work on the ctx stream. */
+typedef struct r3d_tsdf r3d_tsdf;
+#define R3D_TSDF_CHUNK 32 /* frames per integration launch */
+int r3d_tsdf_create(r3d_ctx* ctx, const double* h_origin, double voxel_size, int nx, int ny, int nz, double sdf_trunc,
+                    r3d_tsdf** out);
+int r3d_tsdf_destroy(r3d_tsdf* vol);
+int r3d_tsdf_reset(r3d_tsdf* vol);
+int r3d_tsdf_integrate(r3d_tsdf* vol, const r3d_camera* cam, const void* d_depth, int depth_dtype, int n_frames,
+                       double depth_scale, const double* h_pose_w2c);
+int r3d_tsdf_integrate_host(r3d_tsdf* vol, const r3d_camera* cam, const void* h_depth, int depth_dtype, int n_frames,
+                            double depth_scale, const double* h_pose_w2c);
+int r3d_tsdf_volume(r3d_tsdf* vol, float** d_tsdf_weight_out, int64_t* n_voxels_out);
+int r3d_tsdf_extract_points(r3d_tsdf* vol, double min_weight, float* d_xyz_out, float* d_normals_out, int64_t cap,
+                            int64_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif
