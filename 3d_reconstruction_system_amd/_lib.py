@@ -103,6 +103,7 @@ SIGNATURES = {
     "r3d_select_quantile_f32": (_i, [_vp, _vp, _i64, _d, _vp, _vp]),
     "r3d_select_quantile_f32_dev": (_i, [_vp, _vp, _i64, _d, _vp]),
     "r3d_trimmed_means_f32": (_i, [_vp, _vp, _i, _i64, _d, _vp]),
+    "r3d_select_quantile_classes_f32": (_i, [_vp, _vp, _vp, _i, _i64, _i64, _d, _vp, _vp]),
     "r3d_icp_plane_residuals": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _f, _vp, _vp]),
     "r3d_icp_plane_accumulate": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _f, _f, _f, _vp]),
     "r3d_plane_step_from_sums": (_i, [_vp, _vp, _vp]),

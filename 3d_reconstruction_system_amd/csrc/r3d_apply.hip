@@ -330,7 +330,15 @@ int r3d_apply_T_many(r3d_ctx* ctx, const void* d_xyz_in, int in_dtype, int64_t n
   R3D_REQUIRE(n_points >= 0, "n_points must be >= 0");
   if (n_transforms == 0 || n_points == 0) return R3D_OK;
   R3D_REQUIRE(d_xyz_in && d_xyz_out && d_xyz_in != d_xyz_out, "NULL device pointer, or the copies would overwrite the cloud they are made from");
+  const size_t block = (size_t)n_points * 3 * r3d_xyz_size(out_dtype);
+  {  // apply_common's range test over ALL the blocks: no copy may land on the cloud the other copies are still made from
+    const uintptr_t in0 = (uintptr_t)d_xyz_in, out0 = (uintptr_t)d_xyz_out;
+    const uintptr_t in1 = in0 + (size_t)n_points * 3 * r3d_xyz_size(in_dtype);
+    const uintptr_t out1 = out0 + block * (size_t)n_transforms;
+    R3D_REQUIRE(in1 <= out0 || out1 <= in0, "the output blocks overlap the input cloud: the copies would overwrite the cloud they are made from");
+  }
   if (in_dtype == R3D_F32 && out_dtype == R3D_F32 && n_transforms <= 65535) {
+    r3d_wrote(ctx, d_xyz_out, block * (size_t)n_transforms);   // an ICP loop working on these points is over
     // the table of matrices travels through a scratch slot; the copy is enqueued from a staging copy that outlives the call
     void* d_T = nullptr;
     if ((rc = r3d_scratch(ctx, 4, (size_t)n_transforms * 16 * sizeof(double), &d_T))) return rc;
@@ -342,7 +350,6 @@ int r3d_apply_T_many(r3d_ctx* ctx, const void* d_xyz_in, int in_dtype, int64_t n
     R3D_HIP(hipGetLastError());
     return R3D_OK;
   }
-  const size_t block = (size_t)n_points * 3 * r3d_xyz_size(out_dtype);
   for (int k = 0; k < n_transforms; ++k) {
     rc = apply_common<false>(ctx, d_xyz_in, in_dtype, n_points, h_Ts + 16 * (size_t)k, static_cast<char*>(d_xyz_out) + block * (size_t)k,
                              out_dtype);

@@ -540,6 +540,30 @@ int r3d_select_quantile_f32_dev(r3d_ctx* ctx, const float* d_values, int64_t n, 
   return R3D_OK;
 }
 
+// r3d_internal_api.h: the per-class selection as plane_sums_impl and r3d_trimmed_means_f32 enqueue it, reachable for the tests
+int r3d_select_quantile_classes_f32(r3d_ctx* ctx, const float* d_values, const unsigned char* d_class, int n_classes, int64_t per_class,
+                                    int64_t n, double q, float* h_values_out, int64_t* h_counts_out) {
+  int rc = r3d_ctx_enter(ctx);
+  if (rc) return rc;
+  R3D_REQUIRE(n_classes >= 1 && n_classes <= kMaxBuckets, "1..%d classes", kMaxBuckets);
+  R3D_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "n must be in [0, 2^31)");
+  R3D_REQUIRE(q >= 0.0 && q <= 1.0, "q must be in [0, 1]");
+  R3D_REQUIRE(d_class ? per_class == 0 : per_class >= 1, "a class byte per element (per_class 0), or contiguous blocks of per_class >= 1");
+  R3D_REQUIRE(n == 0 || d_values != nullptr, "NULL device pointer");
+  R3D_REQUIRE(h_values_out && h_counts_out, "NULL host pointer");
+  Workspace ws;
+  if ((rc = workspace(ctx, n_classes, 0, &ws))) return rc;
+  if ((rc = select_enqueue(ctx, d_values, d_class, n_classes, n, q, ws, per_class))) return rc;
+  SelectOut o[kMaxBuckets];
+  R3D_HIP(hipMemcpyAsync(o, ws.out, (size_t)n_classes * sizeof(SelectOut), hipMemcpyDeviceToHost, ctx->stream));
+  R3D_HIP(hipStreamSynchronize(ctx->stream));
+  for (int c = 0; c < n_classes; ++c) {
+    h_values_out[c] = o[c].value;
+    h_counts_out[c] = (int64_t)o[c].count;
+  }
+  return R3D_OK;
+}
+
 int r3d_trimmed_means_f32(r3d_ctx* ctx, const float* d_values, int n_classes, int64_t per_class, double keep, double* h_means_out) {
   int rc = r3d_ctx_enter(ctx);
   if (rc) return rc;

@@ -30,7 +30,9 @@ int r3d_sort_u64_bits(r3d_ctx* ctx, uint64_t* d_keys, int64_t n_keys, int first_
 int r3d_apply_T_dev(r3d_ctx* ctx, const void* d_xyz_in, int in_dtype, int64_t n_points, const double* d_T,
                     void* d_xyz_out, int out_dtype);
 /* n_transforms copies of one cloud, copy k moved by h_Ts[16 k .. 16 k + 15] (row-major 4x4) and written to block k of
- * d_xyz_out (n_points rows each): the candidates of a multi-start in one call.  Asynchronous. */
+ * d_xyz_out (n_points rows each): the candidates of a multi-start in one call.  The output range, all n_transforms blocks
+ * of it, must not overlap the input cloud anywhere (R3D_ERR_INVALID, nothing written): there is no in-place form, the
+ * copies would overwrite the cloud the other copies are still made from.  Asynchronous. */
 int r3d_apply_T_many(r3d_ctx* ctx, const void* d_xyz_in, int in_dtype, int64_t n_points, const double* h_Ts, int n_transforms,
                      void* d_xyz_out, int out_dtype);
 
@@ -46,7 +48,9 @@ int r3d_nn_index_knn_stats(r3d_nn_index* index, int64_t* h_pairs);
 int r3d_gather_rows(r3d_ctx* ctx, const float* d_xyz, int64_t n_points, const uint32_t* d_rows, int64_t n_out, float* d_xyz_out);
 /* d_inverse_out[d_perm[j]] = j for a permutation of 0..n-1 (uint32), and d_values[k] <- d_table[d_values[k]] in place
  * (0xffffffff where d_values[k] >= n_table): row numbers reported against one ordering of a cloud, re-expressed in another --
- * e.g. neighbours found through an index built before r3d_nn_index_sort_cloud rearranged the cloud.  Asynchronous. */
+ * e.g. neighbours found through an index built before r3d_nn_index_sort_cloud rearranged the cloud.  An entry d_perm[j] >= n
+ * is skipped, and a slot of d_inverse_out that no entry names keeps its previous contents; d_perm and d_inverse_out must
+ * not be the same array.  Asynchronous. */
 int r3d_permutation_invert(r3d_ctx* ctx, const uint32_t* d_perm, int64_t n, uint32_t* d_inverse_out);
 int r3d_remap_u32(r3d_ctx* ctx, uint32_t* d_values, int64_t n, const uint32_t* d_table, int64_t n_table);
 /* Rows first, first + step, ... (n_out of them) of a device xyz cloud into d_xyz_out: strided samples without a trip to the
@@ -57,7 +61,8 @@ int r3d_gather_rows_strided(r3d_ctx* ctx, const float* d_xyz, int64_t n_points, 
 /* The same, for a cloud that still holds rows which are no points: rows with a NaN / inf coordinate end up BEHIND the
  * valid ones (in their input order), *n_valid_out = the number of valid rows in front (synchronous: it waits for the
  * count).  With r3d_cloud_zero_rows_to_nan first -- the (0,0,0) rows gentxtcord emits for pixels without depth
- * (pixel_to_camera.py:34-44) -- this replaces the host-side row filter in front of an ICP (4 ms of NumPy for 307k rows). */
+ * (pixel_to_camera.py:34-44) -- this replaces the host-side row filter in front of an ICP (4 ms of NumPy for 307k rows).
+ * A row is zero when all three coordinates compare equal to 0, so -0.0 counts; every other row keeps its bits. */
 int r3d_nn_index_sort_cloud_valid(r3d_nn_index* index, float* d_xyz, int64_t n_points, uint32_t* d_perm_out,
                                   int64_t* n_valid_out);
 int r3d_cloud_zero_rows_to_nan(r3d_ctx* ctx, float* d_xyz, int64_t n_points);
@@ -86,9 +91,18 @@ int r3d_select_quantile_f32(r3d_ctx* ctx, const float* d_values, int64_t n, doub
 /* The same selection left in HBM: d_out8 receives {float value; uint32 count} (8 bytes).  Asynchronous. */
 int r3d_select_quantile_f32_dev(r3d_ctx* ctx, const float* d_values, int64_t n, double q, void* d_out8);
 /* Robust means of n_classes (<= 32) consecutive blocks of per_class device floats: per block the fp64 mean of the finite values
- * that are <= the block's `keep` order statistic (the rule above); +inf for a block without finite values.  The estimator's
+ * that are <= the block's `keep` order statistic (the rule above); +inf for a block without finite values.  The comparison
+ * is the arithmetic one: every value that ties with the statistic counts, and +0.0 passes a statistic of -0.0.  The estimator's
  * multi-start judges all its candidate poses with one such call per direction.  Synchronous; n_classes doubles come back. */
 int r3d_trimmed_means_f32(r3d_ctx* ctx, const float* d_values, int n_classes, int64_t per_class, double keep, double* h_means_out);
+/* Test hook: the per-class selection that r3d_icp_plane_accumulate (24 direction classes) and r3d_trimmed_means_f32 run, on
+ * its own.  For each of n_classes (1..32) classes the order statistic of rank floor(q (m - 1)) of the class's m finite values
+ * (r3d_select_quantile_f32's rule; +inf and 0 for a class without any) goes to h_values_out[c] / h_counts_out[c].  The class
+ * of element i is d_class[i] (a byte >= n_classes: the element takes part in no class; per_class must be 0), or with
+ * d_class == NULL the contiguous block i / per_class (per_class >= 1; blocks >= n_classes take part in no class).
+ * 0 <= n < 2^31.  Synchronous. */
+int r3d_select_quantile_classes_f32(r3d_ctx* ctx, const float* d_values, const unsigned char* d_class, int n_classes,
+                                    int64_t per_class, int64_t n, double q, float* h_values_out, int64_t* h_counts_out);
 /* One matched pair = (p = src[k], q = tgt[idx[k]], n = tgt_normals[idx[k]]); it is ADMISSIBLE when idx[k] < n_tgt, n is not
  * the zero vector, p, q, n are finite, and (max_d2 < 0 or d2[k] <= max_d2).  Residual r = n.x (p.x - q.x) + n.y (p.y - q.y)
  * + n.z (p.z - q.z) in fp64, left to right.  r3d_icp_plane_residuals writes (float)(r r) per source row, +inf for pairs that

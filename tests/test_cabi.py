@@ -36,7 +36,7 @@ def test_library_exports_every_header_symbol():
     stable, internal = header_symbols(("r3d.h",)), header_symbols(("r3d_internal_api.h",))
     assert not set(stable) & set(internal) and len(internal) >= 15
     for s in ("r3d_selftest_magic_div", "r3d_permutation_invert", "r3d_remap_u32", "r3d_gather_rows_strided", "r3d_select_quantile_f32",
-              "r3d_sort_u64_bits"):
+              "r3d_sort_u64_bits", "r3d_select_quantile_classes_f32"):
         assert s in internal and s not in stable
     assert lib.r3d_version() == 200
 
