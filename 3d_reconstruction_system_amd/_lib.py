@@ -175,6 +175,7 @@ SIGNATURES = {
     "r3d_tsdf_integrate_host": (_i, [_vp, _vp, _vp, _i, _i, _d, _vp]),
     "r3d_tsdf_volume": (_i, [_vp, _pvp, _vp]),
     "r3d_tsdf_extract_points": (_i, [_vp, _d, _vp, _vp, _i64, _vp]),
+    "r3d_tsdf_extract_mesh": (_i, [_vp, _d, _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
 }
 
 _lib = None

@@ -458,6 +458,67 @@ def read_ply_normals(path):
     return np.ascontiguousarray(six[:, :3]), np.ascontiguousarray(six[:, 3:])
 
 
+def _mesh_triangles(triangles, n_vertices, what):
+    t = np.asarray(triangles)
+    if t.ndim != 2 or t.shape[1] != 3 or t.dtype.kind not in 'iu':
+        raise ValueError("%s: triangles must be [M,3] integers, got %s of shape %r" % (what, t.dtype, t.shape))
+    if t.size and (int(t.min()) < 0 or int(t.max()) >= n_vertices):
+        raise ValueError("%s: a triangle names a vertex outside [0, %d)" % (what, n_vertices))
+    return np.ascontiguousarray(t, dtype='<i4')
+
+
+def write_ply_mesh(path, xyz, normals, triangles):
+    """Binary little-endian PLY of an indexed triangle mesh: write_ply_normals' vertex rows (float x y z nx ny nz), then
+    `element face M` with `property list uchar int vertex_indices` -- what MeshLab shades.  triangles: [M,3] integers, every
+    index inside [0, N).  read_ply_mesh reads it back."""
+    xyz = np.ascontiguousarray(xyz, dtype='<f4')
+    normals = np.ascontiguousarray(normals, dtype='<f4')
+    if xyz.ndim != 2 or xyz.shape[1] != 3:
+        raise ValueError("vertices must be [N,3]")
+    if normals.shape != xyz.shape:
+        raise ValueError("normals must be [N,3] like the vertices, got %r for %r" % (normals.shape, xyz.shape))
+    if xyz.shape[0] >= 1 << 31:
+        raise ValueError("a mesh of %d vertices does not fit int indices" % xyz.shape[0])
+    tri = _mesh_triangles(triangles, xyz.shape[0], "write_ply_mesh")
+    faces = np.empty(tri.shape[0], dtype=np.dtype([('n', 'u1'), ('v', '<i4', (3,))]))
+    faces['n'] = 3
+    faces['v'] = tri
+    head = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % xyz.shape[0]
+    head += "".join("property float %s\n" % name for name in ('x', 'y', 'z', 'nx', 'ny', 'nz'))
+    head += "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % tri.shape[0]
+    with open(path, 'wb') as f:
+        f.write(head.encode('ascii'))
+        f.write(np.ascontiguousarray(np.concatenate([xyz, normals], axis=1)).tobytes())
+        f.write(faces.tobytes())
+
+
+def read_ply_mesh(path):
+    """(xyz [N,3] float32, normals [N,3] float32, triangles [M,3] int32) of a PLY in write_ply_mesh's layout."""
+    with open(path, 'rb') as f:
+        data = f.read()
+    end = data.find(b'end_header\n')
+    if end < 0 or not data.startswith(b'ply'):
+        raise ValueError("%s: not a PLY file" % path)
+    lines = [s.strip() for s in data[:end].decode('ascii', errors='replace').split('\n') if s.strip()]
+    want = ["ply", "format binary_little_endian 1.0", None] + ["property float %s" % p for p in ('x', 'y', 'z', 'nx', 'ny', 'nz')] + \
+           [None, "property list uchar int vertex_indices"]
+    lines = [s for s in lines if not s.startswith(("comment", "obj_info"))]
+    ok = len(lines) == len(want) and all(w is None or w == s for w, s in zip(want, lines))
+    ev, ef = (lines[2].split(), lines[9].split()) if ok else ([], [])
+    if not (ok and len(ev) == 3 and ev[:2] == ["element", "vertex"] and len(ef) == 3 and ef[:2] == ["element", "face"]):
+        raise ValueError("%s: not a triangle mesh in write_ply_mesh's layout (float x y z nx ny nz, list uchar int faces)" % path)
+    n, m = int(ev[2]), int(ef[2])
+    start = end + len(b'end_header\n')
+    if n < 0 or m < 0 or len(data) - start < n * 24 + m * 13:
+        raise ValueError("%s: %d vertices and %d faces announced, file is too short" % (path, n, m))
+    six = np.frombuffer(data, dtype='<f4', count=n * 6, offset=start).reshape(n, 6).astype(np.float32)
+    faces = np.frombuffer(data, dtype=np.dtype([('n', 'u1'), ('v', '<i4', (3,))]), count=m, offset=start + n * 24)
+    if m and (faces['n'] != 3).any():
+        raise ValueError("%s: a face is not a triangle" % path)
+    tri = _mesh_triangles(faces['v'].astype(np.int32).reshape(m, 3), n, path)
+    return np.ascontiguousarray(six[:, :3]), np.ascontiguousarray(six[:, 3:]), tri.astype(np.int32)
+
+
 def _parse_rows_native(buf, offset, separator):
     """[N,3] float64 from the text in `buf[offset:]` by the library's threaded parser, or None when a line is not plain
     'x<sep>y<sep>z[...]' in the subset std::from_chars shares with float() -- the caller then parses it Python's way."""

@@ -14,9 +14,12 @@
 //                           fixed by construction, no atomics on the output cursor.
 #include "r3d_internal.h"
 #include "r3d_sort_dev.h"
+#include "r3d_tsdf_dev.h"
 
 #include <cmath>
 #include <new>
+
+using namespace r3d_tsdf_dev;   // TsdfGrid, voxel indexing, crossings, emit_points: shared with r3d_tsdf_mesh.hip
 
 namespace {
 
@@ -32,18 +35,11 @@ struct TsdfFrame {   // world -> camera, f32: p_cam = R p_w + t
 };
 static_assert(sizeof(TsdfFrame) == 64, "one pose row is 64 bytes");
 
-struct TsdfGrid {
-  int nx, ny, nz;
-  float ox, oy, oz, vs, tr;
-};
-
 struct TsdfCam {
   float fx, fy, cx, cy, wf, hf, scale;
   int width;
   uint32_t frame_px;   // height * width
 };
-
-__device__ __forceinline__ float centre(float o, int idx, float vs) { return o + ((float)idx + 0.5f) * vs; }
 
 // one frame into one voxel; returns whether the frame touched it
 template <typename D>
@@ -107,38 +103,6 @@ __global__ __launch_bounds__(kThreads) void tsdf_integrate_kernel(float2* __rest
 }
 
 // ---- extraction ------------------------------------------------------------------------------------------------------------------
-struct Vox {
-  int x, y, z;
-};
-
-__device__ __forceinline__ Vox vox_of(int64_t i, const TsdfGrid& g) {
-  const uint32_t row = (uint32_t)i / (uint32_t)g.nx;   // i < 2^31
-  Vox v;
-  v.x = (int)((uint32_t)i - row * (uint32_t)g.nx);
-  v.z = (int)(row / (uint32_t)g.ny);
-  v.y = (int)(row - (uint32_t)v.z * (uint32_t)g.ny);
-  return v;
-}
-
-__device__ __forceinline__ int64_t step_of(int a, const TsdfGrid& g) { return a == 0 ? 1 : a == 1 ? (int64_t)g.nx : (int64_t)g.nx * g.ny; }
-__device__ __forceinline__ int coord_of(const Vox& v, int a) { return a == 0 ? v.x : a == 1 ? v.y : v.z; }
-__device__ __forceinline__ int dim_of(const TsdfGrid& g, int a) { return a == 0 ? g.nx : a == 1 ? g.ny : g.nz; }
-
-// bit a: the edge from voxel i towards +axis a carries a surface point
-__device__ __forceinline__ uint32_t crossings(const float2* __restrict__ vol, const TsdfGrid& g, int64_t i, float mw) {
-  const float2 A = vol[i];
-  if (!(A.y >= mw)) return 0;
-  const Vox v = vox_of(i, g);
-  uint32_t m = 0;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    if (coord_of(v, a) + 1 >= dim_of(g, a)) continue;
-    const float2 B = vol[i + step_of(a, g)];
-    if (B.y >= mw && ((A.x < 0.0f) != (B.x < 0.0f))) m |= 1u << a;
-  }
-  return m;
-}
-
 __global__ __launch_bounds__(kThreads) void tsdf_count_kernel(const float2* __restrict__ vol, TsdfGrid g, int64_t n, float mw,
                                                               uint32_t* __restrict__ hist) {
   const int64_t base = (int64_t)blockIdx.x * kSortTile + (int64_t)threadIdx.x * kPer;
@@ -154,23 +118,6 @@ __global__ __launch_bounds__(kThreads) void tsdf_count_kernel(const float2* __re
   if (threadIdx.x == 0) hist[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
 }
 
-// the neighbour's tsdf if it is inside the volume and valid, else the voxel's own
-__device__ __forceinline__ float tsdf_or(const float2* __restrict__ vol, int64_t j, bool inside, float mw, float own) {
-  if (!inside) return own;
-  const float2 q = vol[j];
-  return q.y >= mw ? q.x : own;
-}
-
-__device__ __forceinline__ void gradient(const float2* __restrict__ vol, const TsdfGrid& g, int64_t i, const Vox& v, float mw, float (&out)[3]) {
-  const float own = vol[i].x;
-#pragma unroll
-  for (int b = 0; b < 3; ++b) {
-    const int64_t s = step_of(b, g);
-    const int c = coord_of(v, b);
-    out[b] = tsdf_or(vol, i + s, c + 1 < dim_of(g, b), mw, own) - tsdf_or(vol, i - s, c >= 1, mw, own);
-  }
-}
-
 // hist: the tiles' exclusive prefixes (r3d_sort_launch_scan)
 __global__ __launch_bounds__(kThreads) void tsdf_emit_kernel(const float2* __restrict__ vol, TsdfGrid g, int64_t n, float mw,
                                                              const uint32_t* __restrict__ hist, float* __restrict__ xyz_out,
@@ -181,38 +128,8 @@ __global__ __launch_bounds__(kThreads) void tsdf_emit_kernel(const float2* __res
   for (int e = 0; e < kPer; ++e)
     if (base + e < n) mask |= (uint64_t)crossings(vol, g, base + e, mw) << (3 * e);
   __shared__ uint64_t wave_total[kThreads / 64];
-  uint64_t at = hist[blockIdx.x] + r3d_sort::block_exclusive_scan_256((uint64_t)__popcll(mask), wave_total);
-  while (mask && at < cap) {
-    const int bit = __ffsll((long long)mask) - 1;
-    mask &= mask - 1;
-    const int e = bit / 3, a = bit - 3 * e;
-    const int64_t i = base + e, j = i + step_of(a, g);
-    const Vox v = vox_of(i, g);
-    Vox w = v;
-    if (a == 0) ++w.x; else if (a == 1) ++w.y; else ++w.z;
-    const float A = vol[i].x, B = vol[j].x;
-    const float r = A / (A - B);
-    float pos[3] = {centre(g.ox, v.x, g.vs), centre(g.oy, v.y, g.vs), centre(g.oz, v.z, g.vs)};
-    const float moved = pos[a] + r * g.vs;
-    if (a == 0) pos[0] = moved; else if (a == 1) pos[1] = moved; else pos[2] = moved;
-    if (xyz_out) {
-      xyz_out[3 * at + 0] = pos[0];
-      xyz_out[3 * at + 1] = pos[1];
-      xyz_out[3 * at + 2] = pos[2];
-    }
-    if (normals_out) {
-      float gv[3], gn[3], m[3];
-      gradient(vol, g, i, v, mw, gv);
-      gradient(vol, g, j, w, mw, gn);
-#pragma unroll
-      for (int b = 0; b < 3; ++b) m[b] = gv[b] + r * (gn[b] - gv[b]);
-      const float len = sqrtf((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]);
-      const bool ok = len > 0.0f;
-#pragma unroll
-      for (int b = 0; b < 3; ++b) normals_out[3 * at + b] = ok ? m[b] / len : 0.0f;
-    }
-    ++at;
-  }
+  const uint64_t at = hist[blockIdx.x] + r3d_sort::block_exclusive_scan_256((uint64_t)__popcll(mask), wave_total);
+  emit_points(vol, g, base, mw, mask, at, cap, xyz_out, normals_out);
 }
 
 }  // namespace
@@ -289,6 +206,15 @@ int r3d_tsdf_reset(r3d_tsdf* v) {
   int rc = r3d_ctx_enter(v->ctx);
   if (rc) return rc;
   R3D_HIP(hipMemsetAsync(v->d_vol, 0, (size_t)v->n * sizeof(float2), v->ctx->stream));
+  return R3D_OK;
+}
+
+int r3d_tsdf_device_view(r3d_tsdf* v, r3d_ctx** ctx, TsdfGrid* grid, const float2** d_vol, int64_t* n_voxels) {
+  R3D_REQUIRE(v != nullptr, "TSDF volume is NULL");
+  *ctx = v->ctx;
+  *grid = v->g;
+  *d_vol = v->d_vol;
+  *n_voxels = v->n;
   return R3D_OK;
 }
 

@@ -2,12 +2,14 @@
 """TSDF integration of a drop-in working directory on the MI355X: the frames camera_to_world.py fuses into a cloud are averaged in a
 truncated signed distance volume instead, and the volume's zero level set is written as oriented surface points.
 
-    python integrate_tsdf.py --voxel-size S --trunc T [--origin X Y Z] [--dims NX NY NZ] [--margin M] [--min-weight W]
+    python integrate_tsdf.py --voxel-size S --trunc T [--origin X Y Z] [--dims NX NY NZ] [--margin M] [--min-weight W] [--mesh]
 
 Run from a directory holding ./camera_pose/image_colmap_simi_2.txt and ./depth/ (the inputs of camera_to_world.py; the same
 environment overrides apply: R3D_FX .. R3D_CY, R3D_POSE_SCALE, R3D_DEVICE).  Writes ./ply/tsdf_surface.ply: binary PLY, float
 x y z nx ny nz, the normals pointing towards the cameras.  Without --origin / --dims the volume is the bounding box of the camera
 centres padded by M on every side (default M = 16 T), cut into voxels of S.  A depth of 0 is "no measurement".
+--mesh also writes ./ply/tsdf_mesh.ply: the same vertices plus the marching-cubes triangles over them (a face element MeshLab
+shades), and prints a second line "triangles M -> path".
 """
 import argparse
 import math
@@ -22,6 +24,7 @@ else:
 
 POSE_FILE = './camera_pose/image_colmap_simi_2.txt'
 OUT_FILE = './ply/tsdf_surface.ply'
+MESH_FILE = './ply/tsdf_mesh.ply'
 
 
 def parse_args(argv):
@@ -33,6 +36,7 @@ def parse_args(argv):
     p.add_argument("--margin", type=float, default=None,
                    help="padding of the camera centres' bounding box when --origin / --dims are not given (default 16 x --trunc)")
     p.add_argument("--min-weight", type=float, default=1.0, help="frames a voxel needs to count (default 1)")
+    p.add_argument("--mesh", action="store_true", help="also write the triangle mesh of the surface to %s" % MESH_FILE)
     args = p.parse_args(argv)
     for name in ("voxel_size", "trunc", "min_weight"):
         v = getattr(args, name)
@@ -80,12 +84,16 @@ def main(argv=None):
     vol.integrate(depths, quats, ts, intrinsics=_common.intrinsics())
     _common.stamp("integrate")
     xyz, normals = vol.extract_point_cloud(args.min_weight)
+    mesh = vol.extract_triangle_mesh(args.min_weight) if args.mesh else None
     vol.close()
     _common.stamp("extract")
     os.makedirs(os.path.dirname(OUT_FILE), exist_ok=True)
     r3d.cloud_io.write_ply_normals(OUT_FILE, xyz, normals)
     print("origin %.9g %.9g %.9g dims %d %d %d voxel %.9g trunc %.9g frames %d points %d -> %s"
           % (origin[0], origin[1], origin[2], dims[0], dims[1], dims[2], args.voxel_size, args.trunc, len(names), len(xyz), OUT_FILE))
+    if mesh is not None:
+        r3d.cloud_io.write_ply_mesh(MESH_FILE, *mesh)
+        print("triangles %d -> %s" % (len(mesh[2]), MESH_FILE))
 
 
 if __name__ == "__main__":

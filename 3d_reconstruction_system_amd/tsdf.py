@@ -1,7 +1,7 @@
 """Dense TSDF volume on the MI355X: depth frames + poses are integrated into a truncated signed distance volume, and its zero
-level set comes back as oriented surface points -- what users of a depth + pose pipeline expect before meshing (Open3D's
-UniformTSDFVolume; no parity with Open3D is claimed).  Where fuse_frames concatenates the frames' points, the volume averages
-overlapping frames.  Semantics: include/r3d.h (r3d_tsdf_*) and DESIGN.md section 4.5i.
+level set comes back as oriented surface points or as an indexed triangle mesh over those points (marching cubes) -- what users
+of a depth + pose pipeline expect (Open3D's UniformTSDFVolume; no parity with Open3D is claimed).  Where fuse_frames concatenates the frames' points, the volume averages
+overlapping frames.  Semantics: include/r3d.h (r3d_tsdf_*) and DESIGN.md sections 4.5i and 4.5j.
 
 The volume takes the inputs camera_to_world.py already has: [F,H,W] depth, one pose-file row per frame, a pinhole camera.  Its
 poses are WORLD -> CAMERA (p_cam = R p_w + t: the pose file's quaternion and t as they stand, poses_w2c), not the inverted table
@@ -154,3 +154,33 @@ class TSDFVolume:
         finally:
             d_xyz.free()
             d_nrm.free()
+
+    def extract_mesh_device(self, min_weight, d_xyz, d_normals, cap_vertices, d_tri, cap_triangles):
+        """The indexed triangle mesh into d_xyz / d_normals ([cap_vertices][3] float32) and d_tri ([cap_triangles][3] int32) at raw
+        device addresses (d_normals may be None; d_xyz with cap_vertices == 0 and d_tri with cap_triangles == 0 too); returns the
+        TRUE (n_vertices, n_triangles), of which at most cap_* rows each were written.  The vertices are extract_points_device's
+        rows.  Synchronises."""
+        mw = _positive_f32(min_weight, "min_weight")
+        nv, nt = C.c_int64(), C.c_int64()
+        L.check(self.ctx.lib.r3d_tsdf_extract_mesh(self.handle, mw, d_xyz, d_normals, int(cap_vertices), d_tri, int(cap_triangles),
+                                                   C.byref(nv), C.byref(nt)))
+        return nv.value, nt.value
+
+    def extract_triangle_mesh(self, min_weight=1.0):
+        """(xyz [N,3] float32, normals [N,3] float32, triangles [M,3] int32): marching cubes over the cells whose eight voxels
+        have at least min_weight frames each.  The vertices are extract_point_cloud's rows (one per crossing volume edge, so the
+        mesh is welded by construction); a triangle (a, b, c) winds so that (b - a) x (c - a) points towards the cameras, like the
+        vertex normals."""
+        mw = _positive_f32(min_weight, "min_weight")
+        n, m = self.extract_mesh_device(mw, None, None, 0, None, 0)
+        if n == 0:
+            return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32)
+        d_xyz, d_nrm, d_tri = self.ctx.alloc(n * 12), self.ctx.alloc(n * 12), self.ctx.alloc(max(m, 1) * 12)
+        try:
+            got = self.extract_mesh_device(mw, d_xyz.ptr, d_nrm.ptr, n, d_tri.ptr if m else None, m)
+            assert got == (n, m), (got, n, m)
+            tri = d_tri.download(np.int32, 3 * m).reshape(m, 3) if m else np.zeros((0, 3), np.int32)
+            return d_xyz.download(np.float32, 3 * n).reshape(n, 3), d_nrm.download(np.float32, 3 * n).reshape(n, 3), tri
+        finally:
+            for b in (d_xyz, d_nrm, d_tri):
+                b.free()

@@ -662,6 +662,39 @@ int r3d_tsdf_volume(r3d_tsdf* vol, float** d_tsdf_weight_out, int64_t* n_voxels_
 int r3d_tsdf_extract_points(r3d_tsdf* vol, double min_weight, float* d_xyz_out, float* d_normals_out, int64_t cap,
                             int64_t* n_out);
 
+/* ---- TSDF mesh (csrc/r3d_tsdf_mesh.hip; marching cubes over the volume above; this text is the specification).  The result is
+ * an INDEXED triangle mesh.  Its vertices are exactly the rows r3d_tsdf_extract_points writes for the same min_weight: same
+ * count, same order, same bits for positions and normals.  The vertex of the volume edge "(voxel v, axis a)" is that edge's
+ * surface point and its index is its rank in that order, so the mesh is welded by construction.  What is specified here is the
+ * connectivity, which is integer-exact: the same bits whatever the launch geometry.
+ * Cell: one per voxel (x, y, z) with x < nx-1, y < ny-1, z < nz-1.  Corner k = dx + 2 dy + 4 dz is voxel (x+dx, y+dy, z+dz).  A
+ *   cell is active iff all 8 corners are valid (w >= mw, mw = (float) min_weight > 0); corner k is negative iff tsdf < 0 (the
+ *   points' predicate (A < 0)); the case is m = sum of negative(k) << k.  Inactive cells emit nothing.  In an active cell a cell
+ *   edge crosses iff its two corners differ in sign, which is exactly when the edge owns a surface point: every index a triangle
+ *   names exists.
+ * Cell edges: e = 4 a + j, a = the edge's axis, j = u + 2 v with (u, v) the offsets of the edge's lower corner along the two
+ *   other axes in ascending axis order.  Edge e belongs to the voxel at that lower corner, on axis a.
+ * Case table (built by construction -- tools/make_mc_table.py writes csrc/r3d_mc_table.h -- so that shared faces always agree):
+ *   each of the 6 cell faces lists its 4 corners counter-clockwise as seen from outside the cell.  Walking that cycle, every
+ *   maximal run of negative corners preceded by a non-negative corner gives one directed segment: from the cell edge where the
+ *   walk enters the run (between the non-negative corner and the run's first corner) to the cell edge where it leaves the run.
+ *   A face with two diagonal negative corners gives two segments, each cutting off one negative corner; the rule reads only the
+ *   face's own four signs, so the two cells sharing a face draw the same segments in opposite directions.  Faces with 0 or 4
+ *   negative corners give nothing.  The segments of a case form closed directed loops over its crossing edges.  Loops are taken
+ *   in ascending order of their smallest edge id; each starts at that edge and follows the segments as l0, l1, ...; its
+ *   triangles are the fan (l0, l_i, l_i+1), i = 1 .. len-2.  That is 820 triangles over the 256 cases, at most 5 per case
+ *   (cases with 0..5 triangles: 2, 16, 50, 80, 76, 32).  With a single negative corner, (b - a) x (c - a) of the triangle
+ *   (a, b, c) points away from that corner: towards the cameras, the side the vertex normals point to.
+ * Order: cells in linear voxel order (z ny + y) nx + x of corner 0; within a cell the table's order.  Indices are int32.
+ * r3d_tsdf_extract_mesh synchronises (for the counts; the rows are enqueued on the ctx stream).  *n_vertices_out and
+ *   *n_triangles_out are the true counts, always; at most cap_vertices rows of d_xyz_out / d_normals_out ([cap_vertices][3] f32)
+ *   and cap_triangles rows of d_tri_out ([cap_triangles][3] int32) are written and nothing beyond them; triangle rows are
+ *   written as they are, even where an index is >= cap_vertices.  d_normals_out may be NULL; d_xyz_out may be NULL with
+ *   cap_vertices == 0, d_tri_out with cap_triangles == 0.  Argument errors as for r3d_tsdf_extract_points (R3D_ERR_INVALID,
+ *   nothing written).  5 n_voxels >= 2^32, or more than 2^31 - 1 vertices: R3D_ERR_UNSUPPORTED.  The volume is not modified. */
+int r3d_tsdf_extract_mesh(r3d_tsdf* vol, double min_weight, float* d_xyz_out, float* d_normals_out, int64_t cap_vertices,
+                          int32_t* d_tri_out, int64_t cap_triangles, int64_t* n_vertices_out, int64_t* n_triangles_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,8 @@ volume around the room.  hipEvent medians of `reps` runs after two warm-ups, the
 outside the timed window before every run:
   batched      one r3d_tsdf_integrate call of all frames (the frame loop inside the kernel, R3D_TSDF_CHUNK frames per launch);
   per_frame    the same kernel launched one frame at a time (one call per frame);
-  extract      r3d_tsdf_extract_points (count + scan + emit, with normals) of the integrated volume.
+  extract      r3d_tsdf_extract_points (count + scan + emit, with normals) of the integrated volume;
+  mesh         r3d_tsdf_extract_mesh (count + scan + vertices + triangles) of the same volume, alternating with extract.
 Roofs are printed from shapes, not measured: algorithmic bytes of the batched form (16 B per voxel and launch + the rasters once)
 against 8 TB/s, and voxel-frames x the per-voxel-frame instruction count of the disassembly against the VALU rate.
 CPU leg, as reported and not optimised against: tests/tsdf_ref.py (NumPy, one thread) on a 64^3 volume and 10 frames.
@@ -73,7 +74,11 @@ for n in (256, 512):
     batched()
     count = vol.extract_points_device(1.0, None, None, 0)
     d_xyz, d_nrm = ctx.alloc(max(count, 1) * 12), ctx.alloc(max(count, 1) * 12)
-    (e_ms,) = timed_alternating([lambda: vol.extract_points_device(1.0, d_xyz.ptr, d_nrm.ptr, count)], lambda: None)
+    n_v, n_t = vol.extract_mesh_device(1.0, None, None, 0, None, 0)
+    assert n_v == count
+    d_tri = ctx.alloc(max(n_t, 1) * 12)
+    e_ms, m_ms = timed_alternating([lambda: vol.extract_points_device(1.0, d_xyz.ptr, d_nrm.ptr, count),
+                                    lambda: vol.extract_mesh_device(1.0, d_xyz.ptr, d_nrm.ptr, count, d_tri.ptr, n_t)], lambda: None)
     _, w = vol.volume()
     pairs = float(w.sum())                               # (voxel, frame) pairs that passed every test
     launches = -(-FRAMES // T.CHUNK)
@@ -82,12 +87,12 @@ for n in (256, 512):
     roof_valu_ms = voxels * FRAMES * INSTR_PER_VOXEL_FRAME / VALU_LANE_INSTR_PER_S * 1e3
     line = {"volume": "%d^3" % n, "voxel_size": round(vs, 6), "frames": FRAMES, "raster": [H, W], "dtype": "uint8", "reps": reps,
             "integrate_batched_ms": b_ms, "integrate_per_frame_ms": p_ms, "per_frame_over_batched": round(p_ms / b_ms, 3),
-            "extract_ms": e_ms, "surface_points": int(count), "voxel_frame_pairs_accepted": pairs,
+            "extract_ms": e_ms, "mesh_ms": m_ms, "surface_points": int(count), "triangles": int(n_t), "voxel_frame_pairs_accepted": pairs,
             "voxel_frames_per_s_batched": round(voxels * FRAMES / (b_ms * 1e-3), 1),
             "roof_hbm_ms_8TBps": round(roof_bytes_ms, 4), "roof_valu_ms_at_%d_instr" % INSTR_PER_VOXEL_FRAME: round(roof_valu_ms, 4)}
     print(json.dumps(line), flush=True)
     lines.append(line)
-    for b in (d_xyz, d_nrm):
+    for b in (d_xyz, d_nrm, d_tri):
         b.free()
     vol.close()
 if cpu_leg:
