@@ -176,6 +176,7 @@ SIGNATURES = {
     "r3d_tsdf_volume": (_i, [_vp, _pvp, _vp]),
     "r3d_tsdf_extract_points": (_i, [_vp, _d, _vp, _vp, _i64, _vp]),
     "r3d_tsdf_extract_mesh": (_i, [_vp, _d, _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "r3d_tsdf_raycast": (_i, [_vp, _vp, _i, _vp, _d, _d, _d, _d, _vp, _vp, _vp]),
 }
 
 _lib = None

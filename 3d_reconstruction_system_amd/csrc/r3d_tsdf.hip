@@ -28,12 +28,7 @@ constexpr int kChunk = R3D_TSDF_CHUNK;   // frames per launch = rows of one slot
 constexpr int kSlots = 4;                // slots of the pose table: a call's chunks ride the ring without waiting for each other
 constexpr int kPer = kSortTile / kThreads;   // consecutive voxels per thread of the extraction kernels
 
-struct TsdfFrame {   // world -> camera, f32: p_cam = R p_w + t
-  float r[9];
-  float t[3];
-  float pad[4];
-};
-static_assert(sizeof(TsdfFrame) == 64, "one pose row is 64 bytes");
+using TsdfFrame = TsdfPoseRow;   // world -> camera, f32: p_cam = R p_w + t (the ring's row type: r3d_tsdf_dev.h)
 
 struct TsdfCam {
   float fx, fy, cx, cy, wf, hf, scale;
@@ -215,6 +210,15 @@ int r3d_tsdf_device_view(r3d_tsdf* v, r3d_ctx** ctx, TsdfGrid* grid, const float
   *grid = v->g;
   *d_vol = v->d_vol;
   *n_voxels = v->n;
+  return R3D_OK;
+}
+
+int r3d_tsdf_pose_slot(r3d_tsdf* v, TsdfPoseRow** h_rows, TsdfPoseRow** d_rows, hipEvent_t* ev) {
+  R3D_REQUIRE(v != nullptr, "TSDF volume is NULL");
+  const unsigned s = v->next_slot++ % kSlots;
+  *h_rows = v->h_table + (size_t)s * kChunk;
+  *d_rows = v->d_table + (size_t)s * kChunk;
+  *ev = v->ev[s];
   return R3D_OK;
 }
 

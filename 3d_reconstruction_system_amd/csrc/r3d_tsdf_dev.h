@@ -18,6 +18,15 @@ struct TsdfGrid {
   float ox, oy, oz, vs, tr;
 };
 
+// One row of the volume's pose ring (r3d_tsdf.hip), f32, 64 bytes: the world -> camera rotation, row-major, and a vector t --
+// the pose's translation for integration (p_cam = R p_w + t), the camera centre in the world for ray casting.
+struct TsdfPoseRow {
+  float r[9];
+  float t[3];
+  float pad[4];
+};
+static_assert(sizeof(TsdfPoseRow) == 64, "one pose row is 64 bytes");
+
 __device__ __forceinline__ float centre(float o, int idx, float vs) { return o + ((float)idx + 0.5f) * vs; }
 
 struct Vox {
@@ -106,7 +115,31 @@ __device__ __forceinline__ void emit_points(const float2* __restrict__ vol, cons
   }
 }
 
+// The eight voxels of the cell whose corner 0 is voxel i (which has a neighbour on every + side): q[k], k = dx + 2 dy + 4 dz, the
+// mesh's corner numbering.  {tsdf, weight} of a voxel is one 8-byte load; the x pair of a row is 16 contiguous bytes.
+__device__ __forceinline__ void load_cell(const float2* __restrict__ vol, const TsdfGrid& g, int64_t i, float2 (&q)[8]) {
+  const int64_t sy = g.nx, sz = (int64_t)g.nx * g.ny;
+#pragma unroll
+  for (int k = 0; k < 8; k += 2) {
+    const float2* row = vol + (i + (int64_t)((k >> 1) & 1) * sy + (int64_t)(k >> 2) * sz);
+    q[k] = row[0];
+    q[k + 1] = row[1];
+  }
+}
+
+// S = the trilinear value of the cell's tsdf T[k] at fractions f = (f_x, f_y, f_z): x first, then y, then z
+__device__ __forceinline__ float trilinear(const float (&T)[8], const float (&f)[3]) {
+  const float c00 = T[0] + f[0] * (T[1] - T[0]), c10 = T[2] + f[0] * (T[3] - T[2]);   // c[jy][jz]
+  const float c01 = T[4] + f[0] * (T[5] - T[4]), c11 = T[6] + f[0] * (T[7] - T[6]);
+  const float b0 = c00 + f[1] * (c10 - c00), b1 = c01 + f[1] * (c11 - c01);
+  return b0 + f[2] * (b1 - b0);
+}
+
 }  // namespace r3d_tsdf_dev
 
 // r3d_tsdf.hip: what a kernel outside that file needs to read a volume (r3d_tsdf_mesh.hip)
 int r3d_tsdf_device_view(r3d_tsdf* vol, r3d_ctx** ctx, r3d_tsdf_dev::TsdfGrid* grid, const float2** d_vol, int64_t* n_voxels);
+// r3d_tsdf.hip: the next slot of the volume's pose ring for a launch outside that file (r3d_tsdf_raycast.hip).  A slot is
+// R3D_TSDF_CHUNK rows, pinned (*h_rows) and in HBM (*d_rows).  The caller keeps the integrate path's discipline:
+// hipEventSynchronize(*ev), fill the pinned rows, hipMemcpyAsync them to *d_rows on the ctx stream, hipEventRecord(*ev) there.
+int r3d_tsdf_pose_slot(r3d_tsdf* vol, r3d_tsdf_dev::TsdfPoseRow** h_rows, r3d_tsdf_dev::TsdfPoseRow** d_rows, hipEvent_t* ev);

@@ -3,6 +3,7 @@
 truncated signed distance volume instead, and the volume's zero level set is written as oriented surface points.
 
     python integrate_tsdf.py --voxel-size S --trunc T [--origin X Y Z] [--dims NX NY NZ] [--margin M] [--min-weight W] [--mesh]
+                             [--raycast]
 
 Run from a directory holding ./camera_pose/image_colmap_simi_2.txt and ./depth/ (the inputs of camera_to_world.py; the same
 environment overrides apply: R3D_FX .. R3D_CY, R3D_POSE_SCALE, R3D_DEVICE).  Writes ./ply/tsdf_surface.ply: binary PLY, float
@@ -10,6 +11,8 @@ x y z nx ny nz, the normals pointing towards the cameras.  Without --origin / --
 centres padded by M on every side (default M = 16 T), cut into voxels of S.  A depth of 0 is "no measurement".
 --mesh also writes ./ply/tsdf_mesh.ply: the same vertices plus the marching-cubes triangles over them (a face element MeshLab
 shades), and prints a second line "triangles M -> path".
+--raycast also casts the volume from every pose of the pose file at the input rasters' size and writes the depth the model
+predicts (float32, 0 = no surface) to ./raycast/<frame name>.npy, and prints a further line "raycast F frames -> ./raycast/".
 """
 import argparse
 import math
@@ -25,6 +28,7 @@ else:
 POSE_FILE = './camera_pose/image_colmap_simi_2.txt'
 OUT_FILE = './ply/tsdf_surface.ply'
 MESH_FILE = './ply/tsdf_mesh.ply'
+RAYCAST_DIR = './raycast/'
 
 
 def parse_args(argv):
@@ -37,6 +41,8 @@ def parse_args(argv):
                    help="padding of the camera centres' bounding box when --origin / --dims are not given (default 16 x --trunc)")
     p.add_argument("--min-weight", type=float, default=1.0, help="frames a voxel needs to count (default 1)")
     p.add_argument("--mesh", action="store_true", help="also write the triangle mesh of the surface to %s" % MESH_FILE)
+    p.add_argument("--raycast", action="store_true",
+                   help="also ray-cast the volume from every pose and write the predicted depth to %s<frame name>.npy" % RAYCAST_DIR)
     args = p.parse_args(argv)
     for name in ("voxel_size", "trunc", "min_weight"):
         v = getattr(args, name)
@@ -59,6 +65,26 @@ def default_volume(w2c, voxel_size, margin):
     lo, hi = centres.min(axis=0) - margin, centres.max(axis=0) + margin
     dims = [max(1, int(math.ceil((hi[a] - lo[a]) / voxel_size))) for a in range(3)]
     return lo, dims
+
+
+def raycast_depth(r3d, vol, quats, ts, shape, min_weight):
+    """[F,H,W] float32: the depth the volume predicts at every pose -- the depth map alone (4 bytes per pixel on the device and
+    over the bus, not the 28 of all three maps), one launch's worth of views at a time."""
+    import numpy as np
+    h, w = shape
+    table = r3d.poses_w2c(quats, ts)
+    cam = vol.ctx.camera(h, w, *_common.intrinsics())
+    out = np.empty((len(table), h, w), np.float32)
+    chunk = 32
+    buf = vol.ctx.alloc(max(min(chunk, len(table)) * h * w * 4, 16))
+    try:
+        for lo in range(0, len(table), chunk):
+            n = min(chunk, len(table) - lo)
+            vol.raycast_device(cam, n, table[lo:lo + n], buf.ptr, None, None, min_weight=min_weight)
+            out[lo:lo + n] = buf.download(np.float32, n * h * w).reshape(n, h, w)
+    finally:
+        buf.free()
+    return out
 
 
 def main(argv=None):
@@ -85,6 +111,7 @@ def main(argv=None):
     _common.stamp("integrate")
     xyz, normals = vol.extract_point_cloud(args.min_weight)
     mesh = vol.extract_triangle_mesh(args.min_weight) if args.mesh else None
+    cast = raycast_depth(r3d, vol, quats, ts, depths.shape[-2:], args.min_weight) if args.raycast else None
     vol.close()
     _common.stamp("extract")
     os.makedirs(os.path.dirname(OUT_FILE), exist_ok=True)
@@ -94,6 +121,12 @@ def main(argv=None):
     if mesh is not None:
         r3d.cloud_io.write_ply_mesh(MESH_FILE, *mesh)
         print("triangles %d -> %s" % (len(mesh[2]), MESH_FILE))
+    if cast is not None:
+        import numpy as np
+        os.makedirs(RAYCAST_DIR, exist_ok=True)
+        for name, raster in zip(names, cast):
+            np.save(os.path.join(RAYCAST_DIR, name + ".npy"), raster)
+        print("raycast %d frames -> %s" % (len(names), RAYCAST_DIR))
 
 
 if __name__ == "__main__":

@@ -46,6 +46,20 @@ def _positive_f32(v, what):
     return f
 
 
+def _ray_range(step, t_near, t_far, voxel_size):
+    """(step, t_near, t_far) as floats: step=None means voxel_size; t_near finite and >= 0, t_far > t_near (inf allowed), in float32."""
+    s = _positive_f32(voxel_size if step is None else step, "step")
+    try:
+        tn, tf = float(t_near), float(t_far)
+    except (TypeError, ValueError):
+        raise ValueError("t_near and t_far must be numbers, got %r and %r" % (t_near, t_far))
+    with np.errstate(over="ignore"):
+        n32, f32 = np.float32(tn), np.float32(tf)
+    if isinstance(t_near, bool) or isinstance(t_far, bool) or not (np.isfinite(n32) and n32 >= 0 and f32 > n32):
+        raise ValueError("need 0 <= t_near < t_far with t_near finite (in float32), got %r and %r" % (t_near, t_far))
+    return s, tn, tf
+
+
 def _pose_rows(poses, n_frames):
     p = np.ascontiguousarray(poses, dtype=np.float64)
     if p.ndim != 2 or p.shape != (n_frames, 12):
@@ -183,4 +197,51 @@ class TSDFVolume:
             return d_xyz.download(np.float32, 3 * n).reshape(n, 3), d_nrm.download(np.float32, 3 * n).reshape(n, 3), tri
         finally:
             for b in (d_xyz, d_nrm, d_tri):
+                b.free()
+
+    def raycast_device(self, cam, n_views, poses_w2c, d_depth, d_vertex, d_normal, min_weight=1.0, step=None, t_near=0.0,
+                       t_far=math.inf):
+        """Ray-cast the volume from n_views poses (poses_w2c: [n_views,12] host rows, as integrate_device takes) through cam into
+        d_depth ([n_views][H][W] float32) and d_vertex / d_normal ([n_views][H][W][3] float32, world coordinates) at raw device
+        addresses; any of the three may be None.  A pixel without a surface has depth 0 and NaN vertex and normal rows.  step=None
+        means voxel_size; step + voxel_size <= sdf_trunc keeps both samples that bracket the surface inside the untruncated band.
+        Asynchronous on the context's stream."""
+        n_views = int(n_views)
+        if n_views < 0:
+            raise ValueError("n_views must be >= 0, got %d" % n_views)
+        table = _pose_rows(poses_w2c, n_views)
+        s, tn, tf = _ray_range(step, t_near, t_far, self.voxel_size)
+        L.check(self.ctx.lib.r3d_tsdf_raycast(self.handle, cam.handle, n_views, table.ctypes.data, _positive_f32(min_weight, "min_weight"),
+                                              s, tn, tf, d_depth, d_vertex, d_normal))
+
+    def raycast(self, quats_xyzw, ts, shape, intrinsics=REF_INTRINSICS, min_weight=1.0, step=None, t_near=0.0, t_far=math.inf):
+        """(depth [F,H,W], vertices [F,H,W,3], normals [F,H,W,3]) float32: what the volume predicts for a camera of `intrinsics`
+        and shape = (H, W) at the pose-file rows (quats_xyzw, ts): z-depth, the surface point in the world and the normal towards
+        the camera side, from a march along every pixel's ray in steps of `step` (None: voxel_size) between the distances t_near
+        and t_far, over the cells whose eight voxels have at least min_weight frames.  A pixel without a surface has depth 0 ("no
+        measurement": the raster integrates back as it is) and NaN vertex and normal rows.  step + voxel_size <= sdf_trunc keeps
+        both samples that bracket the surface inside the untruncated band.  The hit rows of vertices / normals are a target cloud
+        with tgt_normals for icp_point_to_plane.  Synchronous."""
+        try:
+            h, w = [int(v) for v in shape]
+            exact = all(int(v) == v and not isinstance(v, bool) for v in shape)
+        except (TypeError, ValueError):
+            raise ValueError("shape must be (H, W), two integers >= 1, got %r" % (shape,))
+        if not exact or h < 1 or w < 1:
+            raise ValueError("shape must be (H, W), two integers >= 1, got %r" % (shape,))
+        mw = _positive_f32(min_weight, "min_weight")
+        _ray_range(step, t_near, t_far, self.voxel_size)   # (raycast_device checks again: this raises before anything is allocated)
+        table = poses_w2c(quats_xyzw, ts)
+        f = table.shape[0]
+        if f == 0:
+            return np.zeros((0, h, w), np.float32), np.zeros((0, h, w, 3), np.float32), np.zeros((0, h, w, 3), np.float32)
+        cam = self.ctx.camera(h, w, *intrinsics)
+        n = f * h * w
+        d_depth, d_vtx, d_nrm = self.ctx.alloc(n * 4), self.ctx.alloc(n * 12), self.ctx.alloc(n * 12)
+        try:
+            self.raycast_device(cam, f, table, d_depth.ptr, d_vtx.ptr, d_nrm.ptr, mw, step, t_near, t_far)
+            return (d_depth.download(np.float32, n).reshape(f, h, w), d_vtx.download(np.float32, 3 * n).reshape(f, h, w, 3),
+                    d_nrm.download(np.float32, 3 * n).reshape(f, h, w, 3))
+        finally:
+            for b in (d_depth, d_vtx, d_nrm):
                 b.free()

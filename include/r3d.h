@@ -695,6 +695,52 @@ int r3d_tsdf_extract_points(r3d_tsdf* vol, double min_weight, float* d_xyz_out, 
 int r3d_tsdf_extract_mesh(r3d_tsdf* vol, double min_weight, float* d_xyz_out, float* d_normals_out, int64_t cap_vertices,
                           int32_t* d_tri_out, int64_t cap_triangles, int64_t* n_vertices_out, int64_t* n_triangles_out);
 
+/* ---- TSDF ray casting (csrc/r3d_tsdf_raycast.hip; the volume above seen from a camera: the depth, surface-point and normal image
+ * the model predicts for a pose -- the third leg of integrate / ray cast / register; this text is the specification).  A ray-cast
+ * vertex and normal map is a target cloud with normals for r3d's point-to-plane ICP (frame-to-model registration), and the depth
+ * map is a hole-filled raster that integrates back.  Every output bit is a chain of IEEE f32 operations in the order written
+ * here: no fused multiply-add, correctly rounded division and square root, f32 denormals kept, independent of launch geometry and
+ * of how the views are split into launches.
+ * Pose, per view: h_pose_w2c holds the 12-double world -> camera rows r3d_tsdf_integrate takes (R row-major, t).  The host
+ *   computes the camera centre in double, in this order: C_k = -((R[0][k] t0 + R[1][k] t1) + R[2][k] t2), then rounds R (9) and
+ *   C (3) once to f32.  The intrinsics are the camera's, rounded to f32.
+ * Ray of pixel (row vi, column ui):
+ *     x = ((float) ui - cx) / fx;  y = ((float) vi - cy) / fy
+ *     len = sqrtf((x x + y y) + 1.0f);  n = (x / len, y / len, 1.0f / len)      the unit direction in the camera frame
+ *     dw_k = (R[0][k] n.x + R[1][k] n.y) + R[2][k] n.z                          the direction in the world
+ *   t is Euclidean distance along the ray: p(t)_a = C_a + t * dw_a.
+ * Sample domain: the box of voxel centres, lo_a = o_a + 0.5f * vs, hi_a = o_a + ((float) (n_a - 1) + 0.5f) * vs.  Slab test per
+ *   axis a = x, y, z from tmin = (float) t_near, tmax = (float) t_far: if dw_a == 0 the ray misses unless lo_a <= C_a <= hi_a;
+ *   otherwise q1 = (lo_a - C_a) / dw_a, q2 = (hi_a - C_a) / dw_a, tmin = fmaxf(tmin, fminf(q1, q2)),
+ *   tmax = fminf(tmax, fmaxf(q1, q2)).  The ray misses unless tmin <= tmax.  A volume with any n_a == 1 has no cell: every
+ *   pixel is a miss.
+ * Sample at t: ivs = 1.0f / vs (once);  g_a = (p_a - o_a) * ivs - 0.5f;  i_a = floorf(g_a);  f_a = g_a - i_a.  The sample is
+ *   invalid unless 0 <= i_a <= n_a - 2 for all axes (compared as floats; NaN fails; where (float) (n_a - 2) is inexact, n_a >
+ *   2^24 + 2, the integer i_a <= n_a - 2 must hold too) and all eight voxels i + d, d in {0, 1}^3, have w >= mw = (float)
+ *   min_weight.  Otherwise it is the trilinear value, x first, then y, then z, with T0 / T1 the tsdf of the x pair:
+ *     c[jy][jz] = T0 + f_x * (T1 - T0);  b[jz] = c[0][jz] + f_y * (c[1][jz] - c[0][jz]);  S = b[0] + f_z * (b[1] - b[0])
+ * March: s = (float) step.  For k = 0, 1, ..., 65536: t_k = tmin + (float) k * s; the loop stops, and the pixel is a miss, unless
+ *   t_k <= tmax.  The first k >= 1 at which sample k-1 and sample k are both valid with A = S_(k-1) > 0 and B = S_k <= 0 is the
+ *   hit; nothing else ends the march.  On the hit: r = A / (A - B);  t* = t_(k-1) + r * s.
+ * Hit point: one more sample at t*; invalid -> miss.  The gradient is analytic, from that cell's eight corners: for axis a with
+ *   the other two axes (b, c) in ascending order, D[jb][jc] = T(a=1, jb, jc) - T(a=0, jb, jc);
+ *   e[jc] = D[0][jc] + f_b * (D[1][jc] - D[0][jc]);  G_a = e[0] + f_c * (e[1] - e[0]).
+ *   L = sqrtf((G_x G_x + G_y G_y) + G_z G_z); the pixel is a miss unless L > 0.  On a hit:
+ *     depth = t* * n.z  (z-depth, the quantity the integrated rasters hold);  vertex_a = C_a + t* * dw_a;  normal_a = G_a / L
+ *   (towards the camera side, like the surface points' normals).
+ * Miss: depth = 0.0f ("no measurement": a ray-cast raster integrates back without special cases); the vertex and the normal row
+ *   are three words of 0x7FC00000 -- a NaN marks a missing row, a point at the world origin is a legitimate point.
+ * d_depth_out: [n_views][H][W] f32; d_vertex_out, d_normal_out: [n_views][H][W][3] f32, world coordinates.  Any of the three may
+ *   be NULL; with all three NULL the call is a valid no-op.  Asynchronous on the ctx stream (the pose rows are copied before it
+ *   returns; R3D_TSDF_CHUNK views per launch).  The volume is not modified; no byte outside the three outputs' extents is written.
+ * R3D_ERR_INVALID, nothing written: NULL volume or camera, a camera of another ctx, n_views < 0, NULL poses with n_views > 0,
+ *   min_weight or step not > 0 and finite in f32, t_near not finite or < 0, t_far not > t_near (+inf is allowed), an output
+ *   overlapping another output or the volume, a march that could pass the loop bound -- vs * sqrt((nx-1)^2 + (ny-1)^2 +
+ *   (nz-1)^2) / s >= 65536, in double from the f32 values -- and the raster-size limits of r3d_tsdf_integrate.
+ *   n_views == 0 -> R3D_OK. */
+int r3d_tsdf_raycast(r3d_tsdf* vol, const r3d_camera* cam, int n_views, const double* h_pose_w2c, double min_weight, double step,
+                     double t_near, double t_far, float* d_depth_out, float* d_vertex_out, float* d_normal_out);
+
 #ifdef __cplusplus
 }
 #endif
