@@ -502,16 +502,11 @@ __global__ __launch_bounds__(kThreads) void fuse_voxel_kernel(const DT* __restri
   }
   __syncthreads();
   flush();
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    n_new += __shfl_down(n_new, off, 64);
-    n_ignored += __shfl_down(n_ignored, off, 64);
-    n_over += __shfl_down(n_over, off, 64);
-  }
+  const auto [w_new, w_ignored, w_over] = r3d_vox::wave_sum(n_new, n_ignored, n_over);
   if (lane == 0) {
-    if (n_new) atomicAdd(&vv.counters[0], (unsigned long long)n_new);
-    if (n_ignored) atomicAdd(&vv.counters[1], (unsigned long long)n_ignored);
-    if (n_over) atomicAdd(&vv.counters[2], (unsigned long long)n_over);
+    if (w_new) atomicAdd(&vv.counters[0], (unsigned long long)w_new);
+    if (w_ignored) atomicAdd(&vv.counters[1], (unsigned long long)w_ignored);
+    if (w_over) atomicAdd(&vv.counters[2], (unsigned long long)w_over);
   }
 }
 
@@ -914,7 +909,7 @@ int r3d_fuse_frames_voxel(r3d_ctx* ctx, const r3d_camera* cam, const void* d_dep
   const bool with_pose = d_pose != nullptr;
   // Which form is faster depends on the CLOUD: where neighbouring pixels share voxels (scans) the one-launch kernel saves
   // reading the cloud back; where nearly every point has a voxel of its own, its per-point CAS into the table is the whole cost
-  // and plain fuse + the sort-merge insert wins 2-3x (r3d_voxel.hip).  So a big batch is probed: the first frames are fused by
+  // and plain fuse + the sort-merge insert wins 2-3x (r3d_voxel_merge.hip).  So a big batch is probed: the first frames are fused by
   // the plain kernel, a sample of THEIR cloud decides for the rest ("voxel_path" 1 / 2 force a form).  Same cloud, same set.
   const int64_t hw = (int64_t)cam->height * cam->width, total = hw * (int64_t)n_frames;
   const int path = ctx->voxel_path;

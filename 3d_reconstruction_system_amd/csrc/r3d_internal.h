@@ -48,7 +48,7 @@ struct r3d_ctx {
   int nn_warm = 0;        // 0 auto: repeated presorted queries start from the previous matches' distances, ICP loops use
                           // nn_warm_kernel from their second iteration on; 1 off; 2 / 3: never / always nn_warm_kernel (A/B)
   int apply_blocks = 0;
-  int voxel_path = 0;     // big inserts: 0 auto (a sample of the cloud decides), 1 LDS-set + CAS kernel, 2 sort-merge (r3d_voxel.hip)
+  int voxel_path = 0;     // big inserts: 0 auto (a sample of the cloud decides), 1 LDS-set + CAS kernel, 2 sort-merge (r3d_voxel_merge.hip)
   int voxel_last_path = 0; // read-only: the path the last r3d_voxelset_insert took (1 / 2)
   int octree_timing = 0;  // 1: the device octree serialiser puts HIP events around its four launches and waits for them ...
   int octree_us[4] = {};  // ... read-only: microseconds of count, scan, own, link of the last such call (r3d_octree.hip)
@@ -67,6 +67,18 @@ struct r3d_ctx {
   size_t pinned_bytes[kPinnedSlots] = {};
   hipEvent_t ev_pipe[6] = {};           // host pipeline: done[2], uploaded[2], entry, spare
   hipStream_t upload_stream = nullptr;  // H2D side of the host pipeline (full-duplex PCIe)
+};
+
+struct r3d_voxelset {   // r3d_voxel.hip; its fields are also read by the sort-merge insert (r3d_voxel_merge.hip)
+  r3d_ctx* ctx = nullptr;
+  int device = 0;  // kept so that destroy never has to touch a ctx that may already be gone
+  double res = 0.1;
+  double factor = 10.0;
+  uint64_t* d_table = nullptr;
+  uint64_t capacity = 0;  // power of two
+  int log2cap = 0;
+  unsigned long long* d_counters = nullptr;  // [0] voxels, [1] ignored points, [2] overflow, [3] compaction cursor
+  bool pristine = true;   // nothing has gone into the table since it was created / cleared (the merge then need not read it)
 };
 
 struct r3d_camera {
@@ -137,8 +149,10 @@ int r3d_host_pipeline_multi(r3d_ctx* ctx, int64_t n_items, const r3d_pipe_buf* i
 int r3d_voxelset_device_view(r3d_voxelset* vs, r3d_ctx** ctx, double* factor, uint64_t** d_table, int* log2cap,
                              unsigned long long** d_counters);
 
-// the two insert paths of a voxel set, and how a big insert chooses between them (r3d_voxel.hip)
+// the two insert paths of a voxel set, and how a big insert chooses between them (r3d_voxel.hip; path 2 and whether it is
+// possible at all: r3d_voxel_merge.hip, whose one entry point r3d_voxelset_insert_path calls and nobody else)
 bool r3d_voxelset_sort_feasible(const r3d_voxelset* vs, int64_t n_points, bool forced);
+__attribute__((visibility("hidden"))) int r3d_voxelset_insert_sorted(r3d_voxelset* vs, const float* d_xyz, int64_t n_points);
 int r3d_voxelset_sample(r3d_voxelset* vs, const float* d_xyz, int64_t n_points, int64_t n_insert, double cas_base_ps, bool* sort_out);
 int r3d_voxelset_insert_path(r3d_voxelset* vs, const float* d_xyz, int64_t n_points, int path);
 // A table of packed keys (kEmpty = free) holding `n` keys -> their ascending Morton codes in scratch slot 1 (slot 2 is the sort's

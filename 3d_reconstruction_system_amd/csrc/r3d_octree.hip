@@ -1,5 +1,5 @@
 // OctoMap ".bt" records of the pruned octree, built on the GPU from ascending unique 48-bit Morton codes (gfx950 / MI355X).
-// Byte-identical to the host serialiser (build_bt in r3d_voxel.hip); DESIGN.md 4.5f has the derivation and the measurements.
+// Byte-identical to the host serialiser (build_bt in r3d_octree_host.cpp); DESIGN.md 4.5f has the derivation and the measurements.
 //
 // One uint16 record per INNER node, depth-first pre-order; child c's 2-bit field at bits 2c..2c+1 (10 leaf, 11 inner).  No
 // recursion: for code j (3-bit digits, digit 0 on top)

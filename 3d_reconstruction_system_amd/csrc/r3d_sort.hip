@@ -162,7 +162,8 @@ __global__ __launch_bounds__(kThreads) void digit_scatter_kernel(const uint64_t*
 // caller asks where it ended up (d_result != NULL: *d_result = d_keys or d_tmp, no copy).
 // The workspace of a sort of n keys (scratch slot 3): hist[bin][r3d_sort_stride(workgroups)] + the 256 bin totals.  A producer that writes the
 // keys tile by tile (kSortTile keys per workgroup, same tiling as the sort) can fill `hist` for the FIRST digit itself and
-// save the sort its first histogram pass (r3d_voxel.hip's key kernel does).
+// save the sort its first histogram pass (no producer in the library does at present: the sort-merge insert, r3d_voxel_merge.hip,
+// has passes of its own).
 // Limit: the bin totals and the tiles' prefixes are uint32, so one sort takes fewer than 2^32 keys; nothing in the library
 // reaches that size, and the check below (tiles < 2^31) does not enforce it.
 int r3d_radix_sort_workspace(r3d_ctx* ctx, int64_t n, uint32_t** hist_out, int* n_blocks_out) {

@@ -1,6 +1,6 @@
 // Device-side pieces of the 8-bit-digit radix passes: how a workgroup ranks its tile of 4096 elements by one digit, stably and
 // without a barrier per round, and where each bin of the tile then sits (r3d_sort.hip, 64-bit keys); the blockIdx -> tile map and
-// the wave scan are shared with the sort-merge insert's passes (r3d_voxel.hip), whose order inside a bin is free -- they rank with
+// the wave scan are shared with the sort-merge insert's passes (r3d_voxel_merge.hip), whose order inside a bin is free -- they rank with
 // one returning LDS add per element instead.  See digit_scatter_kernel (r3d_sort.hip) for the measurements behind the shape.
 #pragma once
 

@@ -1,6 +1,6 @@
-// Device-side pieces of the occupied-voxel set shared by r3d_voxel.hip (insert from a cloud in HBM) and r3d_fuse.hip (insert
-// straight from the fused launch's registers): OctoMap's key arithmetic, the global open-addressing table, the neighbour-lane
-// test, the 48-bit Morton code.  See r3d_voxel.hip for the semantics and their sources.
+// Device-side pieces of the occupied-voxel set shared by r3d_voxel.hip and r3d_voxel_merge.hip (insert from a cloud in HBM),
+// r3d_fuse.hip (insert straight from the fused launch's registers) and r3d_voxelgrid.hip: OctoMap's key arithmetic, the global
+// open-addressing table, the neighbour-lane test, the 48-bit Morton code.  See r3d_voxel.hip for the semantics and their sources.
 //
 // What the sets hold: the three 16-bit OctoMap keys PACKED (x | y << 16 | z << 32), not their Morton code.  The Morton
 // interleave costs ~45 vector instructions and was paid per POINT (of 123 per 64 points in voxel_insert_kernel, which PMC shows
@@ -18,6 +18,10 @@ constexpr uint64_t kEmpty = ~0ull;
 constexpr int kTreeMaxVal = 32768;
 constexpr int kLdsSlots = 2048;      // per-workgroup dedupe table (16 KB)
 constexpr int kLdsKeepBelow = 512;   // it is flushed to the global table once it holds this many codes (then <= 75 % full)
+
+struct __attribute__((packed, aligned(4))) P3 {   // a point of an [n][3] float cloud: one 12-byte load
+  float x, y, z;
+};
 
 // 8 bits -> every third bit of 24, in 32-bit registers (the 64-bit spread costs two instructions per step)
 __device__ __forceinline__ uint32_t spread3_byte(uint32_t x) {
@@ -107,6 +111,29 @@ __device__ __forceinline__ void lds_settle() { asm volatile("s_waitcnt lgkmcnt(0
 // barrier protects nothing but an LDS array this one leaves the wave's global operations in flight.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// Two / three per-lane counts summed down the wave, the shuffles of one step issued together: lane 0 receives the wave's sums
+// (the other lanes partial ones).  By value, to be taken apart with `const auto [a, b] = wave_sum(...)`: the same helper
+// with reference parameters made the compiler number the callers' registers differently.
+struct WaveSum2 { unsigned a, b; };
+struct WaveSum3 { unsigned a, b, c; };
+__device__ __forceinline__ WaveSum2 wave_sum(unsigned a, unsigned b) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    a += __shfl_down(a, off, 64);
+    b += __shfl_down(b, off, 64);
+  }
+  return {a, b};
+}
+__device__ __forceinline__ WaveSum3 wave_sum(unsigned a, unsigned b, unsigned c) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    a += __shfl_down(a, off, 64);
+    b += __shfl_down(b, off, 64);
+    c += __shfl_down(c, off, 64);
+  }
+  return {a, b, c};
+}
+
 // Three per-thread counts reach three global counters as ONE atomicAdd per WORKGROUP and non-zero counter.  Adds to one
 // address complete at ~0.09 G/s on this chip (11 ns each, whoever issues them): a SHORT kernel with many workgroups that each
 // end with per-wave adds waits for them (the sort-merge insert's merge: 32768 adds = 360 of its 455 us; it now leaves per-
@@ -114,19 +141,14 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // `wg`: three words of LDS; every thread of the workgroup calls this once, at the end.
 __device__ __forceinline__ void flush_counts(unsigned n_new, unsigned n_ignored, unsigned n_over, unsigned* wg,
                                              unsigned long long* __restrict__ counters) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    n_new += __shfl_down(n_new, off, 64);
-    n_ignored += __shfl_down(n_ignored, off, 64);
-    n_over += __shfl_down(n_over, off, 64);
-  }
+  const auto [w_new, w_ignored, w_over] = wave_sum(n_new, n_ignored, n_over);
   lds_barrier();
   if (threadIdx.x < 3) wg[threadIdx.x] = 0;
   lds_barrier();
   if ((threadIdx.x & 63) == 0) {
-    if (n_new) atomicAdd(&wg[0], n_new);
-    if (n_ignored) atomicAdd(&wg[1], n_ignored);
-    if (n_over) atomicAdd(&wg[2], n_over);
+    if (w_new) atomicAdd(&wg[0], w_new);
+    if (w_ignored) atomicAdd(&wg[1], w_ignored);
+    if (w_over) atomicAdd(&wg[2], w_over);
   }
   lds_barrier();
   if (threadIdx.x < 3 && wg[threadIdx.x]) atomicAdd(&counters[threadIdx.x], (unsigned long long)wg[threadIdx.x]);
@@ -134,7 +156,7 @@ __device__ __forceinline__ void flush_counts(unsigned n_new, unsigned n_ignored,
 
 // Where a packed key lives in the table: the top log2cap bits of h48 = key * G mod 2^48.  G is odd, so key -> h48 is a
 // BIJECTION of the 48-bit keys (key = h48 * G^-1 mod 2^48): the top 16 bits of h48 name one of 65536 consecutive pieces of the
-// table and the low 32 bits say which of the 2^32 keys of that piece it is.  The sort-merge insert (r3d_voxel.hip) lives on
+// table and the low 32 bits say which of the 2^32 keys of that piece it is.  The sort-merge insert (r3d_voxel_merge.hip) lives on
 // that: once the keys are in piece order a key is its 32-bit remainder -- the sort moves 4-byte words, not 8-byte ones.
 // (Rounds 2-4 hashed with the 64-bit golden-ratio multiplier; the table is internal, its layout was free to change.)
 constexpr uint64_t kMask48 = ((uint64_t)1 << 48) - 1;

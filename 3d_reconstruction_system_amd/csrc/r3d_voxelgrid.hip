@@ -50,13 +50,10 @@ constexpr int kGridKeepBelow = 256;            // flushed once it holds this man
 constexpr int64_t kMaxTilesPerWg = (int64_t)1 << 15;   // <= 2^24 points per workgroup: LDS counts and colour sums fit u32
 constexpr double kFracScale = 2147483648.0;    // 2^31
 using r3d_vox::kEmpty;
+using r3d_vox::P3;
 
 template <bool RGB>
 constexpr int acc_words() { return RGB ? 8 : 4; }   // 64 / 32 bytes per slot: a row never straddles a 64-byte line
-
-struct __attribute__((packed, aligned(4))) P3 {
-  float x, y, z;
-};
 
 // One voxel's partial sums into HBM: claim the key's slot (CAS on the key array only), then no-return adds into its row.
 // A key that finds no slot loses its points: they are counted in n_over.
@@ -250,7 +247,7 @@ __global__ __launch_bounds__(kThreads) void grid_insert_kernel(const float* __re
   __syncthreads();   // every lane's last adds have landed
   flush();
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
+  for (int off = 32; off > 0; off >>= 1) {   // (not r3d_vox::wave_sum: as a call, it moved an instruction of this kernel)
     n_new += __shfl_down(n_new, off, 64);
     n_ignored += __shfl_down(n_ignored, off, 64);
     n_over += __shfl_down(n_over, off, 64);

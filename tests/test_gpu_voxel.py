@@ -470,7 +470,7 @@ def test_fused_cloud_and_voxels_any_run_length(V, ctx, blocks):
 # ---- the sort-merge insert (path 2): keys into per-XCD bin segments, a second pass by piece, table regions updated in LDS -----
 
 @pytest.mark.parametrize("n,log2cap,spread", [(1, 16, 1.0), (1000, 16, 3.0), (4097, 17, 8.0), (300_000, 20, 40.0), (300_000, 19, 40.0),
-                                               (1_000_000, 21, 60.0), (2_000_003, 22, 25.0), (3_000_000, 29, 80.0)])
+                                               (1_000_000, 21, 60.0), (2_000_003, 22, 25.0), (3_000_000, 28, 80.0), (3_000_000, 29, 80.0)])
 def test_sort_merge_insert_matches_oracle_and_the_cas_path(V, ctx, n, log2cap, spread):
     """forced at every size: one region's worth of keys up to millions, tables of 2^16 .. 2^29 slots (regions of 2048, 4096 and
     8192 slots), load factors up to ~0.55; non-finite / out-of-range points and repeats among them; then the SAME table through

@@ -1,5 +1,5 @@
 // What does a scattered run of R 4-byte words cost by its alignment?  The write pattern of the voxel sort's first pass
-// (r3d_voxel.hip, voxel_bin_kernel): G workgroups, each owning a segment per bin (256 bins), walk T tiles of 4096 words and
+// (r3d_voxel_merge.hip, voxel_bin_kernel): G workgroups, each owning a segment per bin (256 bins), walk T tiles of 4096 words and
 // append, per tile and bin, a run of words at the bin's cursor.  Variants: runs of 16 words starting anywhere (what ranking a
 // tile gives), runs of 16 on 64-byte boundaries, whole 128-byte lines (32 words to half the bins per tile), 32-byte sectors.
 // hipcc --offload-arch=gfx950 -O3 tools/scatter_runs.hip -o tools/scatter_runs
