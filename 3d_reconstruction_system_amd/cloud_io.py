@@ -467,10 +467,10 @@ def _mesh_triangles(triangles, n_vertices, what):
     return np.ascontiguousarray(t, dtype='<i4')
 
 
-def write_ply_mesh(path, xyz, normals, triangles):
-    """Binary little-endian PLY of an indexed triangle mesh: write_ply_normals' vertex rows (float x y z nx ny nz), then
-    `element face M` with `property list uchar int vertex_indices` -- what MeshLab shades.  triangles: [M,3] integers, every
-    index inside [0, N).  read_ply_mesh reads it back."""
+def write_ply_mesh(path, xyz, normals, triangles, rgb=None):
+    """Binary little-endian PLY of an indexed triangle mesh: write_ply_normals' vertex rows (float x y z nx ny nz, + uchar red
+    green blue when rgb [N,3] uint8 is given), then `element face M` with `property list uchar int vertex_indices` -- what
+    MeshLab shades.  triangles: [M,3] integers, every index inside [0, N).  read_ply_mesh reads it back."""
     xyz = np.ascontiguousarray(xyz, dtype='<f4')
     normals = np.ascontiguousarray(normals, dtype='<f4')
     if xyz.ndim != 2 or xyz.shape[1] != 3:
@@ -479,21 +479,32 @@ def write_ply_mesh(path, xyz, normals, triangles):
         raise ValueError("normals must be [N,3] like the vertices, got %r for %r" % (normals.shape, xyz.shape))
     if xyz.shape[0] >= 1 << 31:
         raise ValueError("a mesh of %d vertices does not fit int indices" % xyz.shape[0])
+    if rgb is not None:
+        rgb = np.asarray(rgb)
+        if rgb.shape != xyz.shape or rgb.dtype != np.uint8:
+            raise ValueError("rgb must be [N,3] uint8 like the vertices, got %s of shape %r" % (rgb.dtype, rgb.shape))
     tri = _mesh_triangles(triangles, xyz.shape[0], "write_ply_mesh")
     faces = np.empty(tri.shape[0], dtype=np.dtype([('n', 'u1'), ('v', '<i4', (3,))]))
     faces['n'] = 3
     faces['v'] = tri
     head = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % xyz.shape[0]
     head += "".join("property float %s\n" % name for name in ('x', 'y', 'z', 'nx', 'ny', 'nz'))
+    if rgb is not None:
+        head += "".join("property uchar %s\n" % name for name in ('red', 'green', 'blue'))
     head += "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % tri.shape[0]
+    six = np.ascontiguousarray(np.concatenate([xyz, normals], axis=1))
+    if rgb is not None:
+        rows = np.empty(xyz.shape[0], dtype=np.dtype([('f', '<f4', (6,)), ('c', 'u1', (3,))]))
+        rows['f'], rows['c'] = six, rgb
     with open(path, 'wb') as f:
         f.write(head.encode('ascii'))
-        f.write(np.ascontiguousarray(np.concatenate([xyz, normals], axis=1)).tobytes())
+        f.write(six.tobytes() if rgb is None else rows.tobytes())
         f.write(faces.tobytes())
 
 
-def read_ply_mesh(path):
-    """(xyz [N,3] float32, normals [N,3] float32, triangles [M,3] int32) of a PLY in write_ply_mesh's layout."""
+def read_ply_mesh(path, with_colors=False):
+    """(xyz [N,3] float32, normals [N,3] float32, triangles [M,3] int32) of a PLY in write_ply_mesh's layout, with or without
+    its colour bytes.  with_colors: a fourth value, the [N,3] uint8 colours, or None for a file without."""
     with open(path, 'rb') as f:
         data = f.read()
     end = data.find(b'end_header\n')
@@ -503,20 +514,31 @@ def read_ply_mesh(path):
     want = ["ply", "format binary_little_endian 1.0", None] + ["property float %s" % p for p in ('x', 'y', 'z', 'nx', 'ny', 'nz')] + \
            [None, "property list uchar int vertex_indices"]
     lines = [s for s in lines if not s.startswith(("comment", "obj_info"))]
+    colour = ["property uchar %s" % p for p in ('red', 'green', 'blue')]
+    has_rgb = lines[9:12] == colour
+    if has_rgb:
+        del lines[9:12]
+    stride = 27 if has_rgb else 24
     ok = len(lines) == len(want) and all(w is None or w == s for w, s in zip(want, lines))
     ev, ef = (lines[2].split(), lines[9].split()) if ok else ([], [])
     if not (ok and len(ev) == 3 and ev[:2] == ["element", "vertex"] and len(ef) == 3 and ef[:2] == ["element", "face"]):
         raise ValueError("%s: not a triangle mesh in write_ply_mesh's layout (float x y z nx ny nz, list uchar int faces)" % path)
     n, m = int(ev[2]), int(ef[2])
     start = end + len(b'end_header\n')
-    if n < 0 or m < 0 or len(data) - start < n * 24 + m * 13:
+    if n < 0 or m < 0 or len(data) - start < n * stride + m * 13:
         raise ValueError("%s: %d vertices and %d faces announced, file is too short" % (path, n, m))
-    six = np.frombuffer(data, dtype='<f4', count=n * 6, offset=start).reshape(n, 6).astype(np.float32)
-    faces = np.frombuffer(data, dtype=np.dtype([('n', 'u1'), ('v', '<i4', (3,))]), count=m, offset=start + n * 24)
+    rgb = None
+    if has_rgb:
+        rows = np.frombuffer(data, dtype=np.dtype([('f', '<f4', (6,)), ('c', 'u1', (3,))]), count=n, offset=start)
+        six, rgb = rows['f'].astype(np.float32), np.ascontiguousarray(rows['c'])
+    else:
+        six = np.frombuffer(data, dtype='<f4', count=n * 6, offset=start).reshape(n, 6).astype(np.float32)
+    faces = np.frombuffer(data, dtype=np.dtype([('n', 'u1'), ('v', '<i4', (3,))]), count=m, offset=start + n * stride)
     if m and (faces['n'] != 3).any():
         raise ValueError("%s: a face is not a triangle" % path)
     tri = _mesh_triangles(faces['v'].astype(np.int32).reshape(m, 3), n, path)
-    return np.ascontiguousarray(six[:, :3]), np.ascontiguousarray(six[:, 3:]), tri.astype(np.int32)
+    out = (np.ascontiguousarray(six[:, :3]), np.ascontiguousarray(six[:, 3:]), tri.astype(np.int32))
+    return out + (rgb,) if with_colors else out
 
 
 def _parse_rows_native(buf, offset, separator):

@@ -30,33 +30,12 @@ constexpr int kPer = kSortTile / kThreads;   // consecutive voxels per thread of
 
 using TsdfFrame = TsdfPoseRow;   // world -> camera, f32: p_cam = R p_w + t (the ring's row type: r3d_tsdf_dev.h)
 
-struct TsdfCam {
-  float fx, fy, cx, cy, wf, hf, scale;
-  int width;
-  uint32_t frame_px;   // height * width
-};
-
-// one frame into one voxel; returns whether the frame touched it
+// one frame into one voxel; returns whether the frame touched it (the rule itself: r3d_tsdf_dev.h's integrate_frame)
 template <typename D>
 __device__ __forceinline__ bool integrate_one(const TsdfFrame& fr, const TsdfCam& cam, const D* __restrict__ depth, float tr, float cx_,
                                               float cy_, float cz_, float& tsdf, float& w) {
-  const float px = ((fr.r[0] * cx_ + fr.r[1] * cy_) + fr.r[2] * cz_) + fr.t[0];
-  const float py = ((fr.r[3] * cx_ + fr.r[4] * cy_) + fr.r[5] * cz_) + fr.t[1];
-  const float pz = ((fr.r[6] * cx_ + fr.r[7] * cy_) + fr.r[8] * cz_) + fr.t[2];
-  if (!(pz > 0.0f)) return false;
-  const float u = cam.fx * (px / pz) + cam.cx;
-  const float v = cam.fy * (py / pz) + cam.cy;
-  const float ui = floorf(u + 0.5f), vi = floorf(v + 0.5f);
-  if (!(ui >= 0.0f && ui < cam.wf && vi >= 0.0f && vi < cam.hf)) return false;   // NaN fails every comparison
-  const float d = (float)depth[(uint32_t)(int)vi * (uint32_t)cam.width + (uint32_t)(int)ui] * cam.scale;
-  if (!(d > 0.0f && d < INFINITY)) return false;
-  const float sdf = d - pz;
-  if (sdf < -tr) return false;
-  const float tn = fminf(1.0f, sdf / tr);
-  const float w1 = w + 1.0f;
-  tsdf = (tsdf * w + tn) / w1;
-  w = w1;
-  return true;
+  uint32_t pixel;
+  return integrate_frame(fr, cam, depth, tr, cx_, cy_, cz_, tsdf, w, pixel);
 }
 
 // grid: ceil(rows * pairs_per_row / 256) workgroups; lane -> (row, pair) -> voxels x0 = 2 pair and x0 + 1 of row (y, z)
@@ -135,13 +114,15 @@ struct r3d_tsdf {
   TsdfGrid g = {};
   int64_t n = 0;    // voxels
   float2* d_vol = nullptr;
+  uint4* d_col = nullptr;         // the colour plane {sum_r, sum_g, sum_b, n} of a volume created with colour, else NULL
   TsdfFrame* d_table = nullptr;   // [kSlots][kChunk]
   TsdfFrame* h_table = nullptr;   // the same, pinned: what the uploads read
   hipEvent_t ev[kSlots] = {};     // slot s of h_table has been read by its upload
   unsigned next_slot = 0;
 };
 
-int r3d_tsdf_create(r3d_ctx* ctx, const double* h_origin, double voxel_size, int nx, int ny, int nz, double sdf_trunc, r3d_tsdf** out) {
+static int create_volume(r3d_ctx* ctx, const double* h_origin, double voxel_size, int nx, int ny, int nz, double sdf_trunc, bool color,
+                         r3d_tsdf** out) {
   R3D_REQUIRE(out != nullptr, "out is NULL");
   *out = nullptr;
   R3D_REQUIRE(ctx != nullptr && h_origin != nullptr, "NULL argument");
@@ -164,6 +145,7 @@ int r3d_tsdf_create(r3d_ctx* ctx, const double* h_origin, double voxel_size, int
   v->g = TsdfGrid{nx, ny, nz, o[0], o[1], o[2], vs, tr};
   v->n = (int64_t)nx * ny * nz;
   hipError_t e = hipMalloc((void**)&v->d_vol, (size_t)v->n * sizeof(float2));
+  if (e == hipSuccess && color) e = hipMalloc((void**)&v->d_col, (size_t)v->n * sizeof(uint4));
   if (e == hipSuccess) e = hipMalloc((void**)&v->d_table, sizeof(TsdfFrame) * kSlots * kChunk);
   if (e == hipSuccess) e = hipHostMalloc((void**)&v->h_table, sizeof(TsdfFrame) * kSlots * kChunk, hipHostMallocDefault);
   for (int s = 0; s < kSlots && e == hipSuccess; ++s) e = hipEventCreateWithFlags(&v->ev[s], hipEventDisableTiming);
@@ -183,11 +165,20 @@ int r3d_tsdf_create(r3d_ctx* ctx, const double* h_origin, double voxel_size, int
   return R3D_OK;
 }
 
+int r3d_tsdf_create(r3d_ctx* ctx, const double* h_origin, double voxel_size, int nx, int ny, int nz, double sdf_trunc, r3d_tsdf** out) {
+  return create_volume(ctx, h_origin, voxel_size, nx, ny, nz, sdf_trunc, false, out);
+}
+
+int r3d_tsdf_create_rgb(r3d_ctx* ctx, const double* h_origin, double voxel_size, int nx, int ny, int nz, double sdf_trunc, r3d_tsdf** out) {
+  return create_volume(ctx, h_origin, voxel_size, nx, ny, nz, sdf_trunc, true, out);
+}
+
 int r3d_tsdf_destroy(r3d_tsdf* v) {
   if (!v) return R3D_OK;
   (void)hipSetDevice(v->device);
   (void)hipDeviceSynchronize();
   if (v->d_vol) (void)hipFree(v->d_vol);
+  if (v->d_col) (void)hipFree(v->d_col);
   if (v->d_table) (void)hipFree(v->d_table);
   if (v->h_table) (void)hipHostFree(v->h_table);
   for (int s = 0; s < kSlots; ++s)
@@ -201,6 +192,7 @@ int r3d_tsdf_reset(r3d_tsdf* v) {
   int rc = r3d_ctx_enter(v->ctx);
   if (rc) return rc;
   R3D_HIP(hipMemsetAsync(v->d_vol, 0, (size_t)v->n * sizeof(float2), v->ctx->stream));
+  if (v->d_col) R3D_HIP(hipMemsetAsync(v->d_col, 0, (size_t)v->n * sizeof(uint4), v->ctx->stream));
   return R3D_OK;
 }
 
@@ -219,6 +211,12 @@ int r3d_tsdf_pose_slot(r3d_tsdf* v, TsdfPoseRow** h_rows, TsdfPoseRow** d_rows, 
   *h_rows = v->h_table + (size_t)s * kChunk;
   *d_rows = v->d_table + (size_t)s * kChunk;
   *ev = v->ev[s];
+  return R3D_OK;
+}
+
+int r3d_tsdf_color_plane(r3d_tsdf* v, uint4** d_col) {
+  R3D_REQUIRE(v != nullptr, "TSDF volume is NULL");
+  *d_col = v->d_col;
   return R3D_OK;
 }
 
@@ -245,8 +243,10 @@ void launch_integrate(r3d_tsdf* v, const TsdfCam& cam, const void* d_depth, cons
                        table, n, ppr, n_pairs);
 }
 
-int integrate_checks(r3d_tsdf* v, const r3d_camera* cam, const void* depth, int depth_dtype, int n_frames, double depth_scale,
-                     const double* h_pose) {
+}  // namespace
+
+int r3d_tsdf_integrate_checks(r3d_tsdf* v, const r3d_camera* cam, const void* depth, int depth_dtype, int n_frames, double depth_scale,
+                              const double* h_pose) {
   R3D_REQUIRE(v != nullptr, "TSDF volume is NULL");
   R3D_REQUIRE(cam != nullptr, "camera is NULL");
   R3D_REQUIRE(cam->ctx == v->ctx, "the camera belongs to another context than the volume");
@@ -258,6 +258,15 @@ int integrate_checks(r3d_tsdf* v, const r3d_camera* cam, const void* depth, int 
               "raster of %d x %d pixels is too large for the TSDF projection", cam->height, cam->width);
   R3D_REQUIRE(std::isfinite((float)depth_scale), "depth_scale must be finite in f32");
   return R3D_OK;
+}
+
+namespace {
+
+// the depth-only entry points refuse a volume with a colour plane: its n would part from its w
+int integrate_checks(r3d_tsdf* v, const r3d_camera* cam, const void* depth, int depth_dtype, int n_frames, double depth_scale,
+                     const double* h_pose) {
+  R3D_REQUIRE(v == nullptr || v->d_col == nullptr, "the volume carries colour: integrate it with r3d_tsdf_integrate_rgb");
+  return r3d_tsdf_integrate_checks(v, cam, depth, depth_dtype, n_frames, depth_scale, h_pose);
 }
 
 // the launches of one batch whose rasters are in HBM; asynchronous
@@ -325,13 +334,7 @@ int r3d_tsdf_integrate_host(r3d_tsdf* v, const r3d_camera* cam, const void* h_de
   return R3D_OK;
 }
 
-int r3d_tsdf_extract_points(r3d_tsdf* v, double min_weight, float* d_xyz_out, float* d_normals_out, int64_t cap, int64_t* n_out) {
-  R3D_REQUIRE(v != nullptr, "TSDF volume is NULL");
-  R3D_REQUIRE(n_out != nullptr, "n_out is NULL");
-  const float mw = (float)min_weight;
-  R3D_REQUIRE(mw > 0.0f, "min_weight must be > 0 in f32");
-  R3D_REQUIRE(cap >= 0, "cap must be >= 0");
-  R3D_REQUIRE(cap == 0 || d_xyz_out != nullptr, "d_xyz_out is NULL with cap > 0");
+int r3d_tsdf_count_points(r3d_tsdf* v, float mw, const uint32_t** d_prefix, int* tiles_out, int64_t* n_points) {
   r3d_ctx* ctx = v->ctx;
   int rc = r3d_ctx_enter(ctx);
   if (rc) return rc;
@@ -351,12 +354,32 @@ int r3d_tsdf_extract_points(r3d_tsdf* v, double min_weight, float* d_xyz_out, fl
   uint32_t m = 0;
   R3D_HIP(hipMemcpyAsync(&m, total, sizeof(m), hipMemcpyDeviceToHost, st));
   R3D_HIP(hipStreamSynchronize(st));
-  *n_out = (int64_t)m;
-  const uint64_t rows = (uint64_t)((int64_t)m < cap ? (int64_t)m : cap);
+  *d_prefix = hist;
+  *tiles_out = tiles;
+  *n_points = (int64_t)m;
+  return R3D_OK;
+}
+
+int r3d_tsdf_extract_points(r3d_tsdf* v, double min_weight, float* d_xyz_out, float* d_normals_out, int64_t cap, int64_t* n_out) {
+  R3D_REQUIRE(v != nullptr, "TSDF volume is NULL");
+  R3D_REQUIRE(n_out != nullptr, "n_out is NULL");
+  const float mw = (float)min_weight;
+  R3D_REQUIRE(mw > 0.0f, "min_weight must be > 0 in f32");
+  R3D_REQUIRE(cap >= 0, "cap must be >= 0");
+  R3D_REQUIRE(cap == 0 || d_xyz_out != nullptr, "d_xyz_out is NULL with cap > 0");
+  r3d_ctx* ctx = v->ctx;
+  const uint32_t* hist = nullptr;
+  int tiles = 0;
+  int64_t m = 0;
+  int rc = r3d_tsdf_count_points(v, mw, &hist, &tiles, &m);
+  if (rc) return rc;
+  hipStream_t st = ctx->stream;
+  *n_out = m;
+  const uint64_t rows = (uint64_t)(m < cap ? m : cap);
   if (rows == 0) return R3D_OK;
   r3d_wrote(ctx, d_xyz_out, (size_t)rows * 12);
   if (d_normals_out) r3d_wrote(ctx, d_normals_out, (size_t)rows * 12);
-  hipLaunchKernelGGL(tsdf_emit_kernel, dim3(tiles), dim3(kThreads), 0, st, (const float2*)v->d_vol, v->g, v->n, mw, (const uint32_t*)hist,
+  hipLaunchKernelGGL(tsdf_emit_kernel, dim3(tiles), dim3(kThreads), 0, st, (const float2*)v->d_vol, v->g, v->n, mw, hist,
                      d_xyz_out, d_normals_out, rows);
   R3D_HIP(hipGetLastError());
   return R3D_OK;

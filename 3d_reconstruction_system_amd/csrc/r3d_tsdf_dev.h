@@ -1,12 +1,15 @@
 // Device-side pieces of the TSDF volume's surface extraction that r3d_tsdf.hip (points) and r3d_tsdf_mesh.hip (indexed triangle
 // mesh) share: voxel indexing, the crossing predicate and the surface point of a crossing.  The mesh's vertices ARE the points,
 // bit for bit, so both files emit them through emit_points below.  Semantics: include/r3d.h ("TSDF volume").
+// Also the one statement of the per-frame integration rule (integrate_frame), which the depth-only kernels of r3d_tsdf.hip and the
+// colour kernel of r3d_tsdf_color.hip both apply, and the colour of a surface point (emit_colors; "TSDF colour").
 #pragma once
 
 #include "r3d_internal.h"
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 
 struct r3d_tsdf;
@@ -28,6 +31,38 @@ struct TsdfPoseRow {
 static_assert(sizeof(TsdfPoseRow) == 64, "one pose row is 64 bytes");
 
 __device__ __forceinline__ float centre(float o, int idx, float vs) { return o + ((float)idx + 0.5f) * vs; }
+
+struct TsdfCam {
+  float fx, fy, cx, cy, wf, hf, scale;
+  int width;
+  uint32_t frame_px;   // height * width
+};
+
+// One frame into one voxel; returns whether the frame touched it, and then *pixel = vi * width + ui, the pixel it read (the
+// colour kernel gathers the same pixel of the colour image; the depth-only kernels drop it).
+template <typename D>
+__device__ __forceinline__ bool integrate_frame(const TsdfPoseRow& fr, const TsdfCam& cam, const D* __restrict__ depth, float tr, float cx_,
+                                                float cy_, float cz_, float& tsdf, float& w, uint32_t& pixel) {
+  const float px = ((fr.r[0] * cx_ + fr.r[1] * cy_) + fr.r[2] * cz_) + fr.t[0];
+  const float py = ((fr.r[3] * cx_ + fr.r[4] * cy_) + fr.r[5] * cz_) + fr.t[1];
+  const float pz = ((fr.r[6] * cx_ + fr.r[7] * cy_) + fr.r[8] * cz_) + fr.t[2];
+  if (!(pz > 0.0f)) return false;
+  const float u = cam.fx * (px / pz) + cam.cx;
+  const float v = cam.fy * (py / pz) + cam.cy;
+  const float ui = floorf(u + 0.5f), vi = floorf(v + 0.5f);
+  if (!(ui >= 0.0f && ui < cam.wf && vi >= 0.0f && vi < cam.hf)) return false;   // NaN fails every comparison
+  const uint32_t at = (uint32_t)(int)vi * (uint32_t)cam.width + (uint32_t)(int)ui;
+  const float d = (float)depth[at] * cam.scale;
+  if (!(d > 0.0f && d < INFINITY)) return false;
+  const float sdf = d - pz;
+  if (sdf < -tr) return false;
+  const float tn = fminf(1.0f, sdf / tr);
+  const float w1 = w + 1.0f;
+  tsdf = (tsdf * w + tn) / w1;
+  w = w1;
+  pixel = at;
+  return true;
+}
 
 struct Vox {
   int x, y, z;
@@ -115,6 +150,32 @@ __device__ __forceinline__ void emit_points(const float2* __restrict__ vol, cons
   }
 }
 
+// One channel of a surface point's colour ("TSDF colour"): the two voxels' mean colours, interpolated like the position, rounded
+// half up and clamped to a byte.  n == 0 gives a mean of 0 (a valid voxel has n >= 1).
+__device__ __forceinline__ uint32_t color_channel(uint32_t sum_v, uint32_t n_v, uint32_t sum_u, uint32_t n_u, float r) {
+  const float mv = n_v ? (float)sum_v / (float)n_v : 0.0f;
+  const float mu = n_u ? (float)sum_u / (float)n_u : 0.0f;
+  const float m = mv + r * (mu - mv);
+  return (uint32_t)fminf(fmaxf(floorf(m + 0.5f), 0.0f), 255.0f);
+}
+
+// emit_points' sibling: the colour words r | g << 8 | b << 16 of the same crossings, to the same rows under the same at < cap rule
+__device__ __forceinline__ void emit_colors(const float2* __restrict__ vol, const uint4* __restrict__ col, const TsdfGrid& g, int64_t base,
+                                            uint64_t mask, uint64_t at, uint64_t cap, uint32_t* __restrict__ rgba_out) {
+  while (mask && at < cap) {
+    const int bit = __ffsll((long long)mask) - 1;
+    mask &= mask - 1;
+    const int e = bit / 3, a = bit - 3 * e;
+    const int64_t i = base + e, j = i + step_of(a, g);
+    const float A = vol[i].x, B = vol[j].x;
+    const float r = A / (A - B);
+    const uint4 cv = col[i], cu = col[j];
+    rgba_out[at] = color_channel(cv.x, cv.w, cu.x, cu.w, r) | color_channel(cv.y, cv.w, cu.y, cu.w, r) << 8 |
+                   color_channel(cv.z, cv.w, cu.z, cu.w, r) << 16;
+    ++at;
+  }
+}
+
 // The eight voxels of the cell whose corner 0 is voxel i (which has a neighbour on every + side): q[k], k = dx + 2 dy + 4 dz, the
 // mesh's corner numbering.  {tsdf, weight} of a voxel is one 8-byte load; the x pair of a row is 16 contiguous bytes.
 __device__ __forceinline__ void load_cell(const float2* __restrict__ vol, const TsdfGrid& g, int64_t i, float2 (&q)[8]) {
@@ -143,3 +204,11 @@ int r3d_tsdf_device_view(r3d_tsdf* vol, r3d_ctx** ctx, r3d_tsdf_dev::TsdfGrid* g
 // R3D_TSDF_CHUNK rows, pinned (*h_rows) and in HBM (*d_rows).  The caller keeps the integrate path's discipline:
 // hipEventSynchronize(*ev), fill the pinned rows, hipMemcpyAsync them to *d_rows on the ctx stream, hipEventRecord(*ev) there.
 int r3d_tsdf_pose_slot(r3d_tsdf* vol, r3d_tsdf_dev::TsdfPoseRow** h_rows, r3d_tsdf_dev::TsdfPoseRow** d_rows, hipEvent_t* ev);
+// r3d_tsdf.hip, for r3d_tsdf_color.hip: the colour plane ([n_voxels] uint4 {sum_r, sum_g, sum_b, n}), NULL for a volume without;
+int r3d_tsdf_color_plane(r3d_tsdf* vol, uint4** d_col);
+// the argument checks r3d_tsdf_integrate makes (R3D_OK with n_frames == 0 too: the caller returns then);
+int r3d_tsdf_integrate_checks(r3d_tsdf* vol, const r3d_camera* cam, const void* depth, int depth_dtype, int n_frames, double depth_scale,
+                              const double* h_pose);
+// and the first half of r3d_tsdf_extract_points: tsdf_count_kernel + the tile scan into scratch slot 3, the count read back
+// (synchronises).  *d_prefix: the tiles' exclusive prefixes, *tiles their number, *n_points the count.
+int r3d_tsdf_count_points(r3d_tsdf* vol, float mw, const uint32_t** d_prefix, int* tiles, int64_t* n_points);

@@ -3,7 +3,7 @@
 truncated signed distance volume instead, and the volume's zero level set is written as oriented surface points.
 
     python integrate_tsdf.py --voxel-size S --trunc T [--origin X Y Z] [--dims NX NY NZ] [--margin M] [--min-weight W] [--mesh]
-                             [--raycast]
+                             [--raycast] [--color-dir DIR]
 
 Run from a directory holding ./camera_pose/image_colmap_simi_2.txt and ./depth/ (the inputs of camera_to_world.py; the same
 environment overrides apply: R3D_FX .. R3D_CY, R3D_POSE_SCALE, R3D_DEVICE).  Writes ./ply/tsdf_surface.ply: binary PLY, float
@@ -13,6 +13,8 @@ centres padded by M on every side (default M = 16 T), cut into voxels of S.  A d
 shades), and prints a second line "triangles M -> path".
 --raycast also casts the volume from every pose of the pose file at the input rasters' size and writes the depth the model
 predicts (float32, 0 = no surface) to ./raycast/<frame name>.npy, and prints a further line "raycast F frames -> ./raycast/".
+--color-dir DIR reads the colour image DIR/<frame name> of every frame (the size of the depth maps), integrates colour with the
+depth and adds uchar red green blue to the vertices of both PLY files.
 """
 import argparse
 import math
@@ -43,6 +45,8 @@ def parse_args(argv):
     p.add_argument("--mesh", action="store_true", help="also write the triangle mesh of the surface to %s" % MESH_FILE)
     p.add_argument("--raycast", action="store_true",
                    help="also ray-cast the volume from every pose and write the predicted depth to %s<frame name>.npy" % RAYCAST_DIR)
+    p.add_argument("--color-dir", metavar="DIR", default=None,
+                   help="integrate the colour images DIR/<frame name> too and write the colours into the PLY files")
     args = p.parse_args(argv)
     for name in ("voxel_size", "trunc", "min_weight"):
         v = getattr(args, name)
@@ -87,6 +91,22 @@ def raycast_depth(r3d, vol, quats, ts, shape, min_weight):
     return out
 
 
+def read_colors(r3d, color_dir, names, shape):
+    """[F,H,W,3] uint8: DIR/<frame name> of every frame, at the depth maps' size; exits with a message otherwise."""
+    paths = [os.path.join(color_dir, n) for n in names]
+    for path in paths:
+        if not os.path.isfile(path):
+            sys.exit("integrate_tsdf.py: colour image %s not found (--color-dir needs one image per frame of the pose file)" % path)
+    try:
+        rgb = r3d.cloud_io.read_rgb_batch(paths)
+    except (ValueError, r3d.R3DError) as e:
+        sys.exit("integrate_tsdf.py: the colour images in %s cannot be read as one batch (they must all have the depth maps' size): %s"
+                 % (color_dir, e))
+    if rgb.shape[1:3] != tuple(shape):
+        sys.exit("integrate_tsdf.py: the colour images are %d x %d, the depth maps %d x %d" % (rgb.shape[1:3] + tuple(shape)))
+    return rgb
+
+
 def main(argv=None):
     args = parse_args(sys.argv[1:] if argv is None else argv)
     r3d = _common.package()
@@ -105,17 +125,27 @@ def main(argv=None):
     else:
         origin, dims = args.origin, args.dims
     depths = r3d.cloud_io.read_depth_batch([os.path.join('./depth/', n) for n in names])
+    rgb = read_colors(r3d, args.color_dir, names, depths.shape[-2:]) if args.color_dir is not None else None
     _common.stamp("read %d frames" % len(names))
-    vol = r3d.TSDFVolume(origin, args.voxel_size, dims, args.trunc, ctx=_common.context())
-    vol.integrate(depths, quats, ts, intrinsics=_common.intrinsics())
+    if rgb is None:
+        vol = r3d.TSDFVolume(origin, args.voxel_size, dims, args.trunc, ctx=_common.context())
+        vol.integrate(depths, quats, ts, intrinsics=_common.intrinsics())
+    else:
+        vol = r3d.TSDFVolume(origin, args.voxel_size, dims, args.trunc, ctx=_common.context(), color=True)
+        vol.integrate(depths, quats, ts, intrinsics=_common.intrinsics(), rgb=rgb)
     _common.stamp("integrate")
-    xyz, normals = vol.extract_point_cloud(args.min_weight)
-    mesh = vol.extract_triangle_mesh(args.min_weight) if args.mesh else None
+    colors = None
+    if rgb is None:
+        xyz, normals = vol.extract_point_cloud(args.min_weight)
+        mesh = vol.extract_triangle_mesh(args.min_weight) if args.mesh else None
+    else:
+        xyz, normals, colors = vol.extract_point_cloud(args.min_weight, with_colors=True)
+        mesh = vol.extract_triangle_mesh(args.min_weight)[:3] + (colors,) if args.mesh else None   # the vertices are the points
     cast = raycast_depth(r3d, vol, quats, ts, depths.shape[-2:], args.min_weight) if args.raycast else None
     vol.close()
     _common.stamp("extract")
     os.makedirs(os.path.dirname(OUT_FILE), exist_ok=True)
-    r3d.cloud_io.write_ply_normals(OUT_FILE, xyz, normals)
+    r3d.cloud_io.write_ply_normals(OUT_FILE, xyz, normals, rgb=colors)
     print("origin %.9g %.9g %.9g dims %d %d %d voxel %.9g trunc %.9g frames %d points %d -> %s"
           % (origin[0], origin[1], origin[2], dims[0], dims[1], dims[2], args.voxel_size, args.trunc, len(names), len(xyz), OUT_FILE))
     if mesh is not None:

@@ -1,7 +1,8 @@
 """Dense TSDF volume on the MI355X: depth frames + poses are integrated into a truncated signed distance volume, and its zero
 level set comes back as oriented surface points or as an indexed triangle mesh over those points (marching cubes) -- what users
 of a depth + pose pipeline expect (Open3D's UniformTSDFVolume; no parity with Open3D is claimed).  Where fuse_frames concatenates the frames' points, the volume averages
-overlapping frames.  Semantics: include/r3d.h (r3d_tsdf_*) and DESIGN.md sections 4.5i and 4.5j.
+overlapping frames.  A volume created with color=True also averages the frames' colour images and returns a colour with every
+surface point / mesh vertex.  Semantics: include/r3d.h (r3d_tsdf_*) and DESIGN.md sections 4.5i to 4.5l.
 
 The volume takes the inputs camera_to_world.py already has: [F,H,W] depth, one pose-file row per frame, a pinhole camera.  Its
 poses are WORLD -> CAMERA (p_cam = R p_w + t: the pose file's quaternion and t as they stand, poses_w2c), not the inverted table
@@ -60,6 +61,23 @@ def _ray_range(step, t_near, t_far, voxel_size):
     return s, tn, tf
 
 
+def _rgb_batch(rgb, shape):
+    """rgb as a contiguous [F,H,W,3] uint8 array for depth rasters of shape (F, H, W); [H,W,3] is one frame."""
+    c = np.asarray(rgb)
+    if c.ndim == 3:
+        c = c[None]
+    if c.dtype != np.uint8 or c.shape != tuple(shape) + (3,):
+        raise ValueError("rgb must be uint8 of shape %s (R, G, B per pixel of every depth raster), got %s of shape %s"
+                         % (list(shape) + [3], c.dtype, list(np.shape(rgb))))
+    return np.ascontiguousarray(c)
+
+
+def _unpack_rgba(words):
+    """[N,3] uint8 (R, G, B) from the words r | g << 8 | b << 16"""
+    w = np.ascontiguousarray(words, dtype=np.uint32)
+    return np.stack([w & 0xff, (w >> 8) & 0xff, (w >> 16) & 0xff], axis=1).astype(np.uint8)
+
+
 def _pose_rows(poses, n_frames):
     p = np.ascontiguousarray(poses, dtype=np.float64)
     if p.ndim != 2 or p.shape != (n_frames, 12):
@@ -69,9 +87,10 @@ def _pose_rows(poses, n_frames):
 
 class TSDFVolume:
     """origin [3] (the corner of voxel (0, 0, 0); its centre is origin + voxel_size / 2), voxel_size, dims = (nx, ny, nz),
-    sdf_trunc: the truncation distance.  One float2 {tsdf, weight} per voxel in HBM."""
+    sdf_trunc: the truncation distance.  One float2 {tsdf, weight} per voxel in HBM; with color=True a second plane of one
+    uint32[4] {sum_r, sum_g, sum_b, n} per voxel, and every integrate call takes the frames' colour images."""
 
-    def __init__(self, origin, voxel_size, dims, sdf_trunc, ctx=None):
+    def __init__(self, origin, voxel_size, dims, sdf_trunc, ctx=None, color=False):
         o = np.ascontiguousarray(origin, dtype=np.float64)
         if o.shape != (3,) or not np.isfinite(o.astype(np.float32)).all():
             raise ValueError("origin must be three finite numbers, got %r" % (origin,))
@@ -86,8 +105,10 @@ class TSDFVolume:
         self.ctx = ctx or default_context()
         self.origin, self.voxel_size, self.sdf_trunc, self.dims = o, vs, tr, (nx, ny, nz)
         self.n_voxels = nx * ny * nz
+        self.color = bool(color)
         h = C.c_void_p()
-        L.check(self.ctx.lib.r3d_tsdf_create(self.ctx.handle, o.ctypes.data, vs, nx, ny, nz, tr, C.byref(h)))
+        create = self.ctx.lib.r3d_tsdf_create_rgb if self.color else self.ctx.lib.r3d_tsdf_create
+        L.check(create(self.ctx.handle, o.ctypes.data, vs, nx, ny, nz, tr, C.byref(h)))
         self.handle = h.value
         self.ctx.adopt(self)
 
@@ -106,27 +127,47 @@ class TSDFVolume:
         """Back to the fresh volume: all zero bytes."""
         L.check(self.ctx.lib.r3d_tsdf_reset(self.handle))
 
-    def integrate(self, depths, quats_xyzw, ts, intrinsics=REF_INTRINSICS, depth_scale=1.0):
+    def _check_color(self, given, what):
+        if given and not self.color:
+            raise ValueError("%s given to a volume without colour (create it with color=True)" % what)
+        if self.color and not given:
+            raise ValueError("a volume with colour integrates colour images: %s is missing" % what)
+
+    def integrate(self, depths, quats_xyzw, ts, intrinsics=REF_INTRINSICS, depth_scale=1.0, rgb=None):
         """Integrate host rasters [H,W] or [F,H,W] (uint8, uint16 or float32) seen from the pose-file rows (quats_xyzw, ts), in
-        frame order.  Synchronous."""
+        frame order.  A volume with colour takes rgb too: [H,W,3] or [F,H,W,3] uint8 (R, G, B), one image per raster.
+        Synchronous."""
+        self._check_color(rgb is not None, "rgb")
         d = _as_batch(depths)
         f, h, w = d.shape
+        if rgb is not None:
+            rgb = _rgb_batch(rgb, d.shape)
         table = poses_w2c(quats_xyzw, ts)
         if table.shape[0] != f:
             raise ValueError("%d frames but %d poses" % (f, table.shape[0]))
         if f * h * w == 0:
             return
         cam = self.ctx.camera(h, w, *intrinsics)
+        if rgb is not None:
+            L.check(self.ctx.lib.r3d_tsdf_integrate_rgb_host(self.handle, cam.handle, d.ctypes.data, depth_code(d.dtype), f,
+                                                             float(depth_scale), table.ctypes.data, rgb.ctypes.data))
+            return
         L.check(self.ctx.lib.r3d_tsdf_integrate_host(self.handle, cam.handle, d.ctypes.data, depth_code(d.dtype), f, float(depth_scale),
                                                      table.ctypes.data))
 
-    def integrate_device(self, cam, d_depth, depth_dtype, n_frames, poses_w2c, depth_scale=1.0):
+    def integrate_device(self, cam, d_depth, depth_dtype, n_frames, poses_w2c, depth_scale=1.0, d_rgb=None):
         """The same from rasters in HBM (d_depth: [n_frames][H][W] of depth_dtype at a raw device address; cam: ctx.camera(...));
-        poses_w2c: [n_frames,12] host rows.  Asynchronous on the context's stream."""
+        poses_w2c: [n_frames,12] host rows.  A volume with colour takes d_rgb too: [n_frames][H][W][3] uint8 at a raw device
+        address.  Asynchronous on the context's stream."""
         n_frames = int(n_frames)
         if n_frames < 0:
             raise ValueError("n_frames must be >= 0, got %d" % n_frames)
+        self._check_color(d_rgb is not None, "d_rgb")
         table = _pose_rows(poses_w2c, n_frames)
+        if d_rgb is not None:
+            L.check(self.ctx.lib.r3d_tsdf_integrate_rgb(self.handle, cam.handle, d_depth, depth_code(depth_dtype), n_frames,
+                                                        float(depth_scale), table.ctypes.data, d_rgb))
+            return
         L.check(self.ctx.lib.r3d_tsdf_integrate(self.handle, cam.handle, d_depth, depth_code(depth_dtype), n_frames, float(depth_scale),
                                                 table.ctypes.data))
 
@@ -144,6 +185,43 @@ class TSDFVolume:
         nx, ny, nz = self.dims
         return np.ascontiguousarray(raw[:, 0]).reshape(nz, ny, nx), np.ascontiguousarray(raw[:, 1]).reshape(nz, ny, nx)
 
+    def colors_device_view(self):
+        """(raw device address of the [n_voxels][4] uint32 {sum_r, sum_g, sum_b, n} plane, n_voxels) of a volume with colour."""
+        p, n = C.c_void_p(), C.c_int64()
+        L.check(self.ctx.lib.r3d_tsdf_colors(self.handle, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def colors(self):
+        """(sums [nz,ny,nx,3] uint32, n [nz,ny,nx] uint32): per voxel the sums of the red, green and blue bytes over the frames
+        that touched it, and their number."""
+        if not self.color:
+            raise ValueError("the volume was created without colour (color=True makes one with)")
+        p, n = self.colors_device_view()
+        raw = np.empty((n, 4), dtype=np.uint32)
+        L.check(self.ctx.lib.r3d_download(self.ctx.handle, raw.ctypes.data, p, raw.nbytes))   # synchronous
+        nx, ny, nz = self.dims
+        return np.ascontiguousarray(raw[:, :3]).reshape(nz, ny, nx, 3), np.ascontiguousarray(raw[:, 3]).reshape(nz, ny, nx)
+
+    def extract_colors_device(self, min_weight, d_rgba, cap):
+        """The surface points' colours into d_rgba ([cap] uint32 words r | g << 8 | b << 16 at a raw device address; None with
+        cap == 0): word k is the colour of row k of extract_points_device.  Returns the TRUE number of points, of which at most
+        cap words were written.  Synchronises."""
+        mw, n = _positive_f32(min_weight, "min_weight"), C.c_int64()
+        L.check(self.ctx.lib.r3d_tsdf_extract_colors(self.handle, mw, d_rgba, int(cap), C.byref(n)))
+        return n.value
+
+    def _extract_colors(self, mw, n):
+        """[n,3] uint8: the colours of the n surface points"""
+        if n == 0:
+            return np.zeros((0, 3), np.uint8)
+        d_rgba = self.ctx.alloc(n * 4)
+        try:
+            got = self.extract_colors_device(mw, d_rgba.ptr, n)
+            assert got == n, (got, n)
+            return _unpack_rgba(d_rgba.download(np.uint32, n))
+        finally:
+            d_rgba.free()
+
     def extract_points_device(self, min_weight, d_xyz, d_normals, cap):
         """Surface points into d_xyz / d_normals ([cap][3] float32 device addresses; d_normals may be None); returns the TRUE
         number of points, of which at most cap rows were written.  Synchronises."""
@@ -152,19 +230,24 @@ class TSDFVolume:
                                                      C.byref(n)))
         return n.value
 
-    def extract_point_cloud(self, min_weight=1.0):
+    def extract_point_cloud(self, min_weight=1.0, with_colors=False):
         """(xyz [N,3], normals [N,3]) float32: one point per volume edge whose two voxels have at least min_weight frames each and
         tsdf values of different sign, in linear voxel order (x fastest), per voxel the x, y, z edge; the normals point towards the
-        cameras (zero rows where the gradient vanishes)."""
+        cameras (zero rows where the gradient vanishes).  with_colors (a volume with colour): a third array, [N,3] uint8 R, G, B --
+        the two voxels' mean colours, interpolated like the position."""
         mw = _positive_f32(min_weight, "min_weight")
+        if with_colors and not self.color:
+            raise ValueError("with_colors needs a volume created with color=True")
         n = self.extract_points_device(mw, None, None, 0)
         if n == 0:
-            return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32)
+            empty = (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32))
+            return empty + (np.zeros((0, 3), np.uint8),) if with_colors else empty
         d_xyz, d_nrm = self.ctx.alloc(n * 12), self.ctx.alloc(n * 12)
         try:
             got = self.extract_points_device(mw, d_xyz.ptr, d_nrm.ptr, n)
             assert got == n, (got, n)
-            return d_xyz.download(np.float32, 3 * n).reshape(n, 3), d_nrm.download(np.float32, 3 * n).reshape(n, 3)
+            out = (d_xyz.download(np.float32, 3 * n).reshape(n, 3), d_nrm.download(np.float32, 3 * n).reshape(n, 3))
+            return out + (self._extract_colors(mw, n),) if with_colors else out
         finally:
             d_xyz.free()
             d_nrm.free()
@@ -180,21 +263,26 @@ class TSDFVolume:
                                                    C.byref(nv), C.byref(nt)))
         return nv.value, nt.value
 
-    def extract_triangle_mesh(self, min_weight=1.0):
+    def extract_triangle_mesh(self, min_weight=1.0, with_colors=False):
         """(xyz [N,3] float32, normals [N,3] float32, triangles [M,3] int32): marching cubes over the cells whose eight voxels
         have at least min_weight frames each.  The vertices are extract_point_cloud's rows (one per crossing volume edge, so the
         mesh is welded by construction); a triangle (a, b, c) winds so that (b - a) x (c - a) points towards the cameras, like the
-        vertex normals."""
+        vertex normals.  with_colors (a volume with colour): a fourth array, [N,3] uint8 R, G, B, the vertices' colours --
+        extract_point_cloud's."""
         mw = _positive_f32(min_weight, "min_weight")
+        if with_colors and not self.color:
+            raise ValueError("with_colors needs a volume created with color=True")
         n, m = self.extract_mesh_device(mw, None, None, 0, None, 0)
         if n == 0:
-            return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32)
+            empty = (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32))
+            return empty + (np.zeros((0, 3), np.uint8),) if with_colors else empty
         d_xyz, d_nrm, d_tri = self.ctx.alloc(n * 12), self.ctx.alloc(n * 12), self.ctx.alloc(max(m, 1) * 12)
         try:
             got = self.extract_mesh_device(mw, d_xyz.ptr, d_nrm.ptr, n, d_tri.ptr if m else None, m)
             assert got == (n, m), (got, n, m)
             tri = d_tri.download(np.int32, 3 * m).reshape(m, 3) if m else np.zeros((0, 3), np.int32)
-            return d_xyz.download(np.float32, 3 * n).reshape(n, 3), d_nrm.download(np.float32, 3 * n).reshape(n, 3), tri
+            out = (d_xyz.download(np.float32, 3 * n).reshape(n, 3), d_nrm.download(np.float32, 3 * n).reshape(n, 3), tri)
+            return out + (self._extract_colors(mw, n),) if with_colors else out
         finally:
             for b in (d_xyz, d_nrm, d_tri):
                 b.free()

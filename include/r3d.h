@@ -741,6 +741,43 @@ int r3d_tsdf_extract_mesh(r3d_tsdf* vol, double min_weight, float* d_xyz_out, fl
 int r3d_tsdf_raycast(r3d_tsdf* vol, const r3d_camera* cam, int n_views, const double* h_pose_w2c, double min_weight, double step,
                      double t_near, double t_far, float* d_depth_out, float* d_vertex_out, float* d_normal_out);
 
+/* ---- TSDF colour (csrc/r3d_tsdf_color.hip; the volume above fed from RGBD: colour images are integrated next to the depth rasters
+ * and the surface points -- which are the mesh's vertices -- come back with a colour each; this text is the specification).  A
+ * volume without colour is untouched by anything here: same storage, same kernels, same bits.
+ * Storage: a volume made by r3d_tsdf_create_rgb (arguments, errors and R3D_ERR_NOMEM as r3d_tsdf_create) owns a second plane,
+ *   separate from the float2 array, whose layout and device view (r3d_tsdf_volume) stay as they are: one uint32[4] {sum_r, sum_g,
+ *   sum_b, n} per voxel at the same linear index, 16 bytes, 16-byte aligned.  Zero bytes = fresh; r3d_tsdf_reset clears both planes.
+ * Integration: d_rgb is [n_frames][H][W][3] uint8 in R, G, B order (the layout r3d_fuse_frames_rgb takes).  Frame f touches a
+ *   voxel exactly when the depth rule of "TSDF volume" accepts it -- the same tests at the same pixel (vi, ui) -- and then updates
+ *   tsdf and w exactly as written there AND adds the three bytes rgb[f][vi][ui][0..2] to sum_r, sum_g, sum_b and 1 to n, in uint32
+ *   arithmetic.  The tsdf / weight plane is bit-identical to what r3d_tsdf_integrate makes of the same depth and poses.  The
+ *   plane holds integers, so it does not depend on the order of the frames or on how they are split into calls; n == w for fewer
+ *   than 2^24 frames (w is an f32 and stops counting there; the sums and n wrap modulo 2^32, the sums from 2^24 frames of 255 on).
+ *   r3d_tsdf_integrate_rgb is asynchronous (same pose ring, R3D_TSDF_CHUNK frames per launch); r3d_tsdf_integrate_rgb_host uploads
+ *   rasters and images itself, in slabs of whole frames sized for both together, and is synchronous.
+ * Colour of a surface point: row k of r3d_tsdf_extract_points lies on the edge from voxel v to its neighbour u with
+ *   r = A / (A - B) as specified there.  Per channel, all f32, no fused multiply-add, correctly rounded division, uint32 -> f32
+ *   conversions rounding to nearest even:
+ *     mv = (float) sum_v / (float) n_v;  mu = (float) sum_u / (float) n_u      (a mean is 0.0f where n == 0: no division by zero is
+ *                                                                              specified; a valid voxel has w >= 1, hence n >= 1)
+ *     m  = mv + r * (mu - mv);  q = fminf(fmaxf(floorf(m + 0.5f), 0.0f), 255.0f)
+ *   The row is the word r | g << 8 | b << 16 (what r3d_fuse_frames_rgb writes).  Colour row k belongs to point row k: same count,
+ *   same order, same cap rule -- *n_out is the true count, always; at most cap words are written and nothing beyond them.  The
+ *   mesh's vertices are those rows, so the same call colours the mesh.  r3d_tsdf_extract_colors synchronises.
+ * r3d_tsdf_colors: the device view of the plane ([n_voxels][4] uint32), valid until destroy; either out-pointer may be NULL.
+ * R3D_ERR_INVALID, nothing written: a colour call (r3d_tsdf_integrate_rgb, _rgb_host, r3d_tsdf_colors, r3d_tsdf_extract_colors) on
+ *   a volume without the plane; r3d_tsdf_integrate / _host on a volume WITH the plane (n and w would part), whatever n_frames;
+ *   NULL d_rgb / h_rgb with n_frames > 0; and the argument errors of r3d_tsdf_integrate and r3d_tsdf_extract_points.
+ *   n_frames == 0 -> R3D_OK. */
+int r3d_tsdf_create_rgb(r3d_ctx* ctx, const double* h_origin, double voxel_size, int nx, int ny, int nz, double sdf_trunc,
+                        r3d_tsdf** out);
+int r3d_tsdf_integrate_rgb(r3d_tsdf* vol, const r3d_camera* cam, const void* d_depth, int depth_dtype, int n_frames,
+                           double depth_scale, const double* h_pose_w2c, const uint8_t* d_rgb);
+int r3d_tsdf_integrate_rgb_host(r3d_tsdf* vol, const r3d_camera* cam, const void* h_depth, int depth_dtype, int n_frames,
+                                double depth_scale, const double* h_pose_w2c, const uint8_t* h_rgb);
+int r3d_tsdf_colors(r3d_tsdf* vol, uint32_t** d_sums_out, int64_t* n_voxels_out);
+int r3d_tsdf_extract_colors(r3d_tsdf* vol, double min_weight, uint32_t* d_rgba_out, int64_t cap, int64_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,10 @@ outside the timed window before every run:
   batched      one r3d_tsdf_integrate call of all frames (the frame loop inside the kernel, R3D_TSDF_CHUNK frames per launch);
   per_frame    the same kernel launched one frame at a time (one call per frame);
   extract      r3d_tsdf_extract_points (count + scan + emit, with normals) of the integrated volume;
-  mesh         r3d_tsdf_extract_mesh (count + scan + vertices + triangles) of the same volume, alternating with extract.
+  mesh         r3d_tsdf_extract_mesh (count + scan + vertices + triangles) of the same volume, alternating with extract;
+  rgb          a second volume with the colour plane: one r3d_tsdf_integrate_rgb call of all frames (seeded noise images in HBM),
+               alternating with the depth-only batched call on the first volume, both volumes reset outside the window;
+  colors       r3d_tsdf_extract_colors of the integrated colour volume, alternating with r3d_tsdf_extract_points on it.
 Roofs are printed from shapes, not measured: algorithmic bytes of the batched form (16 B per voxel and launch + the rasters once)
 against 8 TB/s, and voxel-frames x the per-voxel-frame instruction count of the disassembly against the VALU rate.
 CPU leg, as reported and not optimised against: tests/tsdf_ref.py (NumPy, one thread) on a 64^3 volume and 10 frames.
@@ -56,6 +59,9 @@ del depth
 poses = T.poses_w2c(quats, ts)
 cam = ctx.camera(H, W, *K)
 d_depth = ctx.alloc(depth_u8.nbytes).upload(depth_u8)
+rgb = np.random.default_rng(0).integers(0, 256, (FRAMES, H, W, 3), dtype=np.uint8)
+d_rgb = ctx.alloc(rgb.nbytes).upload(rgb)
+del rgb
 lo, hi = S.ROOM_LO - 0.3, S.ROOM_HI + 0.3
 lines = []
 for n in (256, 512):
@@ -79,6 +85,26 @@ for n in (256, 512):
     d_tri = ctx.alloc(max(n_t, 1) * 12)
     e_ms, m_ms = timed_alternating([lambda: vol.extract_points_device(1.0, d_xyz.ptr, d_nrm.ptr, count),
                                     lambda: vol.extract_mesh_device(1.0, d_xyz.ptr, d_nrm.ptr, count, d_tri.ptr, n_t)], lambda: None)
+    # the colour legs
+    cvol = T.TSDFVolume(lo, vs, (n, n, n), 4 * vs, ctx=ctx, color=True)
+
+    def batched_rgb():
+        cvol.integrate_device(cam, d_depth.ptr, np.uint8, FRAMES, poses, 1.0 / 32, d_rgb=d_rgb.ptr)
+
+    def reset_both():
+        vol.reset()
+        cvol.reset()
+
+    d_ms, c_ms = timed_alternating([batched, batched_rgb], reset_both)
+    reset_both()
+    batched()
+    batched_rgb()
+    assert cvol.extract_colors_device(1.0, None, 0) == count
+    d_rgba = ctx.alloc(max(count, 1) * 4)
+    ec_ms, ep_ms = timed_alternating([lambda: cvol.extract_colors_device(1.0, d_rgba.ptr, count),
+                                      lambda: cvol.extract_points_device(1.0, d_xyz.ptr, d_nrm.ptr, count)], lambda: None)
+    d_rgba.free()
+    cvol.close()
     _, w = vol.volume()
     pairs = float(w.sum())                               # (voxel, frame) pairs that passed every test
     launches = -(-FRAMES // T.CHUNK)
@@ -87,7 +113,8 @@ for n in (256, 512):
     roof_valu_ms = voxels * FRAMES * INSTR_PER_VOXEL_FRAME / VALU_LANE_INSTR_PER_S * 1e3
     line = {"volume": "%d^3" % n, "voxel_size": round(vs, 6), "frames": FRAMES, "raster": [H, W], "dtype": "uint8", "reps": reps,
             "integrate_batched_ms": b_ms, "integrate_per_frame_ms": p_ms, "per_frame_over_batched": round(p_ms / b_ms, 3),
-            "extract_ms": e_ms, "mesh_ms": m_ms, "surface_points": int(count), "triangles": int(n_t), "voxel_frame_pairs_accepted": pairs,
+            "extract_ms": e_ms, "mesh_ms": m_ms, "integrate_rgb_batched_ms": c_ms, "integrate_depth_only_same_legs_ms": d_ms,
+            "rgb_over_depth_only": round(c_ms / d_ms, 3), "extract_colors_ms": ec_ms, "extract_points_color_volume_ms": ep_ms, "surface_points": int(count), "triangles": int(n_t), "voxel_frame_pairs_accepted": pairs,
             "voxel_frames_per_s_batched": round(voxels * FRAMES / (b_ms * 1e-3), 1),
             "roof_hbm_ms_8TBps": round(roof_bytes_ms, 4), "roof_valu_ms_at_%d_instr" % INSTR_PER_VOXEL_FRAME: round(roof_valu_ms, 4)}
     print(json.dumps(line), flush=True)
