@@ -26,6 +26,7 @@ from .normals import (Normals, estimate_normals, estimate_normals_device, estima
                       fused_viewpoints)
 from .segmentation import PlaneSegment, segment_plane, segment_planes, segment_plane_device  # noqa: F401
 from .tsdf import TSDFVolume, poses_w2c  # noqa: F401
+from .tracking import TrackDevice, track_sums  # noqa: F401
 from . import cloud_io, device_text  # noqa: F401
 
 __version__ = "0.2.0"

@@ -1,0 +1,372 @@
+// Frame-to-model tracking for gfx950 (MI355X): projective point-to-plane ICP of a new depth frame against the maps the TSDF
+// volume predicts for a pose (r3d_tsdf_raycast) -- the fourth leg of integrate / extract / ray cast / track.  NOT IN THE
+// REFERENCE (its poses come from COLMAP): build-defined, specified in include/r3d.h ("TSDF tracking").
+//
+//   track_kernel         one lane per source pixel: move it by M = T_total . S, project it into the model camera, gather the
+//                        model vertex and normal at the nearest pixel, gate, and add the pair to the 29 fp64 sums of
+//                        r3d_plane_sums.h.  A 256-thread workgroup owns 1024 consecutive pixels (thread t: base + t + 256 k,
+//                        k = 0..3) and leaves one partial row: the launch shape is a function of the raster alone, so the sums
+//                        are the same bits on every device and under every tuning.  Source rows are read coalesced (12 B per
+//                        lane, consecutive); the gather lands near the lane's own pixel for the small motions tracking sees.
+//                        M, the model pose and the intrinsics are wave-uniform.  The only LDS is the reduction's.
+//   track_finish_kernel  ONE workgroup: partial rows in fixed order -> 29 sums -> Cholesky solve + exponential map -> the ICP
+//                        state in HBM (the pattern of r3d_plane.hip's finish kernel, same state layout)
+// No atomics: bitwise repeatable.  No search structure, no sort, no index: the association is one projection and one gather.
+#include <cmath>
+
+#include "r3d_icp_sums.h"
+#include "r3d_internal.h"
+#include "r3d_plane_sums.h"
+#include "r3d_tsdf_dev.h"
+
+namespace {
+
+constexpr int kThreads = r3d_plane::kThreads;
+constexpr int kPerLane = 4;
+constexpr int kTile = kThreads * kPerLane;   // pixels per workgroup: part of the specification
+using r3d_plane::kSums;
+
+struct __attribute__((packed, aligned(4))) P3 {
+  float x, y, z;
+};
+
+struct TrackParams {
+  double fx, fy, cx, cy;   // the camera's doubles
+  double rm[9], tm[3];     // the pose the model maps were cast from, world -> camera
+  double s[16];            // the guess: source camera -> world, row-major 4x4
+  double dist2;            // dist_max * dist_max
+  double cos_min;
+  double wd, hd;           // (double) W, (double) H
+  int width;
+  int n_px;
+};
+
+__device__ __forceinline__ bool finite3(const P3& p) { return isfinite(p.x) && isfinite(p.y) && isfinite(p.z); }
+
+__global__ __launch_bounds__(kThreads) void track_kernel(const float* __restrict__ src_vertex, const float* __restrict__ src_normal,
+                                                         const float* __restrict__ model_vertex,
+                                                         const float* __restrict__ model_normal, const TrackParams a,
+                                                         const double* __restrict__ state, double* __restrict__ partials,
+                                                         int32_t* __restrict__ match_out, float* __restrict__ residual_out) {
+  __shared__ double red[kThreads / 64][kSums];
+  // M = T_total . S, the loop of the solve's T_total update: every entry summed over m = 0..3 from 0.0 (rows 0..2 are used)
+  double M[12];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      double v = 0.0;
+#pragma unroll
+      for (int m = 0; m < 4; ++m) {
+        const double t = state ? state[r3d_icp::kStateTTotal + 4 * r + m] : (r == m ? 1.0 : 0.0);
+        v += t * a.s[4 * m + c];
+      }
+      M[4 * r + c] = v;
+    }
+  double acc[kSums];
+#pragma unroll
+  for (int k = 0; k < kSums; ++k) acc[k] = 0.0;
+  const P3* SV = reinterpret_cast<const P3*>(src_vertex);
+  const P3* SN = reinterpret_cast<const P3*>(src_normal);
+  const P3* MV = reinterpret_cast<const P3*>(model_vertex);
+  const P3* MN = reinterpret_cast<const P3*>(model_normal);
+  const int base = (int)blockIdx.x * kTile + (int)threadIdx.x;   // n_px < 2^31 - kTile (checked by the host)
+  for (int k = 0; k < kPerLane; ++k) {
+    const int i = base + k * kThreads;
+    if (i >= a.n_px) break;
+    const P3 sv = SV[i];
+    int32_t code = -1;
+    double r = 0.0;
+    if (finite3(sv) && sv.z > 0.0f) {
+      const double x = (double)sv.x, y = (double)sv.y, z = (double)sv.z;
+      double p[3], pm[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) p[c] = ((M[4 * c] * x + M[4 * c + 1] * y) + M[4 * c + 2] * z) + M[4 * c + 3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) pm[c] = ((a.rm[3 * c] * p[0] + a.rm[3 * c + 1] * p[1]) + a.rm[3 * c + 2] * p[2]) + a.tm[c];
+      code = -2;
+      if (pm[2] > 0.0) {
+        const double u = a.fx * (pm[0] / pm[2]) + a.cx, v = a.fy * (pm[1] / pm[2]) + a.cy;
+        const double uj = floor(u + 0.5), vj = floor(v + 0.5);
+        if (uj >= 0.0 && uj < a.wd && vj >= 0.0 && vj < a.hd) {   // NaN fails every comparison
+          const int j = (int)vj * a.width + (int)uj;              // inside [0, n_px)
+          const P3 qv = MV[j], qn = MN[j];
+          code = -3;
+          if (finite3(qv) && finite3(qn) && !(qn.x == 0.0f && qn.y == 0.0f && qn.z == 0.0f)) {
+            const double q[3] = {(double)qv.x, (double)qv.y, (double)qv.z};
+            const double n[3] = {(double)qn.x, (double)qn.y, (double)qn.z};
+            const double d0 = p[0] - q[0], d1 = p[1] - q[1], d2 = p[2] - q[2];
+            code = -4;
+            if ((d0 * d0 + d1 * d1) + d2 * d2 <= a.dist2) {
+              bool ok = true;
+              if (SN) {
+                const P3 sn = SN[i];
+                ok = finite3(sn) && !(sn.x == 0.0f && sn.y == 0.0f && sn.z == 0.0f);
+                if (ok) {
+                  const double n0 = (double)sn.x, n1 = (double)sn.y, n2 = (double)sn.z;
+                  double g[3];
+#pragma unroll
+                  for (int c = 0; c < 3; ++c) g[c] = (M[4 * c] * n0 + M[4 * c + 1] * n1) + M[4 * c + 2] * n2;
+                  ok = (g[0] * n[0] + g[1] * n[1]) + g[2] * n[2] >= a.cos_min;
+                }
+              }
+              code = -5;
+              if (ok) {
+                r = r3d_plane::plane_residual(p, q, n);
+                r3d_plane::pair_accumulate(acc, 1.0, p, n, r);
+                code = j;
+              }
+            }
+          }
+        }
+      }
+    }
+    if (match_out) match_out[i] = code;
+    if (residual_out) residual_out[i] = code >= 0 ? (float)r : 0.0f;
+  }
+  r3d_plane::block_reduce_store(acc, red, partials + (int64_t)blockIdx.x * kSums);
+}
+
+// One thread: step from the sums; T_total <- step . T_total; history.  The arithmetic of r3d_plane.hip's plane_solve_step, so
+// that this loop's state means what the other loops' states mean (a degenerate step is the identity: T_total stays).
+__device__ void track_solve_step(const double* s, double* __restrict__ st) {
+  double T[16], rms = 0.0;
+  const int bad = r3d_plane::step_from_sums(s, T, &rms);
+  double tot[16], nt[16];
+  for (int k = 0; k < 16; ++k) tot[k] = st[r3d_icp::kStateTTotal + k];
+  for (int r = 0; r < 4; ++r)
+    for (int c = 0; c < 4; ++c) {
+      double v = 0.0;
+      for (int m = 0; m < 4; ++m) v += T[4 * r + m] * tot[4 * m + c];
+      nt[4 * r + c] = v;
+    }
+  for (int k = 0; k < 16; ++k) {
+    st[r3d_icp::kStateTStep + k] = T[k];
+    st[r3d_icp::kStateTTotal + k] = nt[k];
+  }
+  const int it = (int)st[r3d_icp::kStateIters];
+  if (r3d_icp::kStateHistory + it < r3d_icp::kStateDoubles) st[r3d_icp::kStateHistory + it] = rms;
+  st[r3d_icp::kStateIters] = (double)(it + 1);
+  if (bad) st[r3d_icp::kStateStatus] = 1.0;
+  st[r3d_icp::kStateRms] = rms;
+  st[r3d_icp::kStatePairs] = s[0];
+}
+
+__global__ __launch_bounds__(kThreads) void track_finish_kernel(const double* __restrict__ partials, int n_rows,
+                                                                double* __restrict__ sums_out, double* __restrict__ state) {
+  __shared__ double red[kThreads / 64][kSums];
+  __shared__ double total[kSums];
+  double acc[kSums];
+#pragma unroll
+  for (int k = 0; k < kSums; ++k) acc[k] = 0.0;
+  for (int b = threadIdx.x; b < n_rows; b += kThreads) {
+#pragma unroll
+    for (int k = 0; k < kSums; ++k) acc[k] += partials[(int64_t)b * kSums + k];
+  }
+  r3d_plane::block_reduce_store(acc, red, total);
+  __syncthreads();
+  if (threadIdx.x < kSums && sums_out) sums_out[threadIdx.x] = total[threadIdx.x];
+  if (threadIdx.x == 0 && state != nullptr) {
+    double s[kSums];
+    for (int k = 0; k < kSums; ++k) s[k] = total[k];
+    track_solve_step(s, state);
+  }
+}
+
+bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  if (!a || !b || !a_bytes || !b_bytes) return false;
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+struct Maps {
+  const float *src_vertex, *src_normal, *model_vertex, *model_normal;
+};
+
+// the argument checks the three entry points share; fills *p
+int track_checks(r3d_ctx* ctx, const r3d_camera* cam, const Maps& m, const double* h_model_pose_w2c, const double* h_S, double dist_max,
+                 double cos_min, TrackParams* p) {
+  R3D_REQUIRE(ctx != nullptr, "ctx is NULL");
+  R3D_REQUIRE(cam != nullptr, "camera is NULL");
+  R3D_REQUIRE(cam->ctx == ctx, "the camera belongs to another context");
+  R3D_REQUIRE(m.src_vertex && m.model_vertex && m.model_normal, "NULL map pointer");
+  R3D_REQUIRE(h_model_pose_w2c && h_S, "NULL pose pointer");
+  R3D_REQUIRE(dist_max > 0.0 && std::isfinite(dist_max), "dist_max must be positive and finite");
+  R3D_REQUIRE(cos_min >= -1.0 && cos_min <= 1.0, "cos_min must be in [-1, 1]");
+  R3D_REQUIRE((int64_t)cam->width * cam->height < ((int64_t)1 << 31) - kTile, "raster of %d x %d pixels is too large for tracking",
+              cam->height, cam->width);
+  p->fx = cam->fx, p->fy = cam->fy, p->cx = cam->cx, p->cy = cam->cy;
+  for (int k = 0; k < 9; ++k) p->rm[k] = h_model_pose_w2c[k];
+  for (int k = 0; k < 3; ++k) p->tm[k] = h_model_pose_w2c[9 + k];
+  for (int k = 0; k < 16; ++k) p->s[k] = h_S[k];
+  p->dist2 = dist_max * dist_max;
+  p->cos_min = cos_min;
+  p->wd = (double)cam->width, p->hd = (double)cam->height;
+  p->width = cam->width;
+  p->n_px = cam->width * cam->height;
+  return R3D_OK;
+}
+
+// the caller's device outputs against the four input maps and against each other
+int output_checks(const TrackParams& p, const Maps& m, const void* const* outs, const size_t* out_bytes, int n_outs) {
+  const size_t map = (size_t)p.n_px * 12;
+  const void* in[4] = {m.src_vertex, m.src_normal, m.model_vertex, m.model_normal};
+  for (int a = 0; a < n_outs; ++a) {
+    for (int b = 0; b < 4; ++b) R3D_REQUIRE(!overlap(outs[a], out_bytes[a], in[b], map), "an output overlaps an input map");
+    for (int b = a + 1; b < n_outs; ++b) R3D_REQUIRE(!overlap(outs[a], out_bytes[a], outs[b], out_bytes[b]), "outputs overlap each other");
+  }
+  return R3D_OK;
+}
+
+int n_tiles(const TrackParams& p) { return (p.n_px + kTile - 1) / kTile; }
+
+// partial rows (+ one row for the one-pass form's sums) in scratch slot 4, the slot the other paths keep their partial rows in
+int rows_workspace(r3d_ctx* ctx, int tiles, double** rows) {
+  void* v = nullptr;
+  int rc = r3d_scratch(ctx, 4, ((size_t)tiles + 2) * kSums * sizeof(double), &v);
+  if (rc) return rc;
+  *rows = static_cast<double*>(v);
+  return R3D_OK;
+}
+
+// one pass on the stream: association + sums, then the finish (and, with a state, the solve)
+void enqueue_pass(r3d_ctx* ctx, const TrackParams& p, const Maps& m, const double* d_state_in, double* rows, double* d_sums_out,
+                  double* d_state, int32_t* d_match_out, float* d_residual_out) {
+  const int tiles = n_tiles(p);
+  hipLaunchKernelGGL(track_kernel, dim3(tiles), dim3(kThreads), 0, ctx->stream, m.src_vertex, m.src_normal, m.model_vertex,
+                     m.model_normal, p, d_state_in, rows, d_match_out, d_residual_out);
+  hipLaunchKernelGGL(track_finish_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, (const double*)rows, tiles, d_sums_out, d_state);
+}
+
+int iterate_impl(r3d_ctx* ctx, const TrackParams& p, const Maps& m, int n_iters, double* d_state) {
+  double* rows = nullptr;
+  int rc = rows_workspace(ctx, n_tiles(p), &rows);
+  if (rc) return rc;
+  for (int it = 0; it < n_iters; ++it) enqueue_pass(ctx, p, m, d_state, rows, nullptr, d_state, nullptr, nullptr);
+  R3D_HIP(hipGetLastError());
+  return R3D_OK;
+}
+
+constexpr int kMaxIters = R3D_ICP_STATE_DOUBLES - R3D_ICP_STATE_HISTORY;   // what the history holds
+
+}  // namespace
+
+extern "C" {
+
+int r3d_track_accumulate(r3d_ctx* ctx, const r3d_camera* cam, const float* d_src_vertex, const float* d_src_normal,
+                         const float* d_model_vertex, const float* d_model_normal, const double* h_model_pose_w2c, const double* h_S,
+                         double dist_max, double cos_min, double* h_sums, int32_t* d_match_out, float* d_residual_out) {
+  TrackParams p;
+  const Maps m = {d_src_vertex, d_src_normal, d_model_vertex, d_model_normal};
+  int rc = track_checks(ctx, cam, m, h_model_pose_w2c, h_S, dist_max, cos_min, &p);
+  if (rc) return rc;
+  R3D_REQUIRE(h_sums != nullptr, "h_sums is NULL");
+  const void* outs[2] = {d_match_out, d_residual_out};
+  const size_t out_bytes[2] = {(size_t)p.n_px * 4, (size_t)p.n_px * 4};
+  if ((rc = output_checks(p, m, outs, out_bytes, 2))) return rc;
+  if ((rc = r3d_ctx_enter(ctx))) return rc;
+  double* rows = nullptr;
+  const int tiles = n_tiles(p);
+  if ((rc = rows_workspace(ctx, tiles, &rows))) return rc;
+  for (int a = 0; a < 2; ++a)
+    if (outs[a]) r3d_wrote(ctx, outs[a], out_bytes[a]);
+  double* d_sums = rows + (size_t)tiles * kSums;
+  enqueue_pass(ctx, p, m, nullptr, rows, d_sums, nullptr, d_match_out, d_residual_out);
+  R3D_HIP(hipGetLastError());
+  R3D_HIP(hipMemcpyAsync(h_sums, d_sums, kSums * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  R3D_HIP(hipStreamSynchronize(ctx->stream));
+  return R3D_OK;
+}
+
+int r3d_track_iterate(r3d_ctx* ctx, const r3d_camera* cam, const float* d_src_vertex, const float* d_src_normal,
+                      const float* d_model_vertex, const float* d_model_normal, const double* h_model_pose_w2c, const double* h_S,
+                      double dist_max, double cos_min, int n_iters, double* d_state) {
+  TrackParams p;
+  const Maps m = {d_src_vertex, d_src_normal, d_model_vertex, d_model_normal};
+  int rc = track_checks(ctx, cam, m, h_model_pose_w2c, h_S, dist_max, cos_min, &p);
+  if (rc) return rc;
+  R3D_REQUIRE(d_state != nullptr, "d_state is NULL");
+  R3D_REQUIRE(n_iters >= 0 && n_iters <= kMaxIters, "n_iters must be in [0, %d]", kMaxIters);
+  const void* outs[1] = {d_state};
+  const size_t out_bytes[1] = {R3D_ICP_STATE_DOUBLES * sizeof(double)};
+  if ((rc = output_checks(p, m, outs, out_bytes, 1))) return rc;
+  if ((rc = r3d_ctx_enter(ctx))) return rc;
+  if (n_iters == 0) return R3D_OK;
+  r3d_wrote(ctx, d_state, out_bytes[0]);
+  return iterate_impl(ctx, p, m, n_iters, d_state);
+}
+
+int r3d_tsdf_track(r3d_tsdf* vol, const r3d_camera* cam, const void* d_depth, int depth_dtype, double depth_scale,
+                   const double* h_pose_guess_w2c, double min_weight, double step, double t_near, double t_far, float max_jump,
+                   double dist_max, double cos_min, int n_iters, double* h_pose_out, double* h_info_out) {
+  int rc = r3d_tsdf_integrate_checks(vol, cam, d_depth, depth_dtype, 1, depth_scale, h_pose_guess_w2c);
+  if (rc) return rc;
+  R3D_REQUIRE(h_pose_out && h_info_out, "NULL output pointer");
+  R3D_REQUIRE(!overlap(h_pose_out, 12 * sizeof(double), h_info_out, 4 * sizeof(double)) &&
+                  !overlap(h_pose_out, 12 * sizeof(double), h_pose_guess_w2c, 12 * sizeof(double)) &&
+                  !overlap(h_info_out, 4 * sizeof(double), h_pose_guess_w2c, 12 * sizeof(double)),
+              "an output overlaps the guess or the other output");
+  R3D_REQUIRE(max_jump >= 0.f, "max_jump must be >= 0");
+  R3D_REQUIRE(n_iters >= 0 && n_iters <= kMaxIters, "n_iters must be in [0, %d]", kMaxIters);
+  r3d_ctx* ctx = cam->ctx;
+  const double* G = h_pose_guess_w2c;
+  for (int k = 0; k < 12; ++k) R3D_REQUIRE(std::isfinite(G[k]), "the pose guess must be finite");
+  // S = the inverse of the guess, in double: the transposed rotation and C_k = -((R[0][k] t0 + R[1][k] t1) + R[2][k] t2)
+  double S[16];
+  for (int a = 0; a < 3; ++a) {
+    for (int b = 0; b < 3; ++b) S[4 * a + b] = G[3 * b + a];
+    S[4 * a + 3] = -((G[a] * G[9] + G[3 + a] * G[10]) + G[6 + a] * G[11]);
+    S[12 + a] = 0.0;
+  }
+  S[15] = 1.0;
+  // the four maps and the state: scratch slot 7 (the rank-trimming residuals' slot; nothing of that path runs in here)
+  const size_t px = (size_t)cam->width * cam->height, map = (px * 12 + 255) & ~(size_t)255;
+  const bool gate = cos_min > -1.0;   // -1 admits every angle: the source normals are neither computed nor asked for
+  TrackParams p;
+  {   // the checks that need no buffer, before anything is enqueued
+    const float dummy = 0.f;
+    const Maps probe = {&dummy, nullptr, &dummy, &dummy};
+    if ((rc = track_checks(ctx, cam, probe, G, S, dist_max, cos_min, &p))) return rc;
+  }
+  // the ray cast's own argument checks, before anything is reserved: with no output it validates and does nothing else
+  if ((rc = r3d_tsdf_raycast(vol, cam, 1, G, min_weight, step, t_near, t_far, nullptr, nullptr, nullptr))) return rc;
+  if ((rc = r3d_ctx_enter(ctx))) return rc;
+  void* ws = nullptr;
+  if ((rc = r3d_scratch(ctx, 7, 4 * map + R3D_ICP_STATE_DOUBLES * sizeof(double), &ws))) return rc;
+  char* c = static_cast<char*>(ws);
+  float *model_vertex = reinterpret_cast<float*>(c), *model_normal = reinterpret_cast<float*>(c + map);
+  float *src_vertex = reinterpret_cast<float*>(c + 2 * map), *src_normal = reinterpret_cast<float*>(c + 3 * map);
+  double* d_state = reinterpret_cast<double*>(c + 4 * map);
+  if ((rc = r3d_tsdf_raycast(vol, cam, 1, G, min_weight, step, t_near, t_far, nullptr, model_vertex, model_normal))) return rc;
+  if ((rc = r3d_unproject(ctx, cam, d_depth, depth_dtype, 1, depth_scale, src_vertex, R3D_F32))) return rc;
+  if (gate && (rc = r3d_normals_organized(ctx, src_vertex, 1, cam->height, cam->width, max_jump, nullptr, src_normal))) return rc;
+  if ((rc = r3d_icp_state_reset(ctx, d_state))) return rc;
+  const Maps m = {src_vertex, gate ? src_normal : nullptr, model_vertex, model_normal};
+  if (n_iters > 0 && (rc = iterate_impl(ctx, p, m, n_iters, d_state))) return rc;
+  double st[r3d_icp::kStatePairs + 1];
+  R3D_HIP(hipMemcpyAsync(st, d_state, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
+  R3D_HIP(hipStreamSynchronize(ctx->stream));
+  const bool bad = st[r3d_icp::kStateStatus] != 0.0;
+  if (bad) {
+    for (int k = 0; k < 12; ++k) h_pose_out[k] = G[k];   // a degenerate step: the guess comes back as it was given
+  } else {
+    double M[16];
+    for (int r = 0; r < 4; ++r)
+      for (int cc = 0; cc < 4; ++cc) {
+        double v = 0.0;
+        for (int k = 0; k < 4; ++k) v += st[r3d_icp::kStateTTotal + 4 * r + k] * S[4 * k + cc];
+        M[4 * r + cc] = v;
+      }
+    for (int a = 0; a < 3; ++a) {
+      for (int b = 0; b < 3; ++b) h_pose_out[3 * a + b] = M[4 * b + a];
+      h_pose_out[9 + a] = -((M[a] * M[3] + M[4 + a] * M[7]) + M[8 + a] * M[11]);
+    }
+  }
+  h_info_out[0] = st[r3d_icp::kStatePairs];
+  h_info_out[1] = st[r3d_icp::kStateRms];
+  h_info_out[2] = bad ? 1.0 : 0.0;
+  h_info_out[3] = st[r3d_icp::kStateIters];
+  return R3D_OK;
+}
+
+}  // extern "C"

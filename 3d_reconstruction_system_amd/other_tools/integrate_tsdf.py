@@ -3,7 +3,7 @@
 truncated signed distance volume instead, and the volume's zero level set is written as oriented surface points.
 
     python integrate_tsdf.py --voxel-size S --trunc T [--origin X Y Z] [--dims NX NY NZ] [--margin M] [--min-weight W] [--mesh]
-                             [--raycast] [--color-dir DIR]
+                             [--raycast] [--color-dir DIR] [--track]
 
 Run from a directory holding ./camera_pose/image_colmap_simi_2.txt and ./depth/ (the inputs of camera_to_world.py; the same
 environment overrides apply: R3D_FX .. R3D_CY, R3D_POSE_SCALE, R3D_DEVICE).  Writes ./ply/tsdf_surface.ply: binary PLY, float
@@ -15,6 +15,13 @@ shades), and prints a second line "triangles M -> path".
 predicts (float32, 0 = no surface) to ./raycast/<frame name>.npy, and prints a further line "raycast F frames -> ./raycast/".
 --color-dir DIR reads the colour image DIR/<frame name> of every frame (the size of the depth maps), integrates colour with the
 depth and adds uchar red green blue to the vertices of both PLY files.
+--track reconstructs from the depth maps and ONE pose: only the first row of the pose file is used (its names still list the
+frames).  A pose file that is missing or lists no frame gives the identity as the first pose and the files of ./depth/ in
+sorted order as the frames (--origin / --dims are then the caller's to choose around a camera at the origin).  Every later
+frame is tracked against the model from the previous frame's pose (projective point-to-plane ICP on the ray-cast maps: small
+motions between frames) and integrated at the pose found.  The estimated poses are written to
+./camera_pose/image_colmap_simi_2_tracked.txt in the pose file's own format, and a further line "tracked F frames -> path" is
+printed.  Without --origin / --dims the volume is then built around the first camera centre alone.  Not with --color-dir.
 """
 import argparse
 import math
@@ -31,6 +38,7 @@ POSE_FILE = './camera_pose/image_colmap_simi_2.txt'
 OUT_FILE = './ply/tsdf_surface.ply'
 MESH_FILE = './ply/tsdf_mesh.ply'
 RAYCAST_DIR = './raycast/'
+TRACKED_FILE = './camera_pose/image_colmap_simi_2_tracked.txt'
 
 
 def parse_args(argv):
@@ -47,7 +55,11 @@ def parse_args(argv):
                    help="also ray-cast the volume from every pose and write the predicted depth to %s<frame name>.npy" % RAYCAST_DIR)
     p.add_argument("--color-dir", metavar="DIR", default=None,
                    help="integrate the colour images DIR/<frame name> too and write the colours into the PLY files")
+    p.add_argument("--track", action="store_true",
+                   help="use only the first pose of the pose file, estimate the others by tracking and write them to %s" % TRACKED_FILE)
     args = p.parse_args(argv)
+    if args.track and args.color_dir is not None:
+        p.error("--track takes depth maps only (not with --color-dir)")
     for name in ("voxel_size", "trunc", "min_weight"):
         v = getattr(args, name)
         if not (math.isfinite(v) and v > 0.0):
@@ -91,6 +103,37 @@ def raycast_depth(r3d, vol, quats, ts, shape, min_weight):
     return out
 
 
+def quat_xyzw(R):
+    """scalar-last unit quaternion of a rotation matrix (Shepperd's method: the largest of w, x, y, z first)"""
+    import numpy as np
+    t = np.trace(R)
+    cand = [t, R[0, 0], R[1, 1], R[2, 2]]
+    k = int(np.argmax(cand))
+    if k == 0:
+        w = math.sqrt(1.0 + t) / 2.0
+        q = [(R[2, 1] - R[1, 2]) / (4 * w), (R[0, 2] - R[2, 0]) / (4 * w), (R[1, 0] - R[0, 1]) / (4 * w), w]
+    else:
+        a = k - 1
+        b, c = (a + 1) % 3, (a + 2) % 3
+        x = math.sqrt(1.0 + R[a, a] - R[b, b] - R[c, c]) / 2.0
+        q = [0.0, 0.0, 0.0, (R[c, b] - R[b, c]) / (4 * x)]
+        q[a], q[b], q[c] = x, (R[b, a] + R[a, b]) / (4 * x), (R[c, a] + R[a, c]) / (4 * x)
+    return np.array(q)
+
+
+def write_tracked(path, names, rows, scale):
+    """the rows (world -> camera, R row-major then t) as a pose file read_pose_file parses; t is divided by the pose scale again"""
+    header = "id,tx,ty,tz,qx,qy,qz,qw,name,tail"
+    if os.path.isfile(POSE_FILE):
+        with open(POSE_FILE, 'r') as f:
+            header = f.readline().rstrip("\n") or header
+    with open(path, 'w') as f:
+        f.write(header + "\n")
+        for k, (name, row) in enumerate(zip(names, rows)):
+            q, t = quat_xyzw(row[:9].reshape(3, 3)), row[9:] / scale
+            f.write(",".join([str(k + 1)] + [repr(float(v)) for v in t] + [repr(float(v)) for v in q] + [name, "tracked"]) + "\n")
+
+
 def read_colors(r3d, color_dir, names, shape):
     """[F,H,W,3] uint8: DIR/<frame name> of every frame, at the depth maps' size; exits with a message otherwise."""
     paths = [os.path.join(color_dir, n) for n in names]
@@ -110,15 +153,20 @@ def read_colors(r3d, color_dir, names, shape):
 def main(argv=None):
     args = parse_args(sys.argv[1:] if argv is None else argv)
     r3d = _common.package()
-    if not os.path.isfile(POSE_FILE):
+    if not os.path.isfile(POSE_FILE) and not args.track:
         sys.exit("integrate_tsdf.py: %s not found (run from the data directory)" % POSE_FILE)
-    names, quats, ts = r3d.read_pose_file(POSE_FILE)
+    names, quats, ts = r3d.read_pose_file(POSE_FILE) if os.path.isfile(POSE_FILE) else ([], None, None)
+    if not names and args.track and os.path.isdir('./depth/'):
+        import numpy as np
+        names = sorted(n for n in os.listdir('./depth/') if os.path.isfile(os.path.join('./depth/', n)))
+        quats, ts = np.tile([0.0, 0.0, 0.0, 1.0], (len(names), 1)), np.zeros((len(names), 3))   # row 0 is the identity; the rest unused
     if not names:
         sys.exit("integrate_tsdf.py: %s lists no frames" % POSE_FILE)
     ts = ts * _common.pose_scale()
     if args.origin is None:
         margin = 16.0 * args.trunc if args.margin is None else args.margin
-        origin, dims = default_volume(r3d.poses_w2c(quats, ts), args.voxel_size, margin)
+        known = r3d.poses_w2c(quats, ts)
+        origin, dims = default_volume(known[:1] if args.track else known, args.voxel_size, margin)
         if dims[0] * dims[1] * dims[2] >= 1 << 31:
             sys.exit("integrate_tsdf.py: the default volume has %d x %d x %d voxels; choose a larger --voxel-size or give --origin / --dims"
                      % tuple(dims))
@@ -127,7 +175,17 @@ def main(argv=None):
     depths = r3d.cloud_io.read_depth_batch([os.path.join('./depth/', n) for n in names])
     rgb = read_colors(r3d, args.color_dir, names, depths.shape[-2:]) if args.color_dir is not None else None
     _common.stamp("read %d frames" % len(names))
-    if rgb is None:
+    tracked = None
+    if args.track:
+        vol = r3d.TSDFVolume(origin, args.voxel_size, dims, args.trunc, ctx=_common.context())
+        try:
+            tracked = vol.track_and_integrate(depths, r3d.poses_w2c(quats[:1], ts[:1])[0], intrinsics=_common.intrinsics(),
+                                              min_weight=args.min_weight)
+        except RuntimeError as e:
+            sys.exit("integrate_tsdf.py: --track: %s" % e)
+        quats = [quat_xyzw(row[:9].reshape(3, 3)) for row in tracked]
+        ts = tracked[:, 9:]
+    elif rgb is None:
         vol = r3d.TSDFVolume(origin, args.voxel_size, dims, args.trunc, ctx=_common.context())
         vol.integrate(depths, quats, ts, intrinsics=_common.intrinsics())
     else:
@@ -157,6 +215,10 @@ def main(argv=None):
         for name, raster in zip(names, cast):
             np.save(os.path.join(RAYCAST_DIR, name + ".npy"), raster)
         print("raycast %d frames -> %s" % (len(names), RAYCAST_DIR))
+    if tracked is not None:
+        os.makedirs(os.path.dirname(TRACKED_FILE), exist_ok=True)
+        write_tracked(TRACKED_FILE, names, tracked, _common.pose_scale())
+        print("tracked %d frames -> %s" % (len(names), TRACKED_FILE))
 
 
 if __name__ == "__main__":

@@ -1,0 +1,178 @@
+"""Frame-to-model tracking on the MI355X: projective point-to-plane ICP of a new depth frame against the vertex and normal map a
+TSDF volume predicts for a pose (TSDFVolume.raycast).  The model maps are organised rasters, so a source point's partner is one
+projection and one gather away -- no nearest-neighbour index.  Semantics: include/r3d.h ("TSDF tracking"), DESIGN.md section 4.5m.
+
+track_sums is one association pass from host arrays (the 29 sums of the point-to-plane step, the per-pixel match and residual);
+TrackDevice keeps the maps and the ICP state in HBM and runs whole iterations without a host round trip.  The whole step for one
+depth frame -- ray cast, unproject, normals, loop, pose -- is TSDFVolume.track.
+"""
+import numpy as np
+
+from . import _lib as L
+from .device import default_context
+from .icp import PLANE_SUMS, STATE_DOUBLES, STATE_HISTORY
+
+MAX_ITERS = STATE_DOUBLES - STATE_HISTORY   # what the state's history holds
+
+
+def inverse_pose(pose_w2c):
+    """4x4 camera -> world of a 12-double world -> camera row (R row-major, t), in the library's order:
+    S[a][b] = R[b][a], S[a][3] = -((R[0][a] t0 + R[1][a] t1) + R[2][a] t2)."""
+    g = _pose_row(pose_w2c, "pose_w2c")
+    R, t = g[:9].reshape(3, 3), g[9:]
+    S = np.zeros((4, 4), dtype=np.float64)
+    for a in range(3):
+        for b in range(3):
+            S[a, b] = R[b, a]
+        S[a, 3] = -((R[0, a] * t[0] + R[1, a] * t[1]) + R[2, a] * t[2])
+    S[3, 3] = 1.0
+    return S
+
+
+def _matmul4(A, B):
+    """A . B of two 4x4, every entry summed over m = 0..3 in ascending order from 0.0 (the device solve's loop)."""
+    out = np.zeros((4, 4), dtype=np.float64)
+    for r in range(4):
+        for c in range(4):
+            v = 0.0
+            for m in range(4):
+                v += A[r, m] * B[m, c]
+            out[r, c] = v
+    return out
+
+
+def pose_from_state(T_total, S):
+    """The world -> camera row (12 doubles) of M = T_total . S: R = M[:3,:3]^T, t = -R . M[:3,3]."""
+    M = _matmul4(np.asarray(T_total, dtype=np.float64).reshape(4, 4), np.asarray(S, dtype=np.float64).reshape(4, 4))
+    out = np.empty(12, dtype=np.float64)
+    for a in range(3):
+        for b in range(3):
+            out[3 * a + b] = M[b, a]
+        out[9 + a] = -((M[0, a] * M[0, 3] + M[1, a] * M[1, 3]) + M[2, a] * M[2, 3])
+    return out
+
+
+def _pose_row(p, what):
+    g = np.ascontiguousarray(p, dtype=np.float64).reshape(-1)
+    if g.shape != (12,):
+        raise ValueError("%s must be 12 numbers (R row-major, t), got shape %s" % (what, np.shape(p)))
+    return g
+
+
+def _map(a, what, shape=None):
+    m = np.asarray(a)
+    if m.dtype != np.float32 or m.ndim != 3 or m.shape[2] != 3 or m.shape[0] < 1 or m.shape[1] < 1:
+        raise ValueError("%s must be a float32 [H,W,3] map, got %s of shape %s" % (what, m.dtype, list(m.shape)))
+    if shape is not None and m.shape != shape:
+        raise ValueError("%s has shape %s, the source vertex map %s" % (what, list(m.shape), list(shape)))
+    return np.ascontiguousarray(m)
+
+
+def _gates(dist_max, cos_min):
+    try:
+        d, c = float(dist_max), float(cos_min)
+    except (TypeError, ValueError):
+        raise ValueError("dist_max and cos_min must be numbers, got %r and %r" % (dist_max, cos_min))
+    if not (np.isfinite(d) and d > 0.0):
+        raise ValueError("dist_max must be finite and > 0, got %r" % (dist_max,))
+    if not (-1.0 <= c <= 1.0):
+        raise ValueError("cos_min must be in [-1, 1], got %r" % (cos_min,))
+    return d, c
+
+
+def _check_inputs(src_vertex, src_normal, model_vertex, model_normal, model_pose_w2c, S, intrinsics):
+    sv = _map(src_vertex, "src_vertex")
+    sn = None if src_normal is None else _map(src_normal, "src_normal", sv.shape)
+    mv, mn = _map(model_vertex, "model_vertex", sv.shape), _map(model_normal, "model_normal", sv.shape)
+    pose = _pose_row(model_pose_w2c, "model_pose_w2c")
+    S = np.ascontiguousarray(S, dtype=np.float64)
+    if S.shape != (4, 4):
+        raise ValueError("S must be a 4x4 (source camera -> world), got shape %s" % (S.shape,))
+    try:
+        K = tuple(float(v) for v in intrinsics)
+    except (TypeError, ValueError):
+        raise ValueError("intrinsics must be (fx, fy, cx, cy), got %r" % (intrinsics,))
+    if len(K) != 4:
+        raise ValueError("intrinsics must be (fx, fy, cx, cy), got %r" % (intrinsics,))
+    return sv, sn, mv, mn, pose, S, K
+
+
+class TrackDevice:
+    """The new frame's maps (camera frame) and the model's maps (world) resident on one GPU, with the device-resident ICP state.
+    src_vertex [H,W,3] float32 (fusion.unproject's rows), src_normal the same or None (no normal gate), model_vertex /
+    model_normal [H,W,3] float32 as TSDFVolume.raycast returns them for the pose model_pose_w2c (12 doubles), S the 4x4 guess
+    source camera -> world."""
+
+    def __init__(self, src_vertex, model_vertex, model_normal, model_pose_w2c, S, intrinsics, src_normal=None, ctx=None):
+        sv, sn, mv, mn, self.model_pose, self.S, K = _check_inputs(src_vertex, src_normal, model_vertex, model_normal, model_pose_w2c, S,
+                                                             intrinsics)
+        self.ctx = c = ctx or default_context()
+        self.h, self.w = sv.shape[:2]
+        self.n = self.h * self.w
+        self.cam = c.camera(self.h, self.w, *K)
+        self._bufs = []
+
+        def put(a):
+            b = c.alloc(a.nbytes).upload(a)
+            self._bufs.append(b)
+            return b
+        self.d_src_vertex, self.d_model_vertex, self.d_model_normal = put(sv), put(mv), put(mn)
+        self.d_src_normal = None if sn is None else put(sn)
+        self.d_match, self.d_residual = c.alloc(self.n * 4), c.alloc(self.n * 4)
+        self.d_state = c.alloc(STATE_DOUBLES * 8)
+        self._bufs += [self.d_match, self.d_residual, self.d_state]
+        self.state_reset()
+
+    def _maps(self):
+        return (self.d_src_vertex.ptr, None if self.d_src_normal is None else self.d_src_normal.ptr, self.d_model_vertex.ptr,
+                self.d_model_normal.ptr, self.model_pose.ctypes.data, self.S.ctypes.data)
+
+    def state_reset(self):
+        L.check(self.ctx.lib.r3d_icp_state_reset(self.ctx.handle, self.d_state.ptr))
+
+    def sums(self, dist_max, cos_min=-1.0):
+        """One pass at the guess S itself (T_total = I): (sums [29], match [H,W] int32, residual [H,W] float32)."""
+        d, cm = _gates(dist_max, cos_min)
+        sums = np.zeros(PLANE_SUMS, dtype=np.float64)
+        L.check(self.ctx.lib.r3d_track_accumulate(self.ctx.handle, self.cam.handle, *self._maps(), d, cm, sums.ctypes.data,
+                                                  self.d_match.ptr, self.d_residual.ptr))
+        return (sums, self.d_match.download(np.int32, self.n).reshape(self.h, self.w),
+                self.d_residual.download(np.float32, self.n).reshape(self.h, self.w))
+
+    def iterate(self, n_iters, dist_max, cos_min=-1.0):
+        """n_iters whole iterations (associate at T_total . S, 29 sums, solve, T_total updated) with no host round trip."""
+        d, cm = _gates(dist_max, cos_min)
+        n_iters = int(n_iters)
+        if not 0 <= n_iters <= MAX_ITERS:
+            raise ValueError("n_iters must be in [0, %d], got %d" % (MAX_ITERS, n_iters))
+        L.check(self.ctx.lib.r3d_track_iterate(self.ctx.handle, self.cam.handle, *self._maps(), d, cm, n_iters, self.d_state.ptr))
+
+    def state(self):
+        st = self.d_state.download(np.float64, STATE_DOUBLES)
+        it = int(st[32])
+        return {"T_total": st[0:16].reshape(4, 4).copy(), "T_step": st[16:32].reshape(4, 4).copy(), "iterations": it,
+                "degenerate": bool(st[33]), "rms": float(st[34]), "pairs": float(st[35]),
+                "rms_history": st[STATE_HISTORY:STATE_HISTORY + min(it, MAX_ITERS)].tolist()}
+
+    def pose(self):
+        """The tracked world -> camera row (12 doubles) of the state as it stands."""
+        return pose_from_state(self.state()["T_total"], self.S)
+
+    def free(self):
+        self.ctx.sync()
+        for b in self._bufs:
+            b.free()
+        self._bufs = []
+
+
+def track_sums(src_vertex, model_vertex, model_normal, model_pose_w2c, S, intrinsics, dist_max, cos_min=-1.0, src_normal=None,
+               ctx=None):
+    """One association pass from host arrays: (sums [29] float64, match [H,W] int32, residual [H,W] float32).  match holds the
+    model pixel vj W + uj of every matched source pixel, else the reject code: -1 no source point, -2 projects outside the model
+    image, -3 no model surface there, -4 farther than dist_max, -5 normals disagree (only with src_normal)."""
+    _gates(dist_max, cos_min)
+    dev = TrackDevice(src_vertex, model_vertex, model_normal, model_pose_w2c, S, intrinsics, src_normal=src_normal, ctx=ctx)
+    try:
+        return dev.sums(dist_max, cos_min)
+    finally:
+        dev.free()

@@ -2,7 +2,8 @@
 level set comes back as oriented surface points or as an indexed triangle mesh over those points (marching cubes) -- what users
 of a depth + pose pipeline expect (Open3D's UniformTSDFVolume; no parity with Open3D is claimed).  Where fuse_frames concatenates the frames' points, the volume averages
 overlapping frames.  A volume created with color=True also averages the frames' colour images and returns a colour with every
-surface point / mesh vertex.  Semantics: include/r3d.h (r3d_tsdf_*) and DESIGN.md sections 4.5i to 4.5l.
+surface point / mesh vertex.  track() finds the pose of a new depth frame against the model (tracking.py), so a volume can be
+built from depth frames and one pose.  Semantics: include/r3d.h (r3d_tsdf_*) and DESIGN.md sections 4.5i to 4.5m.
 
 The volume takes the inputs camera_to_world.py already has: [F,H,W] depth, one pose-file row per frame, a pinhole camera.  Its
 poses are WORLD -> CAMERA (p_cam = R p_w + t: the pose file's quaternion and t as they stand, poses_w2c), not the inverted table
@@ -333,3 +334,108 @@ class TSDFVolume:
         finally:
             for b in (d_depth, d_vtx, d_nrm):
                 b.free()
+
+    def _track_args(self, n_iters, dist_max, max_angle_deg, max_jump, min_weight, step, t_near, t_far):
+        """(n_iters, dist_max, cos_min, max_jump, min_weight, step, t_near, t_far) as the library takes them; ValueError otherwise"""
+        from .tracking import MAX_ITERS
+        if isinstance(n_iters, bool) or int(n_iters) != n_iters or not 0 <= int(n_iters) <= MAX_ITERS:
+            raise ValueError("n_iters must be an integer in [0, %d], got %r" % (MAX_ITERS, n_iters))
+        dm = _positive_f32(2.0 * self.sdf_trunc if dist_max is None else dist_max, "dist_max")
+        if max_angle_deg is None:
+            cos_min = -1.0                                    # every angle passes: no source normals are computed
+        else:
+            try:
+                ang = float(max_angle_deg)
+            except (TypeError, ValueError):
+                raise ValueError("max_angle_deg must be a number in [0, 180) or None, got %r" % (max_angle_deg,))
+            if isinstance(max_angle_deg, bool) or not 0.0 <= ang < 180.0:
+                raise ValueError("max_angle_deg must be in [0, 180) or None, got %r" % (max_angle_deg,))
+            cos_min = min(1.0, max(math.cos(math.radians(ang)), math.nextafter(-1.0, 0.0)))
+        try:
+            mj = float(max_jump)
+        except (TypeError, ValueError):
+            raise ValueError("max_jump must be a number >= 0, got %r" % (max_jump,))
+        if not mj >= 0.0:
+            raise ValueError("max_jump must be >= 0, got %r" % (max_jump,))
+        s, tn, tf = _ray_range(step, t_near, t_far, self.voxel_size)
+        return int(n_iters), dm, cos_min, mj, _positive_f32(min_weight, "min_weight"), s, tn, tf
+
+    def track_device(self, cam, d_depth, depth_dtype, pose_guess_w2c, n_iters=10, dist_max=None, max_angle_deg=None, depth_scale=1.0,
+                     max_jump=0.05, min_weight=1.0, step=None, t_near=0.0, t_far=math.inf):
+        """track() from a raster in HBM (d_depth: [H][W] of depth_dtype at a raw device address; cam: ctx.camera(...)).
+        Synchronises (the pose is read back)."""
+        n, dm, cos_min, mj, mw, s, tn, tf = self._track_args(n_iters, dist_max, max_angle_deg, max_jump, min_weight, step, t_near, t_far)
+        guess = _pose_rows(np.asarray(pose_guess_w2c, dtype=np.float64).reshape(1, -1), 1)
+        if not np.isfinite(guess).all():
+            raise ValueError("pose_guess_w2c must be finite")
+        pose, info = np.zeros(12, dtype=np.float64), np.zeros(4, dtype=np.float64)
+        L.check(self.ctx.lib.r3d_tsdf_track(self.handle, cam.handle, d_depth, depth_code(depth_dtype), float(depth_scale),
+                                            guess.ctypes.data, mw, s, tn, tf, mj, dm, cos_min, n, pose.ctypes.data, info.ctypes.data))
+        return pose, {"pairs": float(info[0]), "rms": float(info[1]), "status": int(info[2]), "iterations": int(info[3])}
+
+    def track(self, depth, pose_guess_w2c, intrinsics=REF_INTRINSICS, n_iters=10, dist_max=None, max_angle_deg=None, depth_scale=1.0,
+              max_jump=0.05, min_weight=1.0, step=None, t_near=0.0, t_far=math.inf):
+        """The pose of a new depth raster [H,W] against the model, from a guess (12 doubles, world -> camera: R row-major, t --
+        a row of poses_w2c): the volume is ray-cast at the guess, and n_iters iterations of projective point-to-plane ICP move
+        the frame onto the predicted vertex and normal map (a source point's partner is the model pixel it projects to).
+        Returns (pose [12] float64 in the same layout -- it feeds integrate_device as it is --, info): info["status"] is 0, or 1
+        when a step was degenerate (fewer than 6 pairs, or the matched normals leave a freedom open): the pose is then the
+        guess.  info also has "pairs" and "rms" (of the plane residual) as the last step saw them, and "iterations".
+        dist_max: pairs farther apart never take part (None: 2 x sdf_trunc).  max_angle_deg: pairs whose source and model
+        normals differ by more are left out; None: no source normals are computed or gated.  max_jump: the depth-edge rule of
+        the source normals.  Small motions only: no image pyramid.  Synchronous."""
+        d = np.asarray(depth)
+        if d.ndim != 2 or d.shape[0] < 1 or d.shape[1] < 1:
+            raise ValueError("depth must be one [H,W] raster, got shape %s" % (list(d.shape),))
+        if d.dtype not in (np.uint8, np.uint16, np.float32):
+            raise ValueError("depth must be uint8, uint16 or float32, got %s" % d.dtype)
+        d = np.ascontiguousarray(d)
+        self._track_args(n_iters, dist_max, max_angle_deg, max_jump, min_weight, step, t_near, t_far)   # raises before anything is allocated
+        guess = np.asarray(pose_guess_w2c, dtype=np.float64)
+        if guess.size != 12 or not np.isfinite(guess).all():
+            raise ValueError("pose_guess_w2c must be 12 finite numbers (R row-major, t), got shape %s" % (list(guess.shape),))
+        cam = self.ctx.camera(d.shape[0], d.shape[1], *intrinsics)
+        buf = self.ctx.alloc(d.nbytes).upload(d)
+        try:
+            return self.track_device(cam, buf.ptr, d.dtype, guess, n_iters, dist_max, max_angle_deg, depth_scale, max_jump, min_weight,
+                                     step, t_near, t_far)
+        finally:
+            buf.free()
+
+    def track_and_integrate(self, depths, first_pose_w2c, intrinsics=REF_INTRINSICS, depth_scale=1.0, **track_args):
+        """Reconstruct from depth rasters [F,H,W] and ONE pose: frame 0 is integrated at first_pose_w2c (12 doubles, world ->
+        camera); every later frame is tracked against the model from the previous frame's pose (track(); track_args are its
+        keyword arguments) and integrated at the pose found.  Returns the [F,12] float64 pose rows.  Raises RuntimeError when a
+        frame cannot be tracked (status 1); the frames before it stay integrated.  A volume without colour only."""
+        if self.color:
+            raise ValueError("track_and_integrate takes depth rasters only: the volume was created with color=True")
+        if np.asarray(depths).dtype not in (np.uint8, np.uint16, np.float32):
+            raise ValueError("depths must be uint8, uint16 or float32, got %s" % np.asarray(depths).dtype)
+        d = _as_batch(depths)
+        f, h, w = d.shape
+        first = np.asarray(first_pose_w2c, dtype=np.float64)
+        if first.size != 12 or not np.isfinite(first).all():
+            raise ValueError("first_pose_w2c must be 12 finite numbers (R row-major, t), got shape %s" % (list(first.shape),))
+        self._track_args(track_args.get("n_iters", 10), track_args.get("dist_max"), track_args.get("max_angle_deg"),
+                         track_args.get("max_jump", 0.05), track_args.get("min_weight", 1.0), track_args.get("step"),
+                         track_args.get("t_near", 0.0), track_args.get("t_far", math.inf))
+        poses = np.zeros((f, 12), dtype=np.float64)
+        if f * h * w == 0:
+            return poses
+        cam = self.ctx.camera(h, w, *intrinsics)
+        buf = self.ctx.alloc(d[0].nbytes)
+        try:
+            for k in range(f):
+                buf.upload(d[k])
+                if k == 0:
+                    poses[0] = first.reshape(12)
+                else:
+                    poses[k], info = self.track_device(cam, buf.ptr, d.dtype, poses[k - 1], depth_scale=depth_scale, **track_args)
+                    if info["status"] != 0:
+                        raise RuntimeError("frame %d cannot be tracked against the model: %d pairs, the step is degenerate"
+                                           % (k, int(info["pairs"])))
+                self.integrate_device(cam, buf.ptr, d.dtype, 1, poses[k:k + 1], depth_scale)
+            self.ctx.sync()
+        finally:
+            buf.free()
+        return poses

@@ -778,6 +778,71 @@ int r3d_tsdf_integrate_rgb_host(r3d_tsdf* vol, const r3d_camera* cam, const void
 int r3d_tsdf_colors(r3d_tsdf* vol, uint32_t** d_sums_out, int64_t* n_voxels_out);
 int r3d_tsdf_extract_colors(r3d_tsdf* vol, double min_weight, uint32_t* d_rgba_out, int64_t cap, int64_t* n_out);
 
+/* ---- TSDF tracking (csrc/r3d_track.hip; frame-to-model registration by PROJECTIVE point-to-plane ICP: the pose of a new depth
+ * frame against the vertex and normal map the volume predicts -- the fourth leg of integrate / extract / ray cast / track; NOT IN
+ * THE REFERENCE, this text is the specification).  The model maps are organised rasters, so the partner of a source point is one
+ * projection and one gather away: no search structure is built.  All arithmetic is fp64 in the order written, no fused
+ * multiply-add; the results are the same bits on every run, on every device and under every tuning.
+ * Inputs: a camera (H, W and its intrinsics fx, fy, cx, cy as doubles); the new frame's maps in ITS camera frame, d_src_vertex
+ *   [H][W][3] f32 (what r3d_unproject writes) and optionally d_src_normal [H][W][3] f32 (what r3d_normals_organized writes; a
+ *   zero row = "no normal"; NULL = no normal gate); the model maps in WORLD coordinates, d_model_vertex and d_model_normal
+ *   [H][W][3] f32, exactly what r3d_tsdf_raycast writes (a miss is three NaN words); h_model_pose_w2c, 12 doubles in
+ *   r3d_tsdf_integrate's row layout: the pose the model maps were cast from (Rm row-major, tm); h_S, 16 doubles, a row-major 4x4,
+ *   source camera -> world: the guess; dist_max > 0; cos_min in [-1, 1], used only when source normals are given.
+ * Per source pixel i = vi W + ui with (x, y, z) its source vertex:
+ *   1. reject with code -1 unless x, y, z are finite and z > 0
+ *   2. M = T_total . S, every entry summed over m = 0..3 in ascending order starting from 0.0 (the loop that updates T_total in
+ *      the solve); T_total is the device state's in r3d_track_iterate and the identity in r3d_track_accumulate
+ *   3. p_a = ((M[a][0] x + M[a][1] y) + M[a][2] z) + M[a][3]                      the point in the world
+ *   4. pm_a = ((Rm[a][0] p_0 + Rm[a][1] p_1) + Rm[a][2] p_2) + tm_a               ... in the model camera
+ *   5. reject -2 unless pm_2 > 0;  u = fx (pm_0 / pm_2) + cx;  v = fy (pm_1 / pm_2) + cy;  uj = floor(u + 0.5);
+ *      vj = floor(v + 0.5);  reject -2 unless 0 <= uj < W and 0 <= vj < H, compared as doubles (NaN fails)
+ *   6. j = vj W + uj;  q = model vertex row j, n = model normal row j
+ *   7. reject -3 unless all six are finite and n is not the zero vector
+ *   8. d = p - q;  reject -4 unless (d_0 d_0 + d_1 d_1) + d_2 d_2 <= dist_max dist_max
+ *   9. with source normals, ns = source normal row i: reject -5 unless ns is finite and non-zero; g_a = (M[a][0] ns_0 +
+ *      M[a][1] ns_1) + M[a][2] ns_2; reject -5 unless (g_0 n_0 + g_1 n_1) + g_2 n_2 >= cos_min
+ *  10. r = n_0 (p_0 - q_0) + n_1 (p_1 - q_1) + n_2 (p_2 - q_2), left to right; the pair enters the 29 sums of the point-to-plane
+ *      step with weight 1: J = [p x n ; n], [0] += 1, [1] += r r, [2 + a] += J_a r, [8..28] += the upper triangle of J J^T
+ *      (csrc/r3d_plane_sums.h: pair_accumulate)
+ *   Per-pixel outputs, each may be NULL: d_match_out [H W] int32 = j on a match, else the reject code; d_residual_out [H W] f32 =
+ *   (float) r on a match, else 0.
+ * Sums: a 256-thread workgroup owns 1024 consecutive pixels; thread t takes pixels base + t + 256 k for k = 0..3 in that order;
+ *   its 29 accumulators go through the 64-lane shuffle tree (offsets 32, 16, .., 1), then the workgroup's 4 waves are added in
+ *   ascending order: one partial row per workgroup.  One workgroup then adds the rows -- thread t rows t, t + 256, .. in
+ *   ascending order -- and reduces them the same way.  The launch shape is part of the specification.
+ * r3d_track_accumulate: one pass with T_total = I; h_sums receives the 29 sums.  Synchronous.
+ * r3d_track_iterate: n_iters passes enqueued back to back with no host round trip: the pass above reading T_total from d_state,
+ *   then the reduction and the solve, which updates d_state exactly as r3d_icp_iterate_plane's solve does (the
+ *   R3D_ICP_STATE_DOUBLES layout; r3d_icp_state_reset starts a loop).  A degenerate step (fewer than 6 pairs, or normal equations
+ *   singular to working precision) sets status 1 and leaves T_total as it was.  Asynchronous.
+ * r3d_tsdf_track: the whole step for one frame: r3d_tsdf_raycast of the vertex and normal map at the guess (min_weight, step,
+ *   t_near, t_far as there); r3d_unproject of the depth raster (d_depth: [H][W] of depth_dtype, depth_scale) and, when
+ *   cos_min > -1, its r3d_normals_organized (max_jump; the origin as viewpoint) -- with cos_min == -1 every angle passes, so no
+ *   source normals are computed or asked for; a state reset; r3d_track_iterate with the guess as the model pose and S = its
+ *   inverse, in double on the host: S[a][b] = R[b][a], S[a][3] = -((R[0][a] t_0 + R[1][a] t_1) + R[2][a] t_2); the state is read
+ *   back (synchronises).  With M = T_total . S (the loop of step 2): R_out = the transpose of M's rotation block,
+ *   t_out_a = -((R_out[a][0] M[0][3] + R_out[a][1] M[1][3]) + R_out[a][2] M[2][3]); h_pose_out = 12 doubles in
+ *   r3d_tsdf_integrate's row layout, world -> camera: it feeds straight back into r3d_tsdf_integrate.  h_info_out = 4 doubles:
+ *   pairs and rms of r seen by the last step, status, steps solved.  status 1 = some step was degenerate: h_pose_out is then the
+ *   guess, bit for bit.  The maps and the state live in the context's scratch: nothing is allocated per call after the first.
+ *   A volume with the colour plane is accepted (the volume is only read).
+ * R3D_ERR_INVALID, nothing written: NULL ctx / volume / camera, a camera of another ctx, a NULL required pointer (every map but
+ *   d_src_normal, the poses, h_sums, d_state, h_pose_out, h_info_out), dist_max not > 0 and finite, cos_min outside [-1, 1] or
+ *   NaN, n_iters < 0 or > R3D_ICP_STATE_DOUBLES - R3D_ICP_STATE_HISTORY (what the history holds), a device output overlapping an
+ *   input map or another output (r3d_tsdf_track: a host output overlapping the guess or the other output), a raster of
+ *   2^31 - 1024 pixels or more; r3d_tsdf_track also: a non-finite guess, max_jump < 0, and the argument errors of
+ *   r3d_tsdf_integrate (depth) and r3d_tsdf_raycast.  Not done here: image pyramids / coarse-to-fine, photometric (colour) terms. */
+int r3d_track_accumulate(r3d_ctx* ctx, const r3d_camera* cam, const float* d_src_vertex, const float* d_src_normal,
+                         const float* d_model_vertex, const float* d_model_normal, const double* h_model_pose_w2c, const double* h_S,
+                         double dist_max, double cos_min, double* h_sums, int32_t* d_match_out, float* d_residual_out);
+int r3d_track_iterate(r3d_ctx* ctx, const r3d_camera* cam, const float* d_src_vertex, const float* d_src_normal,
+                      const float* d_model_vertex, const float* d_model_normal, const double* h_model_pose_w2c, const double* h_S,
+                      double dist_max, double cos_min, int n_iters, double* d_state);
+int r3d_tsdf_track(r3d_tsdf* vol, const r3d_camera* cam, const void* d_depth, int depth_dtype, double depth_scale,
+                   const double* h_pose_guess_w2c, double min_weight, double step, double t_near, double t_far, float max_jump,
+                   double dist_max, double cos_min, int n_iters, double* h_pose_out, double* h_info_out);
+
 #ifdef __cplusplus
 }
 #endif
