@@ -161,7 +161,11 @@ int r3d_fuse_frames_rgb_host(r3d_ctx* ctx, const r3d_camera* cam, const void* h_
  * upstream monodepth2 layers.py, not vendored by the reference):
  *     cam_points[b][c][p] = depth[b][p] * (inv_K[b][c][0]*x + inv_K[b][c][1]*y + inv_K[b][c][2]),  c = 0..2;  [b][3][p] = 1
  * with p = y*W + x, all fp32 like the layer.  d_depth [B][H*W], d_inv_K [B][4][4] row-major, d_cam_points [B][4][H*W].
- * The _grad entry point is the layer's backward with respect to depth: grad_depth[b][p] = sum_c grad_cam[b][c][p]*ray_c. */
+ * The _grad entry point is the layer's backward with respect to depth: grad_depth[b][p] = sum_c grad_cam[b][c][p]*ray_c.
+ * f32 evaluation order (the upstream layer's; one rounding per operation, no fused multiply-add, x and y converted exactly):
+ *     ray_c = (k_c0*x + k_c1*y) + k_c2          cam_c = z * ray_c          the fourth plane is exactly 1.0f
+ *     grad_depth = (g0*ray_0 + g1*ray_1) + g2*ray_2
+ * Every per-pixel output of these four entry points is therefore specified bit for bit (NaN sign and payload excepted). */
 int r3d_backproject_depth_f32(r3d_ctx* ctx, const float* d_depth, const float* d_inv_K, int batch, int height, int width,
                               float* d_cam_points);
 int r3d_backproject_depth_grad_f32(r3d_ctx* ctx, const float* d_grad_cam_points, const float* d_inv_K, int batch, int height,
@@ -172,7 +176,16 @@ int r3d_backproject_depth_grad_f32(r3d_ctx* ctx, const float* d_grad_cam_points,
  *     pix[b][p] = ( (c0 / (c2 + eps) / (W-1) - 0.5) * 2,  (c1 / (c2 + eps) / (H-1) - 0.5) * 2 )        grid_sample coordinates
  * d_points [B][4][H*W] (the BackprojectDepth layout), d_pix [B][H][W][2], fp32; upstream eps = 1e-7.
  * The _grad entry point is the backward pass: d_grad_points [B][4][H*W] and/or d_grad_P [B][3][4] (either may be NULL);
- * d_grad_P is a two-stage fixed-order reduction (bitwise repeatable). */
+ * d_grad_P is a two-stage fixed-order reduction (bitwise repeatable).
+ * f32 evaluation order, with (px, py, pz, pw) = points[b][0..3][p] and g = grad_pix[b][p]:
+ *     c_i = ((P_i0*px + P_i1*py) + P_i2*pz) + P_i3*pw          den = c2 + eps
+ *     pix = ( ((c0/den)/(W-1) - 0.5) * 2,  ((c1/den)/(H-1) - 0.5) * 2 )          divisions correctly rounded
+ *     inv = 1/den      d0 = (g.x * (2/(W-1))) * inv      d1 = (g.y * (2/(H-1))) * inv      d2 = (-(d0*c0 + d1*c1)) * inv
+ *     grad_points_k = (P_0k*d0 + P_1k*d1) + P_2k*d2,  k = 0..3          (2/(W-1), 2/(H-1): f32 quotients formed once)
+ *     grad_P_ik = sum over the image's pixels of d_i * x_k; each term is one f32 product of the d_i above.  The order of the
+ *     summation is build-defined and fixed: bitwise repeatable, independent of the other images of the batch, not specified.
+ * H == 1 or W == 1 -> R3D_ERR_INVALID (BackprojectDepth accepts them); batch == 0 -> R3D_OK, nothing written;
+ * batch > 65535, a NULL required pointer with batch > 0 -> R3D_ERR_INVALID, nothing written; both outputs of _grad NULL -> R3D_OK. */
 int r3d_project3d_f32(r3d_ctx* ctx, const float* d_points, const float* d_P, int batch, int height, int width, float eps,
                       float* d_pix);
 int r3d_project3d_grad_f32(r3d_ctx* ctx, const float* d_grad_pix, const float* d_points, const float* d_P, int batch,
