@@ -18,8 +18,8 @@
 //
 // r3d_icp_accumulate -- roofline: HBM/L2 gather, 28 B/pair (12 src + 4 idx + 12 gathered tgt).
 //   fp64 accumulators in registers, wavefront shuffle tree (width 64) -> LDS across the 4 waves
-//   -> per-workgroup partials -> one fixed-order final pass.  No float atomics: bitwise
-//   reproducible run to run.
+//   -> per-workgroup partials -> one fixed-order final pass (r3d_sums_dev.h).  No float atomics:
+//   bitwise reproducible run to run.
 #include <cmath>
 
 #include "r3d_icp_sums.h"
@@ -154,7 +154,6 @@ __global__ __launch_bounds__(kThreads) void nn_merge_kernel(const uint32_t* __re
 }
 
 // ---------------------------------------------------------------------------------------------
-using r3d_icp::block_reduce_store;
 using r3d_icp::kSums;
 using r3d_icp::pair_accumulate;
 using r3d_icp::pair_weight;
@@ -178,71 +177,34 @@ __global__ __launch_bounds__(kThreads) void accumulate_kernel(const float* __res
       pair_accumulate(acc, d2 ? pair_weight(d2[i], dead_zone) : 1.0, p, q);
     }
   }
-  block_reduce_store(acc, red, partials + (int64_t)blockIdx.x * kSums);
+  r3d_sums::block_reduce_store<kSums>(acc, red, partials + (int64_t)blockIdx.x * kSums);
 }
 
 // ---- device-side similarity solve: the ICP loop never waits for the host ---------------------------------
 __global__ void icp_state_reset_kernel(double* __restrict__ st) {
-  for (int k = threadIdx.x; k < r3d_icp::kStateDoubles; k += blockDim.x) {
+  for (int k = threadIdx.x; k < r3d_sums::kStateDoubles; k += blockDim.x) {
     double v = 0.0;
     if (k < 32 && (k % 16) % 5 == 0) v = 1.0;  // T_total = T_step = identity
     st[k] = v;
   }
 }
 
-// One thread: step = umeyama(sums); T_total <- step . T_total; history.  A degenerate fit leaves the identity step.
-__device__ void icp_solve_step(const double* s, int with_scale, double* __restrict__ st) {
-  double T[16], rms = 0.0;
-  const int bad = r3d_icp::umeyama_from_sums(s, with_scale, T, &rms);
-  double tot[16], nt[16];
-  for (int k = 0; k < 16; ++k) tot[k] = st[r3d_icp::kStateTTotal + k];
-  for (int r = 0; r < 4; ++r)
-    for (int c = 0; c < 4; ++c) {
-      double v = 0.0;
-      for (int m = 0; m < 4; ++m) v += T[4 * r + m] * tot[4 * m + c];
-      nt[4 * r + c] = v;
-    }
-  for (int k = 0; k < 16; ++k) {
-    st[r3d_icp::kStateTStep + k] = T[k];
-    st[r3d_icp::kStateTTotal + k] = nt[k];
-  }
-  const int it = (int)st[r3d_icp::kStateIters];
-  if (r3d_icp::kStateHistory + it < r3d_icp::kStateDoubles) st[r3d_icp::kStateHistory + it] = rms;
-  st[r3d_icp::kStateIters] = (double)(it + 1);
-  if (bad) st[r3d_icp::kStateStatus] = 1.0;
-  st[r3d_icp::kStateRms] = rms;
-  st[r3d_icp::kStatePairs] = s[0];
-}
-
+// One thread: step = umeyama(sums), then the state update.  A degenerate fit leaves the identity step.
 __global__ void icp_solve_kernel(const double* __restrict__ sums, int with_scale, double* __restrict__ st) {
-  double s[kSums];
+  double s[kSums], T[16], rms = 0.0;
   for (int k = 0; k < kSums; ++k) s[k] = sums[k];
-  icp_solve_step(s, with_scale, st);
+  const int bad = r3d_icp::umeyama_from_sums(s, with_scale, T, &rms);
+  r3d_sums::icp_state_advance(T, rms, bad, s[0], st);
 }
 
-// ONE workgroup finishes a sums pass: (1) the per-workgroup partial rows, lane t taking rows t, t+256, ... in order;
-// (2) fixed shuffle / LDS tree -> the 18 sums; (3) optionally the similarity solve and the ICP state update by lane 0.
-// Every order is fixed: bitwise repeatable.  One launch instead of (final reduction, solve).
+// ONE workgroup finishes a sums pass (r3d_sums::finish_rows): partial rows -> the 18 sums -> optionally the similarity solve
+// and the ICP state update by lane 0.
 __global__ __launch_bounds__(kThreads) void sums_finish_kernel(const double* __restrict__ partials, int n_rows,
                                                                double* __restrict__ sums_out, int with_scale,
                                                                double* __restrict__ state) {
-  __shared__ double red[kThreads / 64][kSums];
-  __shared__ double total[kSums];
-  double acc[kSums];
-#pragma unroll
-  for (int k = 0; k < kSums; ++k) acc[k] = 0.0;
-  for (int b = threadIdx.x; b < n_rows; b += kThreads) {
-#pragma unroll
-    for (int k = 0; k < kSums; ++k) acc[k] += partials[(int64_t)b * kSums + k];
-  }
-  block_reduce_store(acc, red, total);
-  __syncthreads();
-  if (threadIdx.x < kSums) sums_out[threadIdx.x] = total[threadIdx.x];
-  if (threadIdx.x == 0 && state != nullptr) {
-    double s[kSums];
-    for (int k = 0; k < kSums; ++k) s[k] = total[k];
-    icp_solve_step(s, with_scale, state);
-  }
+  r3d_sums::finish_rows<kSums>(partials, n_rows, sums_out, state, [with_scale](const double* s, double* T, double* rms) {
+    return r3d_icp::umeyama_from_sums(s, with_scale, T, rms);
+  });
 }
 
 }  // namespace
@@ -435,7 +397,7 @@ int r3d_icp_iterate(r3d_ctx* ctx, r3d_nn_index* index, float* d_src, int64_t n_s
       if ((rc = accumulate_impl(ctx, d_src, n_src, d_tgt, n_tgt, d_idx, d_d2, max_d2, 0.f, d_sums, with_scale, d_state)))
         return rc;
     }
-    if ((rc = r3d_apply_T_dev(ctx, d_src, R3D_F32, n_src, d_state + r3d_icp::kStateTStep, d_src, R3D_F32))) return rc;
+    if ((rc = r3d_apply_T_dev(ctx, d_src, R3D_F32, n_src, d_state + r3d_sums::kStateTStep, d_src, R3D_F32))) return rc;
   }
   if (index && n_iters > 0) {
     ctx->loop_state = d_state;

@@ -1,7 +1,7 @@
-// Shared pieces of the ICP estimation path (r3d_icp.hip, r3d_nnindex.hip): the 18 fp64 pair sums, their
-// deterministic workgroup reduction, and the closed-form similarity (Umeyama 1991) solved from them -- the
-// latter as host+device code so that the ICP loop can run without a host round trip per iteration and the
-// very same arithmetic is testable on a CPU-only box (r3d_umeyama_from_sums).
+// Shared pieces of the ICP estimation path (r3d_icp.hip, r3d_nnindex.hip): what one matched pair adds to the 18 fp64 pair
+// sums, and the closed-form similarity (Umeyama 1991) solved from them -- the latter as host+device code so that the ICP
+// loop can run without a host round trip per iteration and the very same arithmetic is testable on a CPU-only box
+// (r3d_umeyama_from_sums).  The rows' deterministic reduction and the ICP state: r3d_sums_dev.h.
 //
 // NOT IN THE REFERENCE: other_tools/transfer_T_icp.py:33-43,99-108 only consumes the T such a fit produces.
 #pragma once
@@ -11,28 +11,13 @@
 #include <cmath>
 #include <cstdint>
 
+#include "r3d_sums_dev.h"
+
 namespace r3d_icp {
 
 constexpr int kSums = 18;     // n, sum p (3), sum q (3), sum p_a q_b (9, a major), sum |p|^2, sum |q|^2
-constexpr int kThreads = 256;
-
-// ---- device-resident ICP state (R3D_ICP_STATE_DOUBLES doubles, see include/r3d.h) ----
-constexpr int kStateTTotal = 0;    // [16] row-major 4x4: product of all steps so far (maps the ORIGINAL source)
-constexpr int kStateTStep = 16;    // [16] the last step
-constexpr int kStateIters = 32;    // iterations solved so far
-constexpr int kStateStatus = 33;   // 0 ok; 1 = a step was degenerate (fewer than 3 pairs / zero variance) and was skipped
-constexpr int kStateRms = 34;      // weighted RMS match distance seen by the last step (before it was applied)
-constexpr int kStatePairs = 35;    // weight sum (= pair count when unweighted) of the last step
-constexpr int kStateHistory = 48;  // rms of step k at [48 + k] while it fits
-constexpr int kStateDoubles = 512;
 
 #if defined(__HIPCC__)
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
 // One matched pair's weight.  dead_zone <= 0: w = 1.  Otherwise the IRLS weight of the cost
 // max(0, d - dead_zone)^2, d = sqrt(d2): w = max(0, 1 - dead_zone/d).  It treats a densely sampled cloud as the
 // solid it samples: a distance below the sampling resolution says nothing about the transform.
@@ -58,27 +43,6 @@ __device__ __forceinline__ void pair_accumulate(double acc[kSums], double w, con
     acc[17] += w * q[a] * q[a];
   }
 }
-
-// Workgroup (256 threads) reduction of per-lane accumulators into one row of 18 partials: shuffle tree over the
-// 64 lanes, LDS across the 4 waves, fixed order -> bitwise repeatable.  `red` is __shared__ [4][kSums].
-__device__ __forceinline__ void block_reduce_store(double acc[kSums], double (*red)[kSums],
-                                                   double* __restrict__ partial_row) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < kSums; ++k) {
-    const double v = wave_sum(acc[k]);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kSums) {
-    double v = 0.0;
-    for (int w = 0; w < kThreads / 64; ++w) v += red[w][threadIdx.x];
-    partial_row[threadIdx.x] = v;
-  }
-}
-#define R3D_HD __host__ __device__
-#else
-#define R3D_HD
 #endif
 
 // ---- 3x3 SVD by one-sided Jacobi (Hestenes): A V = U diag(sig), sig descending, U and V orthogonal.

@@ -190,5 +190,12 @@ int r3d_nn_index_query_solve(r3d_nn_index* index, const float* d_src, int64_t n_
 int r3d_nn_index_query_step(r3d_nn_index* index, const float* d_src, int64_t n_src, uint32_t* d_idx_out, float* d_d2_out,
                             int small_motion, const float* d_src_orig, const double* d_T_move, int* moved_out);
 
+// Do the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte?  A NULL pointer or an empty range overlaps nothing.
+static inline bool r3d_ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  if (!a || !b || !a_bytes || !b_bytes) return false;
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
 static inline size_t r3d_depth_size(int dt) { return dt == R3D_DEPTH_U8 ? 1 : dt == R3D_DEPTH_U16 ? 2 : 4; }
 static inline size_t r3d_xyz_size(int dt) { return dt == R3D_F32 ? 4 : 8; }

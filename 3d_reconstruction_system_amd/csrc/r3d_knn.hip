@@ -29,6 +29,7 @@
 #include "r3d_magic_div.h"
 #include "r3d_nnindex_dev.h"
 #include "r3d_sort_dev.h"
+#include "r3d_sums_dev.h"
 
 namespace {
 
@@ -90,15 +91,11 @@ __device__ __forceinline__ float box_lb(const float* __restrict__ b, float px, f
   return box_lb<POINT_EXACT>(b[0], b[1], b[2], b[3], b[4], b[5], px, py, pz);
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
+using r3d_sums::wave_sum;   // the fp64 shuffle tree every sums row of the library goes through
 
 // the sum of one double per thread of a 256-thread workgroup, in a fixed order; valid in thread 0
 __device__ __forceinline__ double block_sum_f64(double v, double* sh) {
-  v = wave_sum_f64(v);
+  v = wave_sum(v);
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
   __syncthreads();
   double t = 0.0;
@@ -413,8 +410,8 @@ __global__ __launch_bounds__(64) void sor_mean_kernel(const double* __restrict__
     s += partials[2 * r];
     v += partials[2 * r + 1];
   }
-  s = wave_sum_f64(s);
-  v = wave_sum_f64(v);
+  s = wave_sum(s);
+  v = wave_sum(v);
   if (threadIdx.x == 0) {
     stats[0] = v;
     stats[1] = s / v;   // V = 0: NaN (nothing is scored, nothing is kept)
@@ -440,7 +437,7 @@ __global__ __launch_bounds__(64) void sor_threshold_kernel(const double* __restr
                                                            double* __restrict__ stats) {
   double s = 0.0;
   for (int r = threadIdx.x; r < n_rows; r += 64) s += partials[r];
-  s = wave_sum_f64(s);
+  s = wave_sum(s);
   if (threadIdx.x == 0) {
     const double v = stats[0];
     const double sigma = v > 1.0 ? sqrt(s / (v - 1.0)) : 0.0;
@@ -508,12 +505,6 @@ __global__ __launch_bounds__(kThreads) void select_write_kernel(const float* __r
   }
 }
 
-bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  if (!a || !b || !na || !nb) return false;
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return pa < pb + nb && pb < pa + na;
-}
-
 // launches knn_kernel for MODE with the smallest K >= k (asynchronous); resets the index's group counter first
 template <int MODE>
 int knn_launch(r3d_nn_index* ix, KnnArgs& a) {
@@ -548,7 +539,7 @@ int r3d_nn_index_knn_self(r3d_nn_index* ix, int k, uint32_t* d_idx_out, float* d
   R3D_REQUIRE(k >= 1 && k <= 32, "k must be in [1, 32], got %d", k);
   R3D_REQUIRE(d_idx_out != nullptr, "d_idx_out is NULL");
   const size_t bytes = (size_t)ix->n * k * 4;
-  R3D_REQUIRE(!ranges_overlap(d_idx_out, bytes, d_d2_out, bytes), "d_idx_out and d_d2_out overlap");
+  R3D_REQUIRE(!r3d_ranges_overlap(d_idx_out, bytes, d_d2_out, bytes), "d_idx_out and d_d2_out overlap");
   int rc = r3d_ctx_enter(ix->ctx);
   if (rc) return rc;
   r3d_wrote(ix->ctx, d_idx_out, bytes);
@@ -577,8 +568,8 @@ int r3d_normals_knn(r3d_nn_index* ix, int k, double radius, const double* h_view
     size_t bytes;
   } out[4] = {{d_normals_out, (size_t)n * 12}, {d_curvature_out, (size_t)n * 4}, {d_cov_out, (size_t)n * 48}, {d_count_out, (size_t)n * 4}};
   for (int i = 0; i < 4; ++i) {
-    R3D_REQUIRE(!ranges_overlap(out[i].p, out[i].bytes, ix->d_tgt, (size_t)n * 12), "an output overlaps the index's cloud");
-    for (int j = i + 1; j < 4; ++j) R3D_REQUIRE(!ranges_overlap(out[i].p, out[i].bytes, out[j].p, out[j].bytes), "outputs overlap each other");
+    R3D_REQUIRE(!r3d_ranges_overlap(out[i].p, out[i].bytes, ix->d_tgt, (size_t)n * 12), "an output overlaps the index's cloud");
+    for (int j = i + 1; j < 4; ++j) R3D_REQUIRE(!r3d_ranges_overlap(out[i].p, out[i].bytes, out[j].p, out[j].bytes), "outputs overlap each other");
   }
   r3d_ctx* ctx = ix->ctx;
   int rc = r3d_ctx_enter(ctx);
@@ -612,7 +603,7 @@ int r3d_outlier_statistical(r3d_nn_index* ix, int k, double std_ratio, uint8_t* 
   R3D_REQUIRE(std::isfinite(std_ratio) && std_ratio > 0.0, "std_ratio must be finite and > 0, got %g", std_ratio);
   R3D_REQUIRE(d_keep_out != nullptr, "d_keep_out is NULL");
   const int64_t n = ix->n;
-  R3D_REQUIRE(!ranges_overlap(d_keep_out, (size_t)n, d_score_out, (size_t)n * 8), "d_keep_out and d_score_out overlap");
+  R3D_REQUIRE(!r3d_ranges_overlap(d_keep_out, (size_t)n, d_score_out, (size_t)n * 8), "d_keep_out and d_score_out overlap");
   r3d_ctx* ctx = ix->ctx;
   int rc = r3d_ctx_enter(ctx);
   if (rc) return rc;
@@ -659,7 +650,7 @@ int r3d_outlier_radius(r3d_nn_index* ix, double radius, int64_t min_points, uint
   R3D_REQUIRE(min_points >= 1, "min_points must be >= 1, got %lld", (long long)min_points);
   R3D_REQUIRE(d_keep_out != nullptr, "d_keep_out is NULL");
   const int64_t n = ix->n;
-  R3D_REQUIRE(!ranges_overlap(d_keep_out, (size_t)n, d_count_out, (size_t)n * 4), "d_keep_out and d_count_out overlap");
+  R3D_REQUIRE(!r3d_ranges_overlap(d_keep_out, (size_t)n, d_count_out, (size_t)n * 4), "d_keep_out and d_count_out overlap");
   r3d_ctx* ctx = ix->ctx;
   int rc = r3d_ctx_enter(ctx);
   if (rc) return rc;
@@ -697,7 +688,7 @@ int r3d_select_rows(r3d_ctx* ctx, const float* d_xyz, int64_t n, const uint8_t* 
   }
   R3D_REQUIRE(d_xyz && d_keep && d_xyz_out, "NULL device pointer");
   const size_t xb = (size_t)n * 12;
-  R3D_REQUIRE(!ranges_overlap(d_keep, (size_t)n, d_xyz, xb), "d_keep overlaps d_xyz");
+  R3D_REQUIRE(!r3d_ranges_overlap(d_keep, (size_t)n, d_xyz, xb), "d_keep overlaps d_xyz");
   const int tiles = (int)((n + kSortTile - 1) / kSortTile), stride = r3d_sort_stride(tiles);
   void* ws = nullptr;
   if ((rc = r3d_scratch(ctx, 3, (size_t)stride * 4 + 64, &ws))) return rc;
@@ -712,9 +703,9 @@ int r3d_select_rows(r3d_ctx* ctx, const float* d_xyz, int64_t n, const uint8_t* 
   R3D_HIP(hipStreamSynchronize(st));
   // the outputs need room for the kept rows only; none of them may overlap an input or the other output
   const size_t ob = (size_t)m * 12, rb = d_rows_out ? (size_t)m * 4 : 0;
-  R3D_REQUIRE(!ranges_overlap(d_xyz_out, ob, d_xyz, xb) && !ranges_overlap(d_xyz_out, ob, d_keep, (size_t)n) &&
-                  !ranges_overlap(d_rows_out, rb, d_xyz, xb) && !ranges_overlap(d_rows_out, rb, d_keep, (size_t)n) &&
-                  !ranges_overlap(d_rows_out, rb, d_xyz_out, ob),
+  R3D_REQUIRE(!r3d_ranges_overlap(d_xyz_out, ob, d_xyz, xb) && !r3d_ranges_overlap(d_xyz_out, ob, d_keep, (size_t)n) &&
+                  !r3d_ranges_overlap(d_rows_out, rb, d_xyz, xb) && !r3d_ranges_overlap(d_rows_out, rb, d_keep, (size_t)n) &&
+                  !r3d_ranges_overlap(d_rows_out, rb, d_xyz_out, ob),
               "an output range overlaps an input or the other output");
   *h_n_out = (int64_t)m;
   if (m == 0) return R3D_OK;

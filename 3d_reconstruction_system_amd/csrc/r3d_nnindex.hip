@@ -481,7 +481,7 @@ __global__ __launch_bounds__(kThreads) void nn_cull_kernel(const void* __restric
   }
   if (partials) {
     __shared__ double red[kThreads / 64][r3d_icp::kSums];
-    r3d_icp::block_reduce_store(acc, red, partials + (int64_t)blockIdx.x * r3d_icp::kSums);
+    r3d_sums::block_reduce_store<r3d_icp::kSums>(acc, red, partials + (int64_t)blockIdx.x * r3d_icp::kSums);
   }
   if (tid == 0 && stats) atomicAdd(&stats[0], (unsigned long long)swept);
   if ((tid & 63) == 0 && stats) atomicAdd(&stats[1], (unsigned long long)groups_done);  // 32-target groups evaluated, per wave
@@ -697,7 +697,7 @@ __global__ __launch_bounds__(kThreads) void nn_warm_kernel(const float* __restri
   }
   if (partials) {
     __shared__ double red[kThreads / 64][r3d_icp::kSums];
-    r3d_icp::block_reduce_store(acc, red, partials + (int64_t)blockIdx.x * r3d_icp::kSums);
+    r3d_sums::block_reduce_store<r3d_icp::kSums>(acc, red, partials + (int64_t)blockIdx.x * r3d_icp::kSums);
   }
   if (lane == 0 && stats) {
     atomicAdd(&stats[0], (unsigned long long)swept);   // tiles opened, per wave here (per workgroup in nn_cull_kernel)

@@ -231,12 +231,6 @@ __global__ __launch_bounds__(kThreads) void octree_link_kernel(const uint64_t* _
   if (pos < n_records) atomicOr(&rec32[pos >> 1], field << (16 * (uint32_t)(pos & 1)));   // result unused: a no-return atomic
 }
 
-bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  if (!a || !b || !na || !nb) return false;
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return pa < pb + nb && pb < pa + na;
-}
-
 struct Workspace {
   uint8_t* meta = nullptr;
   uint16_t* pre = nullptr;
@@ -384,7 +378,7 @@ int r3d_octree_records_device(r3d_ctx* ctx, const uint64_t* d_codes_sorted, int6
       if (cap_records < n_rec) {
         r3d_set_error("buffer holds %lld records, the tree has %lld", (long long)cap_records, (long long)n_rec);
         rc = R3D_ERR_INVALID;
-      } else if (ranges_overlap(d_records_out, (size_t)n_rec * 2, d_codes_sorted, (size_t)n_codes * 8)) {
+      } else if (r3d_ranges_overlap(d_records_out, (size_t)n_rec * 2, d_codes_sorted, (size_t)n_codes * 8)) {
         r3d_set_error("d_records_out overlaps d_codes_sorted");
         rc = R3D_ERR_INVALID;
       } else {

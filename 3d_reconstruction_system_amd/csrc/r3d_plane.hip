@@ -13,10 +13,10 @@
 //                          accumulators -> wave shuffle tree -> LDS across waves -> one row per workgroup
 //   plane_finish_kernel    ONE workgroup: rows in fixed order -> 29 sums -> Cholesky solve + exponential map -> the ICP
 //                          state (T_total, T_step, history) in HBM, so that whole iterations run without the host
+//                          (the reduction, the finish and the state update are r3d_sums_dev.h's, shared by every loop)
 // No float atomics anywhere: bitwise repeatable run to run.
 #include <cmath>
 
-#include "r3d_icp_sums.h"
 #include "r3d_internal.h"
 #include "r3d_plane_sums.h"
 
@@ -346,52 +346,15 @@ __global__ __launch_bounds__(kThreads) void plane_accumulate_kernel(const float*
     if (!((float)(r * r) <= s_gate[cls])) continue;   // the same fp32 value the selection ranked
     r3d_plane::pair_accumulate(acc, 1.0, p, n, r);
   }
-  r3d_plane::block_reduce_store(acc, red, partials + (int64_t)blockIdx.x * kSums);
+  r3d_sums::block_reduce_store<kSums>(acc, red, partials + (int64_t)blockIdx.x * kSums);
 }
 
-// One thread: step from the sums; T_total <- step . T_total; history (same state layout as the similarity loop).
-__device__ void plane_solve_step(const double* s, double* __restrict__ st) {
-  double T[16], rms = 0.0;
-  const int bad = r3d_plane::step_from_sums(s, T, &rms);
-  double tot[16], nt[16];
-  for (int k = 0; k < 16; ++k) tot[k] = st[r3d_icp::kStateTTotal + k];
-  for (int r = 0; r < 4; ++r)
-    for (int c = 0; c < 4; ++c) {
-      double v = 0.0;
-      for (int m = 0; m < 4; ++m) v += T[4 * r + m] * tot[4 * m + c];
-      nt[4 * r + c] = v;
-    }
-  for (int k = 0; k < 16; ++k) {
-    st[r3d_icp::kStateTStep + k] = T[k];
-    st[r3d_icp::kStateTTotal + k] = nt[k];
-  }
-  const int it = (int)st[r3d_icp::kStateIters];
-  if (r3d_icp::kStateHistory + it < r3d_icp::kStateDoubles) st[r3d_icp::kStateHistory + it] = rms;
-  st[r3d_icp::kStateIters] = (double)(it + 1);
-  if (bad) st[r3d_icp::kStateStatus] = 1.0;
-  st[r3d_icp::kStateRms] = rms;
-  st[r3d_icp::kStatePairs] = s[0];
-}
-
+// ONE workgroup (r3d_sums::finish_rows): partial rows -> the 29 sums -> optionally the step and the ICP state (the state of the
+// similarity loop: same layout, same update)
 __global__ __launch_bounds__(kThreads) void plane_finish_kernel(const double* __restrict__ partials, int n_rows,
                                                                 double* __restrict__ sums_out, double* __restrict__ state) {
-  __shared__ double red[kThreads / 64][kSums];
-  __shared__ double total[kSums];
-  double acc[kSums];
-#pragma unroll
-  for (int k = 0; k < kSums; ++k) acc[k] = 0.0;
-  for (int b = threadIdx.x; b < n_rows; b += kThreads) {
-#pragma unroll
-    for (int k = 0; k < kSums; ++k) acc[k] += partials[(int64_t)b * kSums + k];
-  }
-  r3d_plane::block_reduce_store(acc, red, total);
-  __syncthreads();
-  if (threadIdx.x < kSums && sums_out) sums_out[threadIdx.x] = total[threadIdx.x];
-  if (threadIdx.x == 0 && state != nullptr) {
-    double s[kSums];
-    for (int k = 0; k < kSums; ++k) s[k] = total[k];
-    plane_solve_step(s, state);
-  }
+  r3d_sums::finish_rows<kSums>(partials, n_rows, sums_out, state,
+                               [](const double* s, double* T, double* rms) { return r3d_plane::step_from_sums(s, T, rms); });
 }
 
 // workspace in scratch slot 6: [hist n_buckets x 256 u32][state n_buckets x 4 u64][SelectOut x n_buckets][pad], then the
@@ -464,8 +427,8 @@ __global__ __launch_bounds__(kThreads) void class_sum_below_kernel(const float* 
       cnt += 1.0;
     }
   }
-  sum = r3d_plane::wave_sum(sum);
-  cnt = r3d_plane::wave_sum(cnt);
+  sum = r3d_sums::wave_sum(sum);
+  cnt = r3d_sums::wave_sum(cnt);
   if ((threadIdx.x & 63) == 0) {
     red[0][threadIdx.x >> 6] = sum;
     red[1][threadIdx.x >> 6] = cnt;
@@ -684,14 +647,14 @@ int r3d_icp_iterate_plane(r3d_ctx* ctx, r3d_nn_index* index, const float* d_src_
     int rc2, moved = 0;
     // sources are kept in the index's Morton order by the caller (r3d_nn_index_sort_cloud; rigid moves preserve it)
     if (pending_move && !(warm && d_src_orig)) {   // (cannot happen: a pending move implies both; kept for safety)
-      if ((rc2 = r3d_apply_T_dev(ctx, d_src_orig, R3D_F32, n_src, d_state + r3d_icp::kStateTTotal, d_src, R3D_F32))) return rc2;
+      if ((rc2 = r3d_apply_T_dev(ctx, d_src_orig, R3D_F32, n_src, d_state + r3d_sums::kStateTTotal, d_src, R3D_F32))) return rc2;
       pending_move = false;
     }
     if ((rc2 = r3d_nn_index_query_step(index, d_src, n_src, d_idx, d_d2, warm, pending_move ? d_src_orig : nullptr,
-                                       pending_move ? d_state + r3d_icp::kStateTTotal : nullptr, &moved)))
+                                       pending_move ? d_state + r3d_sums::kStateTTotal : nullptr, &moved)))
       return rc2;
     if (pending_move && !moved) {   // the query took the other kernel after all: it searched the unmoved cloud -- redo properly
-      if ((rc2 = r3d_apply_T_dev(ctx, d_src_orig, R3D_F32, n_src, d_state + r3d_icp::kStateTTotal, d_src, R3D_F32))) return rc2;
+      if ((rc2 = r3d_apply_T_dev(ctx, d_src_orig, R3D_F32, n_src, d_state + r3d_sums::kStateTTotal, d_src, R3D_F32))) return rc2;
       if ((rc2 = r3d_nn_index_query_step(index, d_src, n_src, d_idx, d_d2, warm, nullptr, nullptr, nullptr))) return rc2;
     }
     pending_move = false;
@@ -702,8 +665,8 @@ int r3d_icp_iterate_plane(r3d_ctx* ctx, r3d_nn_index* index, const float* d_src_
       pending_move = true;   // the next iteration's search moves the cloud
       return R3D_OK;
     }
-    if (d_src_orig) return r3d_apply_T_dev(ctx, d_src_orig, R3D_F32, n_src, d_state + r3d_icp::kStateTTotal, d_src, R3D_F32);
-    return r3d_apply_T_dev(ctx, d_src, R3D_F32, n_src, d_state + r3d_icp::kStateTStep, d_src, R3D_F32);
+    if (d_src_orig) return r3d_apply_T_dev(ctx, d_src_orig, R3D_F32, n_src, d_state + r3d_sums::kStateTTotal, d_src, R3D_F32);
+    return r3d_apply_T_dev(ctx, d_src, R3D_F32, n_src, d_state + r3d_sums::kStateTStep, d_src, R3D_F32);
   };
   // (Replaying one captured iteration as a hipGraph -- 14 launches per iteration, each dependent on the one before -- was
   // measured in round 3: 190-198 us per iteration against 184-186 us launch by launch, capture and instantiation included.  The

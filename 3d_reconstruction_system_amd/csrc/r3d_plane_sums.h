@@ -1,6 +1,7 @@
-// Point-to-plane rigid ICP step: the 29 fp64 sums of the linearised 6x6 normal equations, their deterministic
-// workgroup reduction, and the solve (Cholesky + exponential map) as host+device code -- the ICP loop runs without a
-// host round trip per iteration and the very same arithmetic is callable on a CPU-only box (r3d_plane_step_from_sums).
+// Point-to-plane rigid ICP step: what one matched pair adds to the 29 fp64 sums of the linearised 6x6 normal equations, and
+// the solve (Cholesky + exponential map) as host+device code -- the ICP loop runs without a host round trip per iteration and
+// the very same arithmetic is callable on a CPU-only box (r3d_plane_step_from_sums).  The rows' deterministic reduction and
+// the ICP state: r3d_sums_dev.h.
 //
 // NOT IN THE REFERENCE (ICP estimation is build-defined).  What it serves IS the reference's use of
 // ICP: "match the point clouds corresponding to two images" (readme.md:25) -- the relative pose of two single-view
@@ -18,18 +19,13 @@
 #include <cmath>
 #include <cstdint>
 
+#include "r3d_sums_dev.h"
+
 namespace r3d_plane {
 
 constexpr int kSums = 29;
-constexpr int kThreads = 256;
 
 #if defined(__HIPCC__)
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
 // r = n . (p - q), evaluated left to right in fp64 (the differences of fp32 inputs are exact there)
 __device__ __forceinline__ double plane_residual(const double p[3], const double q[3], const double n[3]) {
   return n[0] * (p[0] - q[0]) + n[1] * (p[1] - q[1]) + n[2] * (p[2] - q[2]);
@@ -48,32 +44,12 @@ __device__ __forceinline__ void pair_accumulate(double acc[kSums], double w, con
     for (int b = a; b < 6; ++b) acc[k++] += wj * J[b];
   }
 }
-
-// Workgroup (256 threads) reduction of per-lane accumulators into one row of partials: shuffle tree over the 64 lanes,
-// LDS across the 4 waves, fixed order -> bitwise repeatable.  `red` is __shared__ [4][kSums].
-__device__ __forceinline__ void block_reduce_store(double acc[kSums], double (*red)[kSums], double* __restrict__ row) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < kSums; ++k) {
-    const double v = wave_sum(acc[k]);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kSums) {
-    double v = 0.0;
-    for (int w = 0; w < kThreads / 64; ++w) v += red[w][threadIdx.x];
-    row[threadIdx.x] = v;
-  }
-}
-#define R3D_PLANE_HD __host__ __device__
-#else
-#define R3D_PLANE_HD
 #endif
 
 // T (row-major 4x4, rigid) from the 29 sums.  Returns 0, or 1 when the step is undefined (fewer than 6 pairs, or the
 // normal equations are singular to working precision: the matched normals do not constrain all six freedoms -- one
 // plane, two parallel walls, ...): T is then the identity.  *rms_out (optional) = sqrt(sum w r^2 / sum w).
-R3D_PLANE_HD inline int step_from_sums(const double s[kSums], double T[16], double* rms_out) {
+R3D_HD inline int step_from_sums(const double s[kSums], double T[16], double* rms_out) {
   for (int k = 0; k < 16; ++k) T[k] = (k % 5 == 0) ? 1.0 : 0.0;
   const double n = s[0];
   if (rms_out) *rms_out = n > 0.0 ? sqrt((s[1] > 0.0 ? s[1] : 0.0) / n) : 0.0;

@@ -16,7 +16,7 @@
 //   fold_kernel         per hypothesis, the sum over the chunks (integers: the same bits for every chunking) -> counts
 //   best_kernel         one workgroup: the lowest h among the maximal counts, and the number of valid hypotheses
 //   refit_kernel        the best hypothesis' inliers by the same f32 test; their ten fp64 sums about the anchor, one row per
-//                       workgroup (shuffle tree -> LDS, fixed order)
+//                       workgroup (shuffle tree -> LDS, fixed order: r3d_sums_dev.h)
 //   refit_fold_kernel   one wave folds the rows in a fixed order; also fetches the best hypothesis' three points
 //   mask_kernel         the final fp64 test against the refined plane; per-workgroup inlier counts, integer atomics
 // The 3x3 eigenproblem is solved on the host (as r3d_umeyama_from_sums does its SVD) between refit_fold and mask.
@@ -24,6 +24,7 @@
 #include <cmath>
 
 #include "r3d_internal.h"
+#include "r3d_sums_dev.h"
 
 namespace {
 
@@ -235,12 +236,6 @@ __global__ __launch_bounds__(kThreads) void best_kernel(const uint32_t* __restri
   }
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
 // grid-stride over the points: the best hypothesis' inliers and their sums about the anchor -> partial rows [gridDim.x][kSums]
 __global__ __launch_bounds__(kThreads) void refit_kernel(const float* __restrict__ xyz, int64_t n, const float* __restrict__ hyp, int h_pad,
                                                          float thr, const Misc* __restrict__ misc, double* __restrict__ part) {
@@ -265,18 +260,7 @@ __global__ __launch_bounds__(kThreads) void refit_kernel(const float* __restrict
     }
   }
   __shared__ double red[kThreads / 64][kSums];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < kSums; ++k) {
-    const double v = wave_sum(acc[k]);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kSums) {
-    double v = 0.0;
-    for (int w = 0; w < kThreads / 64; ++w) v += red[w][threadIdx.x];
-    part[(size_t)blockIdx.x * kSums + threadIdx.x] = v;
-  }
+  r3d_sums::block_reduce_store<kSums>(acc, red, part + (size_t)blockIdx.x * kSums);
 }
 
 // one wave: lane k < kSums adds the rows' k-th entries in row order; lanes 16..24 fetch the best hypothesis' three points
@@ -370,12 +354,6 @@ void orient(double n[3]) {
     for (int a = 0; a < 3; ++a) n[a] = -n[a];
 }
 
-bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  if (!a || !b || !na || !nb) return false;
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return pa < pb + nb && pb < pa + na;
-}
-
 template <int R>
 void launch_count(hipStream_t st, int chunks, int h_pad, const float* xyz, int64_t n, int64_t chunk_points, const float* hyp, float thr,
                   uint32_t* partial) {
@@ -402,8 +380,8 @@ int r3d_segment_plane(r3d_ctx* ctx, const float* d_xyz, int64_t n, double thr, i
   R3D_REQUIRE(H >= 1 && H <= 65536, "n_hypotheses must be in [1, 65536], got %d", H);
   R3D_REQUIRE(std::isfinite(thr) && thr > 0.0, "distance_threshold must be finite and > 0, got %g", thr);
   const size_t xb = (size_t)n * 12, cb = d_counts_out ? (size_t)H * 4 : 0;
-  R3D_REQUIRE(!ranges_overlap(d_inlier_out, (size_t)n, d_xyz, xb) && !ranges_overlap(d_counts_out, cb, d_xyz, xb) &&
-                  !ranges_overlap(d_counts_out, cb, d_inlier_out, (size_t)n),
+  R3D_REQUIRE(!r3d_ranges_overlap(d_inlier_out, (size_t)n, d_xyz, xb) && !r3d_ranges_overlap(d_counts_out, cb, d_xyz, xb) &&
+                  !r3d_ranges_overlap(d_counts_out, cb, d_inlier_out, (size_t)n),
               "an output overlaps the cloud or the other output");
   int rc = r3d_ctx_enter(ctx);
   if (rc) return rc;

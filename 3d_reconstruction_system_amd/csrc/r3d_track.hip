@@ -5,23 +5,23 @@
 //   track_kernel         one lane per source pixel: move it by M = T_total . S, project it into the model camera, gather the
 //                        model vertex and normal at the nearest pixel, gate, and add the pair to the 29 fp64 sums of
 //                        r3d_plane_sums.h.  A 256-thread workgroup owns 1024 consecutive pixels (thread t: base + t + 256 k,
-//                        k = 0..3) and leaves one partial row: the launch shape is a function of the raster alone, so the sums
+//                        k = 0..3) and leaves one partial row (r3d_sums_dev.h's reduction): the launch shape is a function of
+//                        the raster alone, so the sums
 //                        are the same bits on every device and under every tuning.  Source rows are read coalesced (12 B per
 //                        lane, consecutive); the gather lands near the lane's own pixel for the small motions tracking sees.
 //                        M, the model pose and the intrinsics are wave-uniform.  The only LDS is the reduction's.
 //   track_finish_kernel  ONE workgroup: partial rows in fixed order -> 29 sums -> Cholesky solve + exponential map -> the ICP
-//                        state in HBM (the pattern of r3d_plane.hip's finish kernel, same state layout)
+//                        state in HBM (r3d_sums_dev.h's finish and state update, as in r3d_plane.hip)
 // No atomics: bitwise repeatable.  No search structure, no sort, no index: the association is one projection and one gather.
 #include <cmath>
 
-#include "r3d_icp_sums.h"
 #include "r3d_internal.h"
 #include "r3d_plane_sums.h"
 #include "r3d_tsdf_dev.h"
 
 namespace {
 
-constexpr int kThreads = r3d_plane::kThreads;
+constexpr int kThreads = r3d_sums::kThreads;
 constexpr int kPerLane = 4;
 constexpr int kTile = kThreads * kPerLane;   // pixels per workgroup: part of the specification
 using r3d_plane::kSums;
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(kThreads) void track_kernel(const float* __restrict
       double v = 0.0;
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
-        const double t = state ? state[r3d_icp::kStateTTotal + 4 * r + m] : (r == m ? 1.0 : 0.0);
+        const double t = state ? state[r3d_sums::kStateTTotal + 4 * r + m] : (r == m ? 1.0 : 0.0);
         v += t * a.s[4 * m + c];
       }
       M[4 * r + c] = v;
@@ -124,59 +124,16 @@ __global__ __launch_bounds__(kThreads) void track_kernel(const float* __restrict
     if (match_out) match_out[i] = code;
     if (residual_out) residual_out[i] = code >= 0 ? (float)r : 0.0f;
   }
-  r3d_plane::block_reduce_store(acc, red, partials + (int64_t)blockIdx.x * kSums);
+  r3d_sums::block_reduce_store<kSums>(acc, red, partials + (int64_t)blockIdx.x * kSums);
 }
 
-// One thread: step from the sums; T_total <- step . T_total; history.  The arithmetic of r3d_plane.hip's plane_solve_step, so
-// that this loop's state means what the other loops' states mean (a degenerate step is the identity: T_total stays).
-__device__ void track_solve_step(const double* s, double* __restrict__ st) {
-  double T[16], rms = 0.0;
-  const int bad = r3d_plane::step_from_sums(s, T, &rms);
-  double tot[16], nt[16];
-  for (int k = 0; k < 16; ++k) tot[k] = st[r3d_icp::kStateTTotal + k];
-  for (int r = 0; r < 4; ++r)
-    for (int c = 0; c < 4; ++c) {
-      double v = 0.0;
-      for (int m = 0; m < 4; ++m) v += T[4 * r + m] * tot[4 * m + c];
-      nt[4 * r + c] = v;
-    }
-  for (int k = 0; k < 16; ++k) {
-    st[r3d_icp::kStateTStep + k] = T[k];
-    st[r3d_icp::kStateTTotal + k] = nt[k];
-  }
-  const int it = (int)st[r3d_icp::kStateIters];
-  if (r3d_icp::kStateHistory + it < r3d_icp::kStateDoubles) st[r3d_icp::kStateHistory + it] = rms;
-  st[r3d_icp::kStateIters] = (double)(it + 1);
-  if (bad) st[r3d_icp::kStateStatus] = 1.0;
-  st[r3d_icp::kStateRms] = rms;
-  st[r3d_icp::kStatePairs] = s[0];
-}
-
+// ONE workgroup (r3d_sums::finish_rows): partial rows -> the 29 sums -> optionally the point-to-plane step and the ICP state.
+// The state update is the one every loop shares, so this loop's state means what theirs mean (a degenerate step is the
+// identity: T_total stays).
 __global__ __launch_bounds__(kThreads) void track_finish_kernel(const double* __restrict__ partials, int n_rows,
                                                                 double* __restrict__ sums_out, double* __restrict__ state) {
-  __shared__ double red[kThreads / 64][kSums];
-  __shared__ double total[kSums];
-  double acc[kSums];
-#pragma unroll
-  for (int k = 0; k < kSums; ++k) acc[k] = 0.0;
-  for (int b = threadIdx.x; b < n_rows; b += kThreads) {
-#pragma unroll
-    for (int k = 0; k < kSums; ++k) acc[k] += partials[(int64_t)b * kSums + k];
-  }
-  r3d_plane::block_reduce_store(acc, red, total);
-  __syncthreads();
-  if (threadIdx.x < kSums && sums_out) sums_out[threadIdx.x] = total[threadIdx.x];
-  if (threadIdx.x == 0 && state != nullptr) {
-    double s[kSums];
-    for (int k = 0; k < kSums; ++k) s[k] = total[k];
-    track_solve_step(s, state);
-  }
-}
-
-bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-  if (!a || !b || !a_bytes || !b_bytes) return false;
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+  r3d_sums::finish_rows<kSums>(partials, n_rows, sums_out, state,
+                               [](const double* s, double* T, double* rms) { return r3d_plane::step_from_sums(s, T, rms); });
 }
 
 struct Maps {
@@ -212,8 +169,8 @@ int output_checks(const TrackParams& p, const Maps& m, const void* const* outs, 
   const size_t map = (size_t)p.n_px * 12;
   const void* in[4] = {m.src_vertex, m.src_normal, m.model_vertex, m.model_normal};
   for (int a = 0; a < n_outs; ++a) {
-    for (int b = 0; b < 4; ++b) R3D_REQUIRE(!overlap(outs[a], out_bytes[a], in[b], map), "an output overlaps an input map");
-    for (int b = a + 1; b < n_outs; ++b) R3D_REQUIRE(!overlap(outs[a], out_bytes[a], outs[b], out_bytes[b]), "outputs overlap each other");
+    for (int b = 0; b < 4; ++b) R3D_REQUIRE(!r3d_ranges_overlap(outs[a], out_bytes[a], in[b], map), "an output overlaps an input map");
+    for (int b = a + 1; b < n_outs; ++b) R3D_REQUIRE(!r3d_ranges_overlap(outs[a], out_bytes[a], outs[b], out_bytes[b]), "outputs overlap each other");
   }
   return R3D_OK;
 }
@@ -302,9 +259,9 @@ int r3d_tsdf_track(r3d_tsdf* vol, const r3d_camera* cam, const void* d_depth, in
   int rc = r3d_tsdf_integrate_checks(vol, cam, d_depth, depth_dtype, 1, depth_scale, h_pose_guess_w2c);
   if (rc) return rc;
   R3D_REQUIRE(h_pose_out && h_info_out, "NULL output pointer");
-  R3D_REQUIRE(!overlap(h_pose_out, 12 * sizeof(double), h_info_out, 4 * sizeof(double)) &&
-                  !overlap(h_pose_out, 12 * sizeof(double), h_pose_guess_w2c, 12 * sizeof(double)) &&
-                  !overlap(h_info_out, 4 * sizeof(double), h_pose_guess_w2c, 12 * sizeof(double)),
+  R3D_REQUIRE(!r3d_ranges_overlap(h_pose_out, 12 * sizeof(double), h_info_out, 4 * sizeof(double)) &&
+                  !r3d_ranges_overlap(h_pose_out, 12 * sizeof(double), h_pose_guess_w2c, 12 * sizeof(double)) &&
+                  !r3d_ranges_overlap(h_info_out, 4 * sizeof(double), h_pose_guess_w2c, 12 * sizeof(double)),
               "an output overlaps the guess or the other output");
   R3D_REQUIRE(max_jump >= 0.f, "max_jump must be >= 0");
   R3D_REQUIRE(n_iters >= 0 && n_iters <= kMaxIters, "n_iters must be in [0, %d]", kMaxIters);
@@ -343,10 +300,10 @@ int r3d_tsdf_track(r3d_tsdf* vol, const r3d_camera* cam, const void* d_depth, in
   if ((rc = r3d_icp_state_reset(ctx, d_state))) return rc;
   const Maps m = {src_vertex, gate ? src_normal : nullptr, model_vertex, model_normal};
   if (n_iters > 0 && (rc = iterate_impl(ctx, p, m, n_iters, d_state))) return rc;
-  double st[r3d_icp::kStatePairs + 1];
+  double st[r3d_sums::kStatePairs + 1];
   R3D_HIP(hipMemcpyAsync(st, d_state, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
   R3D_HIP(hipStreamSynchronize(ctx->stream));
-  const bool bad = st[r3d_icp::kStateStatus] != 0.0;
+  const bool bad = st[r3d_sums::kStateStatus] != 0.0;
   if (bad) {
     for (int k = 0; k < 12; ++k) h_pose_out[k] = G[k];   // a degenerate step: the guess comes back as it was given
   } else {
@@ -354,7 +311,7 @@ int r3d_tsdf_track(r3d_tsdf* vol, const r3d_camera* cam, const void* d_depth, in
     for (int r = 0; r < 4; ++r)
       for (int cc = 0; cc < 4; ++cc) {
         double v = 0.0;
-        for (int k = 0; k < 4; ++k) v += st[r3d_icp::kStateTTotal + 4 * r + k] * S[4 * k + cc];
+        for (int k = 0; k < 4; ++k) v += st[r3d_sums::kStateTTotal + 4 * r + k] * S[4 * k + cc];
         M[4 * r + cc] = v;
       }
     for (int a = 0; a < 3; ++a) {
@@ -362,10 +319,10 @@ int r3d_tsdf_track(r3d_tsdf* vol, const r3d_camera* cam, const void* d_depth, in
       h_pose_out[9 + a] = -((M[a] * M[3] + M[4 + a] * M[7]) + M[8 + a] * M[11]);
     }
   }
-  h_info_out[0] = st[r3d_icp::kStatePairs];
-  h_info_out[1] = st[r3d_icp::kStateRms];
+  h_info_out[0] = st[r3d_sums::kStatePairs];
+  h_info_out[1] = st[r3d_sums::kStateRms];
   h_info_out[2] = bad ? 1.0 : 0.0;
-  h_info_out[3] = st[r3d_icp::kStateIters];
+  h_info_out[3] = st[r3d_sums::kStateIters];
   return R3D_OK;
 }
 

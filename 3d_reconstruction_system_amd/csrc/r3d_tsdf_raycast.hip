@@ -155,11 +155,6 @@ __global__ __launch_bounds__(kThreads) void tsdf_raycast_kernel(const float2* __
   }
 }
 
-bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a && b && na && nb && a0 < b0 + nb && b0 < a0 + na;
-}
-
 }  // namespace
 
 int r3d_tsdf_raycast(r3d_tsdf* v, const r3d_camera* cam, int n_views, const double* h_pose_w2c, double min_weight, double step,
@@ -201,8 +196,8 @@ int r3d_tsdf_raycast(r3d_tsdf* v, const r3d_camera* cam, int n_views, const doub
     size_t bytes;
   } out[3] = {{d_depth_out, map}, {d_vertex_out, 3 * map}, {d_normal_out, 3 * map}};
   for (int a = 0; a < 3; ++a) {
-    R3D_REQUIRE(!ranges_overlap(out[a].p, out[a].bytes, vol, (size_t)n * sizeof(float2)), "an output overlaps the volume");
-    for (int b = a + 1; b < 3; ++b) R3D_REQUIRE(!ranges_overlap(out[a].p, out[a].bytes, out[b].p, out[b].bytes), "outputs overlap each other");
+    R3D_REQUIRE(!r3d_ranges_overlap(out[a].p, out[a].bytes, vol, (size_t)n * sizeof(float2)), "an output overlaps the volume");
+    for (int b = a + 1; b < 3; ++b) R3D_REQUIRE(!r3d_ranges_overlap(out[a].p, out[a].bytes, out[b].p, out[b].bytes), "outputs overlap each other");
   }
   if ((!d_depth_out && !d_vertex_out && !d_normal_out) || c.frame_px == 0) return R3D_OK;
   if ((rc = r3d_ctx_enter(ctx))) return rc;

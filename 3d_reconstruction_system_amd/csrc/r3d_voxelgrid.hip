@@ -303,12 +303,6 @@ __global__ __launch_bounds__(kThreads) void grid_rows_kernel(const uint64_t* __r
   }
 }
 
-bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-  if (!a || !b || !a_bytes || !b_bytes) return false;
-  const uintptr_t alo = (uintptr_t)a, blo = (uintptr_t)b;
-  return alo < blo + b_bytes && blo < alo + a_bytes;
-}
-
 }  // namespace
 
 extern "C" {
@@ -454,7 +448,7 @@ int r3d_voxelgrid_extract(r3d_voxelgrid* vg, float* d_xyz_out, uint32_t* d_rgba_
   const void* out[4] = {d_xyz_out, d_rgba_out, d_count_out, d_codes_out};
   const size_t bytes[4] = {(size_t)n * 12, (size_t)n * 4, (size_t)n * 4, (size_t)n * 8};
   for (int a = 0; a < 4; ++a)
-    for (int b = a + 1; b < 4; ++b) R3D_REQUIRE(!ranges_overlap(out[a], bytes[a], out[b], bytes[b]), "output ranges overlap");
+    for (int b = a + 1; b < 4; ++b) R3D_REQUIRE(!r3d_ranges_overlap(out[a], bytes[a], out[b], bytes[b]), "output ranges overlap");
   if (n == 0) return R3D_OK;
   uint64_t* d_codes = nullptr;
   if ((rc = r3d_voxel_table_sorted_codes(vg->ctx, vg->d_table, vg->capacity, vg->d_counters, n, &d_codes))) return rc;

@@ -257,7 +257,7 @@ def main():
     manifest = {}
     for root, _, files in os.walk(HERE):
         for fn in sorted(files):
-            if fn in ("MANIFEST.json", "make_golden.py") or fn.endswith(".pyc"):
+            if fn in ("MANIFEST.json", "make_golden.py", "make_sums_bits.py") or fn.endswith(".pyc"):
                 continue
             p = os.path.join(root, fn)
             manifest[os.path.relpath(p, HERE)] = sha256_file(p)
