@@ -139,7 +139,8 @@ R3D_HD inline double det3(const double M[9]) {
 }
 
 // T (row-major 4x4) = [sR t; 0 1] minimising sum w |q - (s R p + t)|^2 from the 18 sums (Umeyama, PAMI 13(4) 1991).
-// Returns 0, or 1 when the fit is undefined (weight sum < 3 or no spread in p): T is then the identity.
+// Returns 0, or 1 when the fit is undefined (weight sum < 3, no spread in p, or sums from which no finite T follows): T is
+// then the identity.
 // *rms_out (optional) = sqrt(sum w |p-q|^2 / sum w) of the pairs as they stand.
 R3D_HD inline int umeyama_from_sums(const double s[kSums], int with_scale, double T[16], double* rms_out) {
   for (int k = 0; k < 16; ++k) T[k] = (k % 5 == 0) ? 1.0 : 0.0;
@@ -171,6 +172,14 @@ R3D_HD inline int umeyama_from_sums(const double s[kSums], int with_scale, doubl
   for (int r = 0; r < 3; ++r) {
     for (int c = 0; c < 3; ++c) T[4 * r + c] = scale * R[3 * r + c];
     T[4 * r + 3] = mq[r] - scale * (R[3 * r + 0] * mp[0] + R[3 * r + 1] * mp[1] + R[3 * r + 2] * mp[2]);
+  }
+  // sums that carry a NaN / inf among the q or cross terms pass every test above (with_scale == 0 has no scale test at all):
+  // a step that is not finite is no step
+  double chk = 0.0;
+  for (int k = 0; k < 12; ++k) chk += fabs(T[k]);
+  if (!(chk < INFINITY)) {
+    for (int k = 0; k < 16; ++k) T[k] = (k % 5 == 0) ? 1.0 : 0.0;
+    return 1;
   }
   return 0;
 }

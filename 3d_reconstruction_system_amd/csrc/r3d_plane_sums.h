@@ -48,7 +48,7 @@ __device__ __forceinline__ void pair_accumulate(double acc[kSums], double w, con
 
 // T (row-major 4x4, rigid) from the 29 sums.  Returns 0, or 1 when the step is undefined (fewer than 6 pairs, or the
 // normal equations are singular to working precision: the matched normals do not constrain all six freedoms -- one
-// plane, two parallel walls, ...): T is then the identity.  *rms_out (optional) = sqrt(sum w r^2 / sum w).
+// plane, two parallel walls, ..., or no finite T follows from the sums): T is then the identity.  *rms_out (optional) = sqrt(sum w r^2 / sum w).
 R3D_HD inline int step_from_sums(const double s[kSums], double T[16], double* rms_out) {
   for (int k = 0; k < 16; ++k) T[k] = (k % 5 == 0) ? 1.0 : 0.0;
   const double n = s[0];
@@ -120,6 +120,13 @@ R3D_HD inline int step_from_sums(const double s[kSums], double T[16], double* rm
   for (int r = 0; r < 3; ++r) {
     for (int c = 0; c < 3; ++c) T[4 * r + c] = (r == c ? 1.0 : 0.0) + a_ * K[3 * r + c] + b_ * K2[3 * r + c];
     T[4 * r + 3] = x[3 + r];
+  }
+  // a finite omega beyond 1e154 passes the test above and overflows th2 (sin(inf) is NaN): a step that is not finite is no step
+  double chk = 0.0;
+  for (int k = 0; k < 12; ++k) chk += fabs(T[k]);
+  if (!(chk < INFINITY)) {
+    for (int k = 0; k < 16; ++k) T[k] = (k % 5 == 0) ? 1.0 : 0.0;
+    return 1;
   }
   return 0;
 }

@@ -252,12 +252,18 @@ int r3d_icp_accumulate(r3d_ctx* ctx, const float* d_src, int64_t n_src, const fl
 /* Closed-form similarity from the 18 sums (Umeyama 1991): h_T (16 doubles, row-major 4x4) = [sR t; 0 1] minimising
  * sum w |q - (sRp + t)|^2; with_scale = 0 pins s = 1.  h_rms_out (optional) = sqrt(sum w|p-q|^2 / sum w) before the
  * step.  Pure host arithmetic (3x3 one-sided Jacobi SVD, fp64), no GPU needed -- and the very code the device-side
- * solve runs.  R3D_ERR_INVALID when the fit is undefined (weight sum < 3, no spread). */
+ * solve runs.  R3D_ERR_INVALID (h_T = identity) when the fit is undefined: weight sum < 3, no spread, or sums -- a NaN / inf
+ * among them -- from which no finite T follows. */
 int r3d_umeyama_from_sums(const double* h_sums, int with_scale, double* h_T, double* h_rms_out);
 /* Device-resident ICP state: R3D_ICP_STATE_DOUBLES doubles in HBM.
  *   [0..15] T_total (row-major 4x4, maps the ORIGINAL source onto the target), [16..31] the last step,
  *   [32] steps solved, [33] status (1 = some step was degenerate and skipped), [34] rms seen by the last step,
- *   [35] its weight sum, [48+k] rms seen by step k (while it fits). */
+ *   [35] its weight sum, [36..47] reserved (zero after a reset, never written), [48+k] rms seen by step k for k < 464.
+ * A degenerate step counts like any other: [32] goes up, its rms and weight go to [34] / [35] and its rms into the history;
+ * the step is the identity, T_total keeps its bits, and [33] stays 1 until the next reset (later good steps still compose
+ * onto T_total).  r3d_icp_iterate and r3d_icp_iterate_plane take any number of steps: past 464 the history is full and is
+ * left as it is while [32], [34] and [35] go on ([32] is then larger than the number of history entries);
+ * r3d_track_iterate refuses a call of more than 464 iterations. */
 #define R3D_ICP_STATE_DOUBLES 512
 #define R3D_ICP_STATE_HISTORY 48
 int r3d_icp_state_reset(r3d_ctx* ctx, double* d_state);
