@@ -150,13 +150,15 @@ __device__ __forceinline__ void emit_points(const float2* __restrict__ vol, cons
   }
 }
 
+// an interpolated channel mean as a byte: rounded half up and clamped
+__device__ __forceinline__ uint32_t color_byte(float m) { return (uint32_t)fminf(fmaxf(floorf(m + 0.5f), 0.0f), 255.0f); }
+
 // One channel of a surface point's colour ("TSDF colour"): the two voxels' mean colours, interpolated like the position, rounded
 // half up and clamped to a byte.  n == 0 gives a mean of 0 (a valid voxel has n >= 1).
 __device__ __forceinline__ uint32_t color_channel(uint32_t sum_v, uint32_t n_v, uint32_t sum_u, uint32_t n_u, float r) {
   const float mv = n_v ? (float)sum_v / (float)n_v : 0.0f;
   const float mu = n_u ? (float)sum_u / (float)n_u : 0.0f;
-  const float m = mv + r * (mu - mv);
-  return (uint32_t)fminf(fmaxf(floorf(m + 0.5f), 0.0f), 255.0f);
+  return color_byte(mv + r * (mu - mv));
 }
 
 // emit_points' sibling: the colour words r | g << 8 | b << 16 of the same crossings, to the same rows under the same at < cap rule
@@ -177,12 +179,14 @@ __device__ __forceinline__ void emit_colors(const float2* __restrict__ vol, cons
 }
 
 // The eight voxels of the cell whose corner 0 is voxel i (which has a neighbour on every + side): q[k], k = dx + 2 dy + 4 dz, the
-// mesh's corner numbering.  {tsdf, weight} of a voxel is one 8-byte load; the x pair of a row is 16 contiguous bytes.
-__device__ __forceinline__ void load_cell(const float2* __restrict__ vol, const TsdfGrid& g, int64_t i, float2 (&q)[8]) {
+// mesh's corner numbering.  {tsdf, weight} of a voxel is one 8-byte load; the x pair of a row is 16 contiguous bytes.  With V =
+// uint4 and the colour plane: the same corners' colour records, one 16-byte load each.
+template <typename V>
+__device__ __forceinline__ void load_cell(const V* __restrict__ vol, const TsdfGrid& g, int64_t i, V (&q)[8]) {
   const int64_t sy = g.nx, sz = (int64_t)g.nx * g.ny;
 #pragma unroll
   for (int k = 0; k < 8; k += 2) {
-    const float2* row = vol + (i + (int64_t)((k >> 1) & 1) * sy + (int64_t)(k >> 2) * sz);
+    const V* row = vol + (i + (int64_t)((k >> 1) & 1) * sy + (int64_t)(k >> 2) * sz);
     q[k] = row[0];
     q[k + 1] = row[1];
   }

@@ -11,6 +11,13 @@
 //                         through scalar loads.  A lane leaves the march at its hit or when t_k > tmax; the loop counter is an
 //                         integer with a fixed bound, so a NaN ends a ray instead of spinning it.  The volume is only read.
 //                         No LDS, no atomics; every output word is written once, with vector stores.
+//                         <false> is that kernel and what r3d_tsdf_raycast launches: the flag removes every colour statement, and
+//                         its instructions are the ones it had before the flag existed (the body stays in the kernel: moved into
+//                         an inlined function it allocates its scalar registers differently).  <true>, for r3d_tsdf_raycast_rgb
+//                         ("TSDF ray-cast colour"), is the same ray through the same statements, so the three geometry maps are
+//                         the same bits.  At the hit it also gathers the cell's eight colour records -- eight 16-byte loads, all
+//                         issued before the first is used, once per ray and not per march step --, interpolates the three channel
+//                         means like the tsdf and stores three bytes (a tile row of 8 pixels is 24 contiguous bytes).
 #include "r3d_internal.h"
 #include "r3d_tsdf_dev.h"
 
@@ -36,9 +43,10 @@ struct RayMarch {
   float mw, s, t_near, t_far;
 };
 
-// The cell around p and the fractions inside it; false unless the cell exists and its eight voxels are valid.
+// The cell around p and the fractions inside it; false unless the cell exists and its eight voxels are valid.  cell: the linear
+// index of its corner 0.
 __device__ __forceinline__ bool sample_cell(const float2* __restrict__ vol, const TsdfGrid& g, float ivs, float mw, const float (&p)[3],
-                                            float (&T)[8], float (&f)[3]) {
+                                            float (&T)[8], float (&f)[3], int64_t& cell) {
   const float gx = (p[0] - g.ox) * ivs - 0.5f, gy = (p[1] - g.oy) * ivs - 0.5f, gz = (p[2] - g.oz) * ivs - 0.5f;
   const float ix = floorf(gx), iy = floorf(gy), iz = floorf(gz);
   if (!(ix >= 0.0f && ix <= (float)(g.nx - 2) && iy >= 0.0f && iy <= (float)(g.ny - 2) && iz >= 0.0f && iz <= (float)(g.nz - 2)))
@@ -47,7 +55,8 @@ __device__ __forceinline__ bool sample_cell(const float2* __restrict__ vol, cons
   if (x > g.nx - 2 || y > g.ny - 2 || z > g.nz - 2) return false;   // (float)(n - 2) rounded up: n > 2^24 + 2 only
   f[0] = gx - ix, f[1] = gy - iy, f[2] = gz - iz;
   float2 q[8];
-  load_cell(vol, g, ((int64_t)z * g.ny + y) * g.nx + x, q);
+  cell = ((int64_t)z * g.ny + y) * g.nx + x;
+  load_cell(vol, g, cell, q);
   bool ok = true;
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
@@ -66,11 +75,28 @@ __device__ __forceinline__ float cell_gradient(const float (&T)[8], int sa, int 
   return e0 + fc * (e1 - e0);
 }
 
-// grid: (tiles_x * tiles_y, 1, views of this launch); 256 threads = 2 x 2 waves of 8 x 8 pixels
-__global__ __launch_bounds__(kThreads) void tsdf_raycast_kernel(const float2* __restrict__ vol, TsdfGrid g, RayCam cam,
-                                                                const TsdfPoseRow* __restrict__ table, RayMarch m,
+// The colour of a hit ("TSDF ray-cast colour") from the colour records c[k] of the cell's corners: per channel the eight means
+// (0 where n == 0), interpolated like the tsdf, rounded half up and clamped to a byte
+__device__ __forceinline__ void cell_color(const uint4 (&c)[8], const float (&f)[3], uint8_t (&q)[3]) {
+  float M[3][8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const float n = (float)c[k].w;
+    M[0][k] = c[k].w ? (float)c[k].x / n : 0.0f;
+    M[1][k] = c[k].w ? (float)c[k].y / n : 0.0f;
+    M[2][k] = c[k].w ? (float)c[k].z / n : 0.0f;
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) q[a] = (uint8_t)color_byte(trilinear(M[a], f));
+}
+
+// grid: (tiles_x * tiles_y, 1, views of this launch); 256 threads = 2 x 2 waves of 8 x 8 pixels.  kColor: also the colour image,
+// from the colour plane col into rgb_out (both unused, and NULL, otherwise)
+template <bool kColor>
+__global__ __launch_bounds__(kThreads) void tsdf_raycast_kernel(const float2* __restrict__ vol, const uint4* __restrict__ col, TsdfGrid g,
+                                                                RayCam cam, const TsdfPoseRow* __restrict__ table, RayMarch m,
                                                                 float* __restrict__ depth_out, float* __restrict__ vertex_out,
-                                                                float* __restrict__ normal_out) {
+                                                                float* __restrict__ normal_out, uint8_t* __restrict__ rgb_out) {
   const uint32_t tile_y = blockIdx.x / cam.tiles_x, tile_x = blockIdx.x - tile_y * cam.tiles_x;
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const uint32_t ui = tile_x * kTile + (wave & 1) * 8 + (lane & 7);
@@ -106,6 +132,7 @@ __global__ __launch_bounds__(kThreads) void tsdf_raycast_kernel(const float2* __
 
   const float ivs = 1.0f / g.vs;
   float T[8], f[3], p[3];
+  int64_t cell = 0;
   bool hit = false;
   float tstar = 0.0f;
   if (alive) {
@@ -116,7 +143,7 @@ __global__ __launch_bounds__(kThreads) void tsdf_raycast_kernel(const float2* __
       if (!(t <= tmax)) break;
 #pragma unroll
       for (int a = 0; a < 3; ++a) p[a] = P.t[a] + t * dw[a];
-      const bool ok = sample_cell(vol, g, ivs, m.mw, p, T, f);
+      const bool ok = sample_cell(vol, g, ivs, m.mw, p, T, f, cell);
       const float B = ok ? trilinear(T, f) : 0.0f;
       if (prev_ok && ok && A > 0.0f && B <= 0.0f) {   // (prev_ok: k >= 1)
         const float r = A / (A - B);
@@ -130,11 +157,13 @@ __global__ __launch_bounds__(kThreads) void tsdf_raycast_kernel(const float2* __
   }
 
   float G[3] = {0.0f, 0.0f, 0.0f}, L = 0.0f;
+  uint4 c[8];   // (kColor) the colour records of the hit cell's corners
   if (hit) {
 #pragma unroll
     for (int a = 0; a < 3; ++a) p[a] = P.t[a] + tstar * dw[a];
-    hit = sample_cell(vol, g, ivs, m.mw, p, T, f);
+    hit = sample_cell(vol, g, ivs, m.mw, p, T, f, cell);
     if (hit) {
+      if constexpr (kColor) load_cell(col, g, cell, c);   // all eight in flight while the gradient is computed
       G[0] = cell_gradient(T, 1, 2, 4, f[1], f[2]);
       G[1] = cell_gradient(T, 2, 1, 4, f[0], f[2]);
       G[2] = cell_gradient(T, 4, 1, 2, f[0], f[1]);
@@ -153,12 +182,18 @@ __global__ __launch_bounds__(kThreads) void tsdf_raycast_kernel(const float2* __
 #pragma unroll
     for (int a = 0; a < 3; ++a) normal_out[3 * px + a] = hit ? G[a] / L : none;
   }
+  if constexpr (kColor) {
+    uint8_t q[3] = {0, 0, 0};   // a miss: depth 0 marks it, black is a legitimate colour
+    if (hit) cell_color(c, f, q);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) rgb_out[3 * px + a] = q[a];
+  }
 }
 
-}  // namespace
-
-int r3d_tsdf_raycast(r3d_tsdf* v, const r3d_camera* cam, int n_views, const double* h_pose_w2c, double min_weight, double step,
-                     double t_near, double t_far, float* d_depth_out, float* d_vertex_out, float* d_normal_out) {
+// Both entry points.  rgb_call: r3d_tsdf_raycast_rgb -- the volume must own the colour plane, whatever the pointers; with
+// d_rgb_out == NULL it launches the depth-only kernel, like r3d_tsdf_raycast.
+int raycast(r3d_tsdf* v, const r3d_camera* cam, int n_views, const double* h_pose_w2c, double min_weight, double step, double t_near,
+            double t_far, float* d_depth_out, float* d_vertex_out, float* d_normal_out, uint8_t* d_rgb_out, bool rgb_call) {
   R3D_REQUIRE(v != nullptr, "TSDF volume is NULL");
   R3D_REQUIRE(cam != nullptr, "camera is NULL");
   r3d_ctx* ctx = nullptr;
@@ -167,6 +202,11 @@ int r3d_tsdf_raycast(r3d_tsdf* v, const r3d_camera* cam, int n_views, const doub
   int64_t n = 0;
   int rc = r3d_tsdf_device_view(v, &ctx, &g, &vol, &n);
   if (rc) return rc;
+  uint4* col = nullptr;
+  if (rgb_call) {
+    if ((rc = r3d_tsdf_color_plane(v, &col))) return rc;
+    R3D_REQUIRE(col != nullptr, "the volume was created without colour (r3d_tsdf_create_rgb makes one with)");
+  }
   R3D_REQUIRE(cam->ctx == ctx, "the camera belongs to another context than the volume");
   R3D_REQUIRE(n_views >= 0, "n_views must be >= 0");
   RayMarch m;
@@ -194,14 +234,17 @@ int r3d_tsdf_raycast(r3d_tsdf* v, const r3d_camera* cam, int n_views, const doub
   const struct {
     const void* p;
     size_t bytes;
-  } out[3] = {{d_depth_out, map}, {d_vertex_out, 3 * map}, {d_normal_out, 3 * map}};
-  for (int a = 0; a < 3; ++a) {
+  } out[4] = {{d_depth_out, map}, {d_vertex_out, 3 * map}, {d_normal_out, 3 * map}, {d_rgb_out, (size_t)n_views * c.frame_px * 3}};
+  for (int a = 0; a < 4; ++a) {
     R3D_REQUIRE(!r3d_ranges_overlap(out[a].p, out[a].bytes, vol, (size_t)n * sizeof(float2)), "an output overlaps the volume");
-    for (int b = a + 1; b < 3; ++b) R3D_REQUIRE(!r3d_ranges_overlap(out[a].p, out[a].bytes, out[b].p, out[b].bytes), "outputs overlap each other");
+    // the colour plane is read only when there is a colour image to write
+    R3D_REQUIRE(!d_rgb_out || !r3d_ranges_overlap(out[a].p, out[a].bytes, col, (size_t)n * sizeof(uint4)),
+                "an output overlaps the colour plane");
+    for (int b = a + 1; b < 4; ++b) R3D_REQUIRE(!r3d_ranges_overlap(out[a].p, out[a].bytes, out[b].p, out[b].bytes), "outputs overlap each other");
   }
-  if ((!d_depth_out && !d_vertex_out && !d_normal_out) || c.frame_px == 0) return R3D_OK;
+  if ((!d_depth_out && !d_vertex_out && !d_normal_out && !d_rgb_out) || c.frame_px == 0) return R3D_OK;
   if ((rc = r3d_ctx_enter(ctx))) return rc;
-  for (int a = 0; a < 3; ++a)
+  for (int a = 0; a < 4; ++a)
     if (out[a].p) r3d_wrote(ctx, out[a].p, out[a].bytes);
   for (int lo = 0; lo < n_views; lo += kChunk) {
     const int nv = n_views - lo < kChunk ? n_views - lo : kChunk;
@@ -219,10 +262,28 @@ int r3d_tsdf_raycast(r3d_tsdf* v, const r3d_camera* cam, int n_views, const doub
     R3D_HIP(hipMemcpyAsync(d_rows, h, sizeof(TsdfPoseRow) * nv, hipMemcpyHostToDevice, ctx->stream));
     R3D_HIP(hipEventRecord(ev, ctx->stream));
     const size_t at = (size_t)lo * c.frame_px;
-    hipLaunchKernelGGL(tsdf_raycast_kernel, dim3(tiles, 1, (unsigned)nv), dim3(kThreads), 0, ctx->stream, vol, g, c,
-                       (const TsdfPoseRow*)d_rows, m, d_depth_out ? d_depth_out + at : nullptr,
-                       d_vertex_out ? d_vertex_out + 3 * at : nullptr, d_normal_out ? d_normal_out + 3 * at : nullptr);
+    float* depth = d_depth_out ? d_depth_out + at : nullptr;
+    float* vertex = d_vertex_out ? d_vertex_out + 3 * at : nullptr;
+    float* normal = d_normal_out ? d_normal_out + 3 * at : nullptr;
+    if (d_rgb_out)
+      hipLaunchKernelGGL(tsdf_raycast_kernel<true>, dim3(tiles, 1, (unsigned)nv), dim3(kThreads), 0, ctx->stream, vol, (const uint4*)col, g,
+                         c, (const TsdfPoseRow*)d_rows, m, depth, vertex, normal, d_rgb_out + 3 * at);
+    else
+      hipLaunchKernelGGL(tsdf_raycast_kernel<false>, dim3(tiles, 1, (unsigned)nv), dim3(kThreads), 0, ctx->stream, vol, (const uint4*)nullptr, g,
+                         c, (const TsdfPoseRow*)d_rows, m, depth, vertex, normal, (uint8_t*)nullptr);
     R3D_HIP(hipGetLastError());
   }
   return R3D_OK;
+}
+
+}  // namespace
+
+int r3d_tsdf_raycast(r3d_tsdf* v, const r3d_camera* cam, int n_views, const double* h_pose_w2c, double min_weight, double step,
+                     double t_near, double t_far, float* d_depth_out, float* d_vertex_out, float* d_normal_out) {
+  return raycast(v, cam, n_views, h_pose_w2c, min_weight, step, t_near, t_far, d_depth_out, d_vertex_out, d_normal_out, nullptr, false);
+}
+
+int r3d_tsdf_raycast_rgb(r3d_tsdf* v, const r3d_camera* cam, int n_views, const double* h_pose_w2c, double min_weight, double step,
+                         double t_near, double t_far, float* d_depth_out, float* d_vertex_out, float* d_normal_out, uint8_t* d_rgb_out) {
+  return raycast(v, cam, n_views, h_pose_w2c, min_weight, step, t_near, t_far, d_depth_out, d_vertex_out, d_normal_out, d_rgb_out, true);
 }

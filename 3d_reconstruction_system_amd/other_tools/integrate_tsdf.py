@@ -3,7 +3,7 @@
 truncated signed distance volume instead, and the volume's zero level set is written as oriented surface points.
 
     python integrate_tsdf.py --voxel-size S --trunc T [--origin X Y Z] [--dims NX NY NZ] [--margin M] [--min-weight W] [--mesh]
-                             [--raycast] [--color-dir DIR] [--track]
+                             [--raycast] [--color-dir DIR] [--raycast-color] [--track]
 
 Run from a directory holding ./camera_pose/image_colmap_simi_2.txt and ./depth/ (the inputs of camera_to_world.py; the same
 environment overrides apply: R3D_FX .. R3D_CY, R3D_POSE_SCALE, R3D_DEVICE).  Writes ./ply/tsdf_surface.ply: binary PLY, float
@@ -15,6 +15,9 @@ shades), and prints a second line "triangles M -> path".
 predicts (float32, 0 = no surface) to ./raycast/<frame name>.npy, and prints a further line "raycast F frames -> ./raycast/".
 --color-dir DIR reads the colour image DIR/<frame name> of every frame (the size of the depth maps), integrates colour with the
 depth and adds uchar red green blue to the vertices of both PLY files.
+--raycast-color (with --color-dir) also casts the colour image the model predicts from every pose of the pose file at the input
+rasters' size and writes it (uint8 [H,W,3], R, G, B; 0, 0, 0 = no surface) to ./raycast_color/<frame name>.npy, and prints a
+further line "raycast colour F frames -> ./raycast_color/".
 --track reconstructs from the depth maps and ONE pose: only the first row of the pose file is used (its names still list the
 frames).  A pose file that is missing or lists no frame gives the identity as the first pose and the files of ./depth/ in
 sorted order as the frames (--origin / --dims are then the caller's to choose around a camera at the origin).  Every later
@@ -38,6 +41,7 @@ POSE_FILE = './camera_pose/image_colmap_simi_2.txt'
 OUT_FILE = './ply/tsdf_surface.ply'
 MESH_FILE = './ply/tsdf_mesh.ply'
 RAYCAST_DIR = './raycast/'
+RAYCAST_COLOR_DIR = './raycast_color/'
 TRACKED_FILE = './camera_pose/image_colmap_simi_2_tracked.txt'
 
 
@@ -55,11 +59,16 @@ def parse_args(argv):
                    help="also ray-cast the volume from every pose and write the predicted depth to %s<frame name>.npy" % RAYCAST_DIR)
     p.add_argument("--color-dir", metavar="DIR", default=None,
                    help="integrate the colour images DIR/<frame name> too and write the colours into the PLY files")
+    p.add_argument("--raycast-color", action="store_true",
+                   help="with --color-dir: also ray-cast the colour image from every pose and write it to %s<frame name>.npy"
+                   % RAYCAST_COLOR_DIR)
     p.add_argument("--track", action="store_true",
                    help="use only the first pose of the pose file, estimate the others by tracking and write them to %s" % TRACKED_FILE)
     args = p.parse_args(argv)
     if args.track and args.color_dir is not None:
         p.error("--track takes depth maps only (not with --color-dir)")
+    if args.raycast_color and args.color_dir is None:
+        p.error("--raycast-color needs the colour images (--color-dir)")
     for name in ("voxel_size", "trunc", "min_weight"):
         v = getattr(args, name)
         if not (math.isfinite(v) and v > 0.0):
@@ -98,6 +107,26 @@ def raycast_depth(r3d, vol, quats, ts, shape, min_weight):
             n = min(chunk, len(table) - lo)
             vol.raycast_device(cam, n, table[lo:lo + n], buf.ptr, None, None, min_weight=min_weight)
             out[lo:lo + n] = buf.download(np.float32, n * h * w).reshape(n, h, w)
+    finally:
+        buf.free()
+    return out
+
+
+def raycast_color(r3d, vol, quats, ts, shape, min_weight):
+    """[F,H,W,3] uint8: the colour image the volume predicts at every pose -- that image alone (3 bytes per pixel), one launch's
+    worth of views at a time."""
+    import numpy as np
+    h, w = shape
+    table = r3d.poses_w2c(quats, ts)
+    cam = vol.ctx.camera(h, w, *_common.intrinsics())
+    out = np.empty((len(table), h, w, 3), np.uint8)
+    chunk = 32
+    buf = vol.ctx.alloc(max(min(chunk, len(table)) * h * w * 3, 16))
+    try:
+        for lo in range(0, len(table), chunk):
+            n = min(chunk, len(table) - lo)
+            vol.raycast_device(cam, n, table[lo:lo + n], None, None, None, min_weight=min_weight, d_rgb=buf.ptr)
+            out[lo:lo + n] = buf.download(np.uint8, n * h * w * 3).reshape(n, h, w, 3)
     finally:
         buf.free()
     return out
@@ -200,6 +229,7 @@ def main(argv=None):
         xyz, normals, colors = vol.extract_point_cloud(args.min_weight, with_colors=True)
         mesh = vol.extract_triangle_mesh(args.min_weight)[:3] + (colors,) if args.mesh else None   # the vertices are the points
     cast = raycast_depth(r3d, vol, quats, ts, depths.shape[-2:], args.min_weight) if args.raycast else None
+    cast_rgb = raycast_color(r3d, vol, quats, ts, depths.shape[-2:], args.min_weight) if args.raycast_color else None
     vol.close()
     _common.stamp("extract")
     os.makedirs(os.path.dirname(OUT_FILE), exist_ok=True)
@@ -215,6 +245,12 @@ def main(argv=None):
         for name, raster in zip(names, cast):
             np.save(os.path.join(RAYCAST_DIR, name + ".npy"), raster)
         print("raycast %d frames -> %s" % (len(names), RAYCAST_DIR))
+    if cast_rgb is not None:
+        import numpy as np
+        os.makedirs(RAYCAST_COLOR_DIR, exist_ok=True)
+        for name, image in zip(names, cast_rgb):
+            np.save(os.path.join(RAYCAST_COLOR_DIR, name + ".npy"), image)
+        print("raycast colour %d frames -> %s" % (len(names), RAYCAST_COLOR_DIR))
     if tracked is not None:
         os.makedirs(os.path.dirname(TRACKED_FILE), exist_ok=True)
         write_tracked(TRACKED_FILE, names, tracked, _common.pose_scale())

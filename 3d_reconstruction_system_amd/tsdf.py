@@ -3,7 +3,7 @@ level set comes back as oriented surface points or as an indexed triangle mesh o
 of a depth + pose pipeline expect (Open3D's UniformTSDFVolume; no parity with Open3D is claimed).  Where fuse_frames concatenates the frames' points, the volume averages
 overlapping frames.  A volume created with color=True also averages the frames' colour images and returns a colour with every
 surface point / mesh vertex.  track() finds the pose of a new depth frame against the model (tracking.py), so a volume can be
-built from depth frames and one pose.  Semantics: include/r3d.h (r3d_tsdf_*) and DESIGN.md sections 4.5i to 4.5m.
+built from depth frames and one pose.  Semantics: include/r3d.h (r3d_tsdf_*) and DESIGN.md sections 4.5i to 4.5n.
 
 The volume takes the inputs camera_to_world.py already has: [F,H,W] depth, one pose-file row per frame, a pinhole camera.  Its
 poses are WORLD -> CAMERA (p_cam = R p_w + t: the pose file's quaternion and t as they stand, poses_w2c), not the inverted table
@@ -289,28 +289,40 @@ class TSDFVolume:
                 b.free()
 
     def raycast_device(self, cam, n_views, poses_w2c, d_depth, d_vertex, d_normal, min_weight=1.0, step=None, t_near=0.0,
-                       t_far=math.inf):
+                       t_far=math.inf, d_rgb=None):
         """Ray-cast the volume from n_views poses (poses_w2c: [n_views,12] host rows, as integrate_device takes) through cam into
         d_depth ([n_views][H][W] float32) and d_vertex / d_normal ([n_views][H][W][3] float32, world coordinates) at raw device
         addresses; any of the three may be None.  A pixel without a surface has depth 0 and NaN vertex and normal rows.  step=None
         means voxel_size; step + voxel_size <= sdf_trunc keeps both samples that bracket the surface inside the untruncated band.
-        Asynchronous on the context's stream."""
+        d_rgb (a volume with colour): also the colour image, [n_views][H][W][3] uint8 R, G, B -- the hit cell's eight mean
+        colours, interpolated like the tsdf; 0, 0, 0 where there is no surface.  Asynchronous on the context's stream."""
+        if d_rgb is not None:
+            self._check_color(True, "d_rgb")
         n_views = int(n_views)
         if n_views < 0:
             raise ValueError("n_views must be >= 0, got %d" % n_views)
         table = _pose_rows(poses_w2c, n_views)
         s, tn, tf = _ray_range(step, t_near, t_far, self.voxel_size)
-        L.check(self.ctx.lib.r3d_tsdf_raycast(self.handle, cam.handle, n_views, table.ctypes.data, _positive_f32(min_weight, "min_weight"),
-                                              s, tn, tf, d_depth, d_vertex, d_normal))
+        mw = _positive_f32(min_weight, "min_weight")
+        if d_rgb is not None:
+            L.check(self.ctx.lib.r3d_tsdf_raycast_rgb(self.handle, cam.handle, n_views, table.ctypes.data, mw, s, tn, tf, d_depth, d_vertex,
+                                                      d_normal, d_rgb))
+            return
+        L.check(self.ctx.lib.r3d_tsdf_raycast(self.handle, cam.handle, n_views, table.ctypes.data, mw, s, tn, tf, d_depth, d_vertex, d_normal))
 
-    def raycast(self, quats_xyzw, ts, shape, intrinsics=REF_INTRINSICS, min_weight=1.0, step=None, t_near=0.0, t_far=math.inf):
+    def raycast(self, quats_xyzw, ts, shape, intrinsics=REF_INTRINSICS, min_weight=1.0, step=None, t_near=0.0, t_far=math.inf,
+                with_colors=False):
         """(depth [F,H,W], vertices [F,H,W,3], normals [F,H,W,3]) float32: what the volume predicts for a camera of `intrinsics`
         and shape = (H, W) at the pose-file rows (quats_xyzw, ts): z-depth, the surface point in the world and the normal towards
         the camera side, from a march along every pixel's ray in steps of `step` (None: voxel_size) between the distances t_near
         and t_far, over the cells whose eight voxels have at least min_weight frames.  A pixel without a surface has depth 0 ("no
         measurement": the raster integrates back as it is) and NaN vertex and normal rows.  step + voxel_size <= sdf_trunc keeps
         both samples that bracket the surface inside the untruncated band.  The hit rows of vertices / normals are a target cloud
-        with tgt_normals for icp_point_to_plane.  Synchronous."""
+        with tgt_normals for icp_point_to_plane.  with_colors (a volume with colour): a fourth array, rgb [F,H,W,3] uint8 R, G, B
+        -- the colour image the model predicts: the hit cell's eight mean colours, interpolated like the tsdf; 0, 0, 0 where
+        there is no surface (depth 0 marks it), so depth and rgb integrate back together.  Synchronous."""
+        if with_colors:
+            self._check_color(True, "with_colors")
         try:
             h, w = [int(v) for v in shape]
             exact = all(int(v) == v and not isinstance(v, bool) for v in shape)
@@ -323,16 +335,22 @@ class TSDFVolume:
         table = poses_w2c(quats_xyzw, ts)
         f = table.shape[0]
         if f == 0:
-            return np.zeros((0, h, w), np.float32), np.zeros((0, h, w, 3), np.float32), np.zeros((0, h, w, 3), np.float32)
+            empty = (np.zeros((0, h, w), np.float32), np.zeros((0, h, w, 3), np.float32), np.zeros((0, h, w, 3), np.float32))
+            return empty + (np.zeros((0, h, w, 3), np.uint8),) if with_colors else empty
         cam = self.ctx.camera(h, w, *intrinsics)
         n = f * h * w
-        d_depth, d_vtx, d_nrm = self.ctx.alloc(n * 4), self.ctx.alloc(n * 12), self.ctx.alloc(n * 12)
+        bufs = [self.ctx.alloc(n * 4), self.ctx.alloc(n * 12), self.ctx.alloc(n * 12)]
         try:
-            self.raycast_device(cam, f, table, d_depth.ptr, d_vtx.ptr, d_nrm.ptr, mw, step, t_near, t_far)
-            return (d_depth.download(np.float32, n).reshape(f, h, w), d_vtx.download(np.float32, 3 * n).reshape(f, h, w, 3),
-                    d_nrm.download(np.float32, 3 * n).reshape(f, h, w, 3))
+            if with_colors:
+                bufs.append(self.ctx.alloc(n * 3))
+            d_depth, d_vtx, d_nrm = bufs[:3]
+            self.raycast_device(cam, f, table, d_depth.ptr, d_vtx.ptr, d_nrm.ptr, mw, step, t_near, t_far,
+                                d_rgb=bufs[3].ptr if with_colors else None)
+            out = (d_depth.download(np.float32, n).reshape(f, h, w), d_vtx.download(np.float32, 3 * n).reshape(f, h, w, 3),
+                   d_nrm.download(np.float32, 3 * n).reshape(f, h, w, 3))
+            return out + (bufs[3].download(np.uint8, 3 * n).reshape(f, h, w, 3),) if with_colors else out
         finally:
-            for b in (d_depth, d_vtx, d_nrm):
+            for b in bufs:
                 b.free()
 
     def _track_args(self, n_iters, dist_max, max_angle_deg, max_jump, min_weight, step, t_near, t_far):

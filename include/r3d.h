@@ -797,6 +797,30 @@ int r3d_tsdf_integrate_rgb_host(r3d_tsdf* vol, const r3d_camera* cam, const void
 int r3d_tsdf_colors(r3d_tsdf* vol, uint32_t** d_sums_out, int64_t* n_voxels_out);
 int r3d_tsdf_extract_colors(r3d_tsdf* vol, double min_weight, uint32_t* d_rgba_out, int64_t cap, int64_t* n_out);
 
+/* ---- TSDF ray-cast colour (csrc/r3d_tsdf_raycast.hip; the colour image a volume with colour predicts for a pose, next to the three
+ * maps of "TSDF ray casting"; this text is the specification).  r3d_tsdf_raycast_rgb is r3d_tsdf_raycast with a fourth output: the
+ * ray, the slab test, the march, the hit and the hit-point sample are the ones specified there, word for word, and d_depth_out,
+ * d_vertex_out and d_normal_out receive the same bits that call writes for the same arguments.  r3d_tsdf_raycast itself is as it
+ * was, on volumes with colour too.
+ * d_rgb_out: [n_views][H][W][3] uint8 in R, G, B order -- the layout r3d_tsdf_integrate_rgb takes, so a ray-cast image integrates
+ *   back together with its ray-cast depth.  A miss writes 0, 0, 0: the depth of 0 is what marks a miss, black is a legitimate colour.
+ * Colour of a hit: the cell i and the fractions f of the hit-point sample at t* (the sample the normal uses).  For each corner
+ *   k = jx + 2 jy + 4 jz of the cell and each channel, all f32, no fused multiply-add, correctly rounded division, uint32 -> f32
+ *   conversions rounding to nearest even:
+ *     M_k = (float) sum_k / (float) n_k           (0.0f where n_k == 0, as for the surface points)
+ *   interpolated in the order of the tsdf sample, x first, then y, then z, with M0 / M1 the means of the x pair:
+ *     c[jy][jz] = M0 + f_x * (M1 - M0);  b[jz] = c[0][jz] + f_y * (c[1][jz] - c[0][jz]);  m = b[0] + f_z * (b[1] - b[0])
+ *     q = fminf(fmaxf(floorf(m + 0.5f), 0.0f), 255.0f), stored as a byte.
+ *   Like the maps, it does not depend on launch geometry or on how the views are split into launches.
+ * Any of the four outputs may be NULL; with all four NULL the call is a valid no-op, and with d_rgb_out == NULL it does what
+ *   r3d_tsdf_raycast does.  Asynchronous on the ctx stream (same pose ring, R3D_TSDF_CHUNK views per launch).  The volume and its
+ *   colour plane are only read; no byte outside the outputs' extents is written.
+ * R3D_ERR_INVALID, nothing written: every argument error of r3d_tsdf_raycast; a volume without the colour plane, whatever the
+ *   pointers and n_views; d_rgb_out overlapping another output, the tsdf plane or the colour plane (and, when d_rgb_out is given,
+ *   any other output overlapping the colour plane). */
+int r3d_tsdf_raycast_rgb(r3d_tsdf* vol, const r3d_camera* cam, int n_views, const double* h_pose_w2c, double min_weight, double step,
+                         double t_near, double t_far, float* d_depth_out, float* d_vertex_out, float* d_normal_out, uint8_t* d_rgb_out);
+
 /* ---- TSDF tracking (csrc/r3d_track.hip; frame-to-model registration by PROJECTIVE point-to-plane ICP: the pose of a new depth
  * frame against the vertex and normal map the volume predicts -- the fourth leg of integrate / extract / ray cast / track; NOT IN
  * THE REFERENCE, this text is the specification).  The model maps are organised rasters, so the partner of a source point is one
