@@ -12,6 +12,8 @@
 //                        M, the model pose and the intrinsics are wave-uniform.  The only LDS is the reduction's.
 //   track_finish_kernel  ONE workgroup: partial rows in fixed order -> 29 sums -> Cholesky solve + exponential map -> the ICP
 //                        state in HBM (r3d_sums_dev.h's finish and state update, as in r3d_plane.hip)
+//   track_levels         host: the whole step for one frame -- r3d_tsdf_track (one level) and r3d_tsdf_track_pyramid (coarse to fine
+//                        over the depth pyramid of r3d_pyramid.hip, every level's model maps ray-cast at the guess) share it
 // No atomics: bitwise repeatable.  No search structure, no sort, no index: the association is one projection and one gather.
 #include <cmath>
 
@@ -206,6 +208,130 @@ int iterate_impl(r3d_ctx* ctx, const TrackParams& p, const Maps& m, int n_iters,
 
 constexpr int kMaxIters = R3D_ICP_STATE_DOUBLES - R3D_ICP_STATE_HISTORY;   // what the history holds
 
+// The whole step for one frame over n_levels pyramid levels, fine (0) to coarse; r3d_tsdf_track is the one-level case.  The
+// caller has checked that cams and iters hold n_levels entries (cams[0] may still be NULL: the volume's checks refuse it).
+int track_levels(r3d_tsdf* vol, const r3d_camera* const* cams, int n_levels, const int* iters, const void* d_depth, int depth_dtype,
+                 double depth_scale, const double* h_pose_guess_w2c, double min_weight, double step, double t_near, double t_far,
+                 float max_jump, double dist_max, double cos_min, double* h_pose_out, double* h_info_out, double* h_rms_out) {
+  int rc = r3d_tsdf_integrate_checks(vol, cams[0], d_depth, depth_dtype, 1, depth_scale, h_pose_guess_w2c);
+  if (rc) return rc;
+  R3D_REQUIRE(h_pose_out && h_info_out, "NULL output pointer");
+  R3D_REQUIRE(!r3d_ranges_overlap(h_pose_out, 12 * sizeof(double), h_info_out, 4 * sizeof(double)) &&
+                  !r3d_ranges_overlap(h_pose_out, 12 * sizeof(double), h_pose_guess_w2c, 12 * sizeof(double)) &&
+                  !r3d_ranges_overlap(h_info_out, 4 * sizeof(double), h_pose_guess_w2c, 12 * sizeof(double)),
+              "an output overlaps the guess or the other output");
+  R3D_REQUIRE(max_jump >= 0.f, "max_jump must be >= 0");
+  int64_t total = 0;
+  for (int l = 0; l < n_levels; ++l) {
+    R3D_REQUIRE(iters[l] >= 0, "the iteration count of level %d is negative", l);
+    total += iters[l];
+  }
+  R3D_REQUIRE(total <= kMaxIters, "the iteration counts must add up to at most %d", kMaxIters);
+  if (h_rms_out) {
+    const size_t rms_bytes = (size_t)total * sizeof(double);
+    R3D_REQUIRE(!r3d_ranges_overlap(h_rms_out, rms_bytes, h_pose_out, 12 * sizeof(double)) &&
+                    !r3d_ranges_overlap(h_rms_out, rms_bytes, h_info_out, 4 * sizeof(double)) &&
+                    !r3d_ranges_overlap(h_rms_out, rms_bytes, h_pose_guess_w2c, 12 * sizeof(double)) &&
+                    !r3d_ranges_overlap(h_rms_out, rms_bytes, iters, (size_t)n_levels * sizeof(int)) &&
+                    !r3d_ranges_overlap(h_rms_out, rms_bytes, cams, (size_t)n_levels * sizeof(*cams)),
+                "h_rms_out overlaps another host argument");
+  }
+  r3d_ctx* ctx = cams[0]->ctx;
+  const double* G = h_pose_guess_w2c;
+  for (int k = 0; k < 12; ++k) R3D_REQUIRE(std::isfinite(G[k]), "the pose guess must be finite");
+  // S = the inverse of the guess, in double: the transposed rotation and C_k = -((R[0][k] t0 + R[1][k] t1) + R[2][k] t2)
+  double S[16];
+  for (int a = 0; a < 3; ++a) {
+    for (int b = 0; b < 3; ++b) S[4 * a + b] = G[3 * b + a];
+    S[4 * a + 3] = -((G[a] * G[9] + G[3 + a] * G[10]) + G[6 + a] * G[11]);
+    S[12 + a] = 0.0;
+  }
+  S[15] = 1.0;
+  const bool gate = cos_min > -1.0;   // -1 admits every angle: the source normals are neither computed nor asked for
+  TrackParams p[R3D_TRACK_MAX_LEVELS];
+  for (int l = 0; l < n_levels; ++l) {   // the checks that need no buffer, before anything is enqueued
+    R3D_REQUIRE(cams[l] != nullptr, "the camera of level %d is NULL", l);
+    if (l > 0)
+      R3D_REQUIRE(cams[l]->height == cams[l - 1]->height >> 1 && cams[l]->width == cams[l - 1]->width >> 1,
+                  "the camera of level %d is %d x %d, half of level %d's %d x %d is %d x %d", l, cams[l]->height, cams[l]->width, l - 1,
+                  cams[l - 1]->height, cams[l - 1]->width, cams[l - 1]->height >> 1, cams[l - 1]->width >> 1);
+    const float dummy = 0.f;
+    const Maps probe = {&dummy, nullptr, &dummy, &dummy};
+    if ((rc = track_checks(ctx, cams[l], probe, G, S, dist_max, cos_min, &p[l]))) return rc;
+    // the ray cast's own argument checks, before anything is reserved: with no output it validates and does nothing else
+    if ((rc = r3d_tsdf_raycast(vol, cams[l], 1, G, min_weight, step, t_near, t_far, nullptr, nullptr, nullptr))) return rc;
+  }
+  if ((rc = r3d_ctx_enter(ctx))) return rc;
+  // every level's four maps, the depth rasters of the levels above 0 and the state: scratch slot 7 (the rank-trimming residuals'
+  // slot; nothing of that path runs in here).  A level has a quarter of the pixels of the one below: 4/3 of level 0's maps.
+  size_t map_at[R3D_TRACK_MAX_LEVELS], map[R3D_TRACK_MAX_LEVELS], depth_at[R3D_TRACK_MAX_LEVELS], bytes = 0;
+  for (int l = 0; l < n_levels; ++l) {
+    map[l] = ((size_t)p[l].n_px * 12 + 255) & ~(size_t)255;
+    map_at[l] = bytes;
+    bytes += 4 * map[l];
+  }
+  for (int l = 1; l < n_levels; ++l) {
+    depth_at[l] = bytes;
+    bytes += ((size_t)p[l].n_px * 4 + 255) & ~(size_t)255;
+  }
+  void* ws = nullptr;
+  if ((rc = r3d_scratch(ctx, 7, bytes + R3D_ICP_STATE_DOUBLES * sizeof(double), &ws))) return rc;
+  char* c = static_cast<char*>(ws);
+  double* d_state = reinterpret_cast<double*>(c + bytes);
+  double* rows = nullptr;
+  if ((rc = rows_workspace(ctx, n_tiles(p[0]), &rows))) return rc;   // the largest level's rows: the slot never grows mid-loop
+  Maps m[R3D_TRACK_MAX_LEVELS];
+  for (int l = 0; l < n_levels; ++l) {
+    char* base = c + map_at[l];
+    float *model_vertex = reinterpret_cast<float*>(base), *model_normal = reinterpret_cast<float*>(base + map[l]);
+    float *src_vertex = reinterpret_cast<float*>(base + 2 * map[l]), *src_normal = reinterpret_cast<float*>(base + 3 * map[l]);
+    const bool used = iters[l] > 0;
+    if (used && (rc = r3d_tsdf_raycast(vol, cams[l], 1, G, min_weight, step, t_near, t_far, nullptr, model_vertex, model_normal)))
+      return rc;
+    if (l == 0) {
+      if ((rc = r3d_unproject(ctx, cams[0], d_depth, depth_dtype, 1, depth_scale, src_vertex, R3D_F32))) return rc;
+    } else {
+      // the depth of the level below: level 0's is the z column of its vertex map, whatever dtype the frame came in
+      float* depth = reinterpret_cast<float*>(c + depth_at[l]);
+      const float* below = l == 1 ? m[0].src_vertex + 2 : reinterpret_cast<const float*>(c + depth_at[l - 1]);
+      if ((rc = r3d_depth_half(ctx, below, l == 1 ? 3 : 1, cams[l - 1]->height, cams[l - 1]->width, max_jump, depth))) return rc;
+      if (used && (rc = r3d_unproject(ctx, cams[l], depth, R3D_DEPTH_F32, 1, 1.0, src_vertex, R3D_F32))) return rc;
+    }
+    if (used && gate && (rc = r3d_normals_organized(ctx, src_vertex, 1, cams[l]->height, cams[l]->width, max_jump, nullptr, src_normal)))
+      return rc;
+    m[l] = {src_vertex, gate ? src_normal : nullptr, model_vertex, model_normal};
+  }
+  if ((rc = r3d_icp_state_reset(ctx, d_state))) return rc;
+  for (int l = n_levels - 1; l >= 0; --l)   // coarse to fine on the one state: T_total, the count and the rms history carry over
+    if (iters[l] > 0 && (rc = iterate_impl(ctx, p[l], m[l], iters[l], d_state))) return rc;
+  double st[R3D_ICP_STATE_DOUBLES];
+  const size_t n_read = h_rms_out ? (size_t)R3D_ICP_STATE_HISTORY + (size_t)total : (size_t)r3d_sums::kStatePairs + 1;
+  R3D_HIP(hipMemcpyAsync(st, d_state, n_read * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  R3D_HIP(hipStreamSynchronize(ctx->stream));
+  const bool bad = st[r3d_sums::kStateStatus] != 0.0;
+  if (bad) {
+    for (int k = 0; k < 12; ++k) h_pose_out[k] = G[k];   // a degenerate step: the guess comes back as it was given
+  } else {
+    double M[16];
+    for (int r = 0; r < 4; ++r)
+      for (int cc = 0; cc < 4; ++cc) {
+        double v = 0.0;
+        for (int k = 0; k < 4; ++k) v += st[r3d_sums::kStateTTotal + 4 * r + k] * S[4 * k + cc];
+        M[4 * r + cc] = v;
+      }
+    for (int a = 0; a < 3; ++a) {
+      for (int b = 0; b < 3; ++b) h_pose_out[3 * a + b] = M[4 * b + a];
+      h_pose_out[9 + a] = -((M[a] * M[3] + M[4 + a] * M[7]) + M[8 + a] * M[11]);
+    }
+  }
+  h_info_out[0] = st[r3d_sums::kStatePairs];
+  h_info_out[1] = st[r3d_sums::kStateRms];
+  h_info_out[2] = bad ? 1.0 : 0.0;
+  h_info_out[3] = st[r3d_sums::kStateIters];
+  for (int64_t k = 0; h_rms_out && k < total; ++k) h_rms_out[k] = st[R3D_ICP_STATE_HISTORY + k];
+  return R3D_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -256,74 +382,18 @@ int r3d_track_iterate(r3d_ctx* ctx, const r3d_camera* cam, const float* d_src_ve
 int r3d_tsdf_track(r3d_tsdf* vol, const r3d_camera* cam, const void* d_depth, int depth_dtype, double depth_scale,
                    const double* h_pose_guess_w2c, double min_weight, double step, double t_near, double t_far, float max_jump,
                    double dist_max, double cos_min, int n_iters, double* h_pose_out, double* h_info_out) {
-  int rc = r3d_tsdf_integrate_checks(vol, cam, d_depth, depth_dtype, 1, depth_scale, h_pose_guess_w2c);
-  if (rc) return rc;
-  R3D_REQUIRE(h_pose_out && h_info_out, "NULL output pointer");
-  R3D_REQUIRE(!r3d_ranges_overlap(h_pose_out, 12 * sizeof(double), h_info_out, 4 * sizeof(double)) &&
-                  !r3d_ranges_overlap(h_pose_out, 12 * sizeof(double), h_pose_guess_w2c, 12 * sizeof(double)) &&
-                  !r3d_ranges_overlap(h_info_out, 4 * sizeof(double), h_pose_guess_w2c, 12 * sizeof(double)),
-              "an output overlaps the guess or the other output");
-  R3D_REQUIRE(max_jump >= 0.f, "max_jump must be >= 0");
-  R3D_REQUIRE(n_iters >= 0 && n_iters <= kMaxIters, "n_iters must be in [0, %d]", kMaxIters);
-  r3d_ctx* ctx = cam->ctx;
-  const double* G = h_pose_guess_w2c;
-  for (int k = 0; k < 12; ++k) R3D_REQUIRE(std::isfinite(G[k]), "the pose guess must be finite");
-  // S = the inverse of the guess, in double: the transposed rotation and C_k = -((R[0][k] t0 + R[1][k] t1) + R[2][k] t2)
-  double S[16];
-  for (int a = 0; a < 3; ++a) {
-    for (int b = 0; b < 3; ++b) S[4 * a + b] = G[3 * b + a];
-    S[4 * a + 3] = -((G[a] * G[9] + G[3 + a] * G[10]) + G[6 + a] * G[11]);
-    S[12 + a] = 0.0;
-  }
-  S[15] = 1.0;
-  // the four maps and the state: scratch slot 7 (the rank-trimming residuals' slot; nothing of that path runs in here)
-  const size_t px = (size_t)cam->width * cam->height, map = (px * 12 + 255) & ~(size_t)255;
-  const bool gate = cos_min > -1.0;   // -1 admits every angle: the source normals are neither computed nor asked for
-  TrackParams p;
-  {   // the checks that need no buffer, before anything is enqueued
-    const float dummy = 0.f;
-    const Maps probe = {&dummy, nullptr, &dummy, &dummy};
-    if ((rc = track_checks(ctx, cam, probe, G, S, dist_max, cos_min, &p))) return rc;
-  }
-  // the ray cast's own argument checks, before anything is reserved: with no output it validates and does nothing else
-  if ((rc = r3d_tsdf_raycast(vol, cam, 1, G, min_weight, step, t_near, t_far, nullptr, nullptr, nullptr))) return rc;
-  if ((rc = r3d_ctx_enter(ctx))) return rc;
-  void* ws = nullptr;
-  if ((rc = r3d_scratch(ctx, 7, 4 * map + R3D_ICP_STATE_DOUBLES * sizeof(double), &ws))) return rc;
-  char* c = static_cast<char*>(ws);
-  float *model_vertex = reinterpret_cast<float*>(c), *model_normal = reinterpret_cast<float*>(c + map);
-  float *src_vertex = reinterpret_cast<float*>(c + 2 * map), *src_normal = reinterpret_cast<float*>(c + 3 * map);
-  double* d_state = reinterpret_cast<double*>(c + 4 * map);
-  if ((rc = r3d_tsdf_raycast(vol, cam, 1, G, min_weight, step, t_near, t_far, nullptr, model_vertex, model_normal))) return rc;
-  if ((rc = r3d_unproject(ctx, cam, d_depth, depth_dtype, 1, depth_scale, src_vertex, R3D_F32))) return rc;
-  if (gate && (rc = r3d_normals_organized(ctx, src_vertex, 1, cam->height, cam->width, max_jump, nullptr, src_normal))) return rc;
-  if ((rc = r3d_icp_state_reset(ctx, d_state))) return rc;
-  const Maps m = {src_vertex, gate ? src_normal : nullptr, model_vertex, model_normal};
-  if (n_iters > 0 && (rc = iterate_impl(ctx, p, m, n_iters, d_state))) return rc;
-  double st[r3d_sums::kStatePairs + 1];
-  R3D_HIP(hipMemcpyAsync(st, d_state, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
-  R3D_HIP(hipStreamSynchronize(ctx->stream));
-  const bool bad = st[r3d_sums::kStateStatus] != 0.0;
-  if (bad) {
-    for (int k = 0; k < 12; ++k) h_pose_out[k] = G[k];   // a degenerate step: the guess comes back as it was given
-  } else {
-    double M[16];
-    for (int r = 0; r < 4; ++r)
-      for (int cc = 0; cc < 4; ++cc) {
-        double v = 0.0;
-        for (int k = 0; k < 4; ++k) v += st[r3d_sums::kStateTTotal + 4 * r + k] * S[4 * k + cc];
-        M[4 * r + cc] = v;
-      }
-    for (int a = 0; a < 3; ++a) {
-      for (int b = 0; b < 3; ++b) h_pose_out[3 * a + b] = M[4 * b + a];
-      h_pose_out[9 + a] = -((M[a] * M[3] + M[4 + a] * M[7]) + M[8 + a] * M[11]);
-    }
-  }
-  h_info_out[0] = st[r3d_sums::kStatePairs];
-  h_info_out[1] = st[r3d_sums::kStateRms];
-  h_info_out[2] = bad ? 1.0 : 0.0;
-  h_info_out[3] = st[r3d_sums::kStateIters];
-  return R3D_OK;
+  return track_levels(vol, &cam, 1, &n_iters, d_depth, depth_dtype, depth_scale, h_pose_guess_w2c, min_weight, step, t_near, t_far,
+                      max_jump, dist_max, cos_min, h_pose_out, h_info_out, nullptr);
+}
+
+int r3d_tsdf_track_pyramid(r3d_tsdf* vol, const r3d_camera* const* cams, int n_levels, const int* h_iters, const void* d_depth,
+                           int depth_dtype, double depth_scale, const double* h_pose_guess_w2c, double min_weight, double step,
+                           double t_near, double t_far, float max_jump, double dist_max, double cos_min, double* h_pose_out,
+                           double* h_info_out, double* h_rms_out) {
+  R3D_REQUIRE(n_levels >= 1 && n_levels <= R3D_TRACK_MAX_LEVELS, "n_levels must be in [1, %d], got %d", R3D_TRACK_MAX_LEVELS, n_levels);
+  R3D_REQUIRE(cams != nullptr && h_iters != nullptr, "NULL cams or h_iters");
+  return track_levels(vol, cams, n_levels, h_iters, d_depth, depth_dtype, depth_scale, h_pose_guess_w2c, min_weight, step, t_near, t_far,
+                      max_jump, dist_max, cos_min, h_pose_out, h_info_out, h_rms_out);
 }
 
 }  // extern "C"

@@ -3,7 +3,7 @@
 truncated signed distance volume instead, and the volume's zero level set is written as oriented surface points.
 
     python integrate_tsdf.py --voxel-size S --trunc T [--origin X Y Z] [--dims NX NY NZ] [--margin M] [--min-weight W] [--mesh]
-                             [--raycast] [--color-dir DIR] [--raycast-color] [--track]
+                             [--raycast] [--color-dir DIR] [--raycast-color] [--track [--track-pyramid N0,N1,..]]
 
 Run from a directory holding ./camera_pose/image_colmap_simi_2.txt and ./depth/ (the inputs of camera_to_world.py; the same
 environment overrides apply: R3D_FX .. R3D_CY, R3D_POSE_SCALE, R3D_DEVICE).  Writes ./ply/tsdf_surface.ply: binary PLY, float
@@ -25,6 +25,8 @@ frame is tracked against the model from the previous frame's pose (projective po
 motions between frames) and integrated at the pose found.  The estimated poses are written to
 ./camera_pose/image_colmap_simi_2_tracked.txt in the pose file's own format, and a further line "tracked F frames -> path" is
 printed.  Without --origin / --dims the volume is then built around the first camera centre alone.  Not with --color-dir.
+--track-pyramid N0,N1,.. (with --track) tracks coarse to fine over a depth pyramid: N0 iterations at full size, N1 on the halved
+rasters and so on, e.g. 10,5,4; the coarse levels run first and let the loop follow larger motions between frames.
 """
 import argparse
 import math
@@ -64,7 +66,18 @@ def parse_args(argv):
                    % RAYCAST_COLOR_DIR)
     p.add_argument("--track", action="store_true",
                    help="use only the first pose of the pose file, estimate the others by tracking and write them to %s" % TRACKED_FILE)
+    p.add_argument("--track-pyramid", metavar="N0,N1,..", default=None,
+                   help="with --track: iterations per pyramid level, fine to coarse (e.g. 10,5,4): track coarse to fine")
     args = p.parse_args(argv)
+    if args.track_pyramid is not None:
+        if not args.track:
+            p.error("--track-pyramid needs --track")
+        try:
+            args.track_pyramid = [int(v) for v in args.track_pyramid.split(",")]
+        except ValueError:
+            p.error("--track-pyramid takes integers separated by commas, got %r" % args.track_pyramid)
+        if not 1 <= len(args.track_pyramid) <= 8 or min(args.track_pyramid) < 0:
+            p.error("--track-pyramid takes 1 to 8 iteration counts >= 0, got %r" % (args.track_pyramid,))
     if args.track and args.color_dir is not None:
         p.error("--track takes depth maps only (not with --color-dir)")
     if args.raycast_color and args.color_dir is None:
@@ -209,8 +222,8 @@ def main(argv=None):
         vol = r3d.TSDFVolume(origin, args.voxel_size, dims, args.trunc, ctx=_common.context())
         try:
             tracked = vol.track_and_integrate(depths, r3d.poses_w2c(quats[:1], ts[:1])[0], intrinsics=_common.intrinsics(),
-                                              min_weight=args.min_weight)
-        except RuntimeError as e:
+                                              min_weight=args.min_weight, pyramid_iters=args.track_pyramid)
+        except (RuntimeError, ValueError) as e:
             sys.exit("integrate_tsdf.py: --track: %s" % e)
         quats = [quat_xyzw(row[:9].reshape(3, 3)) for row in tracked]
         ts = tracked[:, 9:]

@@ -4,7 +4,8 @@ projection and one gather away -- no nearest-neighbour index.  Semantics: includ
 
 track_sums is one association pass from host arrays (the 29 sums of the point-to-plane step, the per-pixel match and residual);
 TrackDevice keeps the maps and the ICP state in HBM and runs whole iterations without a host round trip.  The whole step for one
-depth frame -- ray cast, unproject, normals, loop, pose -- is TSDFVolume.track.
+depth frame -- ray cast, unproject, normals, loop, pose -- is TSDFVolume.track; with pyramid_iters it runs coarse to fine over a
+depth pyramid (depth_half, pyramid_intrinsics, pyramid_shape: include/r3d.h "Depth pyramid").
 """
 import numpy as np
 
@@ -13,6 +14,75 @@ from .device import default_context
 from .icp import PLANE_SUMS, STATE_DOUBLES, STATE_HISTORY
 
 MAX_ITERS = STATE_DOUBLES - STATE_HISTORY   # what the state's history holds
+MAX_LEVELS = 8                              # R3D_TRACK_MAX_LEVELS
+
+
+def pyramid_intrinsics(K, level):
+    """(fx, fy, cx, cy) after `level` halvings of the raster (r3d_camera_half's arithmetic, in double): a coarse pixel u' stands
+    for the fine pixels 2 u' and 2 u' + 1, whose centre is 2 u' + 0.5, so fx' = 0.5 fx and cx' = 0.5 (cx - 0.5)."""
+    try:
+        fx, fy, cx, cy = [float(v) for v in K]
+    except (TypeError, ValueError):
+        raise ValueError("intrinsics must be (fx, fy, cx, cy), got %r" % (K,))
+    if isinstance(level, bool) or int(level) != level or level < 0:
+        raise ValueError("level must be an integer >= 0, got %r" % (level,))
+    for _ in range(int(level)):
+        fx, fy, cx, cy = 0.5 * fx, 0.5 * fy, 0.5 * (cx - 0.5), 0.5 * (cy - 0.5)
+    return fx, fy, cx, cy
+
+
+def pyramid_shape(h, w, level):
+    """(H, W) after `level` halvings: an odd last row or column is dropped each time."""
+    if isinstance(level, bool) or int(level) != level or level < 0:
+        raise ValueError("level must be an integer >= 0, got %r" % (level,))
+    return int(h) >> int(level), int(w) >> int(level)
+
+
+def pyramid_levels(pyramid_iters, h, w):
+    """The iteration counts of a coarse-to-fine call as a list of ints, fine to coarse; ValueError for an empty sequence, more
+    than MAX_LEVELS entries, a negative or non-integer entry, a sum over MAX_ITERS or an [h, w] raster too small to be halved
+    len - 1 times."""
+    try:
+        entries = list(pyramid_iters)
+    except TypeError:
+        raise ValueError("pyramid_iters must be a sequence of iteration counts, fine to coarse, got %r" % (pyramid_iters,))
+    if not 1 <= len(entries) <= MAX_LEVELS:
+        raise ValueError("pyramid_iters must have 1 to %d entries, got %d" % (MAX_LEVELS, len(entries)))
+    for v in entries:
+        if isinstance(v, (bool, str, bytes)) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v or v < 0:
+            raise ValueError("pyramid_iters must hold integers >= 0, got %r" % (v,))
+    entries = [int(v) for v in entries]
+    if sum(entries) > MAX_ITERS:
+        raise ValueError("pyramid_iters must add up to at most %d, got %d" % (MAX_ITERS, sum(entries)))
+    if min(pyramid_shape(h, w, len(entries) - 1)) < 1:
+        raise ValueError("a %d x %d raster cannot be halved %d times" % (h, w, len(entries) - 1))
+    return entries
+
+
+def depth_half(depth, max_jump, ctx=None):
+    """One pyramid level: the [H >> 1, W >> 1] float32 raster of a host [H,W] float32 depth raster.  Every output is the mean of
+    the valid (finite, > 0) depths of its 2 x 2 block that lie within max_jump of the block's nearest one -- foreground wins, no
+    depth is invented between two surfaces -- and 0 where the block has none.  max_jump >= 0, inf allowed."""
+    d = np.asarray(depth)
+    if d.dtype != np.float32 or d.ndim != 2 or d.shape[0] < 2 or d.shape[1] < 2:
+        raise ValueError("depth must be a float32 [H,W] raster of at least 2 x 2, got %s of shape %s" % (d.dtype, list(d.shape)))
+    try:
+        mj = float(max_jump)
+    except (TypeError, ValueError):
+        raise ValueError("max_jump must be a number >= 0, got %r" % (max_jump,))
+    if not mj >= 0.0:
+        raise ValueError("max_jump must be >= 0, got %r" % (max_jump,))
+    d = np.ascontiguousarray(d)
+    c = ctx or default_context()
+    h, w = d.shape
+    oh, ow = pyramid_shape(h, w, 1)
+    d_in, d_out = c.alloc(d.nbytes).upload(d), c.alloc(oh * ow * 4)
+    try:
+        L.check(c.lib.r3d_depth_half(c.handle, d_in.ptr, 1, h, w, mj, d_out.ptr))
+        return d_out.download(np.float32, oh * ow).reshape(oh, ow)
+    finally:
+        d_in.free()
+        d_out.free()
 
 
 def inverse_pose(pose_w2c):

@@ -3,7 +3,7 @@ level set comes back as oriented surface points or as an indexed triangle mesh o
 of a depth + pose pipeline expect (Open3D's UniformTSDFVolume; no parity with Open3D is claimed).  Where fuse_frames concatenates the frames' points, the volume averages
 overlapping frames.  A volume created with color=True also averages the frames' colour images and returns a colour with every
 surface point / mesh vertex.  track() finds the pose of a new depth frame against the model (tracking.py), so a volume can be
-built from depth frames and one pose.  Semantics: include/r3d.h (r3d_tsdf_*) and DESIGN.md sections 4.5i to 4.5n.
+built from depth frames and one pose.  Semantics: include/r3d.h (r3d_tsdf_*) and DESIGN.md sections 4.5i to 4.5o.
 
 The volume takes the inputs camera_to_world.py already has: [F,H,W] depth, one pose-file row per frame, a pinhole camera.  Its
 poses are WORLD -> CAMERA (p_cam = R p_w + t: the pose file's quaternion and t as they stand, poses_w2c), not the inverted table
@@ -379,20 +379,37 @@ class TSDFVolume:
         return int(n_iters), dm, cos_min, mj, _positive_f32(min_weight, "min_weight"), s, tn, tf
 
     def track_device(self, cam, d_depth, depth_dtype, pose_guess_w2c, n_iters=10, dist_max=None, max_angle_deg=None, depth_scale=1.0,
-                     max_jump=0.05, min_weight=1.0, step=None, t_near=0.0, t_far=math.inf):
+                     max_jump=0.05, min_weight=1.0, step=None, t_near=0.0, t_far=math.inf, pyramid_iters=None):
         """track() from a raster in HBM (d_depth: [H][W] of depth_dtype at a raw device address; cam: ctx.camera(...)).
         Synchronises (the pose is read back)."""
+        levels = None
+        if pyramid_iters is not None:
+            from .tracking import pyramid_levels
+            levels, n_iters = pyramid_levels(pyramid_iters, cam.height, cam.width), 0
         n, dm, cos_min, mj, mw, s, tn, tf = self._track_args(n_iters, dist_max, max_angle_deg, max_jump, min_weight, step, t_near, t_far)
         guess = _pose_rows(np.asarray(pose_guess_w2c, dtype=np.float64).reshape(1, -1), 1)
         if not np.isfinite(guess).all():
             raise ValueError("pose_guess_w2c must be finite")
         pose, info = np.zeros(12, dtype=np.float64), np.zeros(4, dtype=np.float64)
+        if levels is not None:
+            from .tracking import pyramid_intrinsics, pyramid_shape
+            K = (cam.fx, cam.fy, cam.cx, cam.cy)
+            cams = [cam] + [self.ctx.camera(*pyramid_shape(cam.height, cam.width, l), *pyramid_intrinsics(K, l))
+                            for l in range(1, len(levels))]
+            handles = (C.c_void_p * len(cams))(*[c.handle for c in cams])
+            iters = (C.c_int * len(levels))(*levels)
+            rms = np.zeros(max(sum(levels), 1), dtype=np.float64)
+            L.check(self.ctx.lib.r3d_tsdf_track_pyramid(self.handle, handles, len(cams), iters, d_depth, depth_code(depth_dtype),
+                                                        float(depth_scale), guess.ctypes.data, mw, s, tn, tf, mj, dm, cos_min,
+                                                        pose.ctypes.data, info.ctypes.data, rms.ctypes.data))
+            return pose, {"pairs": float(info[0]), "rms": float(info[1]), "status": int(info[2]), "iterations": int(info[3]),
+                          "rms_history": rms[:sum(levels)].tolist()}
         L.check(self.ctx.lib.r3d_tsdf_track(self.handle, cam.handle, d_depth, depth_code(depth_dtype), float(depth_scale),
                                             guess.ctypes.data, mw, s, tn, tf, mj, dm, cos_min, n, pose.ctypes.data, info.ctypes.data))
         return pose, {"pairs": float(info[0]), "rms": float(info[1]), "status": int(info[2]), "iterations": int(info[3])}
 
     def track(self, depth, pose_guess_w2c, intrinsics=REF_INTRINSICS, n_iters=10, dist_max=None, max_angle_deg=None, depth_scale=1.0,
-              max_jump=0.05, min_weight=1.0, step=None, t_near=0.0, t_far=math.inf):
+              max_jump=0.05, min_weight=1.0, step=None, t_near=0.0, t_far=math.inf, pyramid_iters=None):
         """The pose of a new depth raster [H,W] against the model, from a guess (12 doubles, world -> camera: R row-major, t --
         a row of poses_w2c): the volume is ray-cast at the guess, and n_iters iterations of projective point-to-plane ICP move
         the frame onto the predicted vertex and normal map (a source point's partner is the model pixel it projects to).
@@ -401,14 +418,22 @@ class TSDFVolume:
         guess.  info also has "pairs" and "rms" (of the plane residual) as the last step saw them, and "iterations".
         dist_max: pairs farther apart never take part (None: 2 x sdf_trunc).  max_angle_deg: pairs whose source and model
         normals differ by more are left out; None: no source normals are computed or gated.  max_jump: the depth-edge rule of
-        the source normals.  Small motions only: no image pyramid.  Synchronous."""
+        the source normals (and, with pyramid_iters, of the depth pyramid).  n_iters alone runs at full resolution: small
+        motions only.  pyramid_iters: a sequence of iteration counts, fine to coarse, e.g. (10, 5, 4): the loop runs coarse to
+        fine over a depth pyramid (every level halves the raster; the model is ray-cast at every level's camera) and follows
+        larger motions; n_iters is then not used, and info gains "rms_history", the rms of every step in the order they ran
+        (include/r3d.h "Depth pyramid").  Synchronous."""
         d = np.asarray(depth)
         if d.ndim != 2 or d.shape[0] < 1 or d.shape[1] < 1:
             raise ValueError("depth must be one [H,W] raster, got shape %s" % (list(d.shape),))
         if d.dtype not in (np.uint8, np.uint16, np.float32):
             raise ValueError("depth must be uint8, uint16 or float32, got %s" % d.dtype)
         d = np.ascontiguousarray(d)
-        self._track_args(n_iters, dist_max, max_angle_deg, max_jump, min_weight, step, t_near, t_far)   # raises before anything is allocated
+        if pyramid_iters is not None:
+            from .tracking import pyramid_levels
+            pyramid_levels(pyramid_iters, d.shape[0], d.shape[1])
+        self._track_args(0 if pyramid_iters is not None else n_iters, dist_max, max_angle_deg, max_jump, min_weight, step, t_near,
+                         t_far)   # raises before anything is allocated
         guess = np.asarray(pose_guess_w2c, dtype=np.float64)
         if guess.size != 12 or not np.isfinite(guess).all():
             raise ValueError("pose_guess_w2c must be 12 finite numbers (R row-major, t), got shape %s" % (list(guess.shape),))
@@ -416,15 +441,16 @@ class TSDFVolume:
         buf = self.ctx.alloc(d.nbytes).upload(d)
         try:
             return self.track_device(cam, buf.ptr, d.dtype, guess, n_iters, dist_max, max_angle_deg, depth_scale, max_jump, min_weight,
-                                     step, t_near, t_far)
+                                     step, t_near, t_far, pyramid_iters)
         finally:
             buf.free()
 
     def track_and_integrate(self, depths, first_pose_w2c, intrinsics=REF_INTRINSICS, depth_scale=1.0, **track_args):
         """Reconstruct from depth rasters [F,H,W] and ONE pose: frame 0 is integrated at first_pose_w2c (12 doubles, world ->
         camera); every later frame is tracked against the model from the previous frame's pose (track(); track_args are its
-        keyword arguments) and integrated at the pose found.  Returns the [F,12] float64 pose rows.  Raises RuntimeError when a
-        frame cannot be tracked (status 1); the frames before it stay integrated.  A volume without colour only."""
+        keyword arguments, pyramid_iters among them) and integrated at the pose found.  Returns the [F,12] float64 pose rows.
+        Raises RuntimeError when a frame cannot be tracked (status 1); the frames before it stay integrated.  A volume without
+        colour only."""
         if self.color:
             raise ValueError("track_and_integrate takes depth rasters only: the volume was created with color=True")
         if np.asarray(depths).dtype not in (np.uint8, np.uint16, np.float32):
@@ -434,7 +460,11 @@ class TSDFVolume:
         first = np.asarray(first_pose_w2c, dtype=np.float64)
         if first.size != 12 or not np.isfinite(first).all():
             raise ValueError("first_pose_w2c must be 12 finite numbers (R row-major, t), got shape %s" % (list(first.shape),))
-        self._track_args(track_args.get("n_iters", 10), track_args.get("dist_max"), track_args.get("max_angle_deg"),
+        if track_args.get("pyramid_iters") is not None:
+            from .tracking import pyramid_levels
+            pyramid_levels(track_args["pyramid_iters"], h, w)
+        self._track_args(0 if track_args.get("pyramid_iters") is not None else track_args.get("n_iters", 10),
+                         track_args.get("dist_max"), track_args.get("max_angle_deg"),
                          track_args.get("max_jump", 0.05), track_args.get("min_weight", 1.0), track_args.get("step"),
                          track_args.get("t_near", 0.0), track_args.get("t_far", math.inf))
         poses = np.zeros((f, 12), dtype=np.float64)

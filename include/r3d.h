@@ -875,7 +875,8 @@ int r3d_tsdf_raycast_rgb(r3d_tsdf* vol, const r3d_camera* cam, int n_views, cons
  *   NaN, n_iters < 0 or > R3D_ICP_STATE_DOUBLES - R3D_ICP_STATE_HISTORY (what the history holds), a device output overlapping an
  *   input map or another output (r3d_tsdf_track: a host output overlapping the guess or the other output), a raster of
  *   2^31 - 1024 pixels or more; r3d_tsdf_track also: a non-finite guess, max_jump < 0, and the argument errors of
- *   r3d_tsdf_integrate (depth) and r3d_tsdf_raycast.  Not done here: image pyramids / coarse-to-fine, photometric (colour) terms. */
+ *   r3d_tsdf_integrate (depth) and r3d_tsdf_raycast.  Coarse-to-fine passes over an image pyramid: r3d_tsdf_track_pyramid
+ *   ("Depth pyramid", below).  Not done here: photometric (colour) terms. */
 int r3d_track_accumulate(r3d_ctx* ctx, const r3d_camera* cam, const float* d_src_vertex, const float* d_src_normal,
                          const float* d_model_vertex, const float* d_model_normal, const double* h_model_pose_w2c, const double* h_S,
                          double dist_max, double cos_min, double* h_sums, int32_t* d_match_out, float* d_residual_out);
@@ -885,6 +886,61 @@ int r3d_track_iterate(r3d_ctx* ctx, const r3d_camera* cam, const float* d_src_ve
 int r3d_tsdf_track(r3d_tsdf* vol, const r3d_camera* cam, const void* d_depth, int depth_dtype, double depth_scale,
                    const double* h_pose_guess_w2c, double min_weight, double step, double t_near, double t_far, float max_jump,
                    double dist_max, double cos_min, int n_iters, double* h_pose_out, double* h_info_out);
+
+/* ---- Depth pyramid (csrc/r3d_pyramid.hip, and the coarse-to-fine driver in csrc/r3d_track.hip; NOT IN THE REFERENCE, this text is
+ * the specification).  Projective association pairs a source point with the model pixel it lands on, so a few pixels of image
+ * motion already pair across surfaces; tracking therefore starts on a halved raster, where the same motion is fewer pixels, and
+ * hands its pose down level by level.
+ * The level camera.  Pixel ui of a camera looks along x = (ui - cx) / fx: pixel centres sit at integer coordinates.  A coarse
+ *   pixel u' stands for the fine pixels 2 u' and 2 u' + 1, whose centre is 2 u' + 0.5.  r3d_camera_half: H' = H >> 1, W' = W >> 1
+ *   (an odd last row or column is dropped); fx' = 0.5 fx, fy' = 0.5 fy, cx' = 0.5 (cx - 0.5), cy' = 0.5 (cy - 0.5), in double, in
+ *   that order; the camera is created in cam's context as r3d_camera_create does (destroy it with r3d_camera_destroy).
+ *   R3D_ERR_INVALID with *out untouched for a NULL argument, H < 2 or W < 2.
+ * r3d_depth_half.  d_in holds the depth of pixel (v, u) at d_in[(v width + u) in_stride]: in_stride 1 is an f32 depth raster,
+ *   in_stride 3 the z column of a vertex map (the caller passes vertex + 2).  d_out is [height >> 1][width >> 1] f32.  All of it is
+ *   f32, in the order written, no fused multiply-add, correctly rounded division:
+ *   1. a depth is valid iff it is finite and > 0
+ *   2. for output pixel (v', u') the block is the four inputs (2v', 2u'), (2v', 2u' + 1), (2v' + 1, 2u'), (2v' + 1, 2u' + 1), in that
+ *      order
+ *   3. m = the minimum of the block's valid depths; with no valid depth the output is 0.0f ("no measurement", as a ray-cast miss)
+ *   4. a valid depth d is included iff d - m <= max_jump: foreground wins -- a block that straddles a depth edge averages the near
+ *      side only and never invents a depth between two surfaces
+ *   5. s = 0.0f, then s += d over the included depths in block order; the output is s / (float) count
+ *   max_jump >= 0; +inf is allowed and includes every valid depth.  The result does not depend on the launch geometry.
+ *   Asynchronous on the ctx stream; nothing outside d_out's extent is written.  One lane per output pixel, one launch per level.
+ *   R3D_ERR_INVALID, nothing written: a NULL pointer, in_stride not 1 or 3, height < 2 or width < 2, max_jump NaN or negative, the
+ *   input extent (((height width - 1) in_stride + 1) floats from d_in) overlapping the output, a raster of 2^31 - 1024 pixels or
+ *   more.
+ * r3d_tsdf_track_pyramid: r3d_tsdf_track coarse to fine.  cams[0] is the frame's camera; cams[l] must have the size
+ *   r3d_camera_half gives from cams[l - 1], in the same context (its intrinsics are the caller's: normally r3d_camera_half's; they
+ *   are not checked).  1 <= n_levels <= R3D_TRACK_MAX_LEVELS; h_iters[l] >= 0 iterations at level l, their sum at most
+ *   R3D_ICP_STATE_DOUBLES - R3D_ICP_STATE_HISTORY.  Every other argument means what it means in r3d_tsdf_track.
+ *   Source side: the level-0 vertex map is r3d_unproject of d_depth, as there.  The level-l depth, l >= 1, is r3d_depth_half of the
+ *   level l - 1 depth with max_jump (level 0's is read from the z column of its vertex map, in_stride 3, whatever dtype the frame
+ *   came in); the level-l vertex map is r3d_unproject of that f32 raster with cams[l] and scale 1; with cos_min > -1 each level's
+ *   normals are r3d_normals_organized of its vertex map with max_jump.
+ *   Model side: for every level with h_iters[l] > 0 the vertex and normal map are r3d_tsdf_raycast of the volume AT THE GUESS with
+ *   cams[l] (min_weight, step, t_near, t_far as given): ray-cast, not down-sampled, so every level's maps are what "TSDF ray
+ *   casting" specifies.  The model pose of every level is the guess, and S, its inverse, is the same for all levels.
+ *   Loop: one state reset; then from l = n_levels - 1 down to 0, h_iters[l] passes of r3d_track_iterate's pass at that level's
+ *   camera and maps ON THE SAME STATE: T_total, the iteration count and the rms history carry across levels.  A level with 0
+ *   iterations is skipped.  Everything is enqueued back to back; the state is read once at the end (synchronises).  Status is
+ *   sticky: a degenerate step at any level gives status 1 and h_pose_out = the guess, bit for bit.
+ *   h_pose_out and h_info_out as in r3d_tsdf_track (the iteration count is the total over all levels).  h_rms_out may be NULL;
+ *   otherwise it receives sum(h_iters) doubles: the state's rms history in execution order (coarsest level first).
+ *   With n_levels == 1 the call returns the bytes r3d_tsdf_track returns with n_iters = h_iters[0] (the two share one body).
+ *   All levels' maps, the depth rasters and the state live in the context's scratch (4/3 of the one-level footprint plus the
+ *   depth rasters): nothing is allocated per call after the first.
+ *   R3D_ERR_INVALID, nothing written, all checked before anything is enqueued: every argument error of r3d_tsdf_track; n_levels out
+ *   of range; NULL cams, cams[l] or h_iters; a level camera of the wrong size or of another context; a negative iteration count;
+ *   an iteration sum over the limit; h_rms_out overlapping another host argument. */
+#define R3D_TRACK_MAX_LEVELS 8
+int r3d_camera_half(const r3d_camera* cam, r3d_camera** out);
+int r3d_depth_half(r3d_ctx* ctx, const float* d_in, int in_stride, int height, int width, float max_jump, float* d_out);
+int r3d_tsdf_track_pyramid(r3d_tsdf* vol, const r3d_camera* const* cams, int n_levels, const int* h_iters, const void* d_depth,
+                           int depth_dtype, double depth_scale, const double* h_pose_guess_w2c, double min_weight, double step,
+                           double t_near, double t_far, float max_jump, double dist_max, double cos_min, double* h_pose_out,
+                           double* h_info_out, double* h_rms_out);
 
 #ifdef __cplusplus
 }
