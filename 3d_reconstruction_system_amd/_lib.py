@@ -189,6 +189,10 @@ SIGNATURES = {
     "r3d_camera_half": (_i, [_vp, _pvp]),
     "r3d_depth_half": (_i, [_vp, _vp, _i, _i, _i, _f, _vp]),
     "r3d_tsdf_track_pyramid": (_i, [_vp, _vp, _i, _vp, _vp, _i, _d, _vp, _d, _d, _d, _d, _f, _d, _d, _vp, _vp, _vp]),
+    "r3d_intensity_map": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
+    "r3d_track_accumulate_rgb": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _vp, _vp, _d, _d, _vp, _vp, _vp, _vp]),
+    "r3d_track_iterate_rgb": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _vp, _vp, _d, _d, _i, _vp]),
+    "r3d_tsdf_track_rgb": (_i, [_vp, _vp, _vp, _i, _d, _vp, _vp, _d, _d, _d, _d, _f, _d, _d, _d, _d, _i, _vp, _vp]),
 }
 
 _lib = None

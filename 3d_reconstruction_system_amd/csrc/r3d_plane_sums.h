@@ -31,10 +31,10 @@ __device__ __forceinline__ double plane_residual(const double p[3], const double
   return n[0] * (p[0] - q[0]) + n[1] * (p[1] - q[1]) + n[2] * (p[2] - q[2]);
 }
 
-__device__ __forceinline__ void pair_accumulate(double acc[kSums], double w, const double p[3], const double n[3], double r) {
+// what a residual r with J = [p x n ; n] adds to the normal equations alone, [2..28]: the plane pair below, and any other term
+// whose linearisation has that shape (the photometric term of r3d_track.hip, where n is the pulled-back image gradient)
+__device__ __forceinline__ void jacobian_accumulate(double* acc, double w, const double p[3], const double n[3], double r) {
   const double J[6] = {p[1] * n[2] - p[2] * n[1], p[2] * n[0] - p[0] * n[2], p[0] * n[1] - p[1] * n[0], n[0], n[1], n[2]};
-  acc[0] += w;
-  acc[1] += w * r * r;
   int k = 8;
 #pragma unroll
   for (int a = 0; a < 6; ++a) {
@@ -43,6 +43,12 @@ __device__ __forceinline__ void pair_accumulate(double acc[kSums], double w, con
 #pragma unroll
     for (int b = a; b < 6; ++b) acc[k++] += wj * J[b];
   }
+}
+
+__device__ __forceinline__ void pair_accumulate(double acc[kSums], double w, const double p[3], const double n[3], double r) {
+  acc[0] += w;
+  acc[1] += w * r * r;
+  jacobian_accumulate(acc, w, p, n, r);
 }
 #endif
 

@@ -12,6 +12,9 @@
 //                        M, the model pose and the intrinsics are wave-uniform.  The only LDS is the reduction's.
 //   track_finish_kernel  ONE workgroup: partial rows in fixed order -> 29 sums -> Cholesky solve + exponential map -> the ICP
 //                        state in HBM (r3d_sums_dev.h's finish and state update, as in r3d_plane.hip)
+//   track_rgb_kernel     track_kernel with a photometric term ("TSDF colour tracking"): for an accepted pair, a bilinear tap of the
+//                        model's packed {I, gx, gy, 0} map (r3d_photo.hip), the gradient pulled back to the world, and the pair
+//                        into the same normal equations -- 31 sums, the same tile, reduction, finish and state
 //   track_levels         host: the whole step for one frame -- r3d_tsdf_track (one level) and r3d_tsdf_track_pyramid (coarse to fine
 //                        over the depth pyramid of r3d_pyramid.hip, every level's model maps ray-cast at the guess) share it
 // No atomics: bitwise repeatable.  No search structure, no sort, no index: the association is one projection and one gather.
@@ -45,14 +48,8 @@ struct TrackParams {
 
 __device__ __forceinline__ bool finite3(const P3& p) { return isfinite(p.x) && isfinite(p.y) && isfinite(p.z); }
 
-__global__ __launch_bounds__(kThreads) void track_kernel(const float* __restrict__ src_vertex, const float* __restrict__ src_normal,
-                                                         const float* __restrict__ model_vertex,
-                                                         const float* __restrict__ model_normal, const TrackParams a,
-                                                         const double* __restrict__ state, double* __restrict__ partials,
-                                                         int32_t* __restrict__ match_out, float* __restrict__ residual_out) {
-  __shared__ double red[kThreads / 64][kSums];
-  // M = T_total . S, the loop of the solve's T_total update: every entry summed over m = 0..3 from 0.0 (rows 0..2 are used)
-  double M[12];
+// M = T_total . S, the loop of the solve's T_total update: every entry summed over m = 0..3 from 0.0 (rows 0..2 are used)
+__device__ __forceinline__ void compose_M(const TrackParams& a, const double* __restrict__ state, double M[12]) {
 #pragma unroll
   for (int r = 0; r < 3; ++r)
 #pragma unroll
@@ -65,6 +62,59 @@ __global__ __launch_bounds__(kThreads) void track_kernel(const float* __restrict
       }
       M[4 * r + c] = v;
     }
+}
+
+// what steps 1..10 leave of an accepted pair for the steps that follow them
+struct Pair {
+  double p[3], pm[3];   // the source point in the world and in the model camera
+  double u, v;          // its projection, before rounding
+  double r;             // the plane residual
+};
+
+// Steps 1..10 of "TSDF tracking" for source pixel i: the reject code, or the model pixel j after the pair has entered acc[0..28]
+__device__ __forceinline__ int32_t associate(const TrackParams& a, const double M[12], const P3* __restrict__ SV, const P3* __restrict__ SN,
+                                             const P3* __restrict__ MV, const P3* __restrict__ MN, int i, double* acc, Pair& o) {
+  const P3 sv = SV[i];
+  o.r = 0.0;
+  if (!(finite3(sv) && sv.z > 0.0f)) return -1;
+  const double x = (double)sv.x, y = (double)sv.y, z = (double)sv.z;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) o.p[c] = ((M[4 * c] * x + M[4 * c + 1] * y) + M[4 * c + 2] * z) + M[4 * c + 3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) o.pm[c] = ((a.rm[3 * c] * o.p[0] + a.rm[3 * c + 1] * o.p[1]) + a.rm[3 * c + 2] * o.p[2]) + a.tm[c];
+  if (!(o.pm[2] > 0.0)) return -2;
+  o.u = a.fx * (o.pm[0] / o.pm[2]) + a.cx, o.v = a.fy * (o.pm[1] / o.pm[2]) + a.cy;
+  const double uj = floor(o.u + 0.5), vj = floor(o.v + 0.5);
+  if (!(uj >= 0.0 && uj < a.wd && vj >= 0.0 && vj < a.hd)) return -2;   // NaN fails every comparison
+  const int j = (int)vj * a.width + (int)uj;                             // inside [0, n_px)
+  const P3 qv = MV[j], qn = MN[j];
+  if (!(finite3(qv) && finite3(qn) && !(qn.x == 0.0f && qn.y == 0.0f && qn.z == 0.0f))) return -3;
+  const double q[3] = {(double)qv.x, (double)qv.y, (double)qv.z};
+  const double n[3] = {(double)qn.x, (double)qn.y, (double)qn.z};
+  const double d0 = o.p[0] - q[0], d1 = o.p[1] - q[1], d2 = o.p[2] - q[2];
+  if (!((d0 * d0 + d1 * d1) + d2 * d2 <= a.dist2)) return -4;
+  if (SN) {
+    const P3 sn = SN[i];
+    if (!(finite3(sn) && !(sn.x == 0.0f && sn.y == 0.0f && sn.z == 0.0f))) return -5;
+    const double n0 = (double)sn.x, n1 = (double)sn.y, n2 = (double)sn.z;
+    double g[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) g[c] = (M[4 * c] * n0 + M[4 * c + 1] * n1) + M[4 * c + 2] * n2;
+    if (!((g[0] * n[0] + g[1] * n[1]) + g[2] * n[2] >= a.cos_min)) return -5;
+  }
+  o.r = r3d_plane::plane_residual(o.p, q, n);
+  r3d_plane::pair_accumulate(acc, 1.0, o.p, n, o.r);
+  return j;
+}
+
+__global__ __launch_bounds__(kThreads) void track_kernel(const float* __restrict__ src_vertex, const float* __restrict__ src_normal,
+                                                         const float* __restrict__ model_vertex,
+                                                         const float* __restrict__ model_normal, const TrackParams a,
+                                                         const double* __restrict__ state, double* __restrict__ partials,
+                                                         int32_t* __restrict__ match_out, float* __restrict__ residual_out) {
+  __shared__ double red[kThreads / 64][kSums];
+  double M[12];
+  compose_M(a, state, M);
   double acc[kSums];
 #pragma unroll
   for (int k = 0; k < kSums; ++k) acc[k] = 0.0;
@@ -76,57 +126,91 @@ __global__ __launch_bounds__(kThreads) void track_kernel(const float* __restrict
   for (int k = 0; k < kPerLane; ++k) {
     const int i = base + k * kThreads;
     if (i >= a.n_px) break;
-    const P3 sv = SV[i];
-    int32_t code = -1;
-    double r = 0.0;
-    if (finite3(sv) && sv.z > 0.0f) {
-      const double x = (double)sv.x, y = (double)sv.y, z = (double)sv.z;
-      double p[3], pm[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) p[c] = ((M[4 * c] * x + M[4 * c + 1] * y) + M[4 * c + 2] * z) + M[4 * c + 3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) pm[c] = ((a.rm[3 * c] * p[0] + a.rm[3 * c + 1] * p[1]) + a.rm[3 * c + 2] * p[2]) + a.tm[c];
-      code = -2;
-      if (pm[2] > 0.0) {
-        const double u = a.fx * (pm[0] / pm[2]) + a.cx, v = a.fy * (pm[1] / pm[2]) + a.cy;
-        const double uj = floor(u + 0.5), vj = floor(v + 0.5);
-        if (uj >= 0.0 && uj < a.wd && vj >= 0.0 && vj < a.hd) {   // NaN fails every comparison
-          const int j = (int)vj * a.width + (int)uj;              // inside [0, n_px)
-          const P3 qv = MV[j], qn = MN[j];
-          code = -3;
-          if (finite3(qv) && finite3(qn) && !(qn.x == 0.0f && qn.y == 0.0f && qn.z == 0.0f)) {
-            const double q[3] = {(double)qv.x, (double)qv.y, (double)qv.z};
-            const double n[3] = {(double)qn.x, (double)qn.y, (double)qn.z};
-            const double d0 = p[0] - q[0], d1 = p[1] - q[1], d2 = p[2] - q[2];
-            code = -4;
-            if ((d0 * d0 + d1 * d1) + d2 * d2 <= a.dist2) {
-              bool ok = true;
-              if (SN) {
-                const P3 sn = SN[i];
-                ok = finite3(sn) && !(sn.x == 0.0f && sn.y == 0.0f && sn.z == 0.0f);
-                if (ok) {
-                  const double n0 = (double)sn.x, n1 = (double)sn.y, n2 = (double)sn.z;
-                  double g[3];
-#pragma unroll
-                  for (int c = 0; c < 3; ++c) g[c] = (M[4 * c] * n0 + M[4 * c + 1] * n1) + M[4 * c + 2] * n2;
-                  ok = (g[0] * n[0] + g[1] * n[1]) + g[2] * n[2] >= a.cos_min;
-                }
-              }
-              code = -5;
-              if (ok) {
-                r = r3d_plane::plane_residual(p, q, n);
-                r3d_plane::pair_accumulate(acc, 1.0, p, n, r);
-                code = j;
-              }
-            }
-          }
-        }
-      }
-    }
+    Pair o;
+    const int32_t code = associate(a, M, SV, SN, MV, MN, i, acc, o);
     if (match_out) match_out[i] = code;
-    if (residual_out) residual_out[i] = code >= 0 ? (float)r : 0.0f;
+    if (residual_out) residual_out[i] = code >= 0 ? (float)o.r : 0.0f;
   }
   r3d_sums::block_reduce_store<kSums>(acc, red, partials + (int64_t)blockIdx.x * kSums);
+}
+
+// ---- the same pass with a photometric term ("TSDF colour tracking") ---------------------------------------------------------------
+constexpr int kSumsRgb = kSums + 2;   // [29] the photometric pair count, [30] the sum of rI^2
+
+struct PhotoParams {
+  double w, i_max;   // w_photo (metres^2 per intensity^2) and the residual gate
+};
+
+// Steps 11..16 for a pixel whose geometric pair was accepted: the bilinear tap of the model's packed {I, gx, gy, 0} map at (u, v),
+// the gradient pulled back to a world-space vector a, and the pair into [2..28] with J = [p x a ; a].  Returns (float) rI, or NaN
+// where there is no photometric pair.  The four taps are four 16-byte gathers next to the lane's own pixel.
+__device__ __forceinline__ float photo_pair(const TrackParams& a, const PhotoParams& ph, const float4* __restrict__ MP, float Is_f,
+                                            const Pair& o, double* acc) {
+  const double u0 = floor(o.u), v0 = floor(o.v);
+  if (!(u0 >= 0.0 && u0 + 1.0 <= a.wd - 1.0 && v0 >= 0.0 && v0 + 1.0 <= a.hd - 1.0)) return NAN;
+  const double fu = o.u - u0, fv = o.v - v0;
+  const int j = (int)v0 * a.width + (int)u0;   // j + width + 1 <= n_px - 1
+  const float4 t00 = MP[j], t01 = MP[j + 1], t10 = MP[j + a.width], t11 = MP[j + a.width + 1];
+  const double c00[3] = {(double)t00.x, (double)t00.y, (double)t00.z}, c01[3] = {(double)t01.x, (double)t01.y, (double)t01.z};
+  const double c10[3] = {(double)t10.x, (double)t10.y, (double)t10.z}, c11[3] = {(double)t11.x, (double)t11.y, (double)t11.z};
+  double val[3];   // Im, gx, gy: a NaN tap makes its value NaN
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double top = c00[c] + fu * (c01[c] - c00[c]), bot = c10[c] + fu * (c11[c] - c10[c]);
+    val[c] = top + fv * (bot - top);
+  }
+  const double rI = val[0] - (double)Is_f;
+  const double gfx = val[1] * a.fx, gfy = val[2] * a.fy;
+  const double b0 = gfx / o.pm[2], b1 = gfy / o.pm[2], b2 = -(gfx * o.pm[0] + gfy * o.pm[1]) / (o.pm[2] * o.pm[2]);
+  double g[3];   // Rm^T b
+#pragma unroll
+  for (int c = 0; c < 3; ++c) g[c] = (a.rm[c] * b0 + a.rm[3 + c] * b1) + a.rm[6 + c] * b2;
+  if (!(isfinite(rI) && isfinite(g[0]) && isfinite(g[1]) && isfinite(g[2]) && fabs(rI) <= ph.i_max)) return NAN;
+  r3d_plane::jacobian_accumulate(acc, ph.w, o.p, g, rI);
+  acc[kSums] += 1.0;
+  acc[kSums + 1] += rI * rI;
+  return (float)rI;
+}
+
+// track_kernel's tile and order, 31 sums (62 VGPRs of accumulators); M, the poses and the intrinsics stay wave-uniform
+__global__ __launch_bounds__(kThreads) void track_rgb_kernel(const float* __restrict__ src_vertex, const float* __restrict__ src_normal,
+                                                             const float* __restrict__ model_vertex,
+                                                             const float* __restrict__ model_normal,
+                                                             const float* __restrict__ src_intensity,
+                                                             const float4* __restrict__ model_packed, const TrackParams a,
+                                                             const PhotoParams ph, const double* __restrict__ state,
+                                                             double* __restrict__ partials, int32_t* __restrict__ match_out,
+                                                             float* __restrict__ residual_out, float* __restrict__ photo_out) {
+  __shared__ double red[kThreads / 64][kSumsRgb];
+  double M[12];
+  compose_M(a, state, M);
+  double acc[kSumsRgb];
+#pragma unroll
+  for (int k = 0; k < kSumsRgb; ++k) acc[k] = 0.0;
+  const P3* SV = reinterpret_cast<const P3*>(src_vertex);
+  const P3* SN = reinterpret_cast<const P3*>(src_normal);
+  const P3* MV = reinterpret_cast<const P3*>(model_vertex);
+  const P3* MN = reinterpret_cast<const P3*>(model_normal);
+  const int base = (int)blockIdx.x * kTile + (int)threadIdx.x;   // n_px < 2^31 - kTile (checked by the host)
+  for (int k = 0; k < kPerLane; ++k) {
+    const int i = base + k * kThreads;
+    if (i >= a.n_px) break;
+    Pair o;
+    const int32_t code = associate(a, M, SV, SN, MV, MN, i, acc, o);
+    float rI = NAN;
+    if (code >= 0) rI = photo_pair(a, ph, model_packed, src_intensity[i], o, acc);
+    if (match_out) match_out[i] = code;
+    if (residual_out) residual_out[i] = code >= 0 ? (float)o.r : 0.0f;
+    if (photo_out) photo_out[i] = rI;
+  }
+  r3d_sums::block_reduce_store<kSumsRgb>(acc, red, partials + (int64_t)blockIdx.x * kSumsRgb);
+}
+
+// the finish at K = 31: the step is solved from the first 29, so the state means what track_finish_kernel's means
+__global__ __launch_bounds__(kThreads) void track_rgb_finish_kernel(const double* __restrict__ partials, int n_rows,
+                                                                    double* __restrict__ sums_out, double* __restrict__ state) {
+  r3d_sums::finish_rows<kSumsRgb>(partials, n_rows, sums_out, state,
+                                  [](const double* s, double* T, double* rms) { return r3d_plane::step_from_sums(s, T, rms); });
 }
 
 // ONE workgroup (r3d_sums::finish_rows): partial rows -> the 29 sums -> optionally the point-to-plane step and the ICP state.
@@ -140,7 +224,18 @@ __global__ __launch_bounds__(kThreads) void track_finish_kernel(const double* __
 
 struct Maps {
   const float *src_vertex, *src_normal, *model_vertex, *model_normal;
+  const float *src_intensity = nullptr, *model_packed = nullptr;   // the colour term's: [H][W] f32 and [H][W][4] f32 {I, gx, gy, 0}
 };
+
+// the colour term's own argument checks; fills *ph
+int photo_checks(const Maps& m, double w_photo, double i_max, PhotoParams* ph) {
+  R3D_REQUIRE(m.src_intensity && m.model_packed, "NULL intensity map pointer");
+  R3D_REQUIRE(((uintptr_t)m.model_packed & 15) == 0, "d_model_packed must be 16-byte aligned");
+  R3D_REQUIRE(w_photo >= 0.0 && std::isfinite(w_photo), "w_photo must be >= 0 and finite");
+  R3D_REQUIRE(i_max > 0.0 && std::isfinite(i_max), "i_max must be positive and finite");
+  ph->w = w_photo, ph->i_max = i_max;
+  return R3D_OK;
+}
 
 // the argument checks the three entry points share; fills *p
 int track_checks(r3d_ctx* ctx, const r3d_camera* cam, const Maps& m, const double* h_model_pose_w2c, const double* h_S, double dist_max,
@@ -169,9 +264,10 @@ int track_checks(r3d_ctx* ctx, const r3d_camera* cam, const Maps& m, const doubl
 // the caller's device outputs against the four input maps and against each other
 int output_checks(const TrackParams& p, const Maps& m, const void* const* outs, const size_t* out_bytes, int n_outs) {
   const size_t map = (size_t)p.n_px * 12;
-  const void* in[4] = {m.src_vertex, m.src_normal, m.model_vertex, m.model_normal};
+  const void* in[6] = {m.src_vertex, m.src_normal, m.model_vertex, m.model_normal, m.src_intensity, m.model_packed};
+  const size_t in_bytes[6] = {map, map, map, map, (size_t)p.n_px * 4, (size_t)p.n_px * 16};
   for (int a = 0; a < n_outs; ++a) {
-    for (int b = 0; b < 4; ++b) R3D_REQUIRE(!r3d_ranges_overlap(outs[a], out_bytes[a], in[b], map), "an output overlaps an input map");
+    for (int b = 0; b < 6; ++b) R3D_REQUIRE(!r3d_ranges_overlap(outs[a], out_bytes[a], in[b], in_bytes[b]), "an output overlaps an input map");
     for (int b = a + 1; b < n_outs; ++b) R3D_REQUIRE(!r3d_ranges_overlap(outs[a], out_bytes[a], outs[b], out_bytes[b]), "outputs overlap each other");
   }
   return R3D_OK;
@@ -180,9 +276,9 @@ int output_checks(const TrackParams& p, const Maps& m, const void* const* outs, 
 int n_tiles(const TrackParams& p) { return (p.n_px + kTile - 1) / kTile; }
 
 // partial rows (+ one row for the one-pass form's sums) in scratch slot 4, the slot the other paths keep their partial rows in
-int rows_workspace(r3d_ctx* ctx, int tiles, double** rows) {
+int rows_workspace(r3d_ctx* ctx, int tiles, double** rows, int k_sums = kSums) {
   void* v = nullptr;
-  int rc = r3d_scratch(ctx, 4, ((size_t)tiles + 2) * kSums * sizeof(double), &v);
+  int rc = r3d_scratch(ctx, 4, ((size_t)tiles + 2) * k_sums * sizeof(double), &v);
   if (rc) return rc;
   *rows = static_cast<double*>(v);
   return R3D_OK;
@@ -206,7 +302,121 @@ int iterate_impl(r3d_ctx* ctx, const TrackParams& p, const Maps& m, int n_iters,
   return R3D_OK;
 }
 
+// the same pass with the colour term: 31 sums per row
+void enqueue_pass_rgb(r3d_ctx* ctx, const TrackParams& p, const PhotoParams& ph, const Maps& m, const double* d_state_in, double* rows,
+                      double* d_sums_out, double* d_state, int32_t* d_match_out, float* d_residual_out, float* d_photo_out) {
+  const int tiles = n_tiles(p);
+  hipLaunchKernelGGL(track_rgb_kernel, dim3(tiles), dim3(kThreads), 0, ctx->stream, m.src_vertex, m.src_normal, m.model_vertex,
+                     m.model_normal, m.src_intensity, reinterpret_cast<const float4*>(m.model_packed), p, ph, d_state_in, rows,
+                     d_match_out, d_residual_out, d_photo_out);
+  hipLaunchKernelGGL(track_rgb_finish_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, (const double*)rows, tiles, d_sums_out, d_state);
+}
+
+// every pass leaves its 31 sums in the row after the partial rows: the last pass's photometric count and sum are read from there
+int iterate_rgb_impl(r3d_ctx* ctx, const TrackParams& p, const PhotoParams& ph, const Maps& m, int n_iters, double* d_state,
+                     double** d_sums_out) {
+  double* rows = nullptr;
+  const int tiles = n_tiles(p);
+  int rc = rows_workspace(ctx, tiles, &rows, kSumsRgb);
+  if (rc) return rc;
+  double* d_sums = rows + (size_t)tiles * kSumsRgb;
+  for (int it = 0; it < n_iters; ++it) enqueue_pass_rgb(ctx, p, ph, m, d_state, rows, d_sums, d_state, nullptr, nullptr, nullptr);
+  R3D_HIP(hipGetLastError());
+  if (d_sums_out) *d_sums_out = d_sums;
+  return R3D_OK;
+}
+
 constexpr int kMaxIters = R3D_ICP_STATE_DOUBLES - R3D_ICP_STATE_HISTORY;   // what the history holds
+
+// The whole step for one frame with the colour term, one level ("TSDF colour tracking"): track_levels' one-level case with the
+// model's colour image ray-cast next to its maps and the two intensity maps made of it and of the frame's image.
+int track_rgb(r3d_tsdf* vol, const r3d_camera* cam, const void* d_depth, int depth_dtype, double depth_scale, const uint8_t* d_rgb,
+              const double* h_pose_guess_w2c, double min_weight, double step, double t_near, double t_far, float max_jump, double dist_max,
+              double cos_min, double w_photo, double i_max, int n_iters, double* h_pose_out, double* h_info_out) {
+  int rc = r3d_tsdf_integrate_checks(vol, cam, d_depth, depth_dtype, 1, depth_scale, h_pose_guess_w2c);
+  if (rc) return rc;
+  R3D_REQUIRE(d_rgb != nullptr, "d_rgb is NULL");
+  R3D_REQUIRE(h_pose_out && h_info_out, "NULL output pointer");
+  R3D_REQUIRE(!r3d_ranges_overlap(h_pose_out, 12 * sizeof(double), h_info_out, 6 * sizeof(double)) &&
+                  !r3d_ranges_overlap(h_pose_out, 12 * sizeof(double), h_pose_guess_w2c, 12 * sizeof(double)) &&
+                  !r3d_ranges_overlap(h_info_out, 6 * sizeof(double), h_pose_guess_w2c, 12 * sizeof(double)),
+              "an output overlaps the guess or the other output");
+  R3D_REQUIRE(max_jump >= 0.f, "max_jump must be >= 0");
+  R3D_REQUIRE(n_iters >= 0 && n_iters <= kMaxIters, "n_iters must be in [0, %d]", kMaxIters);
+  r3d_ctx* ctx = cam->ctx;
+  const double* G = h_pose_guess_w2c;
+  for (int k = 0; k < 12; ++k) R3D_REQUIRE(std::isfinite(G[k]), "the pose guess must be finite");
+  double S[16];   // the inverse of the guess, as in track_levels
+  for (int a = 0; a < 3; ++a) {
+    for (int b = 0; b < 3; ++b) S[4 * a + b] = G[3 * b + a];
+    S[4 * a + 3] = -((G[a] * G[9] + G[3 + a] * G[10]) + G[6 + a] * G[11]);
+    S[12 + a] = 0.0;
+  }
+  S[15] = 1.0;
+  const bool gate = cos_min > -1.0;
+  TrackParams p;
+  PhotoParams ph;
+  const float dummy = 0.f;
+  alignas(16) const float dummy4[4] = {0.f, 0.f, 0.f, 0.f};
+  Maps probe = {&dummy, nullptr, &dummy, &dummy};
+  probe.src_intensity = &dummy, probe.model_packed = dummy4;
+  if ((rc = track_checks(ctx, cam, probe, G, S, dist_max, cos_min, &p))) return rc;
+  if ((rc = photo_checks(probe, w_photo, i_max, &ph))) return rc;
+  // the ray cast's own argument checks and the colour plane's presence: with no output it validates and does nothing else
+  if ((rc = r3d_tsdf_raycast_rgb(vol, cam, 1, G, min_weight, step, t_near, t_far, nullptr, nullptr, nullptr, nullptr))) return rc;
+  if ((rc = r3d_ctx_enter(ctx))) return rc;
+  // scratch slot 7, as track_levels: four maps, the model's depth, rgb and packed map, the source intensity, the state
+  const auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t n = (size_t)p.n_px, map = up(n * 12), plane = up(n * 4), img = up(n * 3), packed = up(n * 16);
+  const size_t bytes = 4 * map + 2 * plane + img + packed;
+  void* ws = nullptr;
+  if ((rc = r3d_scratch(ctx, 7, bytes + R3D_ICP_STATE_DOUBLES * sizeof(double), &ws))) return rc;
+  char* c = static_cast<char*>(ws);
+  float *model_vertex = reinterpret_cast<float*>(c), *model_normal = reinterpret_cast<float*>(c + map);
+  float *src_vertex = reinterpret_cast<float*>(c + 2 * map), *src_normal = reinterpret_cast<float*>(c + 3 * map);
+  float* model_packed = reinterpret_cast<float*>(c + 4 * map);
+  float *model_depth = reinterpret_cast<float*>(c + 4 * map + packed), *src_intensity = reinterpret_cast<float*>(c + 4 * map + packed + plane);
+  uint8_t* model_rgb = reinterpret_cast<uint8_t*>(c + 4 * map + packed + 2 * plane);
+  double* d_state = reinterpret_cast<double*>(c + bytes);
+  if ((rc = r3d_tsdf_raycast_rgb(vol, cam, 1, G, min_weight, step, t_near, t_far, model_depth, model_vertex, model_normal, model_rgb)))
+    return rc;
+  if ((rc = r3d_intensity_map(ctx, model_rgb, model_depth, 1, cam->height, cam->width, max_jump, nullptr, model_packed))) return rc;
+  if ((rc = r3d_unproject(ctx, cam, d_depth, depth_dtype, 1, depth_scale, src_vertex, R3D_F32))) return rc;
+  if ((rc = r3d_intensity_map(ctx, d_rgb, src_vertex + 2, 3, cam->height, cam->width, max_jump, src_intensity, nullptr))) return rc;
+  if (gate && (rc = r3d_normals_organized(ctx, src_vertex, 1, cam->height, cam->width, max_jump, nullptr, src_normal))) return rc;
+  Maps m = {src_vertex, gate ? src_normal : nullptr, model_vertex, model_normal};
+  m.src_intensity = src_intensity, m.model_packed = model_packed;
+  if ((rc = r3d_icp_state_reset(ctx, d_state))) return rc;
+  double* d_sums = nullptr;
+  if (n_iters > 0 && (rc = iterate_rgb_impl(ctx, p, ph, m, n_iters, d_state, &d_sums))) return rc;
+  double st[r3d_sums::kStatePairs + 1], sums[kSumsRgb] = {0.0};
+  R3D_HIP(hipMemcpyAsync(st, d_state, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
+  if (d_sums) R3D_HIP(hipMemcpyAsync(sums, d_sums, sizeof(sums), hipMemcpyDeviceToHost, ctx->stream));
+  R3D_HIP(hipStreamSynchronize(ctx->stream));
+  const bool bad = st[r3d_sums::kStateStatus] != 0.0;
+  if (bad) {
+    for (int k = 0; k < 12; ++k) h_pose_out[k] = G[k];   // a degenerate step: the guess comes back as it was given
+  } else {
+    double M[16];
+    for (int r = 0; r < 4; ++r)
+      for (int cc = 0; cc < 4; ++cc) {
+        double v = 0.0;
+        for (int k = 0; k < 4; ++k) v += st[r3d_sums::kStateTTotal + 4 * r + k] * S[4 * k + cc];
+        M[4 * r + cc] = v;
+      }
+    for (int a = 0; a < 3; ++a) {
+      for (int b = 0; b < 3; ++b) h_pose_out[3 * a + b] = M[4 * b + a];
+      h_pose_out[9 + a] = -((M[a] * M[3] + M[4 + a] * M[7]) + M[8 + a] * M[11]);
+    }
+  }
+  h_info_out[0] = st[r3d_sums::kStatePairs];
+  h_info_out[1] = st[r3d_sums::kStateRms];
+  h_info_out[2] = bad ? 1.0 : 0.0;
+  h_info_out[3] = st[r3d_sums::kStateIters];
+  h_info_out[4] = sums[kSums];
+  h_info_out[5] = sums[kSums] > 0.0 ? std::sqrt(sums[kSums + 1] / sums[kSums]) : 0.0;
+  return R3D_OK;
+}
 
 // The whole step for one frame over n_levels pyramid levels, fine (0) to coarse; r3d_tsdf_track is the one-level case.  The
 // caller has checked that cams and iters hold n_levels entries (cams[0] may still be NULL: the volume's checks refuse it).
@@ -377,6 +587,65 @@ int r3d_track_iterate(r3d_ctx* ctx, const r3d_camera* cam, const float* d_src_ve
   if (n_iters == 0) return R3D_OK;
   r3d_wrote(ctx, d_state, out_bytes[0]);
   return iterate_impl(ctx, p, m, n_iters, d_state);
+}
+
+int r3d_track_accumulate_rgb(r3d_ctx* ctx, const r3d_camera* cam, const float* d_src_vertex, const float* d_src_normal,
+                             const float* d_model_vertex, const float* d_model_normal, const double* h_model_pose_w2c, const double* h_S,
+                             double dist_max, double cos_min, const float* d_src_intensity, const float* d_model_packed, double w_photo,
+                             double i_max, double* h_sums, int32_t* d_match_out, float* d_residual_out, float* d_photo_out) {
+  TrackParams p;
+  PhotoParams ph;
+  Maps m = {d_src_vertex, d_src_normal, d_model_vertex, d_model_normal};
+  m.src_intensity = d_src_intensity, m.model_packed = d_model_packed;
+  int rc = track_checks(ctx, cam, m, h_model_pose_w2c, h_S, dist_max, cos_min, &p);
+  if (rc) return rc;
+  if ((rc = photo_checks(m, w_photo, i_max, &ph))) return rc;
+  R3D_REQUIRE(h_sums != nullptr, "h_sums is NULL");
+  const void* outs[3] = {d_match_out, d_residual_out, d_photo_out};
+  const size_t out_bytes[3] = {(size_t)p.n_px * 4, (size_t)p.n_px * 4, (size_t)p.n_px * 4};
+  if ((rc = output_checks(p, m, outs, out_bytes, 3))) return rc;
+  if ((rc = r3d_ctx_enter(ctx))) return rc;
+  double* rows = nullptr;
+  const int tiles = n_tiles(p);
+  if ((rc = rows_workspace(ctx, tiles, &rows, kSumsRgb))) return rc;
+  for (int a = 0; a < 3; ++a)
+    if (outs[a]) r3d_wrote(ctx, outs[a], out_bytes[a]);
+  double* d_sums = rows + (size_t)tiles * kSumsRgb;
+  enqueue_pass_rgb(ctx, p, ph, m, nullptr, rows, d_sums, nullptr, d_match_out, d_residual_out, d_photo_out);
+  R3D_HIP(hipGetLastError());
+  R3D_HIP(hipMemcpyAsync(h_sums, d_sums, kSumsRgb * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  R3D_HIP(hipStreamSynchronize(ctx->stream));
+  return R3D_OK;
+}
+
+int r3d_track_iterate_rgb(r3d_ctx* ctx, const r3d_camera* cam, const float* d_src_vertex, const float* d_src_normal,
+                          const float* d_model_vertex, const float* d_model_normal, const double* h_model_pose_w2c, const double* h_S,
+                          double dist_max, double cos_min, const float* d_src_intensity, const float* d_model_packed, double w_photo,
+                          double i_max, int n_iters, double* d_state) {
+  TrackParams p;
+  PhotoParams ph;
+  Maps m = {d_src_vertex, d_src_normal, d_model_vertex, d_model_normal};
+  m.src_intensity = d_src_intensity, m.model_packed = d_model_packed;
+  int rc = track_checks(ctx, cam, m, h_model_pose_w2c, h_S, dist_max, cos_min, &p);
+  if (rc) return rc;
+  if ((rc = photo_checks(m, w_photo, i_max, &ph))) return rc;
+  R3D_REQUIRE(d_state != nullptr, "d_state is NULL");
+  R3D_REQUIRE(n_iters >= 0 && n_iters <= kMaxIters, "n_iters must be in [0, %d]", kMaxIters);
+  const void* outs[1] = {d_state};
+  const size_t out_bytes[1] = {R3D_ICP_STATE_DOUBLES * sizeof(double)};
+  if ((rc = output_checks(p, m, outs, out_bytes, 1))) return rc;
+  if ((rc = r3d_ctx_enter(ctx))) return rc;
+  if (n_iters == 0) return R3D_OK;
+  r3d_wrote(ctx, d_state, out_bytes[0]);
+  return iterate_rgb_impl(ctx, p, ph, m, n_iters, d_state, nullptr);
+}
+
+int r3d_tsdf_track_rgb(r3d_tsdf* vol, const r3d_camera* cam, const void* d_depth, int depth_dtype, double depth_scale,
+                       const uint8_t* d_rgb, const double* h_pose_guess_w2c, double min_weight, double step, double t_near, double t_far,
+                       float max_jump, double dist_max, double cos_min, double w_photo, double i_max, int n_iters, double* h_pose_out,
+                       double* h_info_out) {
+  return track_rgb(vol, cam, d_depth, depth_dtype, depth_scale, d_rgb, h_pose_guess_w2c, min_weight, step, t_near, t_far, max_jump,
+                   dist_max, cos_min, w_photo, i_max, n_iters, h_pose_out, h_info_out);
 }
 
 int r3d_tsdf_track(r3d_tsdf* vol, const r3d_camera* cam, const void* d_depth, int depth_dtype, double depth_scale,

@@ -3,7 +3,7 @@
 truncated signed distance volume instead, and the volume's zero level set is written as oriented surface points.
 
     python integrate_tsdf.py --voxel-size S --trunc T [--origin X Y Z] [--dims NX NY NZ] [--margin M] [--min-weight W] [--mesh]
-                             [--raycast] [--color-dir DIR] [--raycast-color] [--track [--track-pyramid N0,N1,..]]
+                             [--raycast] [--color-dir DIR] [--raycast-color] [--track [--track-pyramid N0,N1,..] [--track-color [--photo-weight W] [--track-max-jump D]]]
 
 Run from a directory holding ./camera_pose/image_colmap_simi_2.txt and ./depth/ (the inputs of camera_to_world.py; the same
 environment overrides apply: R3D_FX .. R3D_CY, R3D_POSE_SCALE, R3D_DEVICE).  Writes ./ply/tsdf_surface.ply: binary PLY, float
@@ -24,7 +24,13 @@ sorted order as the frames (--origin / --dims are then the caller's to choose ar
 frame is tracked against the model from the previous frame's pose (projective point-to-plane ICP on the ray-cast maps: small
 motions between frames) and integrated at the pose found.  The estimated poses are written to
 ./camera_pose/image_colmap_simi_2_tracked.txt in the pose file's own format, and a further line "tracked F frames -> path" is
-printed.  Without --origin / --dims the volume is then built around the first camera centre alone.  Not with --color-dir.
+printed.  Without --origin / --dims the volume is then built around the first camera centre alone.  Not with --color-dir, unless:
+--track-color (with --track and --color-dir; not with --track-pyramid) tracks every frame with a photometric term next to the
+geometric one -- the frame's colour image against the one the model predicts -- and integrates the colour images, so the PLY
+files carry colour.  It holds what planes alone leave open: sliding along a corridor, over a wall or a floor.
+--photo-weight W is the weight of a photometric pair against a geometric pair's 1, in (length unit)^2 per intensity^2 (default:
+tracking.PHOTO_WEIGHT, chosen for metres); --track-max-jump D the depth step, in length units, across which no image gradient
+is taken (default 0.05, for metres).  Both scale with the unit of the depth maps.
 --track-pyramid N0,N1,.. (with --track) tracks coarse to fine over a depth pyramid: N0 iterations at full size, N1 on the halved
 rasters and so on, e.g. 10,5,4; the coarse levels run first and let the loop follow larger motions between frames.
 """
@@ -68,7 +74,15 @@ def parse_args(argv):
                    help="use only the first pose of the pose file, estimate the others by tracking and write them to %s" % TRACKED_FILE)
     p.add_argument("--track-pyramid", metavar="N0,N1,..", default=None,
                    help="with --track: iterations per pyramid level, fine to coarse (e.g. 10,5,4): track coarse to fine")
+    p.add_argument("--track-color", action="store_true",
+                   help="with --track and --color-dir: track with the colour term too and integrate the colour images")
+    p.add_argument("--photo-weight", type=float, default=None,
+                   help="with --track-color: weight of a photometric pair, (length unit)^2 per intensity^2 (default: for metres)")
+    p.add_argument("--track-max-jump", type=float, default=None,
+                   help="with --track-color: depth step across which no image gradient is taken (default 0.05)")
     args = p.parse_args(argv)
+    if (args.photo_weight is not None or args.track_max_jump is not None) and not args.track_color:
+        p.error("--photo-weight and --track-max-jump need --track-color")
     if args.track_pyramid is not None:
         if not args.track:
             p.error("--track-pyramid needs --track")
@@ -78,8 +92,12 @@ def parse_args(argv):
             p.error("--track-pyramid takes integers separated by commas, got %r" % args.track_pyramid)
         if not 1 <= len(args.track_pyramid) <= 8 or min(args.track_pyramid) < 0:
             p.error("--track-pyramid takes 1 to 8 iteration counts >= 0, got %r" % (args.track_pyramid,))
-    if args.track and args.color_dir is not None:
-        p.error("--track takes depth maps only (not with --color-dir)")
+    if args.track_color and not (args.track and args.color_dir is not None):
+        p.error("--track-color needs --track and the colour images (--color-dir)")
+    if args.track_color and args.track_pyramid is not None:
+        p.error("--track-color runs at one level only (not with --track-pyramid)")
+    if args.track and args.color_dir is not None and not args.track_color:
+        p.error("--track takes depth maps only (not with --color-dir, unless --track-color)")
     if args.raycast_color and args.color_dir is None:
         p.error("--raycast-color needs the colour images (--color-dir)")
     for name in ("voxel_size", "trunc", "min_weight"):
@@ -219,10 +237,13 @@ def main(argv=None):
     _common.stamp("read %d frames" % len(names))
     tracked = None
     if args.track:
-        vol = r3d.TSDFVolume(origin, args.voxel_size, dims, args.trunc, ctx=_common.context())
+        vol = r3d.TSDFVolume(origin, args.voxel_size, dims, args.trunc, ctx=_common.context(), color=args.track_color)
         try:
             tracked = vol.track_and_integrate(depths, r3d.poses_w2c(quats[:1], ts[:1])[0], intrinsics=_common.intrinsics(),
-                                              min_weight=args.min_weight, pyramid_iters=args.track_pyramid)
+                                              min_weight=args.min_weight, pyramid_iters=args.track_pyramid,
+                                              rgbs=rgb if args.track_color else None,
+                                              **({"photo_weight": args.photo_weight, "max_jump": 0.05 if args.track_max_jump is None
+                                                  else args.track_max_jump} if args.track_color else {}))
         except (RuntimeError, ValueError) as e:
             sys.exit("integrate_tsdf.py: --track: %s" % e)
         quats = [quat_xyzw(row[:9].reshape(3, 3)) for row in tracked]

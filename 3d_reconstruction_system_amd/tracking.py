@@ -6,6 +6,10 @@ track_sums is one association pass from host arrays (the 29 sums of the point-to
 TrackDevice keeps the maps and the ICP state in HBM and runs whole iterations without a host round trip.  The whole step for one
 depth frame -- ray cast, unproject, normals, loop, pose -- is TSDFVolume.track; with pyramid_iters it runs coarse to fine over a
 depth pyramid (depth_half, pyramid_intrinsics, pyramid_shape: include/r3d.h "Depth pyramid").
+
+With a colour volume the loop can carry a photometric term next to the geometric one (include/r3d.h "TSDF colour tracking",
+DESIGN.md section 4.5p): intensity_map makes the intensity and gradient maps both sides read, TrackDevice takes them as
+src_intensity= / model_packed= and runs sums_rgb / iterate_rgb, and TSDFVolume.track(rgb=) is the whole step.
 """
 import numpy as np
 
@@ -15,6 +19,11 @@ from .icp import PLANE_SUMS, STATE_DOUBLES, STATE_HISTORY
 
 MAX_ITERS = STATE_DOUBLES - STATE_HISTORY   # what the state's history holds
 MAX_LEVELS = 8                              # R3D_TRACK_MAX_LEVELS
+RGB_SUMS = PLANE_SUMS + 2                   # [29] the photometric pair count, [30] the sum of rI^2
+# the colour term's defaults, from the sweep of DESIGN.md section 4.5p: the weight of a photometric pair against a geometric
+# pair's 1 (metres^2 per intensity^2, intensities in 0..255) and the largest |intensity difference| a pair may have
+PHOTO_WEIGHT = 1e-5
+I_MAX = 40.0
 
 
 def pyramid_intrinsics(K, level):
@@ -83,6 +92,48 @@ def depth_half(depth, max_jump, ctx=None):
     finally:
         d_in.free()
         d_out.free()
+
+
+def photo_args(photo_weight, i_max):
+    """(w_photo, i_max) as the library takes them (None: the defaults above); ValueError otherwise"""
+    try:
+        w = PHOTO_WEIGHT if photo_weight is None else float(photo_weight)
+        im = I_MAX if i_max is None else float(i_max)
+    except (TypeError, ValueError):
+        raise ValueError("photo_weight and i_max must be numbers, got %r and %r" % (photo_weight, i_max))
+    if not (np.isfinite(w) and w >= 0.0):
+        raise ValueError("photo_weight must be finite and >= 0, got %r" % (photo_weight,))
+    if not (np.isfinite(im) and im > 0.0):
+        raise ValueError("i_max must be finite and > 0, got %r" % (i_max,))
+    return w, im
+
+
+def intensity_map(rgb, valid, max_jump, ctx=None):
+    """(I [H,W] float32, packed [H,W,4] float32 {I, gx, gy, 0}) of a host colour image rgb [H,W,3] uint8 (R, G, B): the luma
+    0.299 R + 0.587 G + 0.114 B in 0..255 and its central differences.  valid [H,W] float32 marks the pixels that count (finite
+    and > 0: a depth raster); I is NaN elsewhere, and a gradient is NaN on the raster's border, next to an invalid pixel and
+    across a depth jump of more than max_jump (>= 0, inf allowed)."""
+    c_img, d = np.asarray(rgb), np.asarray(valid)
+    if c_img.dtype != np.uint8 or c_img.ndim != 3 or c_img.shape[2] != 3 or c_img.shape[0] < 1 or c_img.shape[1] < 1:
+        raise ValueError("rgb must be a uint8 [H,W,3] image, got %s of shape %s" % (c_img.dtype, list(c_img.shape)))
+    if d.dtype != np.float32 or d.shape != c_img.shape[:2]:
+        raise ValueError("valid must be a float32 raster of shape %s, got %s of shape %s" % (list(c_img.shape[:2]), d.dtype, list(d.shape)))
+    try:
+        mj = float(max_jump)
+    except (TypeError, ValueError):
+        raise ValueError("max_jump must be a number >= 0, got %r" % (max_jump,))
+    if not mj >= 0.0:
+        raise ValueError("max_jump must be >= 0, got %r" % (max_jump,))
+    c_img, d = np.ascontiguousarray(c_img), np.ascontiguousarray(d)
+    c = ctx or default_context()
+    h, w = d.shape
+    bufs = [c.alloc(c_img.nbytes).upload(c_img), c.alloc(d.nbytes).upload(d), c.alloc(h * w * 4), c.alloc(h * w * 16)]
+    try:
+        L.check(c.lib.r3d_intensity_map(c.handle, bufs[0].ptr, bufs[1].ptr, 1, h, w, mj, bufs[2].ptr, bufs[3].ptr))
+        return bufs[2].download(np.float32, h * w).reshape(h, w), bufs[3].download(np.float32, h * w * 4).reshape(h, w, 4)
+    finally:
+        for b in bufs:
+            b.free()
 
 
 def inverse_pose(pose_w2c):
@@ -171,11 +222,22 @@ class TrackDevice:
     """The new frame's maps (camera frame) and the model's maps (world) resident on one GPU, with the device-resident ICP state.
     src_vertex [H,W,3] float32 (fusion.unproject's rows), src_normal the same or None (no normal gate), model_vertex /
     model_normal [H,W,3] float32 as TSDFVolume.raycast returns them for the pose model_pose_w2c (12 doubles), S the 4x4 guess
-    source camera -> world."""
+    source camera -> world.  src_intensity [H,W] float32 and model_packed [H,W,4] float32 (intensity_map's two results, for the
+    frame's image and for the model's) are the colour term's maps: sums_rgb and iterate_rgb need both."""
 
-    def __init__(self, src_vertex, model_vertex, model_normal, model_pose_w2c, S, intrinsics, src_normal=None, ctx=None):
+    def __init__(self, src_vertex, model_vertex, model_normal, model_pose_w2c, S, intrinsics, src_normal=None, ctx=None,
+                 src_intensity=None, model_packed=None):
         sv, sn, mv, mn, self.model_pose, self.S, K = _check_inputs(src_vertex, src_normal, model_vertex, model_normal, model_pose_w2c, S,
                                                              intrinsics)
+        if (src_intensity is None) != (model_packed is None):
+            raise ValueError("src_intensity and model_packed go together: give both or neither")
+        if src_intensity is not None:
+            si, mp = np.asarray(src_intensity), np.asarray(model_packed)
+            if si.dtype != np.float32 or si.shape != sv.shape[:2]:
+                raise ValueError("src_intensity must be a float32 %s raster, got %s of shape %s" % (list(sv.shape[:2]), si.dtype, list(si.shape)))
+            if mp.dtype != np.float32 or mp.shape != sv.shape[:2] + (4,):
+                raise ValueError("model_packed must be a float32 %s map, got %s of shape %s" % (list(sv.shape[:2]) + [4], mp.dtype, list(mp.shape)))
+            si, mp = np.ascontiguousarray(si), np.ascontiguousarray(mp)
         self.ctx = c = ctx or default_context()
         self.h, self.w = sv.shape[:2]
         self.n = self.h * self.w
@@ -188,6 +250,10 @@ class TrackDevice:
             return b
         self.d_src_vertex, self.d_model_vertex, self.d_model_normal = put(sv), put(mv), put(mn)
         self.d_src_normal = None if sn is None else put(sn)
+        self.d_src_intensity = self.d_model_packed = self.d_photo = None
+        if src_intensity is not None:
+            self.d_src_intensity, self.d_model_packed, self.d_photo = put(si), put(mp), c.alloc(self.n * 4)
+            self._bufs.append(self.d_photo)
         self.d_match, self.d_residual = c.alloc(self.n * 4), c.alloc(self.n * 4)
         self.d_state = c.alloc(STATE_DOUBLES * 8)
         self._bufs += [self.d_match, self.d_residual, self.d_state]
@@ -216,6 +282,34 @@ class TrackDevice:
         if not 0 <= n_iters <= MAX_ITERS:
             raise ValueError("n_iters must be in [0, %d], got %d" % (MAX_ITERS, n_iters))
         L.check(self.ctx.lib.r3d_track_iterate(self.ctx.handle, self.cam.handle, *self._maps(), d, cm, n_iters, self.d_state.ptr))
+
+    def _photo(self, photo_weight, i_max):
+        if self.d_src_intensity is None:
+            raise ValueError("the colour term needs src_intensity= and model_packed= (tracking.intensity_map makes them)")
+        return (self.d_src_intensity.ptr, self.d_model_packed.ptr) + photo_args(photo_weight, i_max)
+
+    def sums_rgb(self, dist_max, cos_min=-1.0, photo_weight=None, i_max=None):
+        """sums() with the colour term: (sums [31], match [H,W] int32, residual [H,W] float32, photo [H,W] float32).  The first
+        29 sums hold both terms' normal equations ([0], [1]: the geometric pairs alone), [29] and [30] the photometric pair count
+        and the sum of their squared intensity differences; photo is that difference per pixel, NaN where no pair entered."""
+        d, cm = _gates(dist_max, cos_min)
+        photo = self._photo(photo_weight, i_max)
+        sums = np.zeros(RGB_SUMS, dtype=np.float64)
+        L.check(self.ctx.lib.r3d_track_accumulate_rgb(self.ctx.handle, self.cam.handle, *self._maps(), d, cm, *photo, sums.ctypes.data,
+                                                      self.d_match.ptr, self.d_residual.ptr, self.d_photo.ptr))
+        return (sums, self.d_match.download(np.int32, self.n).reshape(self.h, self.w),
+                self.d_residual.download(np.float32, self.n).reshape(self.h, self.w),
+                self.d_photo.download(np.float32, self.n).reshape(self.h, self.w))
+
+    def iterate_rgb(self, n_iters, dist_max, cos_min=-1.0, photo_weight=None, i_max=None):
+        """iterate() with the colour term, on the same state."""
+        d, cm = _gates(dist_max, cos_min)
+        photo = self._photo(photo_weight, i_max)
+        n_iters = int(n_iters)
+        if not 0 <= n_iters <= MAX_ITERS:
+            raise ValueError("n_iters must be in [0, %d], got %d" % (MAX_ITERS, n_iters))
+        L.check(self.ctx.lib.r3d_track_iterate_rgb(self.ctx.handle, self.cam.handle, *self._maps(), d, cm, *photo, n_iters,
+                                                   self.d_state.ptr))
 
     def state(self):
         st = self.d_state.download(np.float64, STATE_DOUBLES)

@@ -378,10 +378,23 @@ class TSDFVolume:
         s, tn, tf = _ray_range(step, t_near, t_far, self.voxel_size)
         return int(n_iters), dm, cos_min, mj, _positive_f32(min_weight, "min_weight"), s, tn, tf
 
+    def _check_track_color(self, pyramid_iters, photo_weight, i_max):
+        """ValueError unless a colour image can take part in tracking: a volume with colour, no pyramid, a valid weight and gate"""
+        self._check_color(True, "rgb")
+        if pyramid_iters is not None:
+            raise ValueError("rgb cannot be combined with pyramid_iters: the colour term runs at one level only (the pyramid has no "
+                             "depth-consistent intensity half-sampler yet)")
+        from .tracking import photo_args
+        photo_args(photo_weight, i_max)
+
     def track_device(self, cam, d_depth, depth_dtype, pose_guess_w2c, n_iters=10, dist_max=None, max_angle_deg=None, depth_scale=1.0,
-                     max_jump=0.05, min_weight=1.0, step=None, t_near=0.0, t_far=math.inf, pyramid_iters=None):
-        """track() from a raster in HBM (d_depth: [H][W] of depth_dtype at a raw device address; cam: ctx.camera(...)).
-        Synchronises (the pose is read back)."""
+                     max_jump=0.05, min_weight=1.0, step=None, t_near=0.0, t_far=math.inf, pyramid_iters=None, d_rgb=None,
+                     photo_weight=None, i_max=None):
+        """track() from a raster in HBM (d_depth: [H][W] of depth_dtype at a raw device address; cam: ctx.camera(...)); d_rgb: the
+        frame's colour image, [H][W][3] uint8 at a raw device address, for the colour term.  Synchronises (the pose is read
+        back)."""
+        if d_rgb is not None:
+            self._check_track_color(pyramid_iters, photo_weight, i_max)
         levels = None
         if pyramid_iters is not None:
             from .tracking import pyramid_levels
@@ -404,12 +417,22 @@ class TSDFVolume:
                                                         pose.ctypes.data, info.ctypes.data, rms.ctypes.data))
             return pose, {"pairs": float(info[0]), "rms": float(info[1]), "status": int(info[2]), "iterations": int(info[3]),
                           "rms_history": rms[:sum(levels)].tolist()}
+        if d_rgb is not None:
+            from .tracking import photo_args
+            wp, im = photo_args(photo_weight, i_max)
+            info = np.zeros(6, dtype=np.float64)
+            L.check(self.ctx.lib.r3d_tsdf_track_rgb(self.handle, cam.handle, d_depth, depth_code(depth_dtype), float(depth_scale), d_rgb,
+                                                    guess.ctypes.data, mw, s, tn, tf, mj, dm, cos_min, wp, im, n, pose.ctypes.data,
+                                                    info.ctypes.data))
+            return pose, {"pairs": float(info[0]), "rms": float(info[1]), "status": int(info[2]), "iterations": int(info[3]),
+                          "photo_pairs": float(info[4]), "photo_rms": float(info[5])}
         L.check(self.ctx.lib.r3d_tsdf_track(self.handle, cam.handle, d_depth, depth_code(depth_dtype), float(depth_scale),
                                             guess.ctypes.data, mw, s, tn, tf, mj, dm, cos_min, n, pose.ctypes.data, info.ctypes.data))
         return pose, {"pairs": float(info[0]), "rms": float(info[1]), "status": int(info[2]), "iterations": int(info[3])}
 
     def track(self, depth, pose_guess_w2c, intrinsics=REF_INTRINSICS, n_iters=10, dist_max=None, max_angle_deg=None, depth_scale=1.0,
-              max_jump=0.05, min_weight=1.0, step=None, t_near=0.0, t_far=math.inf, pyramid_iters=None):
+              max_jump=0.05, min_weight=1.0, step=None, t_near=0.0, t_far=math.inf, pyramid_iters=None, rgb=None, photo_weight=None,
+              i_max=None):
         """The pose of a new depth raster [H,W] against the model, from a guess (12 doubles, world -> camera: R row-major, t --
         a row of poses_w2c): the volume is ray-cast at the guess, and n_iters iterations of projective point-to-plane ICP move
         the frame onto the predicted vertex and normal map (a source point's partner is the model pixel it projects to).
@@ -422,7 +445,19 @@ class TSDFVolume:
         motions only.  pyramid_iters: a sequence of iteration counts, fine to coarse, e.g. (10, 5, 4): the loop runs coarse to
         fine over a depth pyramid (every level halves the raster; the model is ray-cast at every level's camera) and follows
         larger motions; n_iters is then not used, and info gains "rms_history", the rms of every step in the order they ran
-        (include/r3d.h "Depth pyramid").  Synchronous."""
+        (include/r3d.h "Depth pyramid").  rgb (a volume with colour; not with pyramid_iters): the frame's colour image [H,W,3]
+        uint8; the loop then carries a photometric term next to the geometric one -- the difference between the frame's
+        intensity and that of the colour image the model predicts at the guess -- which holds the freedoms that planes leave
+        open (sliding along a corridor, over a wall or a floor), where depth alone ends with status 1.  photo_weight: the weight
+        of a photometric pair against a geometric pair's 1, in metres^2 per intensity^2 (None: tracking.PHOTO_WEIGHT); i_max:
+        pairs whose intensities differ by more are left out (None: tracking.I_MAX); info gains "photo_pairs" and "photo_rms"
+        (include/r3d.h "TSDF colour tracking").  Synchronous."""
+        if rgb is not None:
+            self._check_track_color(pyramid_iters, photo_weight, i_max)
+            img = np.asarray(rgb)
+            if img.dtype != np.uint8 or img.shape != np.shape(depth) + (3,):
+                raise ValueError("rgb must be a uint8 %s image, got %s of shape %s" % (list(np.shape(depth)) + [3], img.dtype, list(img.shape)))
+            img = np.ascontiguousarray(img)
         d = np.asarray(depth)
         if d.ndim != 2 or d.shape[0] < 1 or d.shape[1] < 1:
             raise ValueError("depth must be one [H,W] raster, got shape %s" % (list(d.shape),))
@@ -439,24 +474,31 @@ class TSDFVolume:
             raise ValueError("pose_guess_w2c must be 12 finite numbers (R row-major, t), got shape %s" % (list(guess.shape),))
         cam = self.ctx.camera(d.shape[0], d.shape[1], *intrinsics)
         buf = self.ctx.alloc(d.nbytes).upload(d)
+        cbuf = None if rgb is None else self.ctx.alloc(img.nbytes).upload(img)
         try:
             return self.track_device(cam, buf.ptr, d.dtype, guess, n_iters, dist_max, max_angle_deg, depth_scale, max_jump, min_weight,
-                                     step, t_near, t_far, pyramid_iters)
+                                     step, t_near, t_far, pyramid_iters, None if cbuf is None else cbuf.ptr, photo_weight, i_max)
         finally:
             buf.free()
+            if cbuf is not None:
+                cbuf.free()
 
-    def track_and_integrate(self, depths, first_pose_w2c, intrinsics=REF_INTRINSICS, depth_scale=1.0, **track_args):
+    def track_and_integrate(self, depths, first_pose_w2c, intrinsics=REF_INTRINSICS, depth_scale=1.0, rgbs=None, **track_args):
         """Reconstruct from depth rasters [F,H,W] and ONE pose: frame 0 is integrated at first_pose_w2c (12 doubles, world ->
         camera); every later frame is tracked against the model from the previous frame's pose (track(); track_args are its
         keyword arguments, pyramid_iters among them) and integrated at the pose found.  Returns the [F,12] float64 pose rows.
-        Raises RuntimeError when a frame cannot be tracked (status 1); the frames before it stay integrated.  A volume without
-        colour only."""
-        if self.color:
+        Raises RuntimeError when a frame cannot be tracked (status 1); the frames before it stay integrated.  rgbs (a volume
+        with colour): the frames' colour images [F,H,W,3] uint8; every frame is then tracked with the colour term (track(rgb=);
+        photo_weight and i_max among track_args) and integrated with its colour.  Without rgbs: a volume without colour only."""
+        if rgbs is None and self.color:
             raise ValueError("track_and_integrate takes depth rasters only: the volume was created with color=True")
+        if rgbs is not None:
+            self._check_track_color(track_args.get("pyramid_iters"), track_args.get("photo_weight"), track_args.get("i_max"))
         if np.asarray(depths).dtype not in (np.uint8, np.uint16, np.float32):
             raise ValueError("depths must be uint8, uint16 or float32, got %s" % np.asarray(depths).dtype)
         d = _as_batch(depths)
         f, h, w = d.shape
+        img = None if rgbs is None else _rgb_batch(rgbs, d.shape)
         first = np.asarray(first_pose_w2c, dtype=np.float64)
         if first.size != 12 or not np.isfinite(first).all():
             raise ValueError("first_pose_w2c must be 12 finite numbers (R row-major, t), got shape %s" % (list(first.shape),))
@@ -472,18 +514,24 @@ class TSDFVolume:
             return poses
         cam = self.ctx.camera(h, w, *intrinsics)
         buf = self.ctx.alloc(d[0].nbytes)
+        cbuf = None if img is None else self.ctx.alloc(img[0].nbytes)
         try:
             for k in range(f):
                 buf.upload(d[k])
+                if cbuf is not None:
+                    cbuf.upload(img[k])
                 if k == 0:
                     poses[0] = first.reshape(12)
                 else:
-                    poses[k], info = self.track_device(cam, buf.ptr, d.dtype, poses[k - 1], depth_scale=depth_scale, **track_args)
+                    poses[k], info = self.track_device(cam, buf.ptr, d.dtype, poses[k - 1], depth_scale=depth_scale,
+                                                       d_rgb=None if cbuf is None else cbuf.ptr, **track_args)
                     if info["status"] != 0:
                         raise RuntimeError("frame %d cannot be tracked against the model: %d pairs, the step is degenerate"
                                            % (k, int(info["pairs"])))
-                self.integrate_device(cam, buf.ptr, d.dtype, 1, poses[k:k + 1], depth_scale)
+                self.integrate_device(cam, buf.ptr, d.dtype, 1, poses[k:k + 1], depth_scale, d_rgb=None if cbuf is None else cbuf.ptr)
             self.ctx.sync()
         finally:
             buf.free()
+            if cbuf is not None:
+                cbuf.free()
         return poses

@@ -876,7 +876,7 @@ int r3d_tsdf_raycast_rgb(r3d_tsdf* vol, const r3d_camera* cam, int n_views, cons
  *   input map or another output (r3d_tsdf_track: a host output overlapping the guess or the other output), a raster of
  *   2^31 - 1024 pixels or more; r3d_tsdf_track also: a non-finite guess, max_jump < 0, and the argument errors of
  *   r3d_tsdf_integrate (depth) and r3d_tsdf_raycast.  Coarse-to-fine passes over an image pyramid: r3d_tsdf_track_pyramid
- *   ("Depth pyramid", below).  Not done here: photometric (colour) terms. */
+ *   ("Depth pyramid", below).  Photometric (colour) terms: "TSDF colour tracking", further below (one level; not in the pyramid). */
 int r3d_track_accumulate(r3d_ctx* ctx, const r3d_camera* cam, const float* d_src_vertex, const float* d_src_normal,
                          const float* d_model_vertex, const float* d_model_normal, const double* h_model_pose_w2c, const double* h_S,
                          double dist_max, double cos_min, double* h_sums, int32_t* d_match_out, float* d_residual_out);
@@ -941,6 +941,84 @@ int r3d_tsdf_track_pyramid(r3d_tsdf* vol, const r3d_camera* const* cams, int n_l
                            int depth_dtype, double depth_scale, const double* h_pose_guess_w2c, double min_weight, double step,
                            double t_near, double t_far, float max_jump, double dist_max, double cos_min, double* h_pose_out,
                            double* h_info_out, double* h_rms_out);
+
+/* ---- TSDF colour tracking (csrc/r3d_photo.hip and the sibling kernel and drivers in csrc/r3d_track.hip; NOT IN THE REFERENCE, this
+ * text is the specification).  Point-to-plane ICP alone is blind wherever the geometry leaves a freedom open -- sliding along a
+ * corridor, over one wall or a floor: r3d_tsdf_track then reports status 1.  A volume with colour predicts a colour image for the
+ * guess (r3d_tsdf_raycast_rgb), and the frame brings its own: the difference of their intensities constrains what the planes do not.
+ * The linearised photometric residual has the Jacobian shape of the geometric one -- with a the image gradient pulled back to a
+ * world-space 3-vector, J = [p x a ; a] where the plane term has [p x n ; n] -- so a photometric pair enters the same 6 x 6 normal
+ * equations through the same arithmetic; the reduction, the solve and the ICP state are the ones of "TSDF tracking".  Nothing of
+ * "TSDF tracking" changes: r3d_track_accumulate, r3d_track_iterate, r3d_tsdf_track and r3d_tsdf_track_pyramid return the bits they
+ * returned.  Not yet timed on a card.
+ * r3d_intensity_map: one launch, one lane per pixel, asynchronous on the ctx stream.  d_rgb is [H][W][3] uint8 in R, G, B order (the
+ *   layout of r3d_tsdf_integrate_rgb and r3d_tsdf_raycast_rgb).  d_valid is a float raster read as d_valid[(v W + u) valid_stride],
+ *   valid_stride 1 or 3 as in r3d_depth_half: 1 reads a depth raster (the model side passes the ray-cast depth), 3 the z column of a
+ *   camera-frame vertex map (the source side passes src_vertex + 2).  A pixel is valid iff its value is finite and > 0.
+ *   max_jump >= 0; +inf is allowed.  Outputs, either may be NULL (both NULL: a valid no-op): d_intensity_out [H][W] f32;
+ *   d_packed_out [H][W][4] f32 {I, gx, gy, 0}, 16-byte aligned so that one tap is one 16-byte load.  All f32, in the order written,
+ *   no fused multiply-add:
+ *     I  = (0.299f R + 0.587f G) + 0.114f B, in 0..255; NaN where the pixel is invalid
+ *     gx = 0.5f (I(u + 1) - I(u - 1)); NaN if u is 0 or W - 1, if the pixel or either neighbour is invalid, or if
+ *          |d(u +- 1) - d(u)| > max_jump for either neighbour (d = the validity raster's value): no gradient is taken across a depth
+ *          edge
+ *     gy   the same along v
+ *   The neighbours' intensities are recomputed from their bytes (there is no second pass); the result does not depend on the launch
+ *   geometry; nothing outside the outputs' extents is written.
+ *   R3D_ERR_INVALID, nothing written: a NULL required pointer (ctx, d_rgb, d_valid), valid_stride not 1 or 3, H < 1 or W < 1,
+ *   max_jump NaN or negative, d_packed_out not 16-byte aligned, an output overlapping an input (the validity extent is
+ *   ((H W - 1) valid_stride + 1) floats) or the other output, a raster of 2^31 - 1024 pixels or more.
+ * The association pass with a colour term has the tile of "TSDF tracking" (256 threads own 1024 consecutive pixels, thread t takes
+ *   base + t + 256 k), so its launch shape is part of the specification in the same way.  Extra inputs: d_src_intensity [H][W] f32
+ *   (r3d_intensity_map's first output for the frame), d_model_packed [H][W][4] f32, 16-byte aligned (its second output for the
+ *   model's colour image), w_photo >= 0 finite (the weight of a photometric pair against a geometric pair's 1, in metres^2 per
+ *   intensity^2), i_max > 0 finite.  Steps 1..10 are those of "TSDF tracking", word for word.  Then, for a pixel whose geometric
+ *   pair was accepted (code >= 0), all in fp64, left to right, no fused multiply-add:
+ *  11. with u, v, pm of step 5: u0 = floor(u), v0 = floor(v); no photometric pair unless 0 <= u0, u0 + 1 <= W - 1, 0 <= v0 and
+ *      v0 + 1 <= H - 1, compared as doubles; fu = u - u0, fv = v - v0
+ *  12. the four packed model taps t00 = (v0, u0), t01 = (v0, u0 + 1), t10 = (v0 + 1, u0), t11 = (v0 + 1, u0 + 1); for each of I, gx,
+ *      gy: top = t00 + fu (t01 - t00); bot = t10 + fu (t11 - t10); val = top + fv (bot - top).  A NaN tap makes val NaN: that is
+ *      the validity test, there is no separate mask
+ *  13. rI = Im - Is, Is = the source intensity of pixel i
+ *  14. b0 = (gx fx) / pm_2;  b1 = (gy fy) / pm_2;  b2 = -((gx fx) pm_0 + (gy fy) pm_1) / (pm_2 pm_2);
+ *      a_c = (Rm[0][c] b0 + Rm[1][c] b1) + Rm[2][c] b2: Rm^T b, the gradient as a world-space vector
+ *  15. no photometric pair unless rI, a_0, a_1, a_2 are all finite and |rI| <= i_max
+ *  16. with w = w_photo and J = [p x a ; a]: [2 + k] += (w J_k) rI; [8..28] += the upper triangle of (w J_k) J_l (pair_accumulate's
+ *      order); [29] += 1; [30] += rI rI
+ *   Sums [0] and [1] stay purely geometric -- the pair count and sum r^2 in metres -- so the state's pairs, rms and rms history and
+ *   the n >= 6 test of the solve mean what they mean in "TSDF tracking".  31 sums, reduced as the 29 are there; the step is solved
+ *   from the first 29.  Per-pixel outputs: d_match_out and d_residual_out as r3d_track_accumulate's, the same bits; d_photo_out
+ *   [H W] f32 = (float) rI where a photometric pair entered, NaN elsewhere.  Each may be NULL.
+ * r3d_track_accumulate_rgb: r3d_track_accumulate with the colour term; h_sums receives 31 doubles.  With w_photo == 0 the first 29,
+ *   the match and the residual are the bits r3d_track_accumulate gives (step 15 keeps non-finite terms out).  Synchronous.
+ * r3d_track_iterate_rgb: r3d_track_iterate with the colour term, on the same R3D_ICP_STATE_DOUBLES state.  Asynchronous.
+ * r3d_tsdf_track_rgb: the whole step for one frame, one level: r3d_tsdf_raycast_rgb at the guess (depth, vertex, normal, rgb);
+ *   r3d_intensity_map of the model's image with the ray-cast depth as validity (stride 1, max_jump), packed output;
+ *   r3d_unproject of the frame's depth; r3d_intensity_map of d_rgb ([H][W][3] uint8) with the z column of the source vertex map as
+ *   validity (stride 3, max_jump), intensity output only; source normals when cos_min > -1; a state reset; n_iters passes; pose and
+ *   info read back exactly as r3d_tsdf_track does (status 1 gives the guess back bit for bit).  h_info_out = 6 doubles: the four
+ *   of r3d_tsdf_track, then the photometric pair count and the photometric rms sqrt([30] / [29]) the last step saw (0 with no pair
+ *   or no step).  Everything lives in the context's scratch: nothing is allocated per call after the first.
+ * R3D_ERR_INVALID, nothing written, all checked before anything is enqueued: every argument error of the call each extends; a NULL
+ *   d_src_intensity, d_model_packed or d_rgb; a d_model_packed that is not 16-byte aligned; w_photo negative or not finite; i_max
+ *   not > 0 and finite; a device output overlapping an input (the two new maps included) or another output; r3d_tsdf_track_rgb on
+ *   a volume without the colour plane.
+ * Deliberately not done here: a colour term in r3d_tsdf_track_pyramid (it needs a depth-consistent intensity half-sampler), and
+ *   robust (Huber) weights. */
+int r3d_intensity_map(r3d_ctx* ctx, const uint8_t* d_rgb, const float* d_valid, int valid_stride, int height, int width, float max_jump,
+                      float* d_intensity_out, float* d_packed_out);
+int r3d_track_accumulate_rgb(r3d_ctx* ctx, const r3d_camera* cam, const float* d_src_vertex, const float* d_src_normal,
+                             const float* d_model_vertex, const float* d_model_normal, const double* h_model_pose_w2c, const double* h_S,
+                             double dist_max, double cos_min, const float* d_src_intensity, const float* d_model_packed, double w_photo,
+                             double i_max, double* h_sums, int32_t* d_match_out, float* d_residual_out, float* d_photo_out);
+int r3d_track_iterate_rgb(r3d_ctx* ctx, const r3d_camera* cam, const float* d_src_vertex, const float* d_src_normal,
+                          const float* d_model_vertex, const float* d_model_normal, const double* h_model_pose_w2c, const double* h_S,
+                          double dist_max, double cos_min, const float* d_src_intensity, const float* d_model_packed, double w_photo,
+                          double i_max, int n_iters, double* d_state);
+int r3d_tsdf_track_rgb(r3d_tsdf* vol, const r3d_camera* cam, const void* d_depth, int depth_dtype, double depth_scale,
+                       const uint8_t* d_rgb, const double* h_pose_guess_w2c, double min_weight, double step, double t_near, double t_far,
+                       float max_jump, double dist_max, double cos_min, double w_photo, double i_max, int n_iters, double* h_pose_out,
+                       double* h_info_out);
 
 #ifdef __cplusplus
 }
