@@ -193,6 +193,8 @@ SIGNATURES = {
     "r3d_track_accumulate_rgb": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _vp, _vp, _d, _d, _vp, _vp, _vp, _vp]),
     "r3d_track_iterate_rgb": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _vp, _vp, _d, _d, _i, _vp]),
     "r3d_tsdf_track_rgb": (_i, [_vp, _vp, _vp, _i, _d, _vp, _vp, _d, _d, _d, _d, _f, _d, _d, _d, _d, _i, _vp, _vp]),
+    "r3d_bilateral_weights": (_i, [_i, _d, _d, _vp, _vp, _vp, _vp]),
+    "r3d_depth_bilateral": (_i, [_vp, _vp, _i, _i, _i, _i, _d, _d, _vp]),
 }
 
 _lib = None

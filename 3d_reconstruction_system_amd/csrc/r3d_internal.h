@@ -57,9 +57,14 @@ struct r3d_ctx {
   // HIP-event stopwatch
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;
   // grow-only scratch buffers for the *_host entry points and reductions
-  static constexpr int kScratchSlots = 8;   // 6, 7: point-to-plane / selection workspace (r3d_plane.hip)
+  static constexpr int kScratchSlots = 9;   // 6, 7: point-to-plane / selection workspace (r3d_plane.hip); 8: the bilateral
+                                            // filter's weight tables (r3d_bilateral.hip), which no other call may touch
   void* scratch[kScratchSlots] = {};
   size_t scratch_bytes[kScratchSlots] = {};
+  // the (radius, sigma_s, sigma_r) whose tables sit in slot 8: a repeated r3d_depth_bilateral uploads nothing.  radius -1 =
+  // none; the call validates its arguments before it compares them with this key, so no call matches the empty key
+  int bilateral_radius = -1;
+  double bilateral_sigma_s = 0, bilateral_sigma_r = 0;
   // pinned staging buffers of the host pipeline: slot = ((direction * kPipeBufs + array) * 2 + parity)
   static constexpr int kPipeBufs = 2;   // arrays per direction (depth + colour in, xyz + rgba out)
   static constexpr int kPinnedSlots = 2 * kPipeBufs * 2;

@@ -3,7 +3,7 @@
 truncated signed distance volume instead, and the volume's zero level set is written as oriented surface points.
 
     python integrate_tsdf.py --voxel-size S --trunc T [--origin X Y Z] [--dims NX NY NZ] [--margin M] [--min-weight W] [--mesh]
-                             [--raycast] [--color-dir DIR] [--raycast-color] [--track [--track-pyramid N0,N1,..] [--track-color [--photo-weight W] [--track-max-jump D]]]
+                             [--raycast] [--color-dir DIR] [--raycast-color] [--track [--track-pyramid N0,N1,..] [--track-bilateral R,SIGMA_S,SIGMA_R] [--track-color [--photo-weight W] [--track-max-jump D]]]
 
 Run from a directory holding ./camera_pose/image_colmap_simi_2.txt and ./depth/ (the inputs of camera_to_world.py; the same
 environment overrides apply: R3D_FX .. R3D_CY, R3D_POSE_SCALE, R3D_DEVICE).  Writes ./ply/tsdf_surface.ply: binary PLY, float
@@ -33,6 +33,9 @@ tracking.PHOTO_WEIGHT, chosen for metres); --track-max-jump D the depth step, in
 is taken (default 0.05, for metres).  Both scale with the unit of the depth maps.
 --track-pyramid N0,N1,.. (with --track) tracks coarse to fine over a depth pyramid: N0 iterations at full size, N1 on the halved
 rasters and so on, e.g. 10,5,4; the coarse levels run first and let the loop follow larger motions between frames.
+--track-bilateral R,SIGMA_S,SIGMA_R (with --track; combines with --track-pyramid and --track-color) tracks every frame on a
+bilateral-filtered copy of its depth map -- a window of (2 R + 1)^2 pixels, SIGMA_S in pixels, SIGMA_R in length units; depths
+more than 3 SIGMA_R apart never mix -- which keeps sensor noise out of the normals and residuals; the raw maps are integrated.
 """
 import argparse
 import math
@@ -74,6 +77,9 @@ def parse_args(argv):
                    help="use only the first pose of the pose file, estimate the others by tracking and write them to %s" % TRACKED_FILE)
     p.add_argument("--track-pyramid", metavar="N0,N1,..", default=None,
                    help="with --track: iterations per pyramid level, fine to coarse (e.g. 10,5,4): track coarse to fine")
+    p.add_argument("--track-bilateral", metavar="R,SIGMA_S,SIGMA_R", default=None,
+                   help="with --track: track on a bilateral-filtered copy of every frame (window radius in pixels, sigma in pixels, "
+                        "sigma in length units, e.g. 3,2.0,0.03); the raw frames are integrated")
     p.add_argument("--track-color", action="store_true",
                    help="with --track and --color-dir: track with the colour term too and integrate the colour images")
     p.add_argument("--photo-weight", type=float, default=None,
@@ -92,6 +98,16 @@ def parse_args(argv):
             p.error("--track-pyramid takes integers separated by commas, got %r" % args.track_pyramid)
         if not 1 <= len(args.track_pyramid) <= 8 or min(args.track_pyramid) < 0:
             p.error("--track-pyramid takes 1 to 8 iteration counts >= 0, got %r" % (args.track_pyramid,))
+    if args.track_bilateral is not None:
+        if not args.track:
+            p.error("--track-bilateral needs --track")
+        try:
+            r, sigma_s, sigma_r = args.track_bilateral.split(",")
+            args.track_bilateral = (int(r), float(sigma_s), float(sigma_r))
+        except ValueError:
+            p.error("--track-bilateral takes R,SIGMA_S,SIGMA_R (an integer and two numbers), got %r" % args.track_bilateral)
+        if not (0 <= args.track_bilateral[0] <= 8 and 0.0 < args.track_bilateral[1] < math.inf and 0.0 < args.track_bilateral[2] < math.inf):
+            p.error("--track-bilateral takes a radius in 0..8 and two finite sigmas > 0, got %r" % (args.track_bilateral,))
     if args.track_color and not (args.track and args.color_dir is not None):
         p.error("--track-color needs --track and the colour images (--color-dir)")
     if args.track_color and args.track_pyramid is not None:
@@ -241,7 +257,7 @@ def main(argv=None):
         try:
             tracked = vol.track_and_integrate(depths, r3d.poses_w2c(quats[:1], ts[:1])[0], intrinsics=_common.intrinsics(),
                                               min_weight=args.min_weight, pyramid_iters=args.track_pyramid,
-                                              rgbs=rgb if args.track_color else None,
+                                              bilateral=args.track_bilateral, rgbs=rgb if args.track_color else None,
                                               **({"photo_weight": args.photo_weight, "max_jump": 0.05 if args.track_max_jump is None
                                                   else args.track_max_jump} if args.track_color else {}))
         except (RuntimeError, ValueError) as e:

@@ -10,6 +10,9 @@ depth pyramid (depth_half, pyramid_intrinsics, pyramid_shape: include/r3d.h "Dep
 With a colour volume the loop can carry a photometric term next to the geometric one (include/r3d.h "TSDF colour tracking",
 DESIGN.md section 4.5p): intensity_map makes the intensity and gradient maps both sides read, TrackDevice takes them as
 src_intensity= / model_packed= and runs sums_rgb / iterate_rgb, and TSDFVolume.track(rgb=) is the whole step.
+
+depth_bilateral smooths a depth raster without mixing surfaces, from the host-made weight tables bilateral_weights returns
+(include/r3d.h "Depth bilateral filter"); TSDFVolume.track(bilateral=) tracks on the filtered frame.
 """
 import numpy as np
 
@@ -89,6 +92,63 @@ def depth_half(depth, max_jump, ctx=None):
     try:
         L.check(c.lib.r3d_depth_half(c.handle, d_in.ptr, 1, h, w, mj, d_out.ptr))
         return d_out.download(np.float32, oh * ow).reshape(oh, ow)
+    finally:
+        d_in.free()
+        d_out.free()
+
+
+MAX_BILATERAL_RADIUS = 8                    # R3D_BILATERAL_MAX_RADIUS
+BILATERAL_RANGE_BINS = 256                  # R3D_BILATERAL_RANGE_BINS
+
+
+def bilateral_args(bilateral):
+    """(radius, sigma_s, sigma_r) of a `bilateral=` argument as the library takes them; ValueError otherwise"""
+    try:
+        radius, sigma_s, sigma_r = bilateral
+        exact = not isinstance(radius, (bool, str, bytes)) and int(radius) == radius
+        radius, sigma_s, sigma_r = int(radius), float(sigma_s), float(sigma_r)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("bilateral must be (radius, sigma_s, sigma_r), got %r" % (bilateral,))
+    if not exact or not 0 <= radius <= MAX_BILATERAL_RADIUS:
+        raise ValueError("the bilateral radius must be an integer in [0, %d], got %r" % (MAX_BILATERAL_RADIUS, bilateral[0]))
+    if not (np.isfinite(sigma_s) and sigma_s > 0.0 and np.isfinite(sigma_r) and sigma_r > 0.0):
+        raise ValueError("sigma_s and sigma_r must be finite and > 0, got %r and %r" % (sigma_s, sigma_r))
+    with np.errstate(over="ignore", under="ignore"):
+        cut, inv_step = np.float32(3.0 * sigma_r), np.float32(BILATERAL_RANGE_BINS / (3.0 * sigma_r))
+    if not (np.isfinite(cut) and cut > 0.0 and np.isfinite(inv_step) and inv_step > 0.0):
+        raise ValueError("sigma_r = %r leaves the float32 range (cut %r, inv_step %r)" % (sigma_r, cut, inv_step))
+    return radius, sigma_s, sigma_r
+
+
+def bilateral_weights(radius, sigma_s, sigma_r):
+    """The weight tables of the depth bilateral filter exactly as the device call uses them (include/r3d.h "Depth bilateral
+    filter"): (spatial [2r+1, 2r+1] float32, range [256] float32, cut, inv_step).  spatial[dy + r, dx + r] =
+    exp(-(dx^2 + dy^2) / (2 sigma_s^2)), sigma_s in pixels; range[k] = exp(-0.5 (3 k / 256)^2); cut = 3 sigma_r (metres) and
+    inv_step = 256 / cut, as float32.  Host only: needs the library, not a GPU."""
+    r, ss, sr = bilateral_args((radius, sigma_s, sigma_r))
+    import ctypes as C
+    spatial, rng = np.zeros((2 * r + 1, 2 * r + 1), dtype=np.float32), np.zeros(BILATERAL_RANGE_BINS, dtype=np.float32)
+    cut, inv_step = C.c_float(0.0), C.c_float(0.0)
+    L.check(L.load().r3d_bilateral_weights(r, ss, sr, spatial.ctypes.data, rng.ctypes.data, C.addressof(cut), C.addressof(inv_step)))
+    return spatial, rng, float(cut.value), float(inv_step.value)
+
+
+def depth_bilateral(depth, radius, sigma_s, sigma_r, ctx=None):
+    """The bilateral-filtered [H,W] float32 raster of a host [H,W] float32 depth raster: every valid (finite, > 0) pixel becomes
+    the weighted mean of the valid depths of its (2 radius + 1)^2 window that lie within 3 sigma_r (metres) of it, weighted by
+    a Gaussian of sigma_s pixels in the image and of sigma_r in depth (bilateral_weights' tables); an invalid pixel becomes 0.
+    Surfaces more than 3 sigma_r apart never mix; radius 0 returns the valid depths as they are."""
+    d = np.asarray(depth)
+    if d.dtype != np.float32 or d.ndim != 2 or d.shape[0] < 1 or d.shape[1] < 1:
+        raise ValueError("depth must be a float32 [H,W] raster, got %s of shape %s" % (d.dtype, list(d.shape)))
+    r, ss, sr = bilateral_args((radius, sigma_s, sigma_r))
+    d = np.ascontiguousarray(d)
+    c = ctx or default_context()
+    h, w = d.shape
+    d_in, d_out = c.alloc(d.nbytes).upload(d), c.alloc(d.nbytes)
+    try:
+        L.check(c.lib.r3d_depth_bilateral(c.handle, d_in.ptr, 1, h, w, r, ss, sr, d_out.ptr))
+        return d_out.download(np.float32, h * w).reshape(h, w)
     finally:
         d_in.free()
         d_out.free()

@@ -111,10 +111,12 @@ class TSDFVolume:
         create = self.ctx.lib.r3d_tsdf_create_rgb if self.color else self.ctx.lib.r3d_tsdf_create
         L.check(create(self.ctx.handle, o.ctypes.data, vs, nx, ny, nz, tr, C.byref(h)))
         self.handle = h.value
+        self._bilateral_bufs = None   # (pixels, vertex map, filtered raster) of track(bilateral=): _bilateral_raster
         self.ctx.adopt(self)
 
     def close(self):
         if self.handle:
+            self._free_bilateral()
             self.ctx.lib.r3d_tsdf_destroy(self.handle)
             self.handle = None
 
@@ -389,12 +391,15 @@ class TSDFVolume:
 
     def track_device(self, cam, d_depth, depth_dtype, pose_guess_w2c, n_iters=10, dist_max=None, max_angle_deg=None, depth_scale=1.0,
                      max_jump=0.05, min_weight=1.0, step=None, t_near=0.0, t_far=math.inf, pyramid_iters=None, d_rgb=None,
-                     photo_weight=None, i_max=None):
+                     photo_weight=None, i_max=None, bilateral=None):
         """track() from a raster in HBM (d_depth: [H][W] of depth_dtype at a raw device address; cam: ctx.camera(...)); d_rgb: the
-        frame's colour image, [H][W][3] uint8 at a raw device address, for the colour term.  Synchronises (the pose is read
-        back)."""
+        frame's colour image, [H][W][3] uint8 at a raw device address, for the colour term.  bilateral: as in track(); d_depth
+        itself is only read.  Synchronises (the pose is read back)."""
         if d_rgb is not None:
             self._check_track_color(pyramid_iters, photo_weight, i_max)
+        if bilateral is not None:
+            from .tracking import bilateral_args
+            bilateral = bilateral_args(bilateral)
         levels = None
         if pyramid_iters is not None:
             from .tracking import pyramid_levels
@@ -404,6 +409,8 @@ class TSDFVolume:
         if not np.isfinite(guess).all():
             raise ValueError("pose_guess_w2c must be finite")
         pose, info = np.zeros(12, dtype=np.float64), np.zeros(4, dtype=np.float64)
+        if bilateral is not None:
+            d_depth, depth_dtype, depth_scale = self._bilateral_raster(cam, d_depth, depth_dtype, depth_scale, bilateral), np.float32, 1.0
         if levels is not None:
             from .tracking import pyramid_intrinsics, pyramid_shape
             K = (cam.fx, cam.fy, cam.cx, cam.cy)
@@ -430,9 +437,30 @@ class TSDFVolume:
                                             guess.ctypes.data, mw, s, tn, tf, mj, dm, cos_min, n, pose.ctypes.data, info.ctypes.data))
         return pose, {"pairs": float(info[0]), "rms": float(info[1]), "status": int(info[2]), "iterations": int(info[3])}
 
+    def _bilateral_raster(self, cam, d_depth, depth_dtype, depth_scale, bilateral):
+        """The device address of the bilateral-filtered f32 depth raster (metres) of a frame in HBM: the frame is unprojected once
+        (its dtype and scale), and the z column of that vertex map is filtered (include/r3d.h "Depth bilateral filter").  Both
+        buffers belong to the volume: allocated on first use, reused while the raster size holds.  Asynchronous."""
+        n = cam.height * cam.width
+        if self._bilateral_bufs is None or self._bilateral_bufs[0] != n:
+            self._free_bilateral()
+            self._bilateral_bufs = (n, self.ctx.alloc(n * 12), self.ctx.alloc(n * 4))
+        _, vertex, raster = self._bilateral_bufs
+        L.check(self.ctx.lib.r3d_unproject(self.ctx.handle, cam.handle, d_depth, depth_code(depth_dtype), 1, float(depth_scale),
+                                           vertex.ptr, L.F32))
+        L.check(self.ctx.lib.r3d_depth_bilateral(self.ctx.handle, vertex.ptr + 8, 3, cam.height, cam.width, *bilateral, raster.ptr))
+        return raster.ptr
+
+    def _free_bilateral(self):
+        if self._bilateral_bufs is not None:
+            self.ctx.sync()
+            for b in self._bilateral_bufs[1:]:
+                b.free()
+            self._bilateral_bufs = None
+
     def track(self, depth, pose_guess_w2c, intrinsics=REF_INTRINSICS, n_iters=10, dist_max=None, max_angle_deg=None, depth_scale=1.0,
               max_jump=0.05, min_weight=1.0, step=None, t_near=0.0, t_far=math.inf, pyramid_iters=None, rgb=None, photo_weight=None,
-              i_max=None):
+              i_max=None, bilateral=None):
         """The pose of a new depth raster [H,W] against the model, from a guess (12 doubles, world -> camera: R row-major, t --
         a row of poses_w2c): the volume is ray-cast at the guess, and n_iters iterations of projective point-to-plane ICP move
         the frame onto the predicted vertex and normal map (a source point's partner is the model pixel it projects to).
@@ -451,7 +479,13 @@ class TSDFVolume:
         open (sliding along a corridor, over a wall or a floor), where depth alone ends with status 1.  photo_weight: the weight
         of a photometric pair against a geometric pair's 1, in metres^2 per intensity^2 (None: tracking.PHOTO_WEIGHT); i_max:
         pairs whose intensities differ by more are left out (None: tracking.I_MAX); info gains "photo_pairs" and "photo_rms"
-        (include/r3d.h "TSDF colour tracking").  Synchronous."""
+        (include/r3d.h "TSDF colour tracking").  bilateral = (radius, sigma_s, sigma_r): the loop sees a bilateral-filtered copy
+        of the frame instead of the frame -- a window of (2 radius + 1)^2 pixels, sigma_s in pixels, sigma_r in metres; depths
+        more than 3 sigma_r apart never mix -- which keeps a sensor's depth noise out of the source normals and the residuals
+        (include/r3d.h "Depth bilateral filter"); it combines with pyramid_iters and with rgb.  Synchronous."""
+        if bilateral is not None:
+            from .tracking import bilateral_args
+            bilateral_args(bilateral)
         if rgb is not None:
             self._check_track_color(pyramid_iters, photo_weight, i_max)
             img = np.asarray(rgb)
@@ -477,7 +511,8 @@ class TSDFVolume:
         cbuf = None if rgb is None else self.ctx.alloc(img.nbytes).upload(img)
         try:
             return self.track_device(cam, buf.ptr, d.dtype, guess, n_iters, dist_max, max_angle_deg, depth_scale, max_jump, min_weight,
-                                     step, t_near, t_far, pyramid_iters, None if cbuf is None else cbuf.ptr, photo_weight, i_max)
+                                     step, t_near, t_far, pyramid_iters, None if cbuf is None else cbuf.ptr, photo_weight, i_max,
+                                     bilateral)
         finally:
             buf.free()
             if cbuf is not None:
@@ -489,7 +524,11 @@ class TSDFVolume:
         keyword arguments, pyramid_iters among them) and integrated at the pose found.  Returns the [F,12] float64 pose rows.
         Raises RuntimeError when a frame cannot be tracked (status 1); the frames before it stay integrated.  rgbs (a volume
         with colour): the frames' colour images [F,H,W,3] uint8; every frame is then tracked with the colour term (track(rgb=);
-        photo_weight and i_max among track_args) and integrated with its colour.  Without rgbs: a volume without colour only."""
+        photo_weight and i_max among track_args) and integrated with its colour.  Without rgbs: a volume without colour only.
+        With bilateral= among track_args every frame is tracked on its filtered copy and integrated RAW."""
+        if track_args.get("bilateral") is not None:
+            from .tracking import bilateral_args
+            bilateral_args(track_args["bilateral"])
         if rgbs is None and self.color:
             raise ValueError("track_and_integrate takes depth rasters only: the volume was created with color=True")
         if rgbs is not None:

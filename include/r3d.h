@@ -1020,6 +1020,50 @@ int r3d_tsdf_track_rgb(r3d_tsdf* vol, const r3d_camera* cam, const void* d_depth
                        float max_jump, double dist_max, double cos_min, double w_photo, double i_max, int n_iters, double* h_pose_out,
                        double* h_info_out);
 
+/* ---- Depth bilateral filter (csrc/r3d_bilateral.hip; NOT IN THE REFERENCE, this text is the specification).  A sensor's depth
+ * carries millimetres of noise, and r3d_normals_organized differences neighbouring depths: the noise becomes degrees of normal
+ * error, the cos_min gate of tracking throws pairs away and the residuals carry the rest.  The classic remedy is to track on an
+ * edge-preserving smoothing of the raster and to integrate the raw one.  The weights are TABLES made once on the host, so the
+ * kernel does no transcendental arithmetic and its output is reproducible bit for bit from those tables.
+ * Weights (r3d_bilateral_weights; host only, no ctx, no GPU): host doubles, rounded once to f32.  r = radius.
+ *   spatial[(dy + r)(2r + 1) + (dx + r)] = (float) exp(-(dx^2 + dy^2) / (2 sigma_s^2)), dx, dy in -r..r; sigma_s is in pixels
+ *   range[k] = (float) exp(-0.5 t^2) with t = 3.0 k / 256.0, k in 0..255: the LEFT edge of bin k, so range[0] and the centre spatial
+ *              entry are exactly 1.0f
+ *   cut      = (float) (3.0 sigma_r); sigma_r is in metres
+ *   inv_step = (float) (256.0 / (3.0 sigma_r))
+ *   h_spatial receives (2r + 1)^2 floats, h_range R3D_BILATERAL_RANGE_BINS, h_cut and h_inv_step one each.  These are exactly the
+ *   numbers r3d_depth_bilateral uses for the same (radius, sigma_s, sigma_r) (one function makes both): a restatement that takes
+ *   them reproduces the device output bit for bit, whatever the last bit of a libm's exp.
+ *   R3D_ERR_INVALID, nothing written: a NULL pointer, radius outside [0, R3D_BILATERAL_MAX_RADIUS], sigma_s or sigma_r not finite
+ *   or not > 0 (for sigma_r: as a double, and cut and inv_step as f32 -- both must come out finite and > 0).
+ * Filter (r3d_depth_bilateral).  d_in holds the depth of pixel (v, u) at d_in[(v width + u) in_stride], in_stride 1 or 3 as in
+ *   r3d_depth_half: an f32 depth raster, or the z column of a vertex map (the caller passes vertex + 2).  d_out is [height][width]
+ *   f32.  All arithmetic is f32, in the order written, no fused multiply-add, correctly rounded division:
+ *   1. a depth is valid iff it is finite and > 0
+ *   2. output pixel (v, u) with an invalid centre depth dc is 0.0f: no holes are filled
+ *   3. otherwise num = 0.0f, den = 0.0f; then for dy = -r..r (outer) and dx = -r..r (inner), in that order, with d the depth of
+ *      pixel (v + dy, u + dx):
+ *        skip a tap outside the raster; skip an invalid d;
+ *        a = fabsf(d - dc); skip unless a <= cut;
+ *        k = min(255, (int) (a * inv_step));
+ *        w = spatial[dy][dx] * range[k];
+ *        num = num + w * d;  den = den + w
+ *   4. the output is num / den.  The centre tap always enters with w == 1, so den >= 1.
+ *   Properties.  Radius 0 returns the valid inputs bit for bit (and 0.0f for the others).  Two surfaces more than cut apart never
+ *   mix: no depth is invented between them.  The result depends on the pixel's own window only, not on the launch geometry or any
+ *   tuning.  Asynchronous on the ctx stream; nothing outside d_out's extent is written.  The tables are uploaded through the
+ *   context and kept per (radius, sigma_s, sigma_r): a repeated call uploads nothing.  One lane per output pixel, a 32 x 8 tile
+ *   and its halo staged in LDS per workgroup.
+ *   R3D_ERR_INVALID, nothing written: NULL ctx or pointer, in_stride not 1 or 3, height < 1 or width < 1, the argument errors of
+ *   r3d_bilateral_weights, the input extent (((height width - 1) in_stride + 1) floats from d_in) overlapping the output, a raster
+ *   of 2^31 - 1024 pixels or more. */
+#define R3D_BILATERAL_MAX_RADIUS 8
+#define R3D_BILATERAL_RANGE_BINS 256
+int r3d_bilateral_weights(int radius, double sigma_s, double sigma_r, float* h_spatial, float* h_range, float* h_cut,
+                          float* h_inv_step);
+int r3d_depth_bilateral(r3d_ctx* ctx, const float* d_in, int in_stride, int height, int width, int radius, double sigma_s,
+                        double sigma_r, float* d_out);
+
 #ifdef __cplusplus
 }
 #endif

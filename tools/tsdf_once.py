@@ -13,7 +13,8 @@ outside the timed window before every run:
 Roofs are printed from shapes, not measured: algorithmic bytes of the batched form (16 B per voxel and launch + the rasters once)
 against 8 TB/s, and voxel-frames x the per-voxel-frame instruction count of the disassembly against the VALU rate.
 CPU leg, as reported and not optimised against: tests/tsdf_ref.py (NumPy, one thread) on a 64^3 volume and 10 frames.
-usage: tsdf_once.py [reps] [out.json] [cpu: 1|0]"""
+usage: tsdf_once.py [reps] [out.json] [cpu: 1|0]
+       tsdf_once.py bilateral [reps] [out.json]     the depth bilateral filter alone (bilateral_leg below)"""
 import importlib
 import json
 import os
@@ -28,10 +29,61 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 r3d = importlib.import_module("3d_reconstruction_system_amd")
 S = importlib.import_module("3d_reconstruction_system_amd.synthetic")
 T = importlib.import_module("3d_reconstruction_system_amd.tsdf")
+bilateral_only = len(sys.argv) > 1 and sys.argv[1] == "bilateral"
+if bilateral_only:
+    del sys.argv[1]
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 out_path = sys.argv[2] if len(sys.argv) > 2 else None
 cpu_leg = (sys.argv[3] != "0") if len(sys.argv) > 3 else True
 ctx = r3d.Context(0)
+
+
+def bilateral_leg():
+    """r3d_depth_bilateral alone: a noisy room_view raster of 1080 x 1920 and of 480 x 640 in HBM, radius 3 and 6
+    (sigma_s = radius / 1.5 pixels, sigma_r 0.05 m), in_stride 1.  One timed window is CALLS back-to-back calls between two HIP
+    events (a single launch of this size is shorter than the events' own resolution); the figure is the median window of `reps`
+    after two warm-ups, divided by CALLS, the four legs alternating run by run; one untimed call of the leg's parameters goes in
+    front of every window, so the window holds kernels only (the tables are cached by then).  Next to it: one read plus one write of the raster
+    at the HBM rate.  No gate: there is no earlier kernel to compare with."""
+    L = importlib.import_module("3d_reconstruction_system_amd._lib")
+    CALLS = 20
+    legs = []
+    for h, w in ((1080, 1920), (480, 640)):
+        z = S.room_view(h, w, 0.9, np.array([0.3, -0.1, 0.4]), pitch=0.2)[0]
+        z = (z * (1.0 + np.random.default_rng(7).normal(size=z.shape) * 0.005)).astype(np.float32)
+        d_in, d_out = ctx.alloc(z.nbytes).upload(z), ctx.alloc(z.nbytes)
+        for radius in (3, 6):
+            legs.append((h, w, radius, d_in, d_out))
+    times = [[] for _ in legs]
+    for k in range(reps + 2):
+        for i, (h, w, radius, d_in, d_out) in enumerate(legs):
+            # one call of this leg's parameters outside the window: the table build and upload of a changed radius stay out of it
+            L.check(ctx.lib.r3d_depth_bilateral(ctx.handle, d_in.ptr, 1, h, w, radius, radius / 1.5, 0.05, d_out.ptr))
+            ctx.sync()
+            ctx.timer_start()
+            for _ in range(CALLS):
+                L.check(ctx.lib.r3d_depth_bilateral(ctx.handle, d_in.ptr, 1, h, w, radius, radius / 1.5, 0.05, d_out.ptr))
+            t = ctx.timer_stop()
+            if k >= 2:
+                times[i].append(t / CALLS)
+    out = []
+    for (h, w, radius, _, _), t in zip(legs, times):
+        out.append({"kernel": "depth_bilateral", "raster": [h, w], "radius": radius, "reps": reps, "calls_per_window": CALLS,
+                    "ms_per_call_median": round(float(np.median(t)), 5), "ms_per_call_min": round(float(np.min(t)), 5),
+                    "ms_per_call_max": round(float(np.max(t)), 5),
+                    "read_plus_write_at_8TBps_ms": round(2.0 * 4 * h * w / 8.0e12 * 1e3, 5)})
+        print(json.dumps(out[-1]), flush=True)
+    return out
+
+
+if bilateral_only:
+    lines = bilateral_leg()
+    if out_path:
+        with open(out_path, "w") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+    ctx.close()
+    sys.exit(0)
 
 FRAMES, H, W = 100, 384, 1280
 INSTR_PER_VOXEL_FRAME = 125          # from the disassembly of tsdf_integrate_kernel<uint8_t, true>'s frame loop (DESIGN.md 4.5i)
