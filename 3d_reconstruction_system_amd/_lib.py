@@ -159,6 +159,9 @@ SIGNATURES = {
     "r3d_select_rows": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "r3d_segment_plane": (_i, [_vp, _vp, _i64, _d, _i, C.c_uint64, _vp, _vp, _vp, _vp]),
     "r3d_ransac_rows": (_i, [C.c_uint64, C.c_uint64, _i64, _vp]),
+    "r3d_fpfh_knn": (_i, [_vp, _i, _d, _vp, _vp, _vp, _vp]),
+    "r3d_feature_match": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _vp, _vp, _vp, _vp]),
+    "r3d_register_ransac": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _d, _i, C.c_uint64, _vp, _vp, _vp]),
     "r3d_nn_index_knn_stats": (_i, [_vp, _vp]),
     "r3d_sort_u64": (_i, [_vp, _vp, _i64, _i]),
     "r3d_sort_u64_bits": (_i, [_vp, _vp, _i64, _i, _i]),

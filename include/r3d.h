@@ -604,6 +604,87 @@ int r3d_segment_plane(r3d_ctx* ctx, const float* d_xyz, int64_t n, double distan
                       uint8_t* d_inlier_out, uint32_t* d_counts_out, double* h_result, int64_t* n_inliers_out);
 /* The sampler alone (host): rows[j] = r_j(h) for a cloud of n rows.  NULL rows, n < 1 or n >= 2^32 -> R3D_ERR_INVALID. */
 int r3d_ransac_rows(uint64_t seed, uint64_t h, int64_t n, uint32_t* rows);
+/* ---- Global registration: FPFH features, feature matching, RANSAC over correspondences (csrc/r3d_fpfh.hip,
+ * csrc/r3d_register.hip; NOT IN THE REFERENCE -- what users of this kind of pipeline call Open3D's compute_fpfh_feature and
+ * registration_ransac_based_on_feature_matching for, in front of ICP; no parity with Open3D or PCL is claimed, this text is the
+ * specification).  Every output bit is the same on every run and for every launch geometry; all f32 / f64 arithmetic below is
+ * evaluated as written, one rounding per operation, no fused multiply-add, IEEE division and square root.
+ * dot(a, b) = (ax bx + ay by) + az bz and a x b = (ay bz - az by, az bx - ax bz, ax by - ay bx) throughout.
+ *
+ * r3d_fpfh_knn: FPFH of the index's own cloud P (n rows, original order); 3 <= k <= 32; asynchronous on the ctx stream.
+ * d_normals [n][3] f32 as r3d_normals_knn writes them; a row is "no normal" when a component is non-finite or all three are 0.
+ * Neighbourhood: N_i = row i of r3d_nn_index_knn_self(index, k) with its d2 values, in list order, tails dropped, cut when
+ *   radius > 0 at the first entry with d2 > (float)((double) radius * radius) (radius <= 0: no cut).
+ * Pair feature of (i, j), j in N_i, in f32: d = p_j - p_i per component, L = sqrt((dx dx + dy dy) + dz dz).  The pair is skipped
+ *   when L is 0 or non-finite or when i or j has no normal.  a_i = dot(n_i, d), a_j = dot(n_j, d).  If |a_j| > |a_i| the roles
+ *   swap: u = n_j, n_t = n_i, d := -d; otherwise (ties included) u = n_i, n_t = n_j.  d^ = d / L per component; v = d^ x u;
+ *   l_v = sqrt((vx vx + vy vy) + vz vz), the pair is skipped when l_v is 0 or non-finite; v^ = v / l_v; w = u x v^;
+ *   alpha = dot(v^, n_t), phi = dot(u, d^), x = dot(u, n_t), y = dot(w, n_t).  The pair is skipped when one of alpha, phi, x, y
+ *   is non-finite or when x = y = 0.
+ * Bins: 11 per feature, stored in the order theta, alpha, phi (R3D_FPFH_DIM = 33 values per point).  For f = alpha, phi:
+ *   t = (f + 1.0f) * 5.5f, b = 0 when t < 1, 10 when t >= 10, else (int) t.  theta = the direction of (x, y), binned without a
+ *   transcendental: with (c_m, s_m) = R3D_FPFH_THETA_COS / _SIN [m - 1], the f32 roundings of cos / sin of
+ *   beta_m = -pi + 2 pi m / 11, m = 1..10, and cr_m = c_m * y - s_m * x, b_theta = the number of m with
+ *   (y >= 0 || cr_m >= 0) for m <= 5 (beta_m < 0), (y >= 0 && cr_m >= 0) for m >= 6 (beta_m > 0).
+ * SPFH: spfh_i[3][11] = the pairs of point i counted per bin (<= 32: u8) -> d_spfh_out [n][33] u8; c_i = the pairs counted ->
+ *   d_count_out [n] u32.
+ * FPFH (f32): P_j[e] = (float) spfh_j[e] * (100.0f / (float) c_j), all zero when c_j = 0.  A[e] = sum over j in N_i, in list
+ *   order, with d2_ij finite and > 0 (the list's value), of P_j[e] / d2_ij, from 0.0f.  T[s] = sum_b A[s][b], b ascending, from
+ *   0.0f.  d_fpfh_out[i][s][b] = P_i[s][b] + (T[s] > 0 ? A[s][b] * (100.0f / T[s]) : 0.0f).  A point with a non-finite
+ *   coordinate has an empty list and gets 33 zeros.
+ * d_spfh_out, d_count_out may be NULL.  NULL index / d_normals / d_fpfh_out, k out of range, radius NaN, outputs overlapping each
+ *   other, the normals or the index's cloud -> R3D_ERR_INVALID, nothing written. */
+#define R3D_FPFH_DIM 33
+#define R3D_FPFH_THETA_COS \
+  { -0.841253519f, -0.415415019f, 0.142314836f, 0.654860735f, 0.959492981f, 0.959492981f, 0.654860735f, 0.142314836f, -0.415415019f, -0.841253519f }
+#define R3D_FPFH_THETA_SIN \
+  { -0.540640831f, -0.909631968f, -0.989821434f, -0.755749583f, -0.281732559f, 0.281732559f, 0.755749583f, 0.989821434f, 0.909631968f, 0.540640831f }
+int r3d_fpfh_knn(r3d_nn_index* index, int k, double radius, const float* d_normals, float* d_fpfh_out, uint8_t* d_spfh_out,
+                 uint32_t* d_count_out);
+/* r3d_feature_match: d_a [na][33], d_b [nb][33] f32, 1 <= na, nb < 2^32.  dist(i, j) = sum_{b = 0..32} e_b * e_b, e_b = a_ib - b_jb,
+ *   every product and sum its own f32 operation, b ascending, from 0.0f.  d_idx_out [na] u32 = the j with the smallest
+ *   (dist, j) among finite dist, d_dist_out [na] f32 (may be NULL) = that dist; no finite dist: (UINT32_MAX, +inf).
+ * Correspondences (d_corr_out != NULL; this part synchronises): row i is kept iff idx_a[i] != UINT32_MAX and, with mutual = 1,
+ *   idx_b[idx_a[i]] == i, idx_b being the same search from b to a.  d_corr_out [*h_m_out][2] u32 = (i, idx_a[i]) of the kept rows,
+ *   i ascending; the buffer holds [na][2].  d_corr_out == NULL: h_m_out must be NULL and mutual 0; the call is asynchronous.
+ * NULL ctx / d_a / d_b / d_idx_out, sizes out of range, mutual not 0 / 1, one of d_corr_out and h_m_out without the other,
+ *   outputs overlapping each other or an input -> R3D_ERR_INVALID, nothing written. */
+int r3d_feature_match(r3d_ctx* ctx, const float* d_a, int64_t na, const float* d_b, int64_t nb, int mutual, uint32_t* d_idx_out,
+                      float* d_dist_out, uint32_t* d_corr_out, int64_t* h_m_out);
+/* r3d_register_ransac: the rigid motion T with q ~ T p for the most correspondences.  d_src [ns][3], d_tgt [nt][3] f32;
+ *   d_corr [m][2] u32 (source row, target row), 3 <= m < 2^32; thr = distance_threshold, finite and > 0;
+ *   1 <= H = n_hypotheses <= 65536; seed: any u64.  Synchronises.  Pair g is (p_g, q_g) = (src[corr[g][0]], tgt[corr[g][1]]);
+ *   a row number outside its cloud makes that point NaN.
+ * Sampling: hypothesis h takes the pairs r_j(h), j = 0, 1, 2, of r3d_ransac_rows(seed, h, m).
+ * Pose (fp64 from the f32 points): with (a, b, c) the three source points, u = b - a, v = c - a, N = u x v,
+ *   e1 = u / sqrt(|u|^2), e3 = N / sqrt(|N|^2), e2 = e3 x e1, |z|^2 = (zx zx + zy zy) + zz zz; the target points (a', b', c') give
+ *   e1', e2', e3' the same way.  R_rc = (e1'_r e1_c + e2'_r e2_c) + e3'_r e3_c, t_r = a'_r - ((R_r0 ax + R_r1 ay) + R_r2 az).
+ *   Valid iff the three source rows are pairwise different, the three target rows are pairwise different, |u|^2, |N|^2, |u'|^2,
+ *   |N'|^2 are finite and > 0, and | sqrt(|z|^2) - sqrt(|z'|^2) | <= 2 thr for z = b - a, c - a, c - b.
+ * Count: R^, t^ = R, t rounded once to f32; per pair, in f32, q^_r = ((R^_r0 px + R^_r1 py) + R^_r2 pz) + t^_r, e = q^ - q,
+ *   s2 = (ex ex + ey ey) + ez ez; c_h = #{g : s2 <= (float)(thr * thr)} (thr * thr in fp64).  NaN compares false.  An invalid
+ *   hypothesis has c_h = 0.  d_counts_out [H] u32 (may be NULL) = c_h.
+ * Best hypothesis: the lowest h of maximal c_h.  Maximum < 3: R3D_OK, a zero mask, T and the rms NaN, 0 inliers (best h, c_best,
+ *   its pairs and the valid count are still reported).
+ * Refit: I0 = the best hypothesis' inliers by the same test.  With pc = (double) p - (double) a, qc = (double) q - (double) a'
+ *   (a, a' the points of pair r_0), the 18 sums of r3d_icp_accumulate over (pc, qc), each pair adding, for axis = x, y, z in
+ *   turn, pc_axis, qc_axis, pc_axis qc_b (b = x, y, z), pc_axis pc_axis and qc_axis qc_axis to its sum; one accumulator set per
+ *   lane: lane L of G x 256 (G = min(ceil(m / 256), 1024)) takes the pairs L, L + 256 G, ... in order; the lanes of a workgroup
+ *   are added by a halving tree inside each 64 (v_l += v_{l + off}, off = 32, 16, .. 1) and the four sixty-fours in order; the G
+ *   rows are added by 256 lanes (lane t: rows t, t + 256, ... in order) and the same tree.  T_c = r3d_umeyama_from_sums(sums,
+ *   with_scale = 0); R = R_c, t_r = (a'_r + t_c,r) - ((R_r0 ax + R_r1 ay) + R_r2 az).  An undefined fit keeps the hypothesis' own
+ *   fp64 pose.
+ * Final mask: the same f32 test with the refitted pose rounded to f32 -> d_inlier_out [m] u8.
+ * h_result (host, R3D_REGISTER_RESULT_DOUBLES doubles): [0..15] T row-major 4x4, [16] best h, [17] c_best, [18..20] the pairs
+ *   r_0 r_1 r_2 of the best hypothesis, [21] the number of valid hypotheses, [22] the final inlier count, [23] the inlier rms
+ *   sqrt(sum (double) s2 / count) over the final inliers (the same two-stage order; NaN without inliers), [24] 1 when the refit
+ *   was undefined, [25..31] 0.
+ * NULL ctx / d_src / d_tgt / d_corr / d_inlier_out / h_result, sizes, H or thr out of range, outputs overlapping an input or each
+ *   other -> R3D_ERR_INVALID, nothing written to any output. */
+#define R3D_REGISTER_RESULT_DOUBLES 32
+int r3d_register_ransac(r3d_ctx* ctx, const float* d_src, int64_t n_src, const float* d_tgt, int64_t n_tgt, const uint32_t* d_corr,
+                        int64_t n_corr, double distance_threshold, int n_hypotheses, uint64_t seed, uint8_t* d_inlier_out,
+                        uint32_t* d_counts_out, double* h_result);
 /* In-place ascending sort of 64-bit keys in HBM by their low key_bits bits (stable LSD radix sort, 8-bit digits;
  * asynchronous on the ctx stream).  Building block of r3d_voxelset_codes, exported for tests and reuse. */
 int r3d_sort_u64(r3d_ctx* ctx, uint64_t* d_keys, int64_t n_keys, int key_bits);
