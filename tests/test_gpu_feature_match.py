@@ -111,6 +111,53 @@ def test_two_rows_per_lane_and_many_chunks(G, ctx):
     assert np.array_equal(idx, wi) and np.array_equal(dist.view(np.uint32), wd.view(np.uint32)) and idx[5] == 299
 
 
+def _check_with_list(G, ctx, fa, fb, mutuals):
+    (wi, wd), (wbi, _) = REF.nearest_rows(fa, fb), REF.nearest_rows(fb, fa)
+    na = fa.shape[0]
+    kept = {}
+    for mutual in mutuals:
+        idx, dist, corr = device_run(G, ctx, fa, fb, mutual)
+        assert np.array_equal(idx, wi), np.flatnonzero(idx != wi)[:5]
+        assert np.array_equal(dist.view(np.uint32), wd.view(np.uint32)), np.flatnonzero(dist != wd)[:5]
+        keep = wi != REF.NONE
+        if mutual:
+            keep &= wbi[np.where(keep, wi, 0).astype(np.int64)] == np.arange(na, dtype=np.uint32)
+        rows = np.flatnonzero(keep).astype(np.uint32)
+        assert np.array_equal(corr, np.stack([rows, wi[rows]], axis=1).reshape(-1, 2))
+        want, _, _ = REF.match(fa, fb, mutual=mutual)
+        assert np.array_equal(corr, want)
+        kept[mutual] = keep
+    return kept
+
+
+def test_compaction_above_65536_rows(G, ctx):
+    """66 306 source rows: 260 workgroups of keep counts, so keep_scan_kernel's threads own more than one count each (above
+    256 x 256 rows) and its last threads own none.  Every 5th target row is NaN (nobody's neighbour); source rows are copies of
+    target rows or NaN in runs that straddle wave (64) and workgroup (256) boundaries, and whole workgroups keep nothing."""
+    na, nb = 65537 + 256 * 3 + 1, 300
+    fa, fb = features("random", na, nb, 11)
+    fb[::5, 32] = np.nan
+    good = np.flatnonzero(np.isfinite(fb).all(axis=1))
+    rng = np.random.default_rng(12)
+    fa[:] = fb[good[rng.integers(0, good.size, na)]] + (rng.random((na, 33)) * 1e-3).astype(np.float32)
+    for lo, hi in ((40, 90), (200, 300), (256 * 7, 256 * 9), (256 * 100 - 3, 256 * 100 + 70), (65536 - 130, 65536 + 130),
+                   (256 * 258, 256 * 259), (na - 5, na - 1)):
+        fa[lo:hi, 7] = np.nan                                         # dropped in both directions: no neighbour at all
+    kept = _check_with_list(G, ctx, fa, fb, (False, True))
+    assert not kept[False][256 * 7:256 * 9].any() and kept[False][256 * 9] and kept[False][65536 + 130] and kept[False][na - 1]
+    per_block = np.add.reduceat(kept[True].astype(np.int64), np.arange(0, na, 256))
+    assert (per_block == 0).any() and per_block.max() >= 1 and 0 < kept[True].sum() <= nb
+
+
+def test_reverse_search_through_the_two_rows_per_lane_kernel(G, ctx):
+    """300 source rows against 131 073 target rows, mutual: the b -> a search has 131 073 query rows"""
+    fa, fb = features("random", 300, 2 * 256 * 256 + 1, 13)
+    fb[::5, 32] = np.nan
+    fb[131072] = fa[17]
+    kept = _check_with_list(G, ctx, fa, fb, (True,))
+    assert kept[True][17]
+
+
 def test_host_entry_and_repeatability(G, ctx):
     fa, fb = features("ties", 700, 900, 5)
     a, b = G.match_features(fa, fb, mutual=True, ctx=ctx), G.match_features(fa, fb, mutual=True, ctx=ctx)
