@@ -22,7 +22,8 @@
  *     order -- products and differences exactly as written there; the 3-term dot products of the
  *     SE(3) / 4x4 apply are an fma chain fma(r2,dz, fma(r1,dy, r0*dx)) -- and rounded ONCE on
  *     store, so R3D_F32 output is the correctly rounded fp64 result (<= 6e-8 relative per
- *     component), R3D_F64 unprojection is bit-identical to the reference and R3D_F64 world
+ *     component; f32 denormals kept on input and output: gradual underflow, ties to even,
+ *     +-inf past FLT_MAX), R3D_F64 unprojection is bit-identical to the reference and R3D_F64 world
  *     points equal the reference's fp64 up to that dot-product's rounding (~1e-16 relative).
  */
 #ifndef R3D_H
@@ -162,7 +163,8 @@ int r3d_fuse_frames_rgb_host(r3d_ctx* ctx, const r3d_camera* cam, const void* h_
  *     cam_points[b][c][p] = depth[b][p] * (inv_K[b][c][0]*x + inv_K[b][c][1]*y + inv_K[b][c][2]),  c = 0..2;  [b][3][p] = 1
  * with p = y*W + x, all fp32 like the layer.  d_depth [B][H*W], d_inv_K [B][4][4] row-major, d_cam_points [B][4][H*W].
  * The _grad entry point is the layer's backward with respect to depth: grad_depth[b][p] = sum_c grad_cam[b][c][p]*ray_c.
- * f32 evaluation order (the upstream layer's; one rounding per operation, no fused multiply-add, x and y converted exactly):
+ * f32 evaluation order (the upstream layer's; one rounding per operation, no fused multiply-add, f32 denormals kept, x and y
+ * converted exactly):
  *     ray_c = (k_c0*x + k_c1*y) + k_c2          cam_c = z * ray_c          the fourth plane is exactly 1.0f
  *     grad_depth = (g0*ray_0 + g1*ray_1) + g2*ray_2
  * Every per-pixel output of these four entry points is therefore specified bit for bit (NaN sign and payload excepted). */
@@ -179,7 +181,7 @@ int r3d_backproject_depth_grad_f32(r3d_ctx* ctx, const float* d_grad_cam_points,
  * d_grad_P is a two-stage fixed-order reduction (bitwise repeatable).
  * f32 evaluation order, with (px, py, pz, pw) = points[b][0..3][p] and g = grad_pix[b][p]:
  *     c_i = ((P_i0*px + P_i1*py) + P_i2*pz) + P_i3*pw          den = c2 + eps
- *     pix = ( ((c0/den)/(W-1) - 0.5) * 2,  ((c1/den)/(H-1) - 0.5) * 2 )          divisions correctly rounded
+ *     pix = ( ((c0/den)/(W-1) - 0.5) * 2,  ((c1/den)/(H-1) - 0.5) * 2 )          divisions correctly rounded, f32 denormals kept
  *     inv = 1/den      d0 = (g.x * (2/(W-1))) * inv      d1 = (g.y * (2/(H-1))) * inv      d2 = (-(d0*c0 + d1*c1)) * inv
  *     grad_points_k = (P_0k*d0 + P_1k*d1) + P_2k*d2,  k = 0..3          (2/(W-1), 2/(H-1): f32 quotients formed once)
  *     grad_P_ik = sum over the image's pixels of d_i * x_k; each term is one f32 product of the d_i above.  The order of the
@@ -213,7 +215,8 @@ int r3d_apply_T_host(r3d_ctx* ctx, const void* h_xyz_in, int in_dtype, int64_t n
  * T_data.txt made by an external tool; build-defined per SURVEY.md 8(a8)).
  * r3d_icp_nn: for each source point the index of the nearest target point under squared L2
  * computed in fp32 as d2 = fmaf(dz,dz, fmaf(dy,dy, dx*dx)) with dx = sx-tx, dy = sy-ty, dz = sz-tz (one rounding
- * for dx*dx, one per fused multiply-add; no other contraction), lowest index wins exact ties.  This expression IS
+ * for dx*dx, one per fused multiply-add; no other contraction; f32 denormals kept: a subnormal d2 ranks as its value, not as 0),
+ * lowest index wins exact ties.  This expression IS
  * the specification: brute force, culled index and oracle all evaluate exactly it.
  * Non-finite input: a pair whose d2 is NaN or +inf never wins; a source with no finite d2 at all (it, or every target,
  * has a NaN / inf coordinate) gets index 0 and d2 = +inf; the pair sums leave rows with non-finite coordinates out.
@@ -718,7 +721,8 @@ int r3d_voxelset_write_bt(r3d_voxelset* vs, const char* path, int64_t* n_nodes_o
  * before meshing; no parity with Open3D's UniformTSDFVolume is claimed, this text is the specification).  Where r3d_fuse_frames
  * concatenates the frames' points, noise and all, the volume averages overlapping frames and yields the zero level set as
  * oriented points.  Every output bit is a chain of IEEE f32 operations in the order written here: no fused multiply-add,
- * correctly rounded division and square root, independent of launch geometry and of how the frames are split into calls.
+ * correctly rounded division and square root, f32 denormals kept, independent of launch geometry and of how the frames are split
+ * into calls.
  * Volume: origin[3], voxel_size, sdf_trunc are doubles rounded once to f32 (o, vs, tr; o finite, vs > 0, tr > 0), nx, ny, nz >= 1
  *   with nx ny nz < 2^31.  Storage: one float2 {tsdf, weight} per voxel at linear index (z ny + y) nx + x; a fresh or reset volume
  *   is all zero bytes.
@@ -979,7 +983,7 @@ int r3d_tsdf_track(r3d_tsdf* vol, const r3d_camera* cam, const void* d_depth, in
  *   R3D_ERR_INVALID with *out untouched for a NULL argument, H < 2 or W < 2.
  * r3d_depth_half.  d_in holds the depth of pixel (v, u) at d_in[(v width + u) in_stride]: in_stride 1 is an f32 depth raster,
  *   in_stride 3 the z column of a vertex map (the caller passes vertex + 2).  d_out is [height >> 1][width >> 1] f32.  All of it is
- *   f32, in the order written, no fused multiply-add, correctly rounded division:
+ *   f32, in the order written, no fused multiply-add, correctly rounded division, f32 denormals kept:
  *   1. a depth is valid iff it is finite and > 0
  *   2. for output pixel (v', u') the block is the four inputs (2v', 2u'), (2v', 2u' + 1), (2v' + 1, 2u'), (2v' + 1, 2u' + 1), in that
  *      order
@@ -1119,7 +1123,7 @@ int r3d_tsdf_track_rgb(r3d_tsdf* vol, const r3d_camera* cam, const void* d_depth
  *   or not > 0 (for sigma_r: as a double, and cut and inv_step as f32 -- both must come out finite and > 0).
  * Filter (r3d_depth_bilateral).  d_in holds the depth of pixel (v, u) at d_in[(v width + u) in_stride], in_stride 1 or 3 as in
  *   r3d_depth_half: an f32 depth raster, or the z column of a vertex map (the caller passes vertex + 2).  d_out is [height][width]
- *   f32.  All arithmetic is f32, in the order written, no fused multiply-add, correctly rounded division:
+ *   f32.  All arithmetic is f32, in the order written, no fused multiply-add, correctly rounded division, f32 denormals kept:
  *   1. a depth is valid iff it is finite and > 0
  *   2. output pixel (v, u) with an invalid centre depth dc is 0.0f: no holes are filled
  *   3. otherwise num = 0.0f, den = 0.0f; then for dy = -r..r (outer) and dx = -r..r (inner), in that order, with d the depth of

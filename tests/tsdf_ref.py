@@ -73,8 +73,9 @@ def _shift(a, axis, step, fill):
     return out
 
 
-def extract(vol, min_weight=1.0):
-    """(xyz [n,3], normals [n,3]) f32 in the specified order: linear voxel order, per voxel the axes x, y, z."""
+def extract(vol, min_weight=1.0, squares=None):
+    """(xyz [n,3], normals [n,3]) f32 in the specified order: linear voxel order, per voxel the axes x, y, z.  squares: an optional
+    hook (terms [3], total) -> total on the normal's squared length, for tests that look at it or flush its subnormals."""
     mw = F(min_weight)
     assert mw > 0
     T, valid = vol.tsdf, vol.w >= mw
@@ -102,7 +103,11 @@ def extract(vol, min_weight=1.0):
         G = np.stack([g.reshape(-1) for g in grad], axis=1)  # [voxel][b]
         gv, gn = G[vox], G[vox + step]
         m = gv + r[:, None] * (gn - gv)
-        ln = np.sqrt((m[:, 0] * m[:, 0] + m[:, 1] * m[:, 1]) + m[:, 2] * m[:, 2])
+        sq = [m[:, b] * m[:, b] for b in range(3)]
+        total = (sq[0] + sq[1]) + sq[2]
+        if squares is not None:                              # a test's view of (or hand on) the squared length and its terms
+            total = squares(sq, total)
+        ln = np.sqrt(total)
         assert m.dtype == F and ln.dtype == F and pos.dtype == F
         nrm = np.where((ln > 0)[:, None], m / ln[:, None], F(0.0)).astype(F)
     return pos, nrm
