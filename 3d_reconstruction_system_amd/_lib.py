@@ -198,6 +198,9 @@ SIGNATURES = {
     "r3d_tsdf_track_rgb": (_i, [_vp, _vp, _vp, _i, _d, _vp, _vp, _d, _d, _d, _d, _f, _d, _d, _d, _d, _i, _vp, _vp]),
     "r3d_bilateral_weights": (_i, [_i, _d, _d, _vp, _vp, _vp, _vp]),
     "r3d_depth_bilateral": (_i, [_vp, _vp, _i, _i, _i, _i, _d, _d, _vp]),
+    "r3d_registration_sums": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _f, _vp]),
+    "r3d_information_from_sums": (_i, [_vp, _i64, _vp, _vp, _vp]),
+    "r3d_posegraph_optimize": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _d, _d, _d, _i, _vp, _vp]),
 }
 
 _lib = None

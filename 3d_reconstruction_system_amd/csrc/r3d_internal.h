@@ -65,6 +65,9 @@ struct r3d_ctx {
   // none; the call validates its arguments before it compares them with this key, so no call matches the empty key
   int bilateral_radius = -1;
   double bilateral_sigma_s = 0, bilateral_sigma_r = 0;
+  // r3d_registration_sums' own workspace (r3d_reginfo.hip): partial rows + the 11 sums, made once at its largest size and read
+  // and written by that synchronous call alone -- not one of the shared slots above
+  void* reginfo_ws = nullptr;
   // pinned staging buffers of the host pipeline: slot = ((direction * kPipeBufs + array) * 2 + parity)
   static constexpr int kPipeBufs = 2;   // arrays per direction (depth + colour in, xyz + rgba out)
   static constexpr int kPinnedSlots = 2 * kPipeBufs * 2;

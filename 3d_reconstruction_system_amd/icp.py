@@ -115,13 +115,17 @@ INIT_SAMPLES, INIT_KEEP, INIT_PREFER_MOMENTS = 8192, 0.8, 1.05
 
 
 class NNIndex:
-    """Spatially culled exact nearest-neighbour index over a device-resident target cloud (r3d_nn_index)."""
+    """Spatially culled exact nearest-neighbour index over a device-resident target cloud (r3d_nn_index).
+    d_tgt / n: the address and size of the cloud given to the constructor or to rebuild(), for callers that need the indexed
+    cloud itself (posegraph).  They follow this object's methods only: a handle rebuilt through the C API directly leaves them
+    stale, and the caller keeps that buffer alive."""
 
     def __init__(self, ctx, d_tgt_ptr, n_tgt):
         self.ctx = ctx
         h = C.c_void_p()
         L.check(ctx.lib.r3d_nn_index_create(ctx.handle, d_tgt_ptr, int(n_tgt), C.byref(h)))
         self.handle = h.value
+        self.d_tgt, self.n = d_tgt_ptr, int(n_tgt)   # the cloud it indexes (the caller keeps that buffer alive)
         ctx.adopt(self)
 
     def query(self, d_src_ptr, n_src, d_idx_ptr, d_d2_ptr, want_stats=False, presorted=False):
@@ -153,6 +157,7 @@ class NNIndex:
     def rebuild(self, d_tgt_ptr, n_tgt):
         """Index another cloud of at most the size this one was created with, reusing the allocations."""
         L.check(self.ctx.lib.r3d_nn_index_rebuild(self.handle, d_tgt_ptr, int(n_tgt)))
+        self.d_tgt, self.n = d_tgt_ptr, int(n_tgt)
 
     def sort_cloud(self, d_xyz_ptr, n, d_perm_ptr=None):
         L.check(self.ctx.lib.r3d_nn_index_sort_cloud(self.handle, d_xyz_ptr, int(n), d_perm_ptr))

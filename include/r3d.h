@@ -1149,6 +1149,76 @@ int r3d_bilateral_weights(int radius, double sigma_s, double sigma_r, float* h_s
 int r3d_depth_bilateral(r3d_ctx* ctx, const float* d_in, int in_stride, int height, int width, int radius, double sigma_s,
                         double sigma_r, float* d_out);
 
+/* ---- Multiway registration: the information matrix and quality of a registered pair, and pose-graph optimisation
+ * (csrc/r3d_reginfo.hip, csrc/r3d_posegraph.cpp; NOT IN THE REFERENCE -- the step between "register pairs" and "integrate
+ * everything", for which users of this kind of pipeline call Open3D's get_information_matrix_from_point_clouds,
+ * evaluate_registration, PoseGraph and global_optimization; no parity with Open3D is claimed, this text is the specification).
+ *
+ * r3d_registration_sums: the pair sums of a pose under test.  d_src [n_src][3] f32 is the source ALREADY MOVED by that pose
+ *   (r3d_apply_T, f32); d_idx [n_src] u32 / d_d2 [n_src] f32 are what r3d_nn_index_query or r3d_icp_nn wrote for it against
+ *   d_tgt [n_tgt][3] f32.  Pair k takes part iff d_idx[k] < n_tgt (the index array is data: nothing is read past the target
+ *   cloud), all six coordinates of src[k] and q = tgt[d_idx[k]] are finite, and d_d2[k] <= max_d2 -- the pair AT max_d2 is in,
+ *   as in r3d_icp_accumulate; a NaN d2 is out.  With q promoted to fp64, h_sums (host, R3D_REGISTRATION_SUMS doubles):
+ *     [0] n = the pairs taking part, [1..3] sum q, [4..9] sum qx qx, qx qy, qx qz, qy qy, qy qz, qz qz, [10] sum (double) d2.
+ *   One lane per source row, grid-stride, one accumulator set per lane, the fixed two-stage tree of r3d_icp_accumulate, no float
+ *   atomics: the same input gives the same bits run to run.  Synchronous.  n_src == 0: eleven zeros, no launch.
+ *   R3D_ERR_INVALID, nothing written: NULL ctx or h_sums, a NULL device pointer with n_src > 0, a negative count, n_tgt >= 2^32,
+ *   max_d2 < 0 or NaN (an information matrix without a distance gate is meaningless).
+ *
+ * r3d_information_from_sums: pure host fp64 arithmetic, no GPU needed.  Parameter order (rotation, translation).  A small motion
+ *   (w, v) moves a target point q by w x q + v = G (w, v) with G = [ -[q]x | I ]; h_info (36 doubles, row-major 6x6) =
+ *     L = sum G^T G = [[ sum (|q|^2 I - q q^T),  [sum q]x ],
+ *                      [ -[sum q]x,              n I      ]]
+ *   with [a]x = [[0, -az, ay], [az, 0, -ax], [-ay, ax, 0]]; the diagonal of the first block is s[7] + s[9], s[4] + s[9],
+ *   s[4] + s[7], every other entry one sum or its negative.  *h_fitness (may be NULL) = n / n_src, 0 when n_src == 0;
+ *   *h_rmse (may be NULL) = sqrt(s[10] / n), 0 when n == 0.  NULL h_sums / h_info or n_src < 0 -> R3D_ERR_INVALID.
+ *
+ * r3d_posegraph_optimize: pure host fp64 arithmetic, no GPU needed.  All matrices are row-major 4x4 rigid motions [R t; 0 1];
+ *   R is taken to be a rotation (the inverse used is [R^T, -R^T t]).
+ *   Conventions.  The pose X_i of node i maps cloud i into the frame of cloud 0.  An edge (s, t, T) says p_t = T p_s -- the T
+ *   that register_global and icp_point_to_plane(src = s, tgt = t) return -- so a consistent graph has X_s = X_t T.  The residual
+ *   of an edge is xi = (w, v) of E = T^-1 X_t^-1 X_s: w the SO(3) logarithm of E's rotation (|w| <= pi), v E's translation;
+ *   chi2_e = xi^T L_e xi with L_e = h_edge_info[e], symmetrised as (L + L^T) / 2.
+ *   Weights.  Certain edges (h_edge_uncertain[e] == 0) have w_e = 1.  Uncertain edges have w_e = (mu / (mu + chi2_e))^2 (1 when
+ *   mu + chi2_e == 0), recomputed from the current poses in every iteration -- the closed form of the line process of Choi, Zhou
+ *   and Koltun (CVPR 2015) -- with mu = preference_loop_closure x max_correspondence_distance^2 x the mean of L_e[5][5] (the pair
+ *   count of an information matrix made above) over the uncertain edges not yet pruned.  preference_loop_closure = +inf
+ *   switches the robust weights off: every w_e = 1 and nothing is pruned.
+ *   Cost.  C = sum_e w_e chi2_e, weights at the same poses: h_report[0] before the first step, h_report[1] at the end.  The
+ *   step test below uses the line-process objective F = sum_e w_e chi2_e + mu (sqrt(w_e) - 1)^2 (uncertain edges: mu chi2_e /
+ *   (mu + chi2_e)), which the weights minimise in closed form and which, unlike C, grows with every chi2_e; without uncertain
+ *   edges, or with the robust weights off, F = C.
+ *   Solver.  Levenberg-Marquardt over the 6 (n_nodes - 1) parameters of the nodes 1 .. n_nodes - 1; node 0 is fixed, its 16
+ *   doubles keep their bits.  Per iteration: weights, H = sum w_e J_e^T L_e J_e and g = sum w_e J_e^T L_e xi_e (dense; J_e the
+ *   derivative of xi_e by the left perturbations of X_s and X_t), (H + lambda I) d = -g by Cholesky (a failed factorisation
+ *   multiplies lambda by 10 and counts as an iteration); X_i <- exp(d_i) X_i with the SE(3) exponential of d_i = (w, v); the step is
+ *   kept when F falls, lambda then shrinks by max(1/3, 1 - (2 rho - 1)^3), otherwise it grows by 2, 4, 8, ... (Nielsen's rule; it
+ *   starts at 1e-6 x the largest diagonal entry of H).  The loop stops when the largest |component| of d is below 1e-10 (that
+ *   step is still applied when F does not rise), when a kept step changed F by less than 1e-14 F, when F is 0, or after max_iters
+ *   iterations (h_report[4] = 1).  n_nodes <= R3D_POSEGRAPH_MAX_NODES = 512: the normal equations are dense (72 MB and some 1e10
+ *   operations per iteration at the limit); more is R3D_ERR_INVALID.
+ *   Pruning.  After the loop, uncertain edges with w_e < prune_threshold are pruned: they take no further part.  If any was
+ *   pruned, the loop runs once more (again up to max_iters) over the other edges, the kept uncertain edges still weighted by
+ *   the rule above; nothing is pruned after that second loop.  A node held by pruned edges alone stays where it is.
+ *   Outputs.  h_poses [n_nodes][16] in / out.  h_edge_weight_out [n_edges] (may be NULL): the final w_e, 0 for pruned edges.
+ *   h_report (may be NULL; R3D_POSEGRAPH_REPORT_DOUBLES doubles): [0] C at the start, [1] C at the end, [2] iterations (both
+ *   loops), [3] edges pruned, [4] status: 0, or 1 when a loop ended because of max_iters, [5..7] 0.
+ *   R3D_ERR_INVALID, nothing written (the poses keep their bits): n_nodes < 1 or > 512, n_edges < 0, max_iters < 0, a NULL
+ *   h_poses (or edge array with n_edges > 0); a node index out of range or s == t; a non-finite value in a pose, a T, an L,
+ *   max_correspondence_distance or prune_threshold; max_correspondence_distance <= 0; preference_loop_closure NaN or <= 0 (+inf
+ *   is allowed); an L with |L_ab - L_ba| > 1e-9 x its largest |entry| or with a negative diagonal entry; a pose or T whose bottom
+ *   row is not exactly 0 0 0 1; a node that no path of edges connects to node 0. */
+#define R3D_REGISTRATION_SUMS 11
+#define R3D_POSEGRAPH_MAX_NODES 512
+#define R3D_POSEGRAPH_REPORT_DOUBLES 8
+int r3d_registration_sums(r3d_ctx* ctx, const float* d_src, int64_t n_src, const float* d_tgt, int64_t n_tgt, const uint32_t* d_idx,
+                          const float* d_d2, float max_d2, double* h_sums);
+int r3d_information_from_sums(const double* h_sums, int64_t n_src, double* h_info, double* h_fitness, double* h_rmse);
+int r3d_posegraph_optimize(int n_nodes, double* h_poses, int n_edges, const int32_t* h_edge_nodes, const double* h_edge_T,
+                           const double* h_edge_info, const uint8_t* h_edge_uncertain, double max_correspondence_distance,
+                           double preference_loop_closure, double prune_threshold, int max_iters, double* h_edge_weight_out,
+                           double* h_report);
+
 #ifdef __cplusplus
 }
 #endif
