@@ -26,7 +26,8 @@ from .normals import (Normals, estimate_normals, estimate_normals_device, estima
                       fused_viewpoints)
 from .segmentation import PlaneSegment, segment_plane, segment_planes, segment_plane_device  # noqa: F401
 from .registration import (Fpfh, Matches, RansacResult, compute_fpfh, compute_fpfh_device, match_features,  # noqa: F401
-                           registration_ransac, register_global)
+                           registration_ransac, register_global, register_colored)
+from .colored_icp import ColourGradients, colour_gradients, colour_gradients_device, icp_colored  # noqa: F401
 from .posegraph import (PoseGraph, evaluate_registration, registration_information, registration_sums_device,  # noqa: F401
                         register_multiway)
 from .tsdf import TSDFVolume, poses_w2c  # noqa: F401

@@ -201,6 +201,9 @@ SIGNATURES = {
     "r3d_registration_sums": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _f, _vp]),
     "r3d_information_from_sums": (_i, [_vp, _i64, _vp, _vp, _vp]),
     "r3d_posegraph_optimize": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _d, _d, _d, _i, _vp, _vp]),
+    "r3d_color_gradient_knn": (_i, [_vp, _i, _d, _vp, _vp, _vp, _vp, _vp]),
+    "r3d_icp_color_accumulate": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _f, _d, _d, _vp, _vp]),
+    "r3d_icp_iterate_color": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _f, _d, _d, _vp, _vp]),
 }
 
 _lib = None

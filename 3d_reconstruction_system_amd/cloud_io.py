@@ -613,3 +613,37 @@ def read_ply(path):
     lines = data[start:].decode('utf-8', errors='replace').split('\n')
     rows = [s.split()[:3] for s in lines[:n]]
     return np.array(rows, dtype=np.float64).reshape(-1, 3)
+
+
+def read_ply_rgb(path):
+    """(xyz [N,3] float64, rgba [N] uint32 words r | g << 8 | b << 16) of an ASCII PLY in the reference's coloured layout
+    (write_ply_rgb: x y z red green blue [alpha] per vertex row; the alpha column is not read).  ValueError for a file without
+    colour columns."""
+    with open(path, 'rb') as f:
+        data = f.read()
+    n, start, pos, props = None, None, 0, []
+    while pos < len(data):
+        e = data.find(b'\n', pos)
+        e = len(data) if e < 0 else e
+        s = data[pos:e].strip()
+        if s.startswith(b'element vertex'):
+            n = int(s.split()[-1])
+        elif s.startswith(b'property') and n is not None and len(s.split()) == 3:
+            props.append(s.split()[2])
+        pos = e + 1
+        if s == b'end_header':
+            start = pos
+            break
+    if n is None or start is None:
+        raise ValueError("%s: not a PLY with an 'element vertex' header" % path)
+    if b'format ascii' not in data[:start] or props[:6] != [b'x', b'y', b'z', b'red', b'green', b'blue']:
+        raise ValueError("%s: not an ASCII PLY with x y z red green blue vertex rows" % path)
+    rows = [l.split()[:6] for l in data[start:].decode('utf-8', errors='replace').split('\n') if l.strip()][:n]
+    if len(rows) != n or any(len(r) != 6 for r in rows):
+        raise ValueError("%s: expected %d vertex rows of x y z red green blue" % (path, n))
+    xyz = np.array([r[:3] for r in rows], dtype=np.float64).reshape(-1, 3)
+    c = np.array([r[3:] for r in rows], dtype=np.int64).reshape(-1, 3)
+    if c.size and (c.min() < 0 or c.max() > 255):
+        raise ValueError("%s: colour values outside 0..255" % path)
+    c = c.astype(np.uint32)
+    return xyz, (c[:, 0] | (c[:, 1] << 8) | (c[:, 2] << 16)).astype(np.uint32)

@@ -216,6 +216,8 @@ int r3d_ctx_destroy(r3d_ctx* ctx) {
   for (int i = 0; i < r3d_ctx::kScratchSlots; ++i)
     if (ctx->scratch[i]) (void)hipFree(ctx->scratch[i]);
   if (ctx->reginfo_ws) (void)hipFree(ctx->reginfo_ws);
+  if (ctx->color_rows) (void)hipFree(ctx->color_rows);
+  if (ctx->color_lists) (void)hipFree(ctx->color_lists);
   for (int i = 0; i < r3d_ctx::kPinnedSlots; ++i)
     if (ctx->pinned[i]) (void)hipHostFree(ctx->pinned[i]);
   for (int i = 0; i < 6; ++i)

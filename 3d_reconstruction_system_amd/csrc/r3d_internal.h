@@ -68,6 +68,12 @@ struct r3d_ctx {
   // r3d_registration_sums' own workspace (r3d_reginfo.hip): partial rows + the 11 sums, made once at its largest size and read
   // and written by that synchronous call alone -- not one of the shared slots above
   void* reginfo_ws = nullptr;
+  // coloured ICP's own workspaces (r3d_color_icp.hip), not shared slots either: the partial rows + the 31 sums of its sums pass,
+  // made once at their largest size, and the grow-only k-NN lists its gradient kernel reads; only its three entry points touch
+  // them, in stream order
+  void* color_rows = nullptr;
+  void* color_lists = nullptr;
+  size_t color_lists_bytes = 0;
   // pinned staging buffers of the host pipeline: slot = ((direction * kPipeBufs + array) * 2 + parity)
   static constexpr int kPipeBufs = 2;   // arrays per direction (depth + colour in, xyz + rgba out)
   static constexpr int kPinnedSlots = 2 * kPipeBufs * 2;

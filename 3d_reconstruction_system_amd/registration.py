@@ -239,3 +239,52 @@ def register_global(src, tgt, voxel_size, k=32, feature_radius=5.0, num_hypothes
         # the clouds overlap in part only: pairs farther apart than RANSAC's threshold belong to the rest and stay out of ICP
         T, info["icp"] = icp_point_to_plane(down[0], down[1], tgt_normals=nrm[1], init=T, max_dist=thr, ctx=ctx)
     return T, info
+
+
+def register_colored(src, src_rgba, tgt, tgt_rgba, voxel_sizes=(0.04, 0.02, 0.01), iters=(50, 30, 14), init=None, k=None, i_max=None,
+                     lambda_geometric=None, max_dist_voxels=2.0, ctx=None):
+    """(T, info): coloured ICP coarse to fine (colored_icp.icp_colored has the pairwise step; no parity with Open3D's
+    colored_icp recipe is claimed).  Per scale s: both clouds are voxel-downsampled WITH colour to voxel_sizes[s], the target gets
+    normals and colour gradients from its k nearest neighbours, and icp_colored runs iters[s] iterations from the previous scale's
+    T with pairs farther apart than max_dist_voxels x voxel_sizes[s] left out.  voxel_sizes: coarse to fine, in the clouds' unit.
+    info: one icp_colored info per scale under "scales", with the voxel size and the downsampled sizes.  ValueError when a scale's
+    step is undefined (status 1) or a cloud has fewer than 6 occupied voxels."""
+    from . import colored_icp as CI, voxelmap
+    from .normals import estimate_normals
+    src, tgt = _cloud(src), _cloud(tgt)
+    src_w, tgt_w = CI._words(src_rgba, src.shape[0], "src_rgba"), CI._words(tgt_rgba, tgt.shape[0], "tgt_rgba")
+    try:
+        sizes, its = [float(v) for v in voxel_sizes], [int(v) for v in iters]
+    except (TypeError, ValueError):
+        raise ValueError("voxel_sizes must be numbers and iters integers")
+    if not sizes or len(sizes) != len(its):
+        raise ValueError("voxel_sizes and iters must have the same length >= 1, got %d and %d" % (len(sizes), len(its)))
+    for v in sizes:
+        _check_positive(v, "voxel size")
+    if any(i < 1 for i in its):
+        raise ValueError("every entry of iters must be >= 1, got %r" % (its,))
+    k = CI.K if k is None else _check_k(k)
+    i_max = CI.I_MAX if i_max is None else i_max
+    lam = CI.LAMBDA_GEOMETRIC if lambda_geometric is None else lambda_geometric
+    CI.photo_weight(lam)
+    far = _check_positive(max_dist_voxels, "max_dist_voxels")
+    T = np.eye(4)
+    if init is not None:
+        T = np.array(init, dtype=np.float64)
+        if T.shape != (4, 4) or not np.isfinite(T).all():
+            raise ValueError("init must be a finite 4x4 matrix")
+    ctx = ctx or default_context()
+    info = {"scales": []}
+    for vs, it in zip(sizes, its):
+        ds, dt = voxelmap.voxel_down_sample(src, vs, rgba=src_w, ctx=ctx), voxelmap.voxel_down_sample(tgt, vs, rgba=tgt_w, ctx=ctx)
+        if ds.xyz.shape[0] < 6 or dt.xyz.shape[0] < 6:
+            raise ValueError("a cloud has fewer than 6 occupied voxels at voxel size %g" % vs)
+        nrm = estimate_normals(dt.xyz, k, ctx=ctx).normals
+        T, one = CI.icp_colored(ds.xyz, ds.rgba, dt.xyz, dt.rgba, tgt_normals=nrm, init=T, max_iter=it, max_dist=far * vs,
+                                lambda_geometric=lam, i_max=i_max, k=k, ctx=ctx)
+        one.update({"voxel_size": vs, "source_points": int(ds.xyz.shape[0]), "target_points": int(dt.xyz.shape[0])})
+        info["scales"].append(one)
+        if one["status"]:
+            raise ValueError("coloured ICP step undefined at voxel size %g: fewer than 6 pairs, or geometry and colour together "
+                             "leave a freedom unconstrained" % vs)
+    return T, info

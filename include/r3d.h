@@ -1219,6 +1219,94 @@ int r3d_posegraph_optimize(int n_nodes, double* h_poses, int n_edges, const int3
                            double preference_loop_closure, double prune_threshold, int max_iters, double* h_edge_weight_out,
                            double* h_report);
 
+/* ---- Coloured ICP (csrc/r3d_color_icp.hip; NOT IN THE REFERENCE -- the colour-assisted cloud-to-cloud registration of Park, Zhou and
+ * Koltun (ICCV 2017), which users of this kind of pipeline know as Open3D's registration_colored_icp; no parity with Open3D is claimed,
+ * this text is the specification).  Point-to-plane ICP between two unorganised clouds is undefined where the overlap is one wall, a
+ * floor, two parallel walls or a corridor.  Clouds that carry colour (r3d_fuse_frames_rgb, r3d_voxelgrid_extract,
+ * r3d_tsdf_extract_colors: words r | g << 8 | b << 16) constrain the open freedoms: every target point gets the gradient of its
+ * intensity over its tangent plane, and a matched pair then carries a photometric residual next to the geometric one.  Its Jacobian
+ * has the plane term's shape, J = [p x a ; a] with a the tangent gradient, so it enters the 6 x 6 normal equations through the
+ * arithmetic of the tracking calls' colour term (r3d_track_accumulate_rgb); the reduction, the solve and the ICP state are the ones of r3d_icp_iterate_plane.  Nothing
+ * existing changes.  Not yet timed on a card.
+ * All arithmetic below is fp64 unless it says f32, left to right as written, no fused multiply-add; each stored value is rounded once.
+ *
+ * r3d_color_gradient_knn: asynchronous; one lane per point i of the index's own cloud P (n rows, original order), 3 <= k <= 32.
+ *   d_normals [n][3] f32 (r3d_normals_knn's output, or any unit normals), d_rgba [n] u32.
+ *   Neighbourhood: N_i = row i of r3d_nn_index_knn_self(index, k) -- the exact (d2, j) order, ties by row, tails dropped -- cut, when
+ *     radius > 0, at the first entry with d2 > (float)((double) radius * radius) (radius <= 0: no cut).  c_i = |N_i| goes to
+ *     d_count_out [n] u32 (may be NULL).  The lists are stored in HBM by r3d_nn_index_knn_self (a grow-only buffer of the context) and read back.
+ *   Intensity (f32): R = w & 255, G = (w >> 8) & 255, B = (w >> 16) & 255 of the colour word w, each converted to f32;
+ *     I = (0.299f R + 0.587f G) + 0.114f B, in 0..255 -- r3d_intensity_map's rule.  The alpha byte is never read.  I_i goes to
+ *     d_intensity_out [n] f32 for EVERY row, whatever becomes of its gradient.
+ *   Gradient: with n = (double) d_normals[i], p_i = (double) P[i], and A_00, A_01, A_02, A_11, A_12, A_22, b_0, b_1, b_2 = 0.0, for each
+ *     entry j of N_i in list order:
+ *       e_a = (double) p_j,a - p_i,a;  h = (e_0 n_0 + e_1 n_1) + e_2 n_2;  t_a = e_a - h n_a;  dI = (double) I_j - (double) I_i
+ *       A_ab += t_a t_b for ab in 00, 01, 02, 11, 12, 22;  b_a += t_a dI
+ *     then the tangent-plane constraint with c = (double) c_i, c2 = c c:  A_ab += (c2 n_a) n_b for the same six ab.  Adjugate:
+ *       C00 = A_11 A_22 - A_12 A_12;  C01 = A_02 A_12 - A_01 A_22;  C02 = A_01 A_12 - A_02 A_11
+ *       C11 = A_00 A_22 - A_02 A_02;  C12 = A_01 A_02 - A_00 A_12;  C22 = A_00 A_11 - A_01 A_01
+ *       det = (A_00 C00 + A_01 C01) + A_02 C02;  tr = (A_00 + A_11) + A_22
+ *       g_0 = ((C00 b_0 + C01 b_1) + C02 b_2) / det;  g_1 = ((C01 b_0 + C11 b_1) + C12 b_2) / det;
+ *       g_2 = ((C02 b_0 + C12 b_1) + C22 b_2) / det
+ *     d_grad_out [n][3] f32 = (float) g, in intensity per length unit.  The constraint row pins g . n to 0 up to rounding.
+ *   No gradient = a row of three NaN (validity needs no mask, as for r3d_intensity_map's gradients): a normal that is the zero vector or has a
+ *     non-finite component; a point with a non-finite coordinate; c_i < 3; det not finite; det not above the conditioning floor,
+ *     i.e. unless det > R3D_COLOR_GRADIENT_FLOOR ((tr tr) tr).  With collinear tangent offsets det is rounding noise, up to a few
+ *     1e-16 tr^3 when the normal is oblique to the axes; the floor 1e-14 sits well above that.  The constraint row weighs c2 (a pure
+ *     number) against offsets in length^2, so the ratio depends on the cloud's unit: a regular neighbourhood of spacing s has
+ *     det / tr^3 of about s^4 / c2 once s^2 << c_i, and passes down to s of about a thousandth of the unit.
+ *   R3D_ERR_INVALID, nothing written: a NULL index, d_normals, d_rgba, d_intensity_out or d_grad_out; k outside [3, 32]; radius NaN; an
+ *     output overlapping another output, the normals, the colours or the index's cloud.
+ *
+ * r3d_icp_color_accumulate: the coloured sibling of r3d_icp_plane_accumulate without trimming; synchronous, h_sums (host) receives
+ *   R3D_COLOR_ICP_SUMS = 31 doubles.  Inputs: d_src [n_src][3] f32 the MOVED source and d_src_intensity [n_src] f32 in the same order;
+ *   d_tgt [n_tgt][3] f32 with d_tgt_normals [n_tgt][3] f32, d_tgt_intensity [n_tgt] f32 and d_tgt_grad [n_tgt][3] f32 (the two outputs
+ *   above); d_idx [n_src] u32 / d_d2 [n_src] f32 from the NN index; max_d2 (f32; < 0: no gate, d_d2 may then be NULL); w_photo >= 0
+ *   finite (the weight of a photometric pair against a geometric pair's 1, in length^2 per intensity^2); i_max > 0 finite.
+ *   Geometric pair k = (p = src[k], q = tgt[idx[k]], n = tgt_normals[idx[k]]), exactly the untrimmed plane pair: out when idx[k] >=
+ *     n_tgt (the index array is data), when max_d2 >= 0 and not (d2[k] <= max_d2) (the pair AT the gate is in, a NaN d2 is out), when
+ *     n is the zero vector, when r = n_0 (p_0 - q_0) + n_1 (p_1 - q_1) + n_2 (p_2 - q_2) or (p_0 + p_1) + p_2 is not finite.  It adds,
+ *     with J = [p x n ; n]: [0] += 1; [1] += r r; [2 + a] += J_a r; [8..28] += the upper triangle of J_a J_b, row-major.
+ *   Photometric term of an accepted geometric pair, with I_p = d_src_intensity[k], I_q, g = the target's intensity and gradient at q:
+ *       p'_a = p_a - r n_a;  d_a = p'_a - q_a;  rI = ((double) I_q + ((g_0 d_0 + g_1 d_1) + g_2 d_2)) - (double) I_p
+ *       gn = (g_0 n_0 + g_1 n_1) + g_2 n_2;  a_c = g_c - gn n_c
+ *     the pair enters iff rI, a_0, a_1, a_2 are all finite and |rI| <= i_max (the pair AT i_max is in); then with w = w_photo and
+ *     J = [p x a ; a]: [2 + k] += (w J_k) rI; [8..28] += the upper triangle of (w J_k) J_l; [29] += 1; [30] += rI rI.
+ *   Sums [0] and [1] stay purely geometric, so the state's pairs, rms and rms history and the n >= 6 test of the solve mean what they
+ *     mean for r3d_icp_iterate_plane; r3d_plane_step_from_sums solves the step from the first 29.  Grid and reduction are
+ *     r3d_icp_plane_accumulate's: min(ceil(n_src / 256), C) workgroups (C = the device's compute units), one row of 31 partials per
+ *     workgroup, one finishing workgroup, no float atomics: bitwise repeatable, and with w_photo == 0 the first 29 sums are the bits
+ *     of r3d_icp_plane_accumulate(..., trim_q 0, gate_scale 1).  d_photo_out [n_src] f32 (may be NULL) = (float) rI where a
+ *     photometric pair entered, NaN elsewhere.  n_src == 0: 31 zeros, no launch.
+ *   R3D_ERR_INVALID, nothing written: a NULL ctx or h_sums; negative sizes; with n_src > 0 a NULL d_src, d_src_intensity, d_tgt,
+ *     d_tgt_normals, d_tgt_intensity, d_tgt_grad or d_idx; max_d2 >= 0 with a NULL d_d2; max_d2 NaN; w_photo negative or not finite;
+ *     i_max not > 0 and finite; d_photo_out overlapping an input.
+ *
+ * r3d_icp_iterate_color: n_iters whole passes with NO host round trip on the R3D_ICP_STATE_DOUBLES state -- r3d_icp_iterate_plane
+ *   without the direction classes and the rank trimming.  Each pass: culled exact NN (d_src in the index's order,
+ *   r3d_nn_index_sort_cloud; warm-started exactly as the plane loop is) -> the pass above against the index's cloud -> finish, solve
+ *   from the first 29 sums and state update on the device -> d_src = T_total . d_src_orig (d_src_orig NULL: d_src moved in place by
+ *   the step).  d_src_intensity [n_src] f32 is constant and in the order of d_src.  d_tgt_normals, d_tgt_intensity, d_tgt_grad: of
+ *   the index's cloud in its ORIGINAL order.  A singular solve sets the sticky status 1 and moves nothing.  d_sums_out (may be NULL):
+ *   the 31 sums of the last pass, in HBM.  Asynchronous.
+ *   R3D_ERR_INVALID, nothing written: a NULL ctx, index or required device pointer; an index of another context; n_iters < 0;
+ *     n_src < 6; d_src_orig == d_src; max_d2 NaN; w_photo / i_max as above; d_src, d_idx, d_d2, d_state or d_sums_out overlapping one
+ *     another or an input.
+ * Deliberately not done here: colour in register_multiway and register_global; robust (Huber) weights; rank trimming in the coloured
+ *   loop; exposure compensation; a bench.py workload; the multi-GPU path. */
+#define R3D_COLOR_ICP_SUMS 31
+#define R3D_COLOR_GRADIENT_FLOOR 1e-14
+int r3d_color_gradient_knn(r3d_nn_index* index, int k, double radius, const float* d_normals, const uint32_t* d_rgba,
+                           float* d_intensity_out, float* d_grad_out, uint32_t* d_count_out);
+int r3d_icp_color_accumulate(r3d_ctx* ctx, const float* d_src, const float* d_src_intensity, int64_t n_src, const float* d_tgt,
+                             const float* d_tgt_normals, const float* d_tgt_intensity, const float* d_tgt_grad, int64_t n_tgt,
+                             const uint32_t* d_idx, const float* d_d2, float max_d2, double w_photo, double i_max, double* h_sums,
+                             float* d_photo_out);
+int r3d_icp_iterate_color(r3d_ctx* ctx, r3d_nn_index* index, const float* d_src_orig, float* d_src, const float* d_src_intensity,
+                          int64_t n_src, const float* d_tgt_normals, const float* d_tgt_intensity, const float* d_tgt_grad,
+                          uint32_t* d_idx, float* d_d2, int n_iters, float max_d2, double w_photo, double i_max, double* d_state,
+                          double* d_sums_out);
+
 #ifdef __cplusplus
 }
 #endif
