@@ -4,6 +4,8 @@
 // segment_plane on the fused cloud; no parity with Open3D is claimed).  Semantics: include/r3d.h (r3d_segment_plane) and
 // DESIGN.md section 4.5h.
 //
+// The sampler, the launch plan, the scratch layout and the fold and best kernels are r3d_consensus_dev.h's (shared with
+// r3d_register.hip); this file has what a plane is:
 //   hypothesis_kernel   one lane per hypothesis: the counter-based sampler, three row gathers, the fp64 cross product, validity;
 //                       writes the anchor and the f32 unit normal as six SoA floats (an invalid hypothesis gets NaN normals,
 //                       so every one of its tests compares false) and its rows.
@@ -13,51 +15,33 @@
 //                       64 R pairs.  Grid = point chunks x hypothesis blocks; each workgroup writes its partial counts
 //                       [chunk][h] with plain stores.  No atomics, no ballot, no scratch; the tile loop runs to the number of
 //                       points the tile holds, so tail slots are never evaluated.
-//   fold_kernel         per hypothesis, the sum over the chunks (integers: the same bits for every chunking) -> counts
-//   best_kernel         one workgroup: the lowest h among the maximal counts, and the number of valid hypotheses
-//   refit_kernel        the best hypothesis' inliers by the same f32 test; their ten fp64 sums about the anchor, one row per
+//   refit_kernel       the best hypothesis' inliers by the same f32 test; their ten fp64 sums about the anchor, one row per
 //                       workgroup (shuffle tree -> LDS, fixed order: r3d_sums_dev.h)
 //   refit_fold_kernel   one wave folds the rows in a fixed order; also fetches the best hypothesis' three points
 //   mask_kernel         the final fp64 test against the refined plane; per-workgroup inlier counts, integer atomics
-// The 3x3 eigenproblem is solved on the host (as r3d_umeyama_from_sums does its SVD) between refit_fold and mask.
+// The 3x3 eigenproblem (r3d_sym3.h) is solved on the host, as r3d_umeyama_from_sums does its SVD, between refit_fold and mask.
 #include <algorithm>
 #include <cmath>
 
+#include "r3d_consensus_dev.h"
 #include "r3d_internal.h"
 #include "r3d_sums_dev.h"
+#include "r3d_sym3.h"
 
 namespace {
 
-constexpr int kThreads = 256;
+using r3d_consensus::kThreads;
+using r3d_consensus::sample_row;
 constexpr int kTile = 512;            // points per LDS tile: 2 per thread, 8 KiB as float4, two buffers
-constexpr int kMaxWorkgroups = 4096;  // chunks x hypothesis blocks is kept near this: the partial counts stay <= 16 MiB
-constexpr int kMinTiles = 4;
-constexpr int kRefitBlocks = 1024;
 constexpr int kSums = 10;             // m, S1 (3), S2 (6)
 
 // what the host reads back after the refit, one copy
 struct Misc {
-  uint32_t best_h, c_best, n_valid, pad;
-  uint32_t rows[4];
+  r3d_consensus::BestHead head;
   float abc[12];          // the best hypothesis' three points, xyz each
   double sums[kSums];
   unsigned long long n_inliers;
 };
-
-__host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-__host__ __device__ __forceinline__ uint32_t sample_row(uint64_t seed, uint64_t h, int j, uint64_t n) {
-  const uint64_t a = splitmix64(seed + (3 * h + (uint64_t)j + 1) * 0x9E3779B97F4A7C15ull);
-#if defined(__HIP_DEVICE_COMPILE__)
-  return (uint32_t)__umul64hi(a, n);
-#else
-  return (uint32_t)(((unsigned __int128)a * n) >> 64);
-#endif
-}
 
 struct Plane64 {
   double n[3], l2;
@@ -185,61 +169,14 @@ __global__ __launch_bounds__(kThreads) void count_kernel(const float* __restrict
   for (int r = 0; r < R; ++r) partial[(size_t)blockIdx.x * h_pad + hb + t + r * kThreads] = cnt[r];
 }
 
-// counts[h] = valid[h] ? sum over the chunks : 0
-__global__ __launch_bounds__(kThreads) void fold_kernel(const uint32_t* __restrict__ partial, int chunks, int h_pad, int H,
-                                                        const uint32_t* __restrict__ valid, uint32_t* __restrict__ counts,
-                                                        uint32_t* __restrict__ counts_out) {
-  const int h = blockIdx.x * kThreads + threadIdx.x;
-  if (h >= H) return;
-  uint32_t c = 0;
-  for (int k = 0; k < chunks; ++k) c += partial[(size_t)k * h_pad + h];
-  if (!valid[h]) c = 0;
-  counts[h] = c;
-  if (counts_out) counts_out[h] = c;
-}
-
-// one workgroup: key = count << 32 | ~h, the maximum is the lowest h among the maximal counts
-__global__ __launch_bounds__(kThreads) void best_kernel(const uint32_t* __restrict__ counts, const uint32_t* __restrict__ valid,
-                                                        const uint32_t* __restrict__ rows, int H, Misc* __restrict__ misc) {
-  uint64_t key = 0;
-  uint32_t nv = 0;
-  for (int h = threadIdx.x; h < H; h += kThreads) {
-    const uint64_t k = ((uint64_t)counts[h] << 32) | (uint32_t)~(uint32_t)h;
-    key = k > key ? k : key;
-    nv += valid[h];
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const uint64_t o = __shfl_down(key, off, 64);
-    key = o > key ? o : key;
-    nv += __shfl_down(nv, off, 64);
-  }
-  __shared__ uint64_t sk[kThreads / 64];
-  __shared__ uint32_t sv[kThreads / 64];
-  if ((threadIdx.x & 63) == 0) {
-    sk[threadIdx.x >> 6] = key;
-    sv[threadIdx.x >> 6] = nv;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kThreads / 64; ++w) {
-      key = sk[w] > key ? sk[w] : key;
-      nv += sv[w];
-    }
-    const uint32_t h = ~(uint32_t)key;
-    misc->best_h = h;
-    misc->c_best = (uint32_t)(key >> 32);
-    misc->n_valid = nv;
-    misc->pad = 0;
-    for (int j = 0; j < 3; ++j) misc->rows[j] = rows[3 * h + j];
-    misc->rows[3] = 0;
-  }
-}
+struct NoTail {
+  __device__ void operator()(Misc*, int, uint32_t) const {}
+};
 
 // grid-stride over the points: the best hypothesis' inliers and their sums about the anchor -> partial rows [gridDim.x][kSums]
 __global__ __launch_bounds__(kThreads) void refit_kernel(const float* __restrict__ xyz, int64_t n, const float* __restrict__ hyp, int h_pad,
                                                          float thr, const Misc* __restrict__ misc, double* __restrict__ part) {
-  const uint32_t h = misc->best_h;
+  const uint32_t h = misc->head.best_h;
   const float ax = hyp[h], ay = hyp[(size_t)h_pad + h], az = hyp[(size_t)2 * h_pad + h];
   const float nx = hyp[(size_t)3 * h_pad + h], ny = hyp[(size_t)4 * h_pad + h], nz = hyp[(size_t)5 * h_pad + h];
   double acc[kSums] = {};
@@ -273,7 +210,7 @@ __global__ __launch_bounds__(64) void refit_fold_kernel(const double* __restrict
     misc->sums[k] = v;
   } else if (k >= 16 && k < 25) {
     const int j = (k - 16) / 3, a = (k - 16) % 3;
-    misc->abc[3 * j + a] = xyz[(size_t)misc->rows[j] * 3 + a];
+    misc->abc[3 * j + a] = xyz[(size_t)misc->head.rows[j] * 3 + a];
   }
 }
 
@@ -300,49 +237,6 @@ __global__ __launch_bounds__(kThreads) void mask_kernel(const float* __restrict_
     const uint32_t s = sh[0] + sh[1] + sh[2] + sh[3];
     if (s) atomicAdd(total, (unsigned long long)s);
   }
-}
-
-// ---- host: the 3x3 symmetric eigenproblem (cyclic Jacobi, the arithmetic of r3d_knn.hip's normals) -----------------------------
-bool jacobi_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double v[3][3], int p, int q) {
-  if (!(std::fabs(apq) > 5.421010862427522e-20 * (std::fabs(app) + std::fabs(aqq)))) return false;
-  const double theta = (aqq - app) / (2.0 * apq);
-  const double at = std::fabs(theta);
-  double t = at > 1e150 ? 0.5 / at : 1.0 / (at + std::sqrt(at * at + 1.0));
-  t = theta < 0.0 ? -t : t;
-  const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c, tau = s / (1.0 + c);
-  app -= t * apq;
-  aqq += t * apq;
-  apq = 0.0;
-  const double rp = arp, rq = arq;
-  arp = rp - s * (rq + tau * rp);
-  arq = rq + s * (rp - tau * rq);
-  for (int k = 0; k < 3; ++k) {
-    const double a = v[k][p], b = v[k][q];
-    v[k][p] = a - s * (b + tau * a);
-    v[k][q] = b + s * (a - tau * b);
-  }
-  return true;
-}
-
-// eigenvalues l[0] <= l[1] <= l[2] of C (xx xy xz yy yz zz) and the unit eigenvector of l[0] (the lowest column on ties)
-void sym3_smallest(const double C[6], double l[3], double n[3]) {
-  double a00 = C[0], a01 = C[1], a02 = C[2], a11 = C[3], a12 = C[4], a22 = C[5];
-  double v[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-  for (int sweep = 0; sweep < 16; ++sweep) {
-    bool any = jacobi_rotate(a00, a11, a01, a02, a12, v, 0, 1);
-    any |= jacobi_rotate(a00, a22, a02, a01, a12, v, 0, 2);
-    any |= jacobi_rotate(a11, a22, a12, a01, a02, v, 1, 2);
-    if (!any) break;
-  }
-  const int col = (a00 <= a11 && a00 <= a22) ? 0 : (a11 <= a22 ? 1 : 2);
-  l[0] = std::fmin(a00, std::fmin(a11, a22));
-  l[2] = std::fmax(a00, std::fmax(a11, a22));
-  l[1] = std::fmax(std::fmin(a00, a11), std::fmin(std::fmax(a00, a11), a22));
-  const double x = v[0][col], y = v[1][col], z = v[2][col];
-  const double len = std::sqrt(x * x + y * y + z * z);
-  n[0] = x / len;
-  n[1] = y / len;
-  n[2] = z / len;
 }
 
 // the component of largest magnitude is positive, the lowest axis winning ties
@@ -377,59 +271,37 @@ int r3d_segment_plane(r3d_ctx* ctx, const float* d_xyz, int64_t n, double thr, i
   R3D_REQUIRE(ctx != nullptr, "ctx is NULL");
   R3D_REQUIRE(d_xyz && d_inlier_out && h_result && n_inliers_out, "NULL pointer");
   R3D_REQUIRE(n >= 3 && n < ((int64_t)1 << 32), "the cloud needs 3 <= n < 2^32 rows, got %lld", (long long)n);
-  R3D_REQUIRE(H >= 1 && H <= 65536, "n_hypotheses must be in [1, 65536], got %d", H);
-  R3D_REQUIRE(std::isfinite(thr) && thr > 0.0, "distance_threshold must be finite and > 0, got %g", thr);
+  int rc = r3d_consensus::check_args(H, thr);
+  if (rc) return rc;
   const size_t xb = (size_t)n * 12, cb = d_counts_out ? (size_t)H * 4 : 0;
   R3D_REQUIRE(!r3d_ranges_overlap(d_inlier_out, (size_t)n, d_xyz, xb) && !r3d_ranges_overlap(d_counts_out, cb, d_xyz, xb) &&
                   !r3d_ranges_overlap(d_counts_out, cb, d_inlier_out, (size_t)n),
               "an output overlaps the cloud or the other output");
-  int rc = r3d_ctx_enter(ctx);
-  if (rc) return rc;
+  if ((rc = r3d_ctx_enter(ctx))) return rc;
 
-  // R hypotheses per lane: the most the hypothesis count fills one workgroup with
-  const int R = H >= 4 * kThreads ? 4 : H >= 2 * kThreads ? 2 : 1;
-  const int per_block = kThreads * R;
-  const int h_pad = (H + per_block - 1) / per_block * per_block, h_blocks = h_pad / per_block;
-  const int64_t tiles = (n + kTile - 1) / kTile;
-  const int64_t max_chunks = std::max<int64_t>(1, kMaxWorkgroups / h_blocks);
-  // at least kMinTiles tiles per chunk: a workgroup's hypothesis loads and partial-count stores are paid per chunk
-  const int64_t chunk_points = std::max<int64_t>((tiles + max_chunks - 1) / max_chunks, std::min<int64_t>(tiles, kMinTiles)) * kTile;
-  const int chunks = (int)((n + chunk_points - 1) / chunk_points);
-  const int rblocks = (int)std::min<int64_t>((n + kThreads - 1) / kThreads, kRefitBlocks);
-
-  // slot 5: what the host reads, the hypotheses, their rows, validity and counts; slot 4: the partial counts, then the sum rows
-  const size_t misc_b = (sizeof(Misc) + 255) & ~(size_t)255;
-  const size_t hyp_b = (size_t)6 * h_pad * 4, rows_b = ((size_t)3 * H * 4 + 255) & ~(size_t)255, hb = ((size_t)H * 4 + 255) & ~(size_t)255;
-  const size_t part_b = ((size_t)chunks * h_pad * 4 + 255) & ~(size_t)255;
-  void *s5 = nullptr, *s4 = nullptr;
-  if ((rc = r3d_scratch(ctx, 5, misc_b + hyp_b + rows_b + 2 * hb, &s5))) return rc;
-  if ((rc = r3d_scratch(ctx, 4, part_b + (size_t)rblocks * kSums * sizeof(double), &s4))) return rc;
-  char* p5 = static_cast<char*>(s5);
-  Misc* misc = reinterpret_cast<Misc*>(p5);
-  float* hyp = reinterpret_cast<float*>(p5 + misc_b);
-  uint32_t* rows = reinterpret_cast<uint32_t*>(p5 + misc_b + hyp_b);
-  uint32_t* valid = reinterpret_cast<uint32_t*>(p5 + misc_b + hyp_b + rows_b);
-  uint32_t* counts = reinterpret_cast<uint32_t*>(p5 + misc_b + hyp_b + rows_b + hb);
-  uint32_t* partial = static_cast<uint32_t*>(s4);
-  double* part = reinterpret_cast<double*>(static_cast<char*>(s4) + part_b);
+  const r3d_consensus::Plan pn = r3d_consensus::plan(n, H, kTile);
+  r3d_consensus::Layout lay;
+  if ((rc = r3d_consensus::layout(ctx, pn, 6, kSums, sizeof(Misc), &lay))) return rc;
+  Misc* misc = static_cast<Misc*>(lay.misc);
+  const int h_pad = pn.h_pad, rblocks = pn.rblocks;
 
   r3d_wrote(ctx, d_inlier_out, (size_t)n);
   if (d_counts_out) r3d_wrote(ctx, d_counts_out, cb);
   hipStream_t st = ctx->stream;
   const float thr_f = (float)thr;
   R3D_HIP(hipMemsetAsync(misc, 0, sizeof(Misc), st));
-  hipLaunchKernelGGL(hypothesis_kernel, dim3((unsigned)(h_pad / kThreads)), dim3(kThreads), 0, st, d_xyz, (uint64_t)n, H, h_pad, seed, hyp,
-                     rows, valid);
-  if (R == 4) launch_count<4>(st, chunks, h_pad, d_xyz, n, chunk_points, hyp, thr_f, partial);
-  else if (R == 2) launch_count<2>(st, chunks, h_pad, d_xyz, n, chunk_points, hyp, thr_f, partial);
-  else launch_count<1>(st, chunks, h_pad, d_xyz, n, chunk_points, hyp, thr_f, partial);
-  hipLaunchKernelGGL(fold_kernel, dim3((unsigned)((H + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, (const uint32_t*)partial, chunks,
-                     h_pad, H, (const uint32_t*)valid, counts, d_counts_out);
-  hipLaunchKernelGGL(best_kernel, dim3(1), dim3(kThreads), 0, st, (const uint32_t*)counts, (const uint32_t*)valid, (const uint32_t*)rows, H,
-                     misc);
-  hipLaunchKernelGGL(refit_kernel, dim3((unsigned)rblocks), dim3(kThreads), 0, st, d_xyz, n, (const float*)hyp, h_pad, thr_f,
-                     (const Misc*)misc, part);
-  hipLaunchKernelGGL(refit_fold_kernel, dim3(1), dim3(64), 0, st, (const double*)part, rblocks, d_xyz, misc);
+  hipLaunchKernelGGL(hypothesis_kernel, dim3((unsigned)(h_pad / kThreads)), dim3(kThreads), 0, st, d_xyz, (uint64_t)n, H, h_pad, seed, lay.hyp,
+                     lay.rows, lay.valid);
+  if (pn.R == 4) launch_count<4>(st, pn.chunks, h_pad, d_xyz, n, pn.chunk_items, lay.hyp, thr_f, lay.partial);
+  else if (pn.R == 2) launch_count<2>(st, pn.chunks, h_pad, d_xyz, n, pn.chunk_items, lay.hyp, thr_f, lay.partial);
+  else launch_count<1>(st, pn.chunks, h_pad, d_xyz, n, pn.chunk_items, lay.hyp, thr_f, lay.partial);
+  hipLaunchKernelGGL(r3d_consensus::fold_kernel, dim3((unsigned)((H + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
+                     (const uint32_t*)lay.partial, pn.chunks, h_pad, H, (const uint32_t*)lay.valid, lay.counts, d_counts_out);
+  hipLaunchKernelGGL((r3d_consensus::best_kernel<Misc, NoTail>), dim3(1), dim3(kThreads), 0, st, (const uint32_t*)lay.counts,
+                     (const uint32_t*)lay.valid, (const uint32_t*)lay.rows, H, NoTail(), misc);
+  hipLaunchKernelGGL(refit_kernel, dim3((unsigned)rblocks), dim3(kThreads), 0, st, d_xyz, n, (const float*)lay.hyp, h_pad, thr_f,
+                     (const Misc*)misc, lay.part);
+  hipLaunchKernelGGL(refit_fold_kernel, dim3(1), dim3(64), 0, st, (const double*)lay.part, rblocks, d_xyz, misc);
   R3D_HIP(hipGetLastError());
   Misc m;
   R3D_HIP(hipMemcpyAsync(&m, misc, sizeof(Misc), hipMemcpyDeviceToHost, st));
@@ -437,11 +309,11 @@ int r3d_segment_plane(r3d_ctx* ctx, const float* d_xyz, int64_t n, double thr, i
 
   double res[16];
   for (int k = 0; k < 10; ++k) res[k] = NAN;
-  res[10] = m.best_h;
-  res[11] = m.c_best;
-  for (int j = 0; j < 3; ++j) res[12 + j] = m.rows[j];
-  res[15] = m.n_valid;
-  if (m.c_best < 3) {
+  res[10] = m.head.best_h;
+  res[11] = m.head.c_best;
+  for (int j = 0; j < 3; ++j) res[12 + j] = m.head.rows[j];
+  res[15] = m.head.n_valid;
+  if (m.head.c_best < 3) {
     R3D_HIP(hipMemsetAsync(d_inlier_out, 0, (size_t)n, st));
     R3D_HIP(hipStreamSynchronize(st));
     memcpy(h_result, res, sizeof(res));
@@ -458,7 +330,7 @@ int r3d_segment_plane(r3d_ctx* ctx, const float* d_xyz, int64_t n, double thr, i
     for (int a = 0; a < 3; ++a)
       for (int b = a; b < 3; ++b, ++k) C[k] = (s[4 + k] - s[1 + a] * s[1 + b] / cnt) / cnt;
   }
-  sym3_smallest(C, l, pl.n);
+  r3d_sym3::sym3_smallest(C, l, pl.n);
   if (!(l[1] > 0.0)) {   // collinear inliers: the hypothesis' own plane through a
     const Plane64 hp = plane_of(m.abc, m.abc + 3, m.abc + 6, true);
     for (int a = 0; a < 3; ++a) {

@@ -11,12 +11,14 @@
 //   r3d_register_ransac
 //     pair_kernel        gathers the m correspondences into two float4 per pair (source point, target point); a row number
 //                        outside its cloud gives NaN points, which are nobody's inlier and make a hypothesis invalid
-//     pose_kernel        one lane per hypothesis: the counter-based sampler of r3d_ransac.hip, the closed-form fp64 pose from
-//                        three pairs, validity; R^ and t^ as twelve SoA floats (NaN when invalid: every test compares false)
+//     pose_kernel        one lane per hypothesis: the counter-based sampler, the closed-form fp64 pose from three pairs,
+//                        validity; R^ and t^ as twelve SoA floats (NaN when invalid: every test compares false)
 //     count_kernel<R>    the hot path, the shape of r3d_ransac.hip's: lanes own R hypotheses in registers with one u32 count
 //                        apiece, the workgroup's chunk of pairs goes through LDS in tiles and every lane reads the SAME pair
 //                        (two broadcast ds_read_b128 per 64 R tests); partial counts [chunk][h], plain stores, no atomics
-//     fold / best        integer sums over the chunks; the lowest h of maximal count, the number of valid hypotheses
+//     fold / best        r3d_consensus_dev.h's, as are the sampler, the launch plan and the scratch layout: integer sums over
+//                        the chunks; the lowest h of maximal count, the number of valid hypotheses; FetchPairs, best's tail
+//                        here, also fetches the winner's three pairs
 //     refit_kernel       the best pose's inliers by the same f32 test -> the 18 fp64 pair sums about the anchors, one row per
 //                        workgroup, folded by one workgroup in fixed order (r3d_sums_dev.h)
 //     mask_kernel        the final f32 test with the refitted pose; inlier count and sum of squared distances through the same
@@ -25,6 +27,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "r3d_consensus_dev.h"
 #include "r3d_icp_sums.h"
 #include "r3d_internal.h"
 #include "r3d_sums_dev.h"
@@ -34,7 +37,8 @@ int r3d_match_nearest(r3d_ctx* ctx, const float* d_a, int64_t na, const float* d
 
 namespace {
 
-constexpr int kThreads = 256;
+using r3d_consensus::kThreads;
+using r3d_consensus::sample_row;
 constexpr int kDim = R3D_FPFH_DIM;
 constexpr uint32_t kNone = 0xffffffffu;
 
@@ -103,31 +107,16 @@ __global__ __launch_bounds__(kThreads) void keep_write_kernel(const uint32_t* __
 }
 
 // ---- RANSAC over correspondences --------------------------------------------------------------------------------------------------
-constexpr int kTile = 256;            // pairs per LDS tile: one per thread, 8 KiB as two float4, two buffers
-constexpr int kMaxWorkgroups = 4096;
-constexpr int kMinTiles = 4;
-constexpr int kRefitBlocks = 1024;
+constexpr int kTile = 256;              // pairs per LDS tile: one per thread, 8 KiB as two float4, two buffers
 constexpr int kSums = r3d_icp::kSums;   // 18
 constexpr int kMaskSums = 2;            // inliers, sum of their squared distances
 
 struct Misc {
-  uint32_t best_h, c_best, n_valid, pad;
-  uint32_t rows[4];
+  r3d_consensus::BestHead head;
   float pts[24];          // the best hypothesis' three pairs as gathered: source xyz_, target xyz_ each
   double sums[kSums];
   double mask_sums[kMaskSums];
 };
-
-__host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ uint32_t sample_row(uint64_t seed, uint64_t h, int j, uint64_t n) {
-  const uint64_t a = splitmix64(seed + (3 * h + (uint64_t)j + 1) * 0x9E3779B97F4A7C15ull);
-  return (uint32_t)__umul64hi(a, n);
-}
 
 __global__ __launch_bounds__(kThreads) void pair_kernel(const float* __restrict__ src, int64_t ns, const float* __restrict__ tgt, int64_t nt,
                                                         const uint32_t* __restrict__ corr, int64_t m, float4* __restrict__ pairs) {
@@ -280,67 +269,20 @@ __global__ __launch_bounds__(kThreads) void count_kernel(const float4* __restric
   for (int r = 0; r < R; ++r) partial[(size_t)blockIdx.x * h_pad + hb + t + r * kThreads] = cnt[r];
 }
 
-__global__ __launch_bounds__(kThreads) void fold_kernel(const uint32_t* __restrict__ partial, int chunks, int h_pad, int H,
-                                                        const uint32_t* __restrict__ valid, uint32_t* __restrict__ counts,
-                                                        uint32_t* __restrict__ counts_out) {
-  const int h = blockIdx.x * kThreads + threadIdx.x;
-  if (h >= H) return;
-  uint32_t c = 0;
-  for (int k = 0; k < chunks; ++k) c += partial[(size_t)k * h_pad + h];
-  if (!valid[h]) c = 0;
-  counts[h] = c;
-  if (counts_out) counts_out[h] = c;
-}
-
-// one workgroup: key = count << 32 | ~h, the maximum is the lowest h among the maximal counts; also fetches its three pairs
-__global__ __launch_bounds__(kThreads) void best_kernel(const uint32_t* __restrict__ counts, const uint32_t* __restrict__ valid,
-                                                        const uint32_t* __restrict__ rows, int H, const float4* __restrict__ pairs,
-                                                        Misc* __restrict__ misc) {
-  uint64_t key = 0;
-  uint32_t nv = 0;
-  for (int h = threadIdx.x; h < H; h += kThreads) {
-    const uint64_t k = ((uint64_t)counts[h] << 32) | (uint32_t)~(uint32_t)h;
-    key = k > key ? k : key;
-    nv += valid[h];
+// best_kernel's tail: the best hypothesis' three pairs as gathered
+struct FetchPairs {
+  const float4* __restrict__ pairs;
+  __device__ void operator()(Misc* __restrict__ misc, int j, uint32_t r) const {
+    const float4 p = pairs[2 * (size_t)r], q = pairs[2 * (size_t)r + 1];
+    float* d = misc->pts + 8 * j;
+    d[0] = p.x, d[1] = p.y, d[2] = p.z, d[3] = 0.f, d[4] = q.x, d[5] = q.y, d[6] = q.z, d[7] = 0.f;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const uint64_t o = __shfl_down(key, off, 64);
-    key = o > key ? o : key;
-    nv += __shfl_down(nv, off, 64);
-  }
-  __shared__ uint64_t sk[kThreads / 64];
-  __shared__ uint32_t sv[kThreads / 64];
-  if ((threadIdx.x & 63) == 0) {
-    sk[threadIdx.x >> 6] = key;
-    sv[threadIdx.x >> 6] = nv;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kThreads / 64; ++w) {
-      key = sk[w] > key ? sk[w] : key;
-      nv += sv[w];
-    }
-    const uint32_t h = ~(uint32_t)key;
-    misc->best_h = h;
-    misc->c_best = (uint32_t)(key >> 32);
-    misc->n_valid = nv;
-    misc->pad = 0;
-    for (int j = 0; j < 3; ++j) {
-      const uint32_t r = rows[3 * h + j];
-      misc->rows[j] = r;
-      const float4 p = pairs[2 * (size_t)r], q = pairs[2 * (size_t)r + 1];
-      float* d = misc->pts + 8 * j;
-      d[0] = p.x, d[1] = p.y, d[2] = p.z, d[3] = 0.f, d[4] = q.x, d[5] = q.y, d[6] = q.z, d[7] = 0.f;
-    }
-    misc->rows[3] = 0;
-  }
-}
+};
 
 // grid-stride over the pairs: the best pose's inliers and their 18 sums about the anchors (the first pair of the hypothesis)
 __global__ __launch_bounds__(kThreads) void refit_kernel(const float4* __restrict__ pairs, int64_t m, const float* __restrict__ hyp, int h_pad,
                                                          float thr2, const Misc* __restrict__ misc, double* __restrict__ part) {
-  const uint32_t h = misc->best_h;
+  const uint32_t h = misc->head.best_h;
   float P[12];
 #pragma unroll
   for (int k = 0; k < 12; ++k) P[k] = hyp[(size_t)k * h_pad + h];
@@ -455,8 +397,8 @@ int r3d_register_ransac(r3d_ctx* ctx, const float* d_src, int64_t ns, const floa
   R3D_REQUIRE(ns >= 1 && ns < ((int64_t)1 << 32) && nt >= 1 && nt < ((int64_t)1 << 32), "the clouds need 1 <= n < 2^32 rows, got %lld, %lld",
               (long long)ns, (long long)nt);
   R3D_REQUIRE(m >= 3 && m < ((int64_t)1 << 32), "need 3 <= m < 2^32 correspondences, got %lld", (long long)m);
-  R3D_REQUIRE(H >= 1 && H <= 65536, "n_hypotheses must be in [1, 65536], got %d", H);
-  R3D_REQUIRE(std::isfinite(thr) && thr > 0.0, "distance_threshold must be finite and > 0, got %g", thr);
+  int rc = r3d_consensus::check_args(H, thr);
+  if (rc) return rc;
   const size_t cb = d_counts_out ? (size_t)H * 4 : 0;
   const struct {
     const void* p;
@@ -466,36 +408,18 @@ int r3d_register_ransac(r3d_ctx* ctx, const float* d_src, int64_t ns, const floa
     R3D_REQUIRE(!r3d_ranges_overlap(d_inlier_out, (size_t)m, in[i].p, in[i].bytes) && !r3d_ranges_overlap(d_counts_out, cb, in[i].p, in[i].bytes),
                 "an output overlaps an input");
   R3D_REQUIRE(!r3d_ranges_overlap(d_counts_out, cb, d_inlier_out, (size_t)m), "the outputs overlap each other");
-  int rc = r3d_ctx_enter(ctx);
-  if (rc) return rc;
+  if ((rc = r3d_ctx_enter(ctx))) return rc;
 
-  const int R = H >= 4 * kThreads ? 4 : H >= 2 * kThreads ? 2 : 1;
-  const int per_block = kThreads * R;
-  const int h_pad = (H + per_block - 1) / per_block * per_block, h_blocks = h_pad / per_block;
-  const int64_t tiles = (m + kTile - 1) / kTile;
-  const int64_t max_chunks = std::max<int64_t>(1, kMaxWorkgroups / h_blocks);
-  const int64_t chunk_pairs = std::max<int64_t>((tiles + max_chunks - 1) / max_chunks, std::min<int64_t>(tiles, kMinTiles)) * kTile;
-  const int chunks = (int)((m + chunk_pairs - 1) / chunk_pairs);
-  const int rblocks = (int)std::min<int64_t>((m + kThreads - 1) / kThreads, kRefitBlocks);
-
-  // slot 0: the gathered pairs; slot 5: what the host reads, the poses, their rows, validity and counts; slot 4: the partial
-  // counts, then the sum rows
-  const size_t misc_b = (sizeof(Misc) + 255) & ~(size_t)255;
-  const size_t hyp_b = (size_t)12 * h_pad * 4, rows_b = ((size_t)3 * H * 4 + 255) & ~(size_t)255, hb = ((size_t)H * 4 + 255) & ~(size_t)255;
-  const size_t part_b = ((size_t)chunks * h_pad * 4 + 255) & ~(size_t)255;
-  void *s0 = nullptr, *s5 = nullptr, *s4 = nullptr;
+  // slot 0: the gathered pairs; slots 5 and 4: the consensus layout
+  const r3d_consensus::Plan pn = r3d_consensus::plan(m, H, kTile);
+  void* s0 = nullptr;
   if ((rc = r3d_scratch(ctx, 0, (size_t)m * 32, &s0))) return rc;
-  if ((rc = r3d_scratch(ctx, 5, misc_b + hyp_b + rows_b + 2 * hb, &s5))) return rc;
-  if ((rc = r3d_scratch(ctx, 4, part_b + (size_t)rblocks * kSums * sizeof(double), &s4))) return rc;
+  r3d_consensus::Layout lay;
+  if ((rc = r3d_consensus::layout(ctx, pn, 12, kSums, sizeof(Misc), &lay))) return rc;
   float4* pairs = static_cast<float4*>(s0);
-  char* p5 = static_cast<char*>(s5);
-  Misc* misc = reinterpret_cast<Misc*>(p5);
-  float* hyp = reinterpret_cast<float*>(p5 + misc_b);
-  uint32_t* rows = reinterpret_cast<uint32_t*>(p5 + misc_b + hyp_b);
-  uint32_t* valid = reinterpret_cast<uint32_t*>(p5 + misc_b + hyp_b + rows_b);
-  uint32_t* counts = reinterpret_cast<uint32_t*>(p5 + misc_b + hyp_b + rows_b + hb);
-  uint32_t* partial = static_cast<uint32_t*>(s4);
-  double* part = reinterpret_cast<double*>(static_cast<char*>(s4) + part_b);
+  Misc* misc = static_cast<Misc*>(lay.misc);
+  double* part = lay.part;
+  const int h_pad = pn.h_pad, rblocks = pn.rblocks;
 
   r3d_wrote(ctx, d_inlier_out, (size_t)m);
   if (d_counts_out) r3d_wrote(ctx, d_counts_out, cb);
@@ -505,15 +429,15 @@ int r3d_register_ransac(r3d_ctx* ctx, const float* d_src, int64_t ns, const floa
   hipLaunchKernelGGL(pair_kernel, dim3((unsigned)((m + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, d_src, ns, d_tgt, nt, d_corr, m,
                      pairs);
   hipLaunchKernelGGL(pose_kernel, dim3((unsigned)(h_pad / kThreads)), dim3(kThreads), 0, st, (const float4*)pairs, d_corr, (uint64_t)m, thr,
-                     H, h_pad, seed, hyp, rows, valid);
-  if (R == 4) launch_count<4>(st, chunks, h_pad, pairs, m, chunk_pairs, hyp, thr2, partial);
-  else if (R == 2) launch_count<2>(st, chunks, h_pad, pairs, m, chunk_pairs, hyp, thr2, partial);
-  else launch_count<1>(st, chunks, h_pad, pairs, m, chunk_pairs, hyp, thr2, partial);
-  hipLaunchKernelGGL(fold_kernel, dim3((unsigned)((H + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, (const uint32_t*)partial, chunks,
-                     h_pad, H, (const uint32_t*)valid, counts, d_counts_out);
-  hipLaunchKernelGGL(best_kernel, dim3(1), dim3(kThreads), 0, st, (const uint32_t*)counts, (const uint32_t*)valid, (const uint32_t*)rows, H,
-                     (const float4*)pairs, misc);
-  hipLaunchKernelGGL(refit_kernel, dim3((unsigned)rblocks), dim3(kThreads), 0, st, (const float4*)pairs, m, (const float*)hyp, h_pad, thr2,
+                     H, h_pad, seed, lay.hyp, lay.rows, lay.valid);
+  if (pn.R == 4) launch_count<4>(st, pn.chunks, h_pad, pairs, m, pn.chunk_items, lay.hyp, thr2, lay.partial);
+  else if (pn.R == 2) launch_count<2>(st, pn.chunks, h_pad, pairs, m, pn.chunk_items, lay.hyp, thr2, lay.partial);
+  else launch_count<1>(st, pn.chunks, h_pad, pairs, m, pn.chunk_items, lay.hyp, thr2, lay.partial);
+  hipLaunchKernelGGL(r3d_consensus::fold_kernel, dim3((unsigned)((H + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
+                     (const uint32_t*)lay.partial, pn.chunks, h_pad, H, (const uint32_t*)lay.valid, lay.counts, d_counts_out);
+  hipLaunchKernelGGL((r3d_consensus::best_kernel<Misc, FetchPairs>), dim3(1), dim3(kThreads), 0, st, (const uint32_t*)lay.counts,
+                     (const uint32_t*)lay.valid, (const uint32_t*)lay.rows, H, FetchPairs{pairs}, misc);
+  hipLaunchKernelGGL(refit_kernel, dim3((unsigned)rblocks), dim3(kThreads), 0, st, (const float4*)pairs, m, (const float*)lay.hyp, h_pad, thr2,
                      (const Misc*)misc, part);
   hipLaunchKernelGGL((finish_kernel<kSums>), dim3(1), dim3(kThreads), 0, st, (const double*)part, rblocks, misc->sums);
   R3D_HIP(hipGetLastError());
@@ -524,12 +448,12 @@ int r3d_register_ransac(r3d_ctx* ctx, const float* d_src, int64_t ns, const floa
   double res[R3D_REGISTER_RESULT_DOUBLES];
   for (int k = 0; k < R3D_REGISTER_RESULT_DOUBLES; ++k) res[k] = 0.0;
   for (int k = 0; k < 16; ++k) res[k] = NAN;
-  res[16] = mi.best_h;
-  res[17] = mi.c_best;
-  for (int j = 0; j < 3; ++j) res[18 + j] = mi.rows[j];
-  res[21] = mi.n_valid;
+  res[16] = mi.head.best_h;
+  res[17] = mi.head.c_best;
+  for (int j = 0; j < 3; ++j) res[18 + j] = mi.head.rows[j];
+  res[21] = mi.head.n_valid;
   res[23] = NAN;
-  if (mi.c_best < 3) {
+  if (mi.head.c_best < 3) {
     R3D_HIP(hipMemsetAsync(d_inlier_out, 0, (size_t)m, st));
     R3D_HIP(hipStreamSynchronize(st));
     memcpy(h_result, res, sizeof(res));
