@@ -31,6 +31,8 @@ from .colored_icp import ColourGradients, colour_gradients, colour_gradients_dev
 from .posegraph import (PoseGraph, evaluate_registration, registration_information, registration_sums_device,  # noqa: F401
                         register_multiway)
 from .tsdf import TSDFVolume, poses_w2c  # noqa: F401
+from .mesh import (MeshComponents, mesh_components, mesh_components_device, remove_small_components,  # noqa: F401
+                   remove_small_components_device)
 from .tracking import TrackDevice, track_sums  # noqa: F401
 from . import cloud_io, device_text  # noqa: F401
 

@@ -74,6 +74,10 @@ struct r3d_ctx {
   void* color_rows = nullptr;
   void* color_lists = nullptr;
   size_t color_lists_bytes = 0;
+  // the mesh component calls' own workspace (r3d_mesh_cc.hip), not a shared slot either: per-label counters, vertex flags and tile
+  // counters, grown on demand; only r3d_mesh_components and r3d_mesh_filter_components touch it, and both are synchronous
+  void* mesh_cc_ws = nullptr;
+  size_t mesh_cc_ws_bytes = 0;
   // pinned staging buffers of the host pipeline: slot = ((direction * kPipeBufs + array) * 2 + parity)
   static constexpr int kPipeBufs = 2;   // arrays per direction (depth + colour in, xyz + rgba out)
   static constexpr int kPinnedSlots = 2 * kPipeBufs * 2;

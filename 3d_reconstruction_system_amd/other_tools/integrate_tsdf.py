@@ -2,7 +2,8 @@
 """TSDF integration of a drop-in working directory on the MI355X: the frames camera_to_world.py fuses into a cloud are averaged in a
 truncated signed distance volume instead, and the volume's zero level set is written as oriented surface points.
 
-    python integrate_tsdf.py --voxel-size S --trunc T [--origin X Y Z] [--dims NX NY NZ] [--margin M] [--min-weight W] [--mesh]
+    python integrate_tsdf.py --voxel-size S --trunc T [--origin X Y Z] [--dims NX NY NZ] [--margin M] [--min-weight W]
+                             [--mesh [--mesh-min-component N] [--mesh-largest]]
                              [--raycast] [--color-dir DIR] [--raycast-color] [--track [--track-pyramid N0,N1,..] [--track-bilateral R,SIGMA_S,SIGMA_R] [--track-color [--photo-weight W] [--track-max-jump D]]]
 
 Run from a directory holding ./camera_pose/image_colmap_simi_2.txt and ./depth/ (the inputs of camera_to_world.py; the same
@@ -11,6 +12,10 @@ x y z nx ny nz, the normals pointing towards the cameras.  Without --origin / --
 centres padded by M on every side (default M = 16 T), cut into voxels of S.  A depth of 0 is "no measurement".
 --mesh also writes ./ply/tsdf_mesh.ply: the same vertices plus the marching-cubes triangles over them (a face element MeshLab
 shades), and prints a second line "triangles M -> path".
+--mesh-min-component N / --mesh-largest (with --mesh) clean the mesh of floaters on the device before it is written: connected
+pieces (triangles that share a vertex) of fewer than N triangles are dropped, and with --mesh-largest all but the piece with the
+most triangles; vertices no kept triangle names go with them, so the mesh file then has fewer vertices than the surface file.
+A line "components C kept K triangles kept M dropped D" is printed in front of the "triangles" line.
 --raycast also casts the volume from every pose of the pose file at the input rasters' size and writes the depth the model
 predicts (float32, 0 = no surface) to ./raycast/<frame name>.npy, and prints a further line "raycast F frames -> ./raycast/".
 --color-dir DIR reads the colour image DIR/<frame name> of every frame (the size of the depth maps), integrates colour with the
@@ -66,6 +71,9 @@ def parse_args(argv):
                    help="padding of the camera centres' bounding box when --origin / --dims are not given (default 16 x --trunc)")
     p.add_argument("--min-weight", type=float, default=1.0, help="frames a voxel needs to count (default 1)")
     p.add_argument("--mesh", action="store_true", help="also write the triangle mesh of the surface to %s" % MESH_FILE)
+    p.add_argument("--mesh-min-component", type=int, metavar="N", default=None,
+                   help="with --mesh: drop the connected pieces of the mesh that have fewer than N triangles")
+    p.add_argument("--mesh-largest", action="store_true", help="with --mesh: keep only the connected piece with the most triangles")
     p.add_argument("--raycast", action="store_true",
                    help="also ray-cast the volume from every pose and write the predicted depth to %s<frame name>.npy" % RAYCAST_DIR)
     p.add_argument("--color-dir", metavar="DIR", default=None,
@@ -87,6 +95,10 @@ def parse_args(argv):
     p.add_argument("--track-max-jump", type=float, default=None,
                    help="with --track-color: depth step across which no image gradient is taken (default 0.05)")
     args = p.parse_args(argv)
+    if (args.mesh_min_component is not None or args.mesh_largest) and not args.mesh:
+        p.error("--mesh-min-component and --mesh-largest need --mesh")
+    if args.mesh_min_component is not None and args.mesh_min_component < 1:
+        p.error("--mesh-min-component must be >= 1, got %r" % args.mesh_min_component)
     if (args.photo_weight is not None or args.track_max_jump is not None) and not args.track_color:
         p.error("--photo-weight and --track-max-jump need --track-color")
     if args.track_pyramid is not None:
@@ -271,13 +283,18 @@ def main(argv=None):
         vol = r3d.TSDFVolume(origin, args.voxel_size, dims, args.trunc, ctx=_common.context(), color=True)
         vol.integrate(depths, quats, ts, intrinsics=_common.intrinsics(), rgb=rgb)
     _common.stamp("integrate")
-    colors = None
+    colors, mesh_stats = None, None
+    clean = args.mesh and (args.mesh_min_component is not None or args.mesh_largest)
     if rgb is None:
         xyz, normals = vol.extract_point_cloud(args.min_weight)
-        mesh = vol.extract_triangle_mesh(args.min_weight) if args.mesh else None
+        mesh = vol.extract_triangle_mesh(args.min_weight) if args.mesh and not clean else None
     else:
         xyz, normals, colors = vol.extract_point_cloud(args.min_weight, with_colors=True)
-        mesh = vol.extract_triangle_mesh(args.min_weight)[:3] + (colors,) if args.mesh else None   # the vertices are the points
+        mesh = vol.extract_triangle_mesh(args.min_weight)[:3] + (colors,) if args.mesh and not clean else None   # the vertices are the points
+    if clean:
+        got = vol.extract_triangle_mesh(args.min_weight, with_colors=rgb is not None, min_component_triangles=args.mesh_min_component,
+                                        keep_largest=args.mesh_largest, with_stats=True)
+        mesh, mesh_stats = got[:-1], got[-1]
     cast = raycast_depth(r3d, vol, quats, ts, depths.shape[-2:], args.min_weight) if args.raycast else None
     cast_rgb = raycast_color(r3d, vol, quats, ts, depths.shape[-2:], args.min_weight) if args.raycast_color else None
     vol.close()
@@ -288,6 +305,10 @@ def main(argv=None):
           % (origin[0], origin[1], origin[2], dims[0], dims[1], dims[2], args.voxel_size, args.trunc, len(names), len(xyz), OUT_FILE))
     if mesh is not None:
         r3d.cloud_io.write_ply_mesh(MESH_FILE, *mesh)
+        if mesh_stats is not None:
+            print("components %d kept %d triangles kept %d dropped %d" % (mesh_stats["components"], mesh_stats["components_kept"],
+                                                                          mesh_stats["triangles_kept"],
+                                                                          mesh_stats["triangles"] - mesh_stats["triangles_kept"]))
         print("triangles %d -> %s" % (len(mesh[2]), MESH_FILE))
     if cast is not None:
         import numpy as np

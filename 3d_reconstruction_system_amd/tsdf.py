@@ -266,28 +266,63 @@ class TSDFVolume:
                                                    C.byref(nv), C.byref(nt)))
         return nv.value, nt.value
 
-    def extract_triangle_mesh(self, min_weight=1.0, with_colors=False):
+    def extract_triangle_mesh(self, min_weight=1.0, with_colors=False, min_component_triangles=None, keep_largest=False,
+                              with_stats=False):
         """(xyz [N,3] float32, normals [N,3] float32, triangles [M,3] int32): marching cubes over the cells whose eight voxels
         have at least min_weight frames each.  The vertices are extract_point_cloud's rows (one per crossing volume edge, so the
         mesh is welded by construction); a triangle (a, b, c) winds so that (b - a) x (c - a) points towards the cameras, like the
         vertex normals.  with_colors (a volume with colour): a fourth array, [N,3] uint8 R, G, B, the vertices' colours --
-        extract_point_cloud's."""
+        extract_point_cloud's.  min_component_triangles / keep_largest: the mesh is cleaned of floaters on the device before it is
+        downloaded -- connected components (by shared vertex) of fewer than min_component_triangles triangles are dropped, and with
+        keep_largest all but the component with the most triangles; vertices no kept triangle names go with them, and the order of
+        what stays is kept (mesh.remove_small_components; include/r3d.h "Mesh components").  With neither, the call is what it was.
+        with_stats (with either of the two): a last element, the dict {"components", "components_kept", "triangles",
+        "triangles_kept"}."""
         mw = _positive_f32(min_weight, "min_weight")
         if with_colors and not self.color:
             raise ValueError("with_colors needs a volume created with color=True")
+        filtered = min_component_triangles is not None or bool(keep_largest)
+        if with_stats and not filtered:
+            raise ValueError("with_stats needs min_component_triangles or keep_largest")
+        if filtered:
+            from .mesh import _min_triangles
+            min_tris = _min_triangles(1 if min_component_triangles is None else min_component_triangles)
         n, m = self.extract_mesh_device(mw, None, None, 0, None, 0)
         if n == 0:
             empty = (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32))
-            return empty + (np.zeros((0, 3), np.uint8),) if with_colors else empty
+            empty = empty + (np.zeros((0, 3), np.uint8),) if with_colors else empty
+            return empty + ({"components": 0, "components_kept": 0, "triangles": 0, "triangles_kept": 0},) if with_stats else empty
         d_xyz, d_nrm, d_tri = self.ctx.alloc(n * 12), self.ctx.alloc(n * 12), self.ctx.alloc(max(m, 1) * 12)
         try:
             got = self.extract_mesh_device(mw, d_xyz.ptr, d_nrm.ptr, n, d_tri.ptr if m else None, m)
             assert got == (n, m), (got, n, m)
+            if filtered:
+                return self._filtered_mesh(mw, d_xyz, d_nrm, d_tri, n, m, min_tris, bool(keep_largest), with_colors, with_stats)
             tri = d_tri.download(np.int32, 3 * m).reshape(m, 3) if m else np.zeros((0, 3), np.int32)
             out = (d_xyz.download(np.float32, 3 * n).reshape(n, 3), d_nrm.download(np.float32, 3 * n).reshape(n, 3), tri)
             return out + (self._extract_colors(mw, n),) if with_colors else out
         finally:
             for b in (d_xyz, d_nrm, d_tri):
+                b.free()
+
+    def _filtered_mesh(self, mw, d_xyz, d_nrm, d_tri, n, m, min_tris, keep_largest, with_colors, with_stats):
+        """extract_triangle_mesh's result from the n vertices and m triangles in HBM, filtered there (mesh.filter_mesh_device)"""
+        from .mesh import download_rows, filter_mesh_device, mesh_components_device
+        bufs = []
+        try:
+            d_x, d_n, d_t, kept, nk, mk, comps = filter_mesh_device(self.ctx, d_xyz.ptr, d_nrm.ptr, d_tri.ptr, n, m, min_tris, keep_largest,
+                                                                    bufs)
+            out = (download_rows(d_x, np.float32, nk, 3), download_rows(d_n, np.float32, nk, 3), download_rows(d_t, np.int32, mk, 3))
+            if with_colors:
+                out += (self._extract_colors(mw, n)[kept],)
+            if with_stats:
+                d_lab = self.ctx.alloc(max(nk * 4, 16))
+                bufs.append(d_lab)
+                kept_comps, _ = mesh_components_device(self.ctx, d_t.ptr, mk, nk, d_lab.ptr)
+                out += ({"components": comps, "components_kept": kept_comps, "triangles": m, "triangles_kept": mk},)
+            return out
+        finally:
+            for b in bufs:
                 b.free()
 
     def raycast_device(self, cam, n_views, poses_w2c, d_depth, d_vertex, d_normal, min_weight=1.0, step=None, t_near=0.0,

@@ -799,6 +799,62 @@ int r3d_tsdf_extract_points(r3d_tsdf* vol, double min_weight, float* d_xyz_out, 
 int r3d_tsdf_extract_mesh(r3d_tsdf* vol, double min_weight, float* d_xyz_out, float* d_normals_out, int64_t cap_vertices,
                           int32_t* d_tri_out, int64_t cap_triangles, int64_t* n_vertices_out, int64_t* n_triangles_out);
 
+/* ---- Mesh components (csrc/r3d_mesh_cc.hip; NOT IN THE REFERENCE, this text is the specification).  A volume fused from noisy
+ * depth leaves marching cubes as one large surface plus floaters of a few triangles each; these two calls label the connected
+ * pieces of an indexed triangle mesh, count them, and keep the big ones or the biggest, on the device, between
+ * r3d_tsdf_extract_mesh and the download.  Users of this kind of pipeline know the step as Open3D's cluster_connected_triangles
+ * followed by remove_triangles_by_mask; NO parity with Open3D is claimed: connectivity here is by SHARED VERTEX, not by shared
+ * edge (for a welded marching-cubes mesh the two separate the same floaters).  Everything is integer-exact: the same bits
+ * whatever the launch geometry, the scheduling or the order of the triangles.  Not yet timed on a card.
+ * The mesh: d_tri [n_triangles][3] int32 vertex indices into n_vertices vertices (their positions are never read).
+ *
+ * r3d_mesh_components
+ *   Validity: a triangle is valid iff its three indices lie in [0, n_vertices); the indices are checked before any of them is used
+ *     as an address.  An invalid triangle joins nothing, its triangle label is 0xFFFFFFFF, and it is counted in *n_invalid_out.
+ *   A valid triangle with repeated indices ((a, a, b), (a, a, a)) joins what it names and counts like any other; a triangle that
+ *     occurs twice counts twice.
+ *   Connectivity: two vertices are connected iff a chain of valid triangles links them through shared vertex indices.
+ *   d_vertex_label_out [n_vertices] u32: the smallest vertex index of the vertex's component.  A vertex no valid triangle names is
+ *     its own label.
+ *   d_tri_label_out [n_triangles] u32 (may be NULL): the label of the triangle's first index; 0xFFFFFFFF for an invalid triangle.
+ *   d_comp_out [cap_components][3] u32 rows {label, n_vertices, n_triangles}: the components that have at least one valid
+ *     triangle, in ascending label; n_vertices = the vertices that carry the label, n_triangles = the valid triangles whose label
+ *     it is.  May be NULL with cap_components == 0.  *n_components_out is the true count, always; at most cap_components rows are
+ *     written and nothing beyond them (call with cap 0 for the count, then with room).
+ *   n_triangles == 0: every vertex is its own label, 0 components.  n_vertices == 0 (every triangle is then invalid) is fine too.
+ *   R3D_ERR_INVALID, nothing written: a NULL ctx, n_components_out or n_invalid_out; a negative size or cap; a NULL d_tri with
+ *     n_triangles > 0, d_vertex_label_out with n_vertices > 0 or d_comp_out with cap_components > 0; an output overlapping the
+ *     triangles or another output.  n_vertices or n_triangles > 2^31 - 1: R3D_ERR_UNSUPPORTED.
+ *   How: lock-free union-find in d_vertex_label_out itself (csrc/r3d_unionfind_dev.h): parent[v] <= v always, the larger of two
+ *     roots is hooked under the smaller with atomicMin and a lost race is answered by finding again; no lane waits for another, and
+ *     every loop walks a strictly decreasing sequence of vertex numbers.  The next launch flattens.  Counts are integer atomics,
+ *     the rows are placed by a scan.  The call synchronises once, for the two counts.
+ *
+ * r3d_mesh_filter_components: d_vertex_label [n_vertices] u32 = the labels r3d_mesh_components wrote for this mesh.  The call
+ *   recounts the valid triangles per label (the label of a triangle's first index) itself, in integers.  A label that is not in
+ *   [0, n_vertices) is data, never an address: its triangles count as invalid.
+ *   A triangle is kept iff it is valid and its component has at least min_triangles valid triangles (min_triangles >= 1), and,
+ *     with keep_largest != 0, its component is also the one with the greatest triangle count, ties going to the smallest label;
+ *     both conditions apply together (the largest component is dropped too when it is smaller than min_triangles).
+ *   Kept triangles stay in their original order.  A vertex is kept iff a kept triangle names it; kept vertices stay in ascending
+ *     old index.  d_kept_vertices_out [cap_vertices] u32: entry new = the old index -- the row list r3d_gather_rows takes, so
+ *     positions and normals are compacted with that call.  d_tri_out [cap_triangles][3] int32: the kept triangles, naming the NEW
+ *     indices.  *n_vertices_out and *n_triangles_out are the true counts, always; at most cap rows each are written and nothing
+ *     beyond them; a cap smaller than a count is not an error, and triangle rows are written as they are even where a new index
+ *     is >= cap_vertices.  Either output may be NULL with its cap 0.  The call synchronises once, for the two counts.
+ *   R3D_ERR_INVALID, nothing written: a NULL ctx, n_vertices_out or n_triangles_out; a negative size or cap; min_triangles < 1; a
+ *     NULL d_tri with n_triangles > 0, d_vertex_label with n_vertices > 0, or output with a cap > 0; an output overlapping an input
+ *     or the other output.  n_vertices or n_triangles > 2^31 - 1: R3D_ERR_UNSUPPORTED.
+ * Neither call modifies its inputs.  Both keep their workspace (8 bytes per vertex, and 4 per 4096 vertices or triangles) in the
+ *   context, apart from the scratch other calls share: results do not depend on what ran before on the context. */
+int r3d_mesh_components(r3d_ctx* ctx, const int32_t* d_tri, int64_t n_triangles, int64_t n_vertices, uint32_t* d_vertex_label_out,
+                        uint32_t* d_tri_label_out, uint32_t* d_comp_out, int64_t cap_components, int64_t* n_components_out,
+                        int64_t* n_invalid_out);
+int r3d_mesh_filter_components(r3d_ctx* ctx, const int32_t* d_tri, int64_t n_triangles, int64_t n_vertices,
+                               const uint32_t* d_vertex_label, int64_t min_triangles, int keep_largest,
+                               uint32_t* d_kept_vertices_out, int64_t cap_vertices, int32_t* d_tri_out, int64_t cap_triangles,
+                               int64_t* n_vertices_out, int64_t* n_triangles_out);
+
 /* ---- TSDF ray casting (csrc/r3d_tsdf_raycast.hip; the volume above seen from a camera: the depth, surface-point and normal image
  * the model predicts for a pose -- the third leg of integrate / ray cast / register; this text is the specification).  A ray-cast
  * vertex and normal map is a target cloud with normals for r3d's point-to-plane ICP (frame-to-model registration), and the depth
