@@ -21,14 +21,14 @@
 //       Unused front slots hold a sentinel below every real entry, so the last slot is always the k-th real one.
 //   sor_mean / sor_dev / sor_threshold / sor_keep: fixed-order fp64 reductions (one row per workgroup, one-wave folds) for
 //       mu, sigma and T, then the mask -- no float atomics, the same bits on every run.
-//   select_count / select_write: order-preserving row selection; the tile counts go through the radix sort's tile scan.
+//   select_count / select_write: order-preserving row selection, the compaction step of r3d_compact_dev.h.
 #include <algorithm>
 #include <cmath>
 
+#include "r3d_compact_dev.h"
 #include "r3d_internal.h"
 #include "r3d_magic_div.h"
 #include "r3d_nnindex_dev.h"
-#include "r3d_sort_dev.h"
 #include "r3d_sums_dev.h"
 #include "r3d_sym3.h"
 
@@ -423,33 +423,33 @@ __global__ __launch_bounds__(kThreads) void sor_keep_kernel(const double* __rest
 }
 
 // ---- order-preserving row selection: 4096 flags per workgroup, 16 consecutive ones per thread -------------------------------
-constexpr int kSelPer = kSortTile / kThreads;
-
+using r3d_compact::kPer;
 __global__ __launch_bounds__(kThreads) void select_count_kernel(const uint8_t* __restrict__ keep, int64_t n, uint32_t* __restrict__ hist) {
-  const int64_t base = (int64_t)blockIdx.x * kSortTile + (int64_t)threadIdx.x * kSelPer;
+  const int64_t base = r3d_compact::tile_base();
   uint32_t c = 0;
 #pragma unroll
-  for (int e = 0; e < kSelPer; ++e)
+  for (int e = 0; e < kPer; ++e)
     if (base + e < n) c += keep[base + e] != 0;
+  // r3d_compact::block_sum written out: behind a function boundary the byte compares change encoding, 245 instructions for 260
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
   __shared__ uint32_t sh[kThreads / 64];
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
   __syncthreads();
-  if (threadIdx.x == 0) hist[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+  r3d_compact::publish(hist, sh[0] + sh[1] + sh[2] + sh[3]);
 }
 
-// hist: the tiles' exclusive prefixes (r3d_sort_launch_scan)
+// hist: the tiles' exclusive prefixes
 __global__ __launch_bounds__(kThreads) void select_write_kernel(const float* __restrict__ xyz, int64_t n, const uint8_t* __restrict__ keep,
                                                                 const uint32_t* __restrict__ hist, float* __restrict__ xyz_out,
                                                                 uint32_t* __restrict__ rows_out) {
-  const int64_t base = (int64_t)blockIdx.x * kSortTile + (int64_t)threadIdx.x * kSelPer;
+  const int64_t base = r3d_compact::tile_base();
   uint32_t mask = 0;
 #pragma unroll
-  for (int e = 0; e < kSelPer; ++e)
+  for (int e = 0; e < kPer; ++e)
     if (base + e < n && keep[base + e] != 0) mask |= 1u << e;
   __shared__ uint64_t wave_total[kThreads / 64];
-  uint64_t at = hist[blockIdx.x] + r3d_sort::block_exclusive_scan_256((uint64_t)__popc(mask), wave_total);
+  uint64_t at = r3d_compact::tile_start(hist, (uint64_t)__popc(mask), wave_total);
   const P3* src = reinterpret_cast<const P3*>(xyz);
   P3* dst = reinterpret_cast<P3*>(xyz_out);
   while (mask) {
@@ -645,18 +645,15 @@ int r3d_select_rows(r3d_ctx* ctx, const float* d_xyz, int64_t n, const uint8_t* 
   R3D_REQUIRE(d_xyz && d_keep && d_xyz_out, "NULL device pointer");
   const size_t xb = (size_t)n * 12;
   R3D_REQUIRE(!r3d_ranges_overlap(d_keep, (size_t)n, d_xyz, xb), "d_keep overlaps d_xyz");
-  const int tiles = (int)((n + kSortTile - 1) / kSortTile), stride = r3d_sort_stride(tiles);
+  const int tiles = r3d_compact::tiles_of(n);
+  r3d_compact::Counters cn(tiles, 1);
   void* ws = nullptr;
-  if ((rc = r3d_scratch(ctx, 3, (size_t)stride * 4 + 64, &ws))) return rc;
-  uint32_t* hist = static_cast<uint32_t*>(ws);
-  uint32_t* total = hist + stride;
+  if ((rc = r3d_scratch(ctx, 3, cn.bytes, &ws))) return rc;
+  cn.place(ws);
   hipStream_t st = ctx->stream;
-  hipLaunchKernelGGL(select_count_kernel, dim3(tiles), dim3(kThreads), 0, st, d_keep, n, hist);
-  r3d_sort_launch_scan(ctx, hist, tiles, stride, total, 1);
-  R3D_HIP(hipGetLastError());
+  hipLaunchKernelGGL(select_count_kernel, dim3(tiles), dim3(kThreads), 0, st, d_keep, n, cn.hist);
   uint32_t m = 0;
-  R3D_HIP(hipMemcpyAsync(&m, total, sizeof(m), hipMemcpyDeviceToHost, st));
-  R3D_HIP(hipStreamSynchronize(st));
+  if ((rc = r3d_compact::scan_totals(ctx, cn, &m))) return rc;
   // the outputs need room for the kept rows only; none of them may overlap an input or the other output
   const size_t ob = (size_t)m * 12, rb = d_rows_out ? (size_t)m * 4 : 0;
   R3D_REQUIRE(!r3d_ranges_overlap(d_xyz_out, ob, d_xyz, xb) && !r3d_ranges_overlap(d_xyz_out, ob, d_keep, (size_t)n) &&
@@ -667,7 +664,7 @@ int r3d_select_rows(r3d_ctx* ctx, const float* d_xyz, int64_t n, const uint8_t* 
   if (m == 0) return R3D_OK;
   r3d_wrote(ctx, d_xyz_out, ob);
   if (d_rows_out) r3d_wrote(ctx, d_rows_out, rb);
-  hipLaunchKernelGGL(select_write_kernel, dim3(tiles), dim3(kThreads), 0, st, d_xyz, n, d_keep, (const uint32_t*)hist, d_xyz_out,
+  hipLaunchKernelGGL(select_write_kernel, dim3(tiles), dim3(kThreads), 0, st, d_xyz, n, d_keep, (const uint32_t*)cn.hist, d_xyz_out,
                      d_rows_out);
   R3D_HIP(hipGetLastError());
   return R3D_OK;

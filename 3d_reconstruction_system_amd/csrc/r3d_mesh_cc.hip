@@ -11,18 +11,19 @@
 //   cc_flatten_kernel  (next launch: the roots are final) label[v] = its root, in place
 //   cc_count_kernel    triangle labels; vertices and valid triangles per label with integer atomics, one add per wave and label
 //                      where the lanes agree (they mostly do)
-//   cc_rows_*          components = roots with a triangle: tile counts, r3d_sort.hip's tile scan, rows written in ascending label
+//   cc_rows_*          components = roots with a triangle, compacted in ascending label (r3d_compact_dev.h)
 // r3d_mesh_filter_components -- recounts per label, picks the largest with one 64-bit atomicMax per root, marks the vertices of the
-//   kept triangles, and compacts vertices and triangles in order with the same count / tile scan / block scan shape (no cursor).
+//   kept triangles, and compacts vertices and triangles in order by the same step, both rows of counters in one scan (no cursor).
 // Workspace: owned by the context (r3d_ctx::mesh_cc_ws), grown on demand, touched by these two synchronous calls alone.
+#include "r3d_compact_dev.h"
 #include "r3d_internal.h"
-#include "r3d_sort_dev.h"
 #include "r3d_unionfind_dev.h"
+
+using namespace r3d_compact;   // kPer consecutive items per thread of the compaction kernels
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kPer = kSortTile / kThreads;   // consecutive items per thread of the compaction kernels
 constexpr uint32_t kNoLabel = 0xFFFFFFFFu;
 
 __device__ __forceinline__ bool tri_valid(int32_t a, int32_t b, int32_t c, uint32_t nv) {
@@ -88,14 +89,6 @@ __global__ __launch_bounds__(kThreads) void cc_count_kernel(const int32_t* __res
   }
 }
 
-__device__ __forceinline__ uint32_t block_sum(uint32_t mine, uint32_t* sh) {   // thread 0 gets the sum
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = mine;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
-
 __device__ __forceinline__ bool is_component(const uint32_t* __restrict__ label, const uint32_t* __restrict__ cnt_t, int64_t v) {
   return label[v] == (uint32_t)v && cnt_t[v] > 0;
 }
@@ -103,12 +96,11 @@ __device__ __forceinline__ bool is_component(const uint32_t* __restrict__ label,
 __global__ __launch_bounds__(kThreads) void cc_rows_count_kernel(const uint32_t* __restrict__ label, const uint32_t* __restrict__ cnt_t,
                                                                  int64_t nv, uint32_t* __restrict__ hist) {
   __shared__ uint32_t sh[kThreads / 64];
-  const int64_t base = (int64_t)blockIdx.x * kSortTile + (int64_t)threadIdx.x * kPer;
+  const int64_t base = tile_base();
   uint32_t n = 0;
   for (int e = 0; e < kPer; ++e)
     if (base + e < nv && is_component(label, cnt_t, base + e)) ++n;
-  const uint32_t total = block_sum(n, sh);
-  if (threadIdx.x == 0) hist[blockIdx.x] = total;
+  publish(hist, block_sum(n, sh));
 }
 
 // hist: the tiles' exclusive prefixes
@@ -116,11 +108,11 @@ __global__ __launch_bounds__(kThreads) void cc_rows_write_kernel(const uint32_t*
                                                                  const uint32_t* __restrict__ cnt_t, int64_t nv,
                                                                  const uint32_t* __restrict__ hist, uint32_t* __restrict__ rows, uint64_t cap) {
   __shared__ uint64_t wave_total[kThreads / 64];
-  const int64_t base = (int64_t)blockIdx.x * kSortTile + (int64_t)threadIdx.x * kPer;
+  const int64_t base = tile_base();
   uint32_t flags = 0;
   for (int e = 0; e < kPer; ++e)
     if (base + e < nv && is_component(label, cnt_t, base + e)) flags |= 1u << e;
-  uint64_t at = hist[blockIdx.x] + r3d_sort::block_exclusive_scan_256((uint64_t)__popc(flags), wave_total);
+  uint64_t at = tile_start(hist, (uint64_t)__popc(flags), wave_total);
   for (int e = 0; e < kPer && at < cap; ++e) {
     if (!((flags >> e) & 1u)) continue;
     rows[3 * at] = (uint32_t)(base + e);
@@ -163,7 +155,7 @@ __global__ __launch_bounds__(kThreads) void cc_mark_kernel(const int32_t* __rest
                                                            uint32_t* __restrict__ vflag, uint32_t* __restrict__ hist_t) {
   __shared__ uint32_t sh[kThreads / 64];
   const unsigned long long bw = *best;
-  const int64_t base = (int64_t)blockIdx.x * kSortTile + (int64_t)threadIdx.x * kPer;
+  const int64_t base = tile_base();
   uint32_t n = 0;
   for (int e = 0; e < kPer; ++e) {
     int32_t idx[3];
@@ -174,29 +166,27 @@ __global__ __launch_bounds__(kThreads) void cc_mark_kernel(const int32_t* __rest
       vflag[idx[2]] = 1u;
     }
   }
-  const uint32_t total = block_sum(n, sh);
-  if (threadIdx.x == 0) hist_t[blockIdx.x] = total;
+  publish(hist_t, block_sum(n, sh));
 }
 
 __global__ __launch_bounds__(kThreads) void cc_vertex_count_kernel(const uint32_t* __restrict__ vflag, int64_t nv, uint32_t* __restrict__ hist_v) {
   __shared__ uint32_t sh[kThreads / 64];
-  const int64_t base = (int64_t)blockIdx.x * kSortTile + (int64_t)threadIdx.x * kPer;
+  const int64_t base = tile_base();
   uint32_t n = 0;
   for (int e = 0; e < kPer; ++e)
     if (base + e < nv && vflag[base + e]) ++n;
-  const uint32_t total = block_sum(n, sh);
-  if (threadIdx.x == 0) hist_v[blockIdx.x] = total;
+  publish(hist_v, block_sum(n, sh));
 }
 
 // vflag[v] becomes v's new index where v is kept (a thread reads its own 16 words, then writes them); kept_out[new] = old
 __global__ __launch_bounds__(kThreads) void cc_vertex_write_kernel(uint32_t* __restrict__ vflag, int64_t nv, const uint32_t* __restrict__ hist_v,
                                                                    uint32_t* __restrict__ kept_out, uint64_t cap) {
   __shared__ uint64_t wave_total[kThreads / 64];
-  const int64_t base = (int64_t)blockIdx.x * kSortTile + (int64_t)threadIdx.x * kPer;
+  const int64_t base = tile_base();
   uint32_t flags = 0;
   for (int e = 0; e < kPer; ++e)
     if (base + e < nv && vflag[base + e]) flags |= 1u << e;
-  uint64_t at = hist_v[blockIdx.x] + r3d_sort::block_exclusive_scan_256((uint64_t)__popc(flags), wave_total);
+  uint64_t at = tile_start(hist_v, (uint64_t)__popc(flags), wave_total);
   for (int e = 0; e < kPer; ++e) {
     if (!((flags >> e) & 1u)) continue;
     vflag[base + e] = (uint32_t)at;
@@ -213,13 +203,13 @@ __global__ __launch_bounds__(kThreads) void cc_tri_write_kernel(const int32_t* _
                                                                 int32_t* __restrict__ tri_out, uint64_t cap) {
   __shared__ uint64_t wave_total[kThreads / 64];
   const unsigned long long bw = *best;
-  const int64_t base = (int64_t)blockIdx.x * kSortTile + (int64_t)threadIdx.x * kPer;
+  const int64_t base = tile_base();
   uint32_t flags = 0;
   for (int e = 0; e < kPer; ++e) {
     int32_t idx[3];
     if (base + e < nt && tri_kept(tri, base + e, nv, label, cnt_t, bw, k, idx)) flags |= 1u << e;
   }
-  uint64_t at = hist_t[blockIdx.x] + r3d_sort::block_exclusive_scan_256((uint64_t)__popc(flags), wave_total);
+  uint64_t at = tile_start(hist_t, (uint64_t)__popc(flags), wave_total);
   for (int e = 0; e < kPer && at < cap; ++e) {
     if (!((flags >> e) & 1u)) continue;
     const int64_t t = base + e;   // kept: its three indices are < nv
@@ -231,7 +221,6 @@ __global__ __launch_bounds__(kThreads) void cc_tri_write_kernel(const int32_t* _
 }
 
 inline unsigned blocks_of(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
-inline int tiles_of(int64_t n) { return (int)((n + kSortTile - 1) / kSortTile); }
 inline size_t align64(size_t b) { return (b + 63) & ~(size_t)63; }
 
 // the context's own workspace, grown on demand (hipFree waits for the device: no launch still uses the old one)
@@ -290,15 +279,16 @@ int r3d_mesh_components(r3d_ctx* ctx, const int32_t* d_tri, int64_t n_triangles,
                   !r3d_ranges_overlap(d_tri_label_out, tl_b, d_comp_out, comp_b),
               "two outputs overlap");
   if ((rc = r3d_ctx_enter(ctx))) return rc;
-  // workspace: cnt_v [nv] | cnt_t [nv] | hist [stride] (64-byte aligned) | {n_components, n_invalid}
-  const int tiles = tiles_of(nv), stride = r3d_sort_stride(tiles > 0 ? tiles : 1);
-  const size_t hist_at = align64((size_t)nv * 8), ws_bytes = hist_at + (size_t)stride * 4 + 64;
+  // workspace: cnt_v [nv] | cnt_t [nv] | the tile counters (64-byte aligned) | {n_components, n_invalid}
+  const int tiles = tiles_of(nv);
+  Counters cn(tiles, 1);
+  const size_t hist_at = align64((size_t)nv * 8), ws_bytes = hist_at + cn.bytes;
   char* ws = nullptr;
   if ((rc = workspace(ctx, ws_bytes, &ws))) return rc;
   uint32_t* cnt_v = reinterpret_cast<uint32_t*>(ws);
   uint32_t* cnt_t = cnt_v + nv;
-  uint32_t* hist = reinterpret_cast<uint32_t*>(ws + hist_at);
-  uint32_t* totals = hist + stride;
+  cn.place(ws + hist_at);
+  uint32_t *hist = cn.hist, *totals = cn.totals;
   hipStream_t st = ctx->stream;
   R3D_HIP(hipMemsetAsync(ws, 0, ws_bytes, st));
   uint32_t* label = d_vertex_label_out;
@@ -316,17 +306,15 @@ int r3d_mesh_components(r3d_ctx* ctx, const int32_t* d_tri, int64_t n_triangles,
                        (const uint32_t*)label, d_tri_label_out, cnt_v, cnt_t);
   if (nv) {
     hipLaunchKernelGGL(cc_rows_count_kernel, dim3(tiles), dim3(kThreads), 0, st, (const uint32_t*)label, (const uint32_t*)cnt_t, nv, hist);
-    r3d_sort_launch_scan(ctx, hist, tiles, stride, totals, 1);
+    launch_scan(ctx, cn);
     if (comp_rows) {
       r3d_wrote(ctx, d_comp_out, comp_b);
       hipLaunchKernelGGL(cc_rows_write_kernel, dim3(tiles), dim3(kThreads), 0, st, (const uint32_t*)label, (const uint32_t*)cnt_v,
                          (const uint32_t*)cnt_t, nv, (const uint32_t*)hist, d_comp_out, (uint64_t)comp_rows);
     }
   }
-  R3D_HIP(hipGetLastError());
   uint32_t m[2] = {0, 0};
-  R3D_HIP(hipMemcpyAsync(m, totals, sizeof(m), hipMemcpyDeviceToHost, st));
-  R3D_HIP(hipStreamSynchronize(st));
+  if ((rc = read_totals(ctx, cn, m, 2))) return rc;
   *n_components_out = (int64_t)m[0];
   *n_invalid_out = (int64_t)m[1];
   return R3D_OK;
@@ -352,16 +340,16 @@ int r3d_mesh_filter_components(r3d_ctx* ctx, const int32_t* d_tri, int64_t n_tri
               "an output overlaps an input");
   R3D_REQUIRE(!r3d_ranges_overlap(d_kept_vertices_out, kept_b, d_tri_out, out_b), "the two outputs overlap");
   if ((rc = r3d_ctx_enter(ctx))) return rc;
-  // workspace: cnt_t [nv] | vflag [nv] | hist [2][stride] (64-byte aligned; row 0 vertices, row 1 triangles) | totals [2] | best u64
-  const int tiles_v = tiles_of(nv), tiles_t = tiles_of(nt), tiles = tiles_v > tiles_t ? tiles_v : tiles_t;
-  const int stride = r3d_sort_stride(tiles > 0 ? tiles : 1);
-  const size_t hist_at = align64((size_t)nv * 8), ws_bytes = hist_at + (size_t)stride * 8 + 64;
+  // workspace: cnt_t [nv] | vflag [nv] | the tile counters (64-byte aligned; row 0 vertices, row 1 triangles) | totals [2] | best u64
+  const int tiles_v = tiles_of(nv), tiles_t = tiles_of(nt);
+  Counters cn(tiles_v > tiles_t ? tiles_v : tiles_t, 2);
+  const size_t hist_at = align64((size_t)nv * 8), ws_bytes = hist_at + cn.bytes;
   char* ws = nullptr;
   if ((rc = workspace(ctx, ws_bytes, &ws))) return rc;
   uint32_t* cnt_t = reinterpret_cast<uint32_t*>(ws);
   uint32_t* vflag = cnt_t + nv;
-  uint32_t* hist = reinterpret_cast<uint32_t*>(ws + hist_at);
-  uint32_t* totals = hist + 2 * (size_t)stride;
+  cn.place(ws + hist_at);
+  uint32_t* totals = cn.totals;
   unsigned long long* best = reinterpret_cast<unsigned long long*>(totals + 2);   // 8-byte aligned: stride is a multiple of 8 words
   hipStream_t st = ctx->stream;
   R3D_HIP(hipMemsetAsync(ws, 0, ws_bytes, st));   // (the tile counters beyond either row's own tiles must read 0 in the scan)
@@ -371,24 +359,22 @@ int r3d_mesh_filter_components(r3d_ctx* ctx, const int32_t* d_tri, int64_t n_tri
                        (uint32_t*)nullptr, (uint32_t*)nullptr, cnt_t);
     hipLaunchKernelGGL(cc_best_kernel, dim3(blocks_of(nv)), dim3(kThreads), 0, st, (const uint32_t*)cnt_t, (uint32_t)nv, best);
     hipLaunchKernelGGL(cc_mark_kernel, dim3(tiles_t), dim3(kThreads), 0, st, d_tri, nt, (uint32_t)nv, d_vertex_label, (const uint32_t*)cnt_t,
-                       (const unsigned long long*)best, keep, vflag, hist + stride);
-    hipLaunchKernelGGL(cc_vertex_count_kernel, dim3(tiles_v), dim3(kThreads), 0, st, (const uint32_t*)vflag, nv, hist);
-    r3d_sort_launch_scan(ctx, hist, tiles, stride, totals, 2);
+                       (const unsigned long long*)best, keep, vflag, cn.row(1));
+    hipLaunchKernelGGL(cc_vertex_count_kernel, dim3(tiles_v), dim3(kThreads), 0, st, (const uint32_t*)vflag, nv, cn.row(0));
+    launch_scan(ctx, cn);
     if (vrows) r3d_wrote(ctx, d_kept_vertices_out, kept_b);
     // (the triangles need every kept vertex's new index even when no vertex row is wanted)
-    hipLaunchKernelGGL(cc_vertex_write_kernel, dim3(tiles_v), dim3(kThreads), 0, st, vflag, nv, (const uint32_t*)hist, d_kept_vertices_out,
+    hipLaunchKernelGGL(cc_vertex_write_kernel, dim3(tiles_v), dim3(kThreads), 0, st, vflag, nv, (const uint32_t*)cn.row(0), d_kept_vertices_out,
                        (uint64_t)vrows);
     if (trows) {
       r3d_wrote(ctx, d_tri_out, out_b);
       hipLaunchKernelGGL(cc_tri_write_kernel, dim3(tiles_t), dim3(kThreads), 0, st, d_tri, nt, (uint32_t)nv, d_vertex_label,
                          (const uint32_t*)cnt_t, (const unsigned long long*)best, keep, (const uint32_t*)vflag,
-                         (const uint32_t*)(hist + stride), d_tri_out, (uint64_t)trows);
+                         (const uint32_t*)cn.row(1), d_tri_out, (uint64_t)trows);
     }
   }
-  R3D_HIP(hipGetLastError());
   uint32_t m[2] = {0, 0};
-  R3D_HIP(hipMemcpyAsync(m, totals, sizeof(m), hipMemcpyDeviceToHost, st));
-  R3D_HIP(hipStreamSynchronize(st));
+  if ((rc = read_totals(ctx, cn, m, 2))) return rc;
   *n_vertices_out = (int64_t)m[0];
   *n_triangles_out = (int64_t)m[1];
   return R3D_OK;

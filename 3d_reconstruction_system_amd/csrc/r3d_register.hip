@@ -6,8 +6,8 @@
 //
 //   r3d_feature_match    the nearest-row search of r3d_fpfh.hip in one or both directions, then
 //     keep_count_kernel  per workgroup of 256 source rows, how many pass the filter
-//     keep_scan_kernel   one workgroup: exclusive prefix of those counts (each thread a contiguous run, 256 run totals in LDS)
-//     keep_write_kernel  the kept rows in ascending order: ballot ranks inside a wave, the waves in order
+//     (scan)             r3d_compact_dev.h's, over that one row of counts: exclusive prefixes and the total
+//     keep_write_kernel  the kept rows in ascending order: ballot ranks inside a wave, the waves in order (one row per thread)
 //   r3d_register_ransac
 //     pair_kernel        gathers the m correspondences into two float4 per pair (source point, target point); a row number
 //                        outside its cloud gives NaN points, which are nobody's inlier and make a hypothesis invalid
@@ -27,6 +27,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "r3d_compact_dev.h"
 #include "r3d_consensus_dev.h"
 #include "r3d_icp_sums.h"
 #include "r3d_internal.h"
@@ -54,39 +55,8 @@ __device__ __forceinline__ bool kept(const uint32_t* __restrict__ idx_a, const u
 __global__ __launch_bounds__(kThreads) void keep_count_kernel(const uint32_t* __restrict__ idx_a, const uint32_t* __restrict__ idx_b,
                                                               int64_t na, int64_t nb, uint32_t* __restrict__ block_counts) {
   const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  const unsigned long long mask = __ballot(kept(idx_a, idx_b, na, nb, i));
   __shared__ uint32_t sh[kThreads / 64];
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = (uint32_t)__popcll(mask);
-  __syncthreads();
-  if (threadIdx.x == 0) block_counts[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
-}
-
-// counts [n_blocks] -> exclusive prefixes in place, the total behind them at counts[n_blocks]
-__global__ __launch_bounds__(kThreads) void keep_scan_kernel(uint32_t* __restrict__ counts, int n_blocks) {
-  __shared__ uint32_t run[kThreads];
-  const int per = (n_blocks + kThreads - 1) / kThreads;
-  const int first = (int)threadIdx.x * per;
-  const int lo = first < n_blocks ? first : n_blocks, hi = lo + per < n_blocks ? lo + per : n_blocks;
-  uint32_t s = 0;
-  for (int b = lo; b < hi; ++b) s += counts[b];
-  run[threadIdx.x] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t at = 0;
-    for (int t = 0; t < kThreads; ++t) {
-      const uint32_t v = run[t];
-      run[t] = at;
-      at += v;
-    }
-    counts[n_blocks] = at;
-  }
-  __syncthreads();
-  uint32_t at = run[threadIdx.x];
-  for (int b = lo; b < hi; ++b) {
-    const uint32_t v = counts[b];
-    counts[b] = at;
-    at += v;
-  }
+  r3d_compact::publish(block_counts, r3d_compact::block_sum<uint32_t>(kept(idx_a, idx_b, na, nb, i), sh));
 }
 
 __global__ __launch_bounds__(kThreads) void keep_write_kernel(const uint32_t* __restrict__ idx_a, const uint32_t* __restrict__ idx_b,
@@ -366,26 +336,25 @@ int r3d_feature_match(r3d_ctx* ctx, const float* d_a, int64_t na, const float* d
   if (rc) return rc;
   // slot 4 / 2: the partial minima of a -> b / b -> a; slot 3: the b -> a rows; slot 5: the per-workgroup keep counts
   const int n_blocks = (int)((na + kThreads - 1) / kThreads);
+  r3d_compact::Counters cn(n_blocks, 1);
   void *idx_b_v = nullptr, *counts_v = nullptr;
   if (mutual && (rc = r3d_scratch(ctx, 3, (size_t)nb * 4, &idx_b_v))) return rc;
-  if (d_corr_out && (rc = r3d_scratch(ctx, 5, ((size_t)n_blocks + 1) * 4, &counts_v))) return rc;
+  if (d_corr_out && (rc = r3d_scratch(ctx, 5, cn.bytes, &counts_v))) return rc;
   for (int i = 0; i < 3; ++i)
     if (out[i].p) r3d_wrote(ctx, out[i].p, out[i].bytes);
   if ((rc = r3d_match_nearest(ctx, d_a, na, d_b, nb, d_idx_out, d_dist_out, 4))) return rc;
   if (!d_corr_out) return R3D_OK;
   uint32_t* idx_b = static_cast<uint32_t*>(idx_b_v);
   if (mutual && (rc = r3d_match_nearest(ctx, d_b, nb, d_a, na, idx_b, nullptr, 2))) return rc;
-  uint32_t* counts = static_cast<uint32_t*>(counts_v);
+  cn.place(counts_v);
   hipStream_t st = ctx->stream;
   hipLaunchKernelGGL(keep_count_kernel, dim3((unsigned)n_blocks), dim3(kThreads), 0, st, (const uint32_t*)d_idx_out, (const uint32_t*)idx_b,
-                     na, nb, counts);
-  hipLaunchKernelGGL(keep_scan_kernel, dim3(1), dim3(kThreads), 0, st, counts, n_blocks);
+                     na, nb, cn.hist);
+  r3d_compact::launch_scan(ctx, cn);
   hipLaunchKernelGGL(keep_write_kernel, dim3((unsigned)n_blocks), dim3(kThreads), 0, st, (const uint32_t*)d_idx_out,
-                     (const uint32_t*)idx_b, na, nb, (const uint32_t*)counts, d_corr_out);
-  R3D_HIP(hipGetLastError());
+                     (const uint32_t*)idx_b, na, nb, (const uint32_t*)cn.hist, d_corr_out);
   uint32_t total = 0;
-  R3D_HIP(hipMemcpyAsync(&total, counts + n_blocks, 4, hipMemcpyDeviceToHost, st));
-  R3D_HIP(hipStreamSynchronize(st));
+  if ((rc = r3d_compact::read_totals(ctx, cn, &total, 1))) return rc;
   *h_m_out = (int64_t)total;
   return R3D_OK;
 }

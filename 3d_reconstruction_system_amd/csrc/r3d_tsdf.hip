@@ -8,12 +8,11 @@
 //                           once -- and only if a frame touched it.  The per-frame pose (12 floats) is wave-uniform and comes
 //                           from a small device table through scalar loads; the depth read is a gather, neighbouring lanes
 //                           hitting neighbouring pixels.  No LDS, no atomics.
-//   tsdf_count_kernel       extraction, the shape of r3d_select_rows: surface points per tile of 4096 voxels,
-//   (tile scan)             r3d_sort.hip's digit_scan_kernel over the tile counts,
-//   tsdf_emit_kernel        every tile writes its points at its prefix + an in-block scan: linear voxel order, then x, y, z --
-//                           fixed by construction, no atomics on the output cursor.
+//   tsdf_count_kernel       extraction, the compaction step of r3d_compact_dev.h: surface points per tile of 4096 voxels, the
+//   tsdf_emit_kernel        tile scan, every tile writes its points at its start: linear voxel order, then x, y, z -- fixed by
+//                           construction, no atomics on the output cursor.
+#include "r3d_compact_dev.h"
 #include "r3d_internal.h"
-#include "r3d_sort_dev.h"
 #include "r3d_tsdf_dev.h"
 
 #include <cmath>
@@ -26,7 +25,7 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kChunk = R3D_TSDF_CHUNK;   // frames per launch = rows of one slot of the pose table
 constexpr int kSlots = 4;                // slots of the pose table: a call's chunks ride the ring without waiting for each other
-constexpr int kPer = kSortTile / kThreads;   // consecutive voxels per thread of the extraction kernels
+using r3d_compact::kPer;                 // consecutive voxels per thread of the extraction kernels
 
 using TsdfFrame = TsdfPoseRow;   // world -> camera, f32: p_cam = R p_w + t (the ring's row type: r3d_tsdf_dev.h)
 
@@ -79,30 +78,26 @@ __global__ __launch_bounds__(kThreads) void tsdf_integrate_kernel(float2* __rest
 // ---- extraction ------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void tsdf_count_kernel(const float2* __restrict__ vol, TsdfGrid g, int64_t n, float mw,
                                                               uint32_t* __restrict__ hist) {
-  const int64_t base = (int64_t)blockIdx.x * kSortTile + (int64_t)threadIdx.x * kPer;
+  const int64_t base = r3d_compact::tile_base();
   uint32_t c = 0;
 #pragma unroll 4
   for (int e = 0; e < kPer; ++e)
     if (base + e < n) c += (uint32_t)__popc(crossings(vol, g, base + e, mw));
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
   __shared__ uint32_t sh[kThreads / 64];
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) hist[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+  r3d_compact::publish(hist, r3d_compact::block_sum(c, sh));
 }
 
-// hist: the tiles' exclusive prefixes (r3d_sort_launch_scan)
+// hist: the tiles' exclusive prefixes
 __global__ __launch_bounds__(kThreads) void tsdf_emit_kernel(const float2* __restrict__ vol, TsdfGrid g, int64_t n, float mw,
                                                              const uint32_t* __restrict__ hist, float* __restrict__ xyz_out,
                                                              float* __restrict__ normals_out, uint64_t cap) {
-  const int64_t base = (int64_t)blockIdx.x * kSortTile + (int64_t)threadIdx.x * kPer;
+  const int64_t base = r3d_compact::tile_base();
   uint64_t mask = 0;   // 3 bits per voxel, voxel-major: the order of the output
 #pragma unroll 4
   for (int e = 0; e < kPer; ++e)
     if (base + e < n) mask |= (uint64_t)crossings(vol, g, base + e, mw) << (3 * e);
   __shared__ uint64_t wave_total[kThreads / 64];
-  const uint64_t at = hist[blockIdx.x] + r3d_sort::block_exclusive_scan_256((uint64_t)__popcll(mask), wave_total);
+  const uint64_t at = r3d_compact::tile_start(hist, (uint64_t)__popcll(mask), wave_total);
   emit_points(vol, g, base, mw, mask, at, cap, xyz_out, normals_out);
 }
 
@@ -342,19 +337,15 @@ int r3d_tsdf_count_points(r3d_tsdf* v, float mw, const uint32_t** d_prefix, int*
     r3d_set_error("surface extraction takes volumes of fewer than 2^32 / 3 voxels");
     return R3D_ERR_UNSUPPORTED;
   }
-  const int tiles = (int)((v->n + kSortTile - 1) / kSortTile), stride = r3d_sort_stride(tiles);
+  const int tiles = r3d_compact::tiles_of(v->n);
+  r3d_compact::Counters cn(tiles, 1);
   void* ws = nullptr;
-  if ((rc = r3d_scratch(ctx, 3, (size_t)stride * 4 + 64, &ws))) return rc;
-  uint32_t* hist = static_cast<uint32_t*>(ws);
-  uint32_t* total = hist + stride;
-  hipStream_t st = ctx->stream;
-  hipLaunchKernelGGL(tsdf_count_kernel, dim3(tiles), dim3(kThreads), 0, st, (const float2*)v->d_vol, v->g, v->n, mw, hist);
-  r3d_sort_launch_scan(ctx, hist, tiles, stride, total, 1);
-  R3D_HIP(hipGetLastError());
+  if ((rc = r3d_scratch(ctx, 3, cn.bytes, &ws))) return rc;
+  cn.place(ws);
+  hipLaunchKernelGGL(tsdf_count_kernel, dim3(tiles), dim3(kThreads), 0, ctx->stream, (const float2*)v->d_vol, v->g, v->n, mw, cn.hist);
   uint32_t m = 0;
-  R3D_HIP(hipMemcpyAsync(&m, total, sizeof(m), hipMemcpyDeviceToHost, st));
-  R3D_HIP(hipStreamSynchronize(st));
-  *d_prefix = hist;
+  if ((rc = r3d_compact::scan_totals(ctx, cn, &m))) return rc;
+  *d_prefix = cn.hist;
   *tiles_out = tiles;
   *n_points = (int64_t)m;
   return R3D_OK;

@@ -9,11 +9,11 @@
 //                               a record is 16-byte aligned whatever nx), adds the three bytes of the pixel an accepted frame
 //                               read (byte gathers: a colour row is 3 W bytes) and stores every record a frame touched, once.
 //                               No LDS, no atomics.
-//   tsdf_emit_colors_kernel     r3d_tsdf_extract_points' third step for the colours: r3d_tsdf.hip's count kernel and the tile
-//                               scan give the tiles' prefixes (r3d_tsdf_count_points), every tile writes its colour words at its
-//                               prefix + an in-block scan -- the rows of the points, no atomics on the output cursor.
+//   tsdf_emit_colors_kernel     r3d_tsdf_extract_points' write step (r3d_compact_dev.h) for the colours: r3d_tsdf.hip's count
+//                               kernel and the tile scan give the tiles' prefixes (r3d_tsdf_count_points), every tile writes its
+//                               colour words at its start -- the rows of the points, no atomics on the output cursor.
+#include "r3d_compact_dev.h"
 #include "r3d_internal.h"
-#include "r3d_sort_dev.h"
 #include "r3d_tsdf_dev.h"
 
 using namespace r3d_tsdf_dev;
@@ -22,7 +22,7 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kChunk = R3D_TSDF_CHUNK;
-constexpr int kPer = kSortTile / kThreads;   // consecutive voxels per thread of the extraction kernels
+using r3d_compact::kPer;   // consecutive voxels per thread of the extraction kernels
 
 __device__ __forceinline__ void add_pixel(uint4& c, const uint8_t* __restrict__ rgb, uint32_t pixel) {
   const uint8_t* q = rgb + (size_t)pixel * 3;
@@ -89,13 +89,13 @@ __global__ __launch_bounds__(kThreads) void tsdf_integrate_rgb_kernel(float2* __
 __global__ __launch_bounds__(kThreads) void tsdf_emit_colors_kernel(const float2* __restrict__ vol, const uint4* __restrict__ col, TsdfGrid g,
                                                                     int64_t n, float mw, const uint32_t* __restrict__ prefix,
                                                                     uint32_t* __restrict__ rgba_out, uint64_t cap) {
-  const int64_t base = (int64_t)blockIdx.x * kSortTile + (int64_t)threadIdx.x * kPer;
+  const int64_t base = r3d_compact::tile_base();
   uint64_t mask = 0;   // 3 bits per voxel, voxel-major: the order of the output
 #pragma unroll 4
   for (int e = 0; e < kPer; ++e)
     if (base + e < n) mask |= (uint64_t)crossings(vol, g, base + e, mw) << (3 * e);
   __shared__ uint64_t wave_total[kThreads / 64];
-  const uint64_t at = prefix[blockIdx.x] + r3d_sort::block_exclusive_scan_256((uint64_t)__popcll(mask), wave_total);
+  const uint64_t at = r3d_compact::tile_start(prefix, (uint64_t)__popcll(mask), wave_total);
   emit_colors(vol, col, g, base, mask, at, cap, rgba_out);
 }
 

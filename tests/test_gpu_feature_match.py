@@ -131,8 +131,8 @@ def _check_with_list(G, ctx, fa, fb, mutuals):
 
 
 def test_compaction_above_65536_rows(G, ctx):
-    """66 306 source rows: 260 workgroups of keep counts, so keep_scan_kernel's threads own more than one count each (above
-    256 x 256 rows) and its last threads own none.  Every 5th target row is NaN (nobody's neighbour); source rows are copies of
+    """66 306 source rows: 260 workgroups of keep counts, more than the 256 threads of the scan's one workgroup (above 256 x 256
+    rows).  Every 5th target row is NaN (nobody's neighbour); source rows are copies of
     target rows or NaN in runs that straddle wave (64) and workgroup (256) boundaries, and whole workgroups keep nothing."""
     na, nb = 65537 + 256 * 3 + 1, 300
     fa, fb = features("random", na, nb, 11)
@@ -147,6 +147,37 @@ def test_compaction_above_65536_rows(G, ctx):
     assert not kept[False][256 * 7:256 * 9].any() and kept[False][256 * 9] and kept[False][65536 + 130] and kept[False][na - 1]
     per_block = np.add.reduceat(kept[True].astype(np.int64), np.arange(0, na, 256))
     assert (per_block == 0).any() and per_block.max() >= 1 and 0 < kept[True].sum() <= nb
+
+
+SCAN_SEGMENT = 1024 * 256   # rows of `a` behind one segment of the shared tile scan: 1024 counters, one per workgroup of 256 rows
+
+
+@pytest.mark.parametrize("na", [SCAN_SEGMENT - 1, SCAN_SEGMENT, SCAN_SEGMENT + 1, 2 * SCAN_SEGMENT + 257])
+def test_keep_counts_across_the_scan_segments(G, ctx, na):
+    """The keep counts go through the library's tile scan (r3d_compact_dev.h), which walks a row of counters in segments of 1024:
+    source rows up to, at and past one segment, and two segments plus a workgroup and a row.  nb = 8.  A seeded 30 % of the source
+    rows are all NaN (holes in every workgroup), one workgroup is all NaN and one is clean.  The expected list is not searched
+    for again: it is the rule of include/r3d.h applied in NumPy to the d_idx_out the call wrote and, for mutual, to the rows of
+    a plain b -> a call.  A mutual list holds at most nb = 8 rows, so only the plain list can fill a workgroup."""
+    nb = 8
+    rng = np.random.default_rng([21, na])
+    fa, fb = (rng.random((na, 33)) * 100).astype(np.float32), (rng.random((nb, 33)) * 100).astype(np.float32)
+    fa[rng.random(na) < 0.3] = np.nan
+    fa[256 * 5:256 * 6] = np.nan
+    fa[256 * 6:256 * 7] = (rng.random((256, 33)) * 100).astype(np.float32)
+    fa[256 * 6 + 9] = fb[3]                                              # one pair that is mutual whatever the rest does
+    idx_ba, _, _ = device_run(G, ctx, fb, fa, False, want_corr=False)
+    for mutual in (False, True):
+        idx, _, corr = device_run(G, ctx, fa, fb, mutual)
+        keep = idx != REF.NONE
+        if mutual:
+            keep &= idx_ba[np.where(keep, idx, 0).astype(np.int64)] == np.arange(na, dtype=np.uint32)
+        per_block = np.add.reduceat(keep.astype(np.int64), np.arange(0, na, 256))
+        assert 0 < keep.sum() < na and (per_block == 0).any()
+        assert mutual or (per_block == 256).any()
+        rows = np.flatnonzero(keep).astype(np.uint32)
+        assert corr.shape[0] == rows.size                                # h_m_out
+        assert np.array_equal(corr, np.stack([rows, idx[rows]], axis=1).reshape(-1, 2))
 
 
 def test_reverse_search_through_the_two_rows_per_lane_kernel(G, ctx):

@@ -1057,3 +1057,31 @@ def test_binary_ply_flag_round_trips(R, tmp_path):
     assert R.cloud_io.read_ply(str(tmp_path / "e.ply")).shape == (0, 3)
     with pytest.raises(R.R3DError):
         R.cloud_io.write_ply_binary(str(tmp_path / "no_such_dir" / "x.ply"), xyz)
+
+
+def test_compaction_counters_layout(tmp_path):
+    """csrc/r3d_compact_dev.h's Counters, the tile counters of every compaction call, through tests/c/compact_layout_check.cpp (a
+    stand-alone program, host code under AddressSanitizer and UndefinedBehaviorSanitizer, which writes every word it lays out
+    into a block of exactly `bytes` bytes): rows of r3d_sort_stride(tiles) counters, 32-byte aligned, in order; the totals
+    behind the last row; the byte size covers them.  No tile: the one tile's row r3d_mesh_cc.hip has always asked for."""
+    import subprocess
+    csrc = os.path.join(ROOT, PKG, "csrc")
+    exe = str(tmp_path / "compact_layout_check")
+    build = subprocess.run(["/opt/rocm/bin/hipcc", "-O1", "-g", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
+                            "-I" + csrc, "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined",
+                            "-x", "hip", os.path.join(ROOT, "tests", "c", "compact_layout_check.cpp"), "-fsanitize=address,undefined",
+                            "-o", exe], capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr[-2000:]
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0 and "layout check OK" in run.stdout, run.stdout[-1000:] + run.stderr[-2000:]
+    assert "Sanitizer" not in run.stderr and "runtime error" not in run.stderr, run.stderr[-2000:]
+    seen = set()
+    for line in run.stdout.splitlines()[:-1]:
+        tiles, rows, stride, nbytes, *at = (int(x) for x in line.split())
+        seen.add((tiles, rows))
+        assert stride == (max(tiles, 1) + 7) // 8 * 8                      # r3d_sort_stride, of one tile at least
+        assert len(at) == rows + 1 and at[:rows] == [4 * stride * k for k in range(rows)]
+        assert all(a % 32 == 0 for a in at)                                 # rows (and the totals) 32-byte aligned
+        assert at[rows] == 4 * stride * rows                                # the totals lie right behind the last row
+        assert nbytes >= at[rows] + 4 * rows and nbytes == 4 * stride * rows + 64
+    assert seen == {(t, r) for t in (0, 1, 7, 8, 9) for r in (1, 2)}
