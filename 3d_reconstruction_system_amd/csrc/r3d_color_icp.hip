@@ -7,10 +7,9 @@
 //                            of r3d_nn_index_knn_self (in a buffer of this file's own), as r3d_fpfh_knn reads them.
 //   color_accumulate_kernel  the 29 fp64 sums of the untrimmed plane pair (r3d_plane_sums.h: plane_residual, pair_accumulate)
 //                            plus, per accepted pair, the photometric term through jacobian_accumulate, its count and sum rI^2
-//   color_finish_kernel      ONE workgroup (r3d_sums::finish_rows<31>): rows in fixed order -> 31 sums -> the plane solver on the
-//                            first 29 -> the ICP state in HBM
+// The finish (r3d_plane::plane_finish_kernel<31>: rows in fixed order -> 31 sums -> the plane solver on the first 29 -> the ICP
+// state in HBM) and the grid of the sums pass are r3d_plane_sums.h's; the loop schedule is r3d_icp_loop_run (r3d_icp.hip).
 // No float atomics anywhere: bitwise repeatable run to run.
-#include <algorithm>
 #include <cmath>
 
 #include "r3d_internal.h"
@@ -23,9 +22,7 @@ constexpr int kSums = R3D_COLOR_ICP_SUMS;
 constexpr uint32_t kNoRow = 0xffffffffu;
 static_assert(kSums == r3d_plane::kSums + 2, "the plane sums, then the photometric count and sum rI^2");
 
-struct __attribute__((packed, aligned(4))) P3 {
-  float x, y, z;
-};
+using r3d_plane::P3;
 
 // r3d_intensity_map's rule on a colour word (r | g << 8 | b << 16; the alpha byte is never read)
 __device__ __forceinline__ float word_intensity(uint32_t w) {
@@ -136,18 +133,6 @@ __global__ __launch_bounds__(kThreads) void color_accumulate_kernel(const float*
   r3d_sums::block_reduce_store<kSums>(acc, red, partials + (int64_t)blockIdx.x * kSums);
 }
 
-__global__ __launch_bounds__(kThreads) void color_finish_kernel(const double* __restrict__ partials, int n_rows,
-                                                                double* __restrict__ sums_out, double* __restrict__ state) {
-  r3d_sums::finish_rows<kSums>(partials, n_rows, sums_out, state,
-                               [](const double* s, double* T, double* rms) { return r3d_plane::step_from_sums(s, T, rms); });
-}
-
-// r3d_icp_plane_accumulate's grid: one workgroup per CU at the most, each leaves one row
-int accumulate_blocks(r3d_ctx* ctx, int64_t n_src) {
-  int blocks = (int)std::min<int64_t>((n_src + kThreads - 1) / kThreads, (int64_t)ctx->num_cus);
-  return blocks < 1 ? 1 : blocks;
-}
-
 struct ColorPass {
   const float *src_I, *nrm, *tgt_I, *tgt_g;
   float max_d2;
@@ -161,31 +146,16 @@ struct ColorPass {
 int color_sums_enqueue(r3d_ctx* ctx, const float* d_src, int64_t n_src, const float* d_tgt, int64_t n_tgt, const uint32_t* d_idx,
                        const float* d_d2, const ColorPass& c, double* d_sums, double* d_state, float* d_photo_out,
                        double** d_sums_used) {
-  const int blocks = accumulate_blocks(ctx, n_src);
+  const int blocks = r3d_plane::accumulate_blocks(ctx->num_cus, n_src);
   if (!ctx->color_rows) R3D_HIP(hipMalloc(&ctx->color_rows, ((size_t)ctx->num_cus + 1) * kSums * sizeof(double)));
   double* rows = static_cast<double*>(ctx->color_rows);
   if (!d_sums && d_sums_used) d_sums = rows + (size_t)blocks * kSums;
   hipLaunchKernelGGL(color_accumulate_kernel, dim3(blocks), dim3(kThreads), 0, ctx->stream, d_src, c.src_I, n_src, d_tgt, c.nrm, c.tgt_I,
                      c.tgt_g, n_tgt, d_idx, d_d2, c.max_d2 >= 0.f ? c.max_d2 : -1.f, c.w_photo, c.i_max, rows, d_photo_out);
-  hipLaunchKernelGGL(color_finish_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, (const double*)rows, blocks, d_sums, d_state);
+  hipLaunchKernelGGL(r3d_plane::plane_finish_kernel<kSums>, dim3(1), dim3(kThreads), 0, ctx->stream, (const double*)rows, blocks, d_sums, d_state);
   R3D_HIP(hipGetLastError());
   if (d_sums_used) *d_sums_used = d_sums;
   return R3D_OK;
-}
-
-struct Range {
-  const void* p;
-  size_t bytes;
-};
-
-bool any_overlap(const Range* outs, int n_out, const Range* ins, int n_in) {
-  for (int i = 0; i < n_out; ++i) {
-    for (int j = i + 1; j < n_out; ++j)
-      if (r3d_ranges_overlap(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes)) return true;
-    for (int j = 0; j < n_in; ++j)
-      if (r3d_ranges_overlap(outs[i].p, outs[i].bytes, ins[j].p, ins[j].bytes)) return true;
-  }
-  return false;
 }
 
 }  // namespace
@@ -203,9 +173,9 @@ int r3d_color_gradient_knn(r3d_nn_index* index, int k, double radius, const floa
   r3d_ctx* ctx = nullptr;
   int rc = r3d_nn_index_target(index, &d_xyz, &n, &ctx);
   if (rc) return rc;
-  const Range outs[3] = {{d_intensity_out, (size_t)n * 4}, {d_grad_out, (size_t)n * 12}, {d_count_out, (size_t)n * 4}};
-  const Range ins[3] = {{d_xyz, (size_t)n * 12}, {d_normals, (size_t)n * 12}, {d_rgba, (size_t)n * 4}};
-  R3D_REQUIRE(!any_overlap(outs, 3, ins, 3), "an output overlaps another output, the normals, the colours or the index's cloud");
+  const r3d_range outs[3] = {{d_intensity_out, (size_t)n * 4}, {d_grad_out, (size_t)n * 12}, {d_count_out, (size_t)n * 4}};
+  const r3d_range ins[3] = {{d_xyz, (size_t)n * 12}, {d_normals, (size_t)n * 12}, {d_rgba, (size_t)n * 4}};
+  R3D_REQUIRE(!r3d_any_overlap(outs, 3, ins, 3), "an output overlaps another output, the normals, the colours or the index's cloud");
   if ((rc = r3d_ctx_enter(ctx))) return rc;
   if (n == 0) return R3D_OK;
   // the lists (idx | d2), stored as r3d_fpfh_knn stores them, in a grow-only buffer of this file's own
@@ -247,11 +217,11 @@ int r3d_icp_color_accumulate(r3d_ctx* ctx, const float* d_src, const float* d_sr
   }
   R3D_REQUIRE(d_src && d_src_intensity && d_tgt && d_tgt_normals && d_tgt_intensity && d_tgt_grad && d_idx, "NULL device pointer");
   R3D_REQUIRE(!(max_d2 >= 0.f) || d_d2 != nullptr, "max_d2 >= 0 needs the d2 array");
-  const Range outs[1] = {{d_photo_out, (size_t)n_src * 4}};
-  const Range ins[8] = {{d_src, (size_t)n_src * 12},       {d_src_intensity, (size_t)n_src * 4}, {d_tgt, (size_t)n_tgt * 12},
-                        {d_tgt_normals, (size_t)n_tgt * 12}, {d_tgt_intensity, (size_t)n_tgt * 4}, {d_tgt_grad, (size_t)n_tgt * 12},
-                        {d_idx, (size_t)n_src * 4},          {d_d2, (size_t)n_src * 4}};
-  R3D_REQUIRE(!any_overlap(outs, 1, ins, 8), "d_photo_out overlaps an input");
+  const r3d_range outs[1] = {{d_photo_out, (size_t)n_src * 4}};
+  const r3d_range ins[8] = {{d_src, (size_t)n_src * 12},         {d_src_intensity, (size_t)n_src * 4}, {d_tgt, (size_t)n_tgt * 12},
+                            {d_tgt_normals, (size_t)n_tgt * 12}, {d_tgt_intensity, (size_t)n_tgt * 4}, {d_tgt_grad, (size_t)n_tgt * 12},
+                            {d_idx, (size_t)n_src * 4},          {d_d2, (size_t)n_src * 4}};
+  R3D_REQUIRE(!r3d_any_overlap(outs, 1, ins, 8), "d_photo_out overlaps an input");
   if (d_photo_out) r3d_wrote(ctx, d_photo_out, (size_t)n_src * 4);
   const ColorPass c = {d_src_intensity, d_tgt_normals, d_tgt_intensity, d_tgt_grad, max_d2, w_photo, i_max};
   double* d_sums = nullptr;
@@ -281,54 +251,20 @@ int r3d_icp_iterate_color(r3d_ctx* ctx, r3d_nn_index* index, const float* d_src_
   r3d_ctx* ictx = nullptr;
   if ((rc = r3d_nn_index_target(index, &d_tgt, &n_tgt, &ictx))) return rc;
   R3D_REQUIRE(ictx == ctx, "the index belongs to another context");
-  const Range outs[5] = {{d_src, (size_t)n_src * 12},
-                         {d_idx, (size_t)n_src * 4},
-                         {d_d2, (size_t)n_src * 4},
-                         {d_state, R3D_ICP_STATE_DOUBLES * sizeof(double)},
-                         {d_sums_out, kSums * sizeof(double)}};
-  const Range ins[6] = {{d_src_orig, (size_t)n_src * 12},    {d_src_intensity, (size_t)n_src * 4}, {d_tgt, (size_t)n_tgt * 12},
-                        {d_tgt_normals, (size_t)n_tgt * 12}, {d_tgt_intensity, (size_t)n_tgt * 4}, {d_tgt_grad, (size_t)n_tgt * 12}};
-  R3D_REQUIRE(!any_overlap(outs, 5, ins, 6), "d_src, d_idx, d_d2, d_state or d_sums_out overlaps another of them or an input");
+  const r3d_range outs[5] = {{d_src, (size_t)n_src * 12},
+                             {d_idx, (size_t)n_src * 4},
+                             {d_d2, (size_t)n_src * 4},
+                             {d_state, R3D_ICP_STATE_DOUBLES * sizeof(double)},
+                             {d_sums_out, kSums * sizeof(double)}};
+  const r3d_range ins[6] = {{d_src_orig, (size_t)n_src * 12},    {d_src_intensity, (size_t)n_src * 4}, {d_tgt, (size_t)n_tgt * 12},
+                            {d_tgt_normals, (size_t)n_tgt * 12}, {d_tgt_intensity, (size_t)n_tgt * 4}, {d_tgt_grad, (size_t)n_tgt * 12}};
+  R3D_REQUIRE(!r3d_any_overlap(outs, 5, ins, 6), "d_src, d_idx, d_d2, d_state or d_sums_out overlaps another of them or an input");
   const ColorPass c = {d_src_intensity, d_tgt_normals, d_tgt_intensity, d_tgt_grad, max_d2, w_photo, i_max};
-  // the same loop going on (r3d_internal.h, r3d_ctx::loop_*): its first iteration starts from the previous matches too
-  const bool going_on = ctx->loop_state == d_state && ctx->loop_src == d_src && ctx->loop_idx == d_idx && ctx->loop_index == index;
-  // r3d_icp_iterate_plane's schedule: with the original cloud at hand the wave-local search of the NEXT iteration writes
-  // d_src = T_total . d_src_orig itself, and only the last iteration of a call moves explicitly
-  bool pending_move = false;   // the state has a pose that d_src does not show yet
-  auto one_iteration = [&](bool warm, bool last) -> int {
-    int rc2, moved = 0;
-    if (pending_move && !(warm && d_src_orig)) {   // (cannot happen: a pending move implies both; kept for safety)
-      if ((rc2 = r3d_apply_T_dev(ctx, d_src_orig, R3D_F32, n_src, d_state + r3d_sums::kStateTTotal, d_src, R3D_F32))) return rc2;
-      pending_move = false;
-    }
-    if ((rc2 = r3d_nn_index_query_step(index, d_src, n_src, d_idx, d_d2, warm, pending_move ? d_src_orig : nullptr,
-                                       pending_move ? d_state + r3d_sums::kStateTTotal : nullptr, &moved)))
-      return rc2;
-    if (pending_move && !moved) {   // the query took the other kernel after all: it searched the unmoved cloud -- redo properly
-      if ((rc2 = r3d_apply_T_dev(ctx, d_src_orig, R3D_F32, n_src, d_state + r3d_sums::kStateTTotal, d_src, R3D_F32))) return rc2;
-      if ((rc2 = r3d_nn_index_query_step(index, d_src, n_src, d_idx, d_d2, warm, nullptr, nullptr, nullptr))) return rc2;
-    }
-    pending_move = false;
-    if ((rc2 = color_sums_enqueue(ctx, d_src, n_src, d_tgt, n_tgt, d_idx, d_d2, c, last ? d_sums_out : nullptr, d_state, nullptr,
-                                  nullptr)))
-      return rc2;
-    if (d_src_orig && !last) {
-      pending_move = true;   // the next iteration's search moves the cloud
-      return R3D_OK;
-    }
-    if (d_src_orig) return r3d_apply_T_dev(ctx, d_src_orig, R3D_F32, n_src, d_state + r3d_sums::kStateTTotal, d_src, R3D_F32);
-    return r3d_apply_T_dev(ctx, d_src, R3D_F32, n_src, d_state + r3d_sums::kStateTStep, d_src, R3D_F32);
-  };
-  for (int it = 0; it < n_iters; ++it)
-    if ((rc = one_iteration(it > 0 || going_on, it == n_iters - 1))) return rc;
-  if (n_iters > 0) {
-    if (d_sums_out) r3d_wrote(ctx, d_sums_out, kSums * sizeof(double));
-    ctx->loop_state = d_state;
-    ctx->loop_src = d_src;
-    ctx->loop_src_bytes = (size_t)n_src * 12;
-    ctx->loop_idx = d_idx;
-    ctx->loop_index = index;
-  }
+  rc = r3d_icp_loop_run(ctx, index, d_src_orig, d_src, n_src, d_idx, d_d2, n_iters, d_state, [&](bool last) {
+    return color_sums_enqueue(ctx, d_src, n_src, d_tgt, n_tgt, d_idx, d_d2, c, last ? d_sums_out : nullptr, d_state, nullptr, nullptr);
+  });
+  if (rc) return rc;
+  if (n_iters > 0 && d_sums_out) r3d_wrote(ctx, d_sums_out, kSums * sizeof(double));
   return R3D_OK;
 }
 

@@ -385,7 +385,7 @@ int r3d_icp_iterate(r3d_ctx* ctx, r3d_nn_index* index, float* d_src, int64_t n_s
   void* d_sums_v = nullptr;
   if ((rc = r3d_scratch(ctx, 3, kSums * sizeof(double), &d_sums_v))) return rc;
   double* d_sums = static_cast<double*>(d_sums_v);
-  const bool going_on = index && ctx->loop_state == d_state && ctx->loop_src == d_src && ctx->loop_idx == d_idx && ctx->loop_index == index;
+  const bool going_on = r3d_icp_loop_going_on(ctx, index, d_state, d_src, d_idx);
   for (int it = 0; it < n_iters; ++it) {
     if (index) {
       // sources are kept in the index's Morton order by the caller (r3d_nn_index_sort_cloud): no sort, sums fused
@@ -399,14 +399,54 @@ int r3d_icp_iterate(r3d_ctx* ctx, r3d_nn_index* index, float* d_src, int64_t n_s
     }
     if ((rc = r3d_apply_T_dev(ctx, d_src, R3D_F32, n_src, d_state + r3d_sums::kStateTStep, d_src, R3D_F32))) return rc;
   }
-  if (index && n_iters > 0) {
-    ctx->loop_state = d_state;
-    ctx->loop_src = d_src;
-    ctx->loop_src_bytes = (size_t)n_src * 12;
-    ctx->loop_idx = d_idx;
-    ctx->loop_index = index;
-  }
+  if (index && n_iters > 0) r3d_icp_loop_remember(ctx, index, d_state, d_src, n_src, d_idx);
   return R3D_OK;
 }
 
 }  // extern "C"
+
+// The schedule of the loops that bring their own sums pass (r3d_icp_iterate_plane, r3d_icp_iterate_color; r3d_icp_iterate above
+// fuses query, sums and solve in r3d_nn_index_query_solve and is a different schedule).
+int r3d_icp_loop_run(r3d_ctx* ctx, r3d_nn_index* index, const float* d_src_orig, float* d_src, int64_t n_src, uint32_t* d_idx,
+                     float* d_d2, int n_iters, double* d_state, const std::function<int(bool)>& enqueue_sums) {
+  const double* T_total = d_state + r3d_sums::kStateTTotal;
+  // With the original cloud at hand every iteration moves IT by the accumulated pose: one rounding per point however many
+  // steps were taken (moving the moved cloud again and again lets fp32 rounding drift by ~1e-7 per step).  That move is
+  // idempotent -- d_src = T_total . d_src_orig -- so an iteration that runs the wave-local search lets the search kernel do it
+  // (r3d_nn_index_query_step) and the move launch of the iteration before is left out; only the LAST iteration of a call
+  // moves explicitly, so that the caller finds d_src where the state says it is.
+  bool pending_move = false;   // the state has a pose that d_src does not show yet
+  auto one_iteration = [&](bool warm, bool last) -> int {
+    int rc, moved = 0;
+    // sources are kept in the index's Morton order by the caller (r3d_nn_index_sort_cloud; rigid moves preserve it)
+    if (pending_move && !(warm && d_src_orig)) {   // (cannot happen: a pending move implies both; kept for safety)
+      if ((rc = r3d_apply_T_dev(ctx, d_src_orig, R3D_F32, n_src, T_total, d_src, R3D_F32))) return rc;
+      pending_move = false;
+    }
+    if ((rc = r3d_nn_index_query_step(index, d_src, n_src, d_idx, d_d2, warm, pending_move ? d_src_orig : nullptr,
+                                      pending_move ? T_total : nullptr, &moved)))
+      return rc;
+    if (pending_move && !moved) {   // the query took the other kernel after all: it searched the unmoved cloud -- redo properly
+      if ((rc = r3d_apply_T_dev(ctx, d_src_orig, R3D_F32, n_src, T_total, d_src, R3D_F32))) return rc;
+      if ((rc = r3d_nn_index_query_step(index, d_src, n_src, d_idx, d_d2, warm, nullptr, nullptr, nullptr))) return rc;
+    }
+    pending_move = false;
+    if ((rc = enqueue_sums(last))) return rc;
+    if (d_src_orig && !last) {
+      pending_move = true;   // the next iteration's search moves the cloud
+      return R3D_OK;
+    }
+    if (d_src_orig) return r3d_apply_T_dev(ctx, d_src_orig, R3D_F32, n_src, T_total, d_src, R3D_F32);
+    return r3d_apply_T_dev(ctx, d_src, R3D_F32, n_src, d_state + r3d_sums::kStateTStep, d_src, R3D_F32);
+  };
+  // (Replaying one captured iteration as a hipGraph -- 14 launches per iteration, each dependent on the one before -- was
+  // measured in round 3: 190-198 us per iteration against 184-186 us launch by launch, capture and instantiation included.  The
+  // host is ahead of the GPU either way; what separates two dependent kernels is the GPU's own dispatch latency.)
+  const bool going_on = r3d_icp_loop_going_on(ctx, index, d_state, d_src, d_idx);
+  for (int it = 0; it < n_iters; ++it) {
+    const int rc = one_iteration(it > 0 || going_on, it == n_iters - 1);
+    if (rc) return rc;
+  }
+  if (n_iters > 0) r3d_icp_loop_remember(ctx, index, d_state, d_src, n_src, d_idx);
+  return R3D_OK;
+}

@@ -208,11 +208,45 @@ int r3d_nn_index_query_solve(r3d_nn_index* index, const float* d_src, int64_t n_
 int r3d_nn_index_query_step(r3d_nn_index* index, const float* d_src, int64_t n_src, uint32_t* d_idx_out, float* d_d2_out,
                             int small_motion, const float* d_src_orig, const double* d_T_move, int* moved_out);
 
+// The continuity record of the ICP loops (r3d_ctx::loop_*).  _going_on: is this call the loop that ran last on the ctx, with
+// nothing in between that ended it (r3d_icp_state_reset, r3d_wrote on the source)?  Its first iteration then starts from the
+// previous matches too.  _remember: a call that ran at least one iteration over an index says so when it is done.
+static inline bool r3d_icp_loop_going_on(const r3d_ctx* ctx, const void* index, const void* d_state, const void* d_src, const void* d_idx) {
+  return index && ctx->loop_state == d_state && ctx->loop_src == d_src && ctx->loop_idx == d_idx && ctx->loop_index == index;
+}
+static inline void r3d_icp_loop_remember(r3d_ctx* ctx, const void* index, const void* d_state, const void* d_src, int64_t n_src,
+                                         const void* d_idx) {
+  ctx->loop_state = d_state;
+  ctx->loop_src = d_src;
+  ctx->loop_src_bytes = (size_t)n_src * 12;
+  ctx->loop_idx = d_idx;
+  ctx->loop_index = index;
+}
+// r3d_icp.hip: n_iters iterations of (presorted query, sums pass, move) for the loops whose sums pass is their own -- plane and
+// coloured ICP.  enqueue_sums(last) enqueues one pass over d_src / d_idx / d_d2 that ends in the state update; `last` is true in
+// the call's final iteration.  d_src_orig (or NULL): the cloud as it was before the loop began.  Keeps the continuity record.
+int r3d_icp_loop_run(r3d_ctx* ctx, r3d_nn_index* index, const float* d_src_orig, float* d_src, int64_t n_src, uint32_t* d_idx,
+                     float* d_d2, int n_iters, double* d_state, const std::function<int(bool)>& enqueue_sums);
+
 // Do the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte?  A NULL pointer or an empty range overlaps nothing.
 static inline bool r3d_ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
   if (!a || !b || !a_bytes || !b_bytes) return false;
   const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
   return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+// Does any of the n_out output ranges overlap a later one of them, or any of the n_in input ranges?
+struct r3d_range {
+  const void* p;
+  size_t bytes;
+};
+static inline bool r3d_any_overlap(const r3d_range* outs, int n_out, const r3d_range* ins, int n_in) {
+  for (int i = 0; i < n_out; ++i) {
+    for (int j = i + 1; j < n_out; ++j)
+      if (r3d_ranges_overlap(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes)) return true;
+    for (int j = 0; j < n_in; ++j)
+      if (r3d_ranges_overlap(outs[i].p, outs[i].bytes, ins[j].p, ins[j].bytes)) return true;
+  }
+  return false;
 }
 
 static inline size_t r3d_depth_size(int dt) { return dt == R3D_DEPTH_U8 ? 1 : dt == R3D_DEPTH_U16 ? 2 : 4; }

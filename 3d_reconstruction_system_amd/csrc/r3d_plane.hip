@@ -24,10 +24,7 @@ namespace {
 
 constexpr int kThreads = 256;
 using r3d_plane::kSums;
-
-struct __attribute__((packed, aligned(4))) P3 {
-  float x, y, z;
-};
+using r3d_plane::P3;
 
 // ---- normals of an organised cloud -------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void normals_kernel(const float* __restrict__ xyz, int64_t n_frames, int h, int w,
@@ -349,14 +346,6 @@ __global__ __launch_bounds__(kThreads) void plane_accumulate_kernel(const float*
   r3d_sums::block_reduce_store<kSums>(acc, red, partials + (int64_t)blockIdx.x * kSums);
 }
 
-// ONE workgroup (r3d_sums::finish_rows): partial rows -> the 29 sums -> optionally the step and the ICP state (the state of the
-// similarity loop: same layout, same update)
-__global__ __launch_bounds__(kThreads) void plane_finish_kernel(const double* __restrict__ partials, int n_rows,
-                                                                double* __restrict__ sums_out, double* __restrict__ state) {
-  r3d_sums::finish_rows<kSums>(partials, n_rows, sums_out, state,
-                               [](const double* s, double* T, double* rms) { return r3d_plane::step_from_sums(s, T, rms); });
-}
-
 // workspace in scratch slot 6: [hist n_buckets x 256 u32][state n_buckets x 4 u64][SelectOut x n_buckets][pad], then the
 // partial rows
 struct Workspace {
@@ -443,13 +432,6 @@ __global__ __launch_bounds__(kThreads) void class_sum_below_kernel(const float* 
     out2[2 * c] = s;
     out2[2 * c + 1] = k;
   }
-}
-
-// one workgroup per CU: every workgroup pays a 29-value fp64 tree reduction and leaves a row for plane_finish_kernel to read
-// (four per CU: accumulate 20 us + finish 19 us per iteration on a 307k-pair cloud, mostly those reductions)
-int accumulate_blocks(r3d_ctx* ctx, int64_t n_src) {
-  int blocks = (int)std::min<int64_t>((n_src + kThreads - 1) / kThreads, (int64_t)ctx->num_cus);
-  return blocks < 1 ? 1 : blocks;
 }
 
 }  // namespace
@@ -567,7 +549,7 @@ int r3d_icp_plane_residuals(r3d_ctx* ctx, const float* d_src, int64_t n_src, con
 static int plane_sums_impl(r3d_ctx* ctx, const float* d_src, int64_t n_src, const float* d_tgt, const float* d_nrm, int64_t n_tgt,
                            const uint32_t* d_idx, const float* d_d2, float max_d2, float trim_q, float gate_scale,
                            double* d_sums_out, double* d_state) {
-  const int blocks = accumulate_blocks(ctx, n_src);
+  const int blocks = r3d_plane::accumulate_blocks(ctx->num_cus, n_src);
   const bool trim = trim_q > 0.f && trim_q < 1.f;
   Workspace ws;
   int rc = workspace(ctx, trim ? kNormalClasses : 1, blocks, &ws);
@@ -584,7 +566,7 @@ static int plane_sums_impl(r3d_ctx* ctx, const float* d_src, int64_t n_src, cons
   }
   hipLaunchKernelGGL(plane_accumulate_kernel, dim3(blocks), dim3(kThreads), 0, ctx->stream, d_src, n_src, d_tgt, d_nrm, n_tgt,
                      d_idx, d_d2, gate_d2, gates, gate_scale, ws.rows);
-  hipLaunchKernelGGL(plane_finish_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, (const double*)ws.rows, blocks, d_sums_out,
+  hipLaunchKernelGGL(r3d_plane::plane_finish_kernel<kSums>, dim3(1), dim3(kThreads), 0, ctx->stream, (const double*)ws.rows, blocks, d_sums_out,
                      d_state);
   R3D_HIP(hipGetLastError());
   return R3D_OK;
@@ -635,52 +617,9 @@ int r3d_icp_iterate_plane(r3d_ctx* ctx, r3d_nn_index* index, const float* d_src_
   r3d_ctx* ictx = nullptr;
   if ((rc = r3d_nn_index_target(index, &d_tgt, &n_tgt, &ictx))) return rc;
   R3D_REQUIRE(ictx == ctx, "the index belongs to another context");
-  // the same loop going on (r3d_internal.h, r3d_ctx::loop_*): its first iteration starts from the previous matches too
-  const bool going_on = ctx->loop_state == d_state && ctx->loop_src == d_src && ctx->loop_idx == d_idx && ctx->loop_index == index;
-  // With the original cloud at hand every iteration moves IT by the accumulated pose: one rounding per point however many
-  // steps were taken (moving the moved cloud again and again lets fp32 rounding drift by ~1e-7 per step).  That move is
-  // idempotent -- d_src = T_total . d_src_orig -- so an iteration that runs the wave-local search lets the search kernel do it
-  // (r3d_nn_index_query_step) and the move launch of the iteration before is left out; only the LAST iteration of a call
-  // moves explicitly, so that the caller finds d_src where the state says it is.
-  bool pending_move = false;   // the state has a pose that d_src does not show yet
-  auto one_iteration = [&](bool warm, bool last) -> int {
-    int rc2, moved = 0;
-    // sources are kept in the index's Morton order by the caller (r3d_nn_index_sort_cloud; rigid moves preserve it)
-    if (pending_move && !(warm && d_src_orig)) {   // (cannot happen: a pending move implies both; kept for safety)
-      if ((rc2 = r3d_apply_T_dev(ctx, d_src_orig, R3D_F32, n_src, d_state + r3d_sums::kStateTTotal, d_src, R3D_F32))) return rc2;
-      pending_move = false;
-    }
-    if ((rc2 = r3d_nn_index_query_step(index, d_src, n_src, d_idx, d_d2, warm, pending_move ? d_src_orig : nullptr,
-                                       pending_move ? d_state + r3d_sums::kStateTTotal : nullptr, &moved)))
-      return rc2;
-    if (pending_move && !moved) {   // the query took the other kernel after all: it searched the unmoved cloud -- redo properly
-      if ((rc2 = r3d_apply_T_dev(ctx, d_src_orig, R3D_F32, n_src, d_state + r3d_sums::kStateTTotal, d_src, R3D_F32))) return rc2;
-      if ((rc2 = r3d_nn_index_query_step(index, d_src, n_src, d_idx, d_d2, warm, nullptr, nullptr, nullptr))) return rc2;
-    }
-    pending_move = false;
-    if ((rc2 = plane_sums_impl(ctx, d_src, n_src, d_tgt, d_tgt_normals, n_tgt, d_idx, d_d2, max_d2, trim_q, gate_scale, nullptr,
-                               d_state)))
-      return rc2;
-    if (d_src_orig && !last) {
-      pending_move = true;   // the next iteration's search moves the cloud
-      return R3D_OK;
-    }
-    if (d_src_orig) return r3d_apply_T_dev(ctx, d_src_orig, R3D_F32, n_src, d_state + r3d_sums::kStateTTotal, d_src, R3D_F32);
-    return r3d_apply_T_dev(ctx, d_src, R3D_F32, n_src, d_state + r3d_sums::kStateTStep, d_src, R3D_F32);
-  };
-  // (Replaying one captured iteration as a hipGraph -- 14 launches per iteration, each dependent on the one before -- was
-  // measured in round 3: 190-198 us per iteration against 184-186 us launch by launch, capture and instantiation included.  The
-  // host is ahead of the GPU either way; what separates two dependent kernels is the GPU's own dispatch latency.)
-  for (int it = 0; it < n_iters; ++it)
-    if ((rc = one_iteration(it > 0 || going_on, it == n_iters - 1))) return rc;
-  if (n_iters > 0) {
-    ctx->loop_state = d_state;
-    ctx->loop_src = d_src;
-    ctx->loop_src_bytes = (size_t)n_src * 12;
-    ctx->loop_idx = d_idx;
-    ctx->loop_index = index;
-  }
-  return R3D_OK;
+  return r3d_icp_loop_run(ctx, index, d_src_orig, d_src, n_src, d_idx, d_d2, n_iters, d_state, [&](bool) {
+    return plane_sums_impl(ctx, d_src, n_src, d_tgt, d_tgt_normals, n_tgt, d_idx, d_d2, max_d2, trim_q, gate_scale, nullptr, d_state);
+  });
 }
 
 }  // extern "C"

@@ -1,7 +1,11 @@
-// Point-to-plane rigid ICP step: what one matched pair adds to the 29 fp64 sums of the linearised 6x6 normal equations, and
-// the solve (Cholesky + exponential map) as host+device code -- the ICP loop runs without a host round trip per iteration and
-// the very same arithmetic is callable on a CPU-only box (r3d_plane_step_from_sums).  The rows' deterministic reduction and
-// the ICP state: r3d_sums_dev.h.
+// Point-to-plane rigid ICP step, stated once for the estimators that take it: plane ICP (r3d_plane.hip), coloured ICP
+// (r3d_color_icp.hip) and frame-to-model tracking with and without its colour term (r3d_track.hip).  Here: what a pair adds
+// to the 29 fp64 sums of the linearised 6x6 normal equations, the solve (Cholesky + exponential map) as host+device code --
+// the ICP loop runs without a host round trip per iteration and the very same arithmetic is callable on a CPU-only box
+// (r3d_plane_step_from_sums) -- the one finish kernel over it (plane_finish_kernel<K>, K = 29, or 31 with the photometric count
+// and sum behind the 29), and the grid of a cloud's sums pass (accumulate_blocks).  The rows' deterministic reduction and the
+// ICP state: r3d_sums_dev.h.  The schedule of the two cloud loops: r3d_icp_loop_run (r3d_icp.hip).  Which pairs may take part
+// stays with each accumulate kernel (plane_pair in r3d_plane.hip, restated in color_accumulate_kernel): DESIGN.md 4.5v.
 //
 // NOT IN THE REFERENCE (ICP estimation is build-defined).  What it serves IS the reference's use of
 // ICP: "match the point clouds corresponding to two images" (readme.md:25) -- the relative pose of two single-view
@@ -16,6 +20,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 
@@ -25,7 +30,19 @@ namespace r3d_plane {
 
 constexpr int kSums = 29;
 
+// One workgroup per CU at the most: every workgroup of a cloud's sums pass pays a K-value fp64 tree reduction and leaves a row for
+// plane_finish_kernel to read (four per CU: accumulate 20 us + finish 19 us per iteration on a 307k-pair cloud, mostly those
+// reductions)
+inline int accumulate_blocks(int num_cus, int64_t n_src) {
+  const int blocks = (int)std::min<int64_t>((n_src + r3d_sums::kThreads - 1) / r3d_sums::kThreads, (int64_t)num_cus);
+  return blocks < 1 ? 1 : blocks;
+}
+
 #if defined(__HIPCC__)
+struct __attribute__((packed, aligned(4))) P3 {
+  float x, y, z;
+};
+
 // r = n . (p - q), evaluated left to right in fp64 (the differences of fp32 inputs are exact there)
 __device__ __forceinline__ double plane_residual(const double p[3], const double q[3], const double n[3]) {
   return n[0] * (p[0] - q[0]) + n[1] * (p[1] - q[1]) + n[2] * (p[2] - q[2]);
@@ -136,5 +153,19 @@ R3D_HD inline int step_from_sums(const double s[kSums], double T[16], double* rm
   }
   return 0;
 }
+
+#if defined(__HIPCC__)
+// ONE workgroup (r3d_sums::finish_rows): partial rows in fixed order -> the K sums -> optionally the step solved from the first
+// 29 and the ICP state.  The state update is the one every loop shares, so every loop's state means the same (a degenerate
+// step is the identity: T_total stays).  static: every source that launches it has its own copy, as r3d_consensus_dev.h's fold.
+template <int K>
+static __global__ __launch_bounds__(r3d_sums::kThreads) void plane_finish_kernel(const double* __restrict__ partials, int n_rows,
+                                                                                 double* __restrict__ sums_out,
+                                                                                 double* __restrict__ state) {
+  static_assert(K >= kSums, "the step is solved from the first 29 sums");
+  r3d_sums::finish_rows<K>(partials, n_rows, sums_out, state,
+                           [](const double* s, double* T, double* rms) { return step_from_sums(s, T, rms); });
+}
+#endif
 
 }  // namespace r3d_plane

@@ -2,7 +2,7 @@
 // volume predicts for a pose (r3d_tsdf_raycast) -- the fourth leg of integrate / extract / ray cast / track.  NOT IN THE
 // REFERENCE (its poses come from COLMAP): build-defined, specified in include/r3d.h ("TSDF tracking").
 //
-//   track_kernel         one lane per source pixel: move it by M = T_total . S, project it into the model camera, gather the
+//   track_kernel<kRgb>   one lane per source pixel: move it by M = T_total . S, project it into the model camera, gather the
 //                        model vertex and normal at the nearest pixel, gate, and add the pair to the 29 fp64 sums of
 //                        r3d_plane_sums.h.  A 256-thread workgroup owns 1024 consecutive pixels (thread t: base + t + 256 k,
 //                        k = 0..3) and leaves one partial row (r3d_sums_dev.h's reduction): the launch shape is a function of
@@ -10,13 +10,15 @@
 //                        are the same bits on every device and under every tuning.  Source rows are read coalesced (12 B per
 //                        lane, consecutive); the gather lands near the lane's own pixel for the small motions tracking sees.
 //                        M, the model pose and the intrinsics are wave-uniform.  The only LDS is the reduction's.
-//   track_finish_kernel  ONE workgroup: partial rows in fixed order -> 29 sums -> Cholesky solve + exponential map -> the ICP
-//                        state in HBM (r3d_sums_dev.h's finish and state update, as in r3d_plane.hip)
-//   track_rgb_kernel     track_kernel with a photometric term ("TSDF colour tracking"): for an accepted pair, a bilinear tap of the
+//                        kRgb adds the photometric term ("TSDF colour tracking"): for an accepted pair, a bilinear tap of the
 //                        model's packed {I, gx, gy, 0} map (r3d_photo.hip), the gradient pulled back to the world, and the pair
 //                        into the same normal equations -- 31 sums, the same tile, reduction, finish and state
+//   the finish           r3d_plane::plane_finish_kernel<29 or 31> (r3d_plane_sums.h), ONE workgroup: partial rows in fixed order ->
+//                        the sums -> Cholesky solve + exponential map -> the ICP state in HBM, as in r3d_plane.hip
 //   track_levels         host: the whole step for one frame -- r3d_tsdf_track (one level) and r3d_tsdf_track_pyramid (coarse to fine
 //                        over the depth pyramid of r3d_pyramid.hip, every level's model maps ray-cast at the guess) share it
+//   track_rgb            host: the one-level step with the colour term; the passes, the guess's inverse and the read-back of the
+//                        state are the ones track_levels uses
 // No atomics: bitwise repeatable.  No search structure, no sort, no index: the association is one projection and one gather.
 #include <cmath>
 
@@ -30,10 +32,8 @@ constexpr int kThreads = r3d_sums::kThreads;
 constexpr int kPerLane = 4;
 constexpr int kTile = kThreads * kPerLane;   // pixels per workgroup: part of the specification
 using r3d_plane::kSums;
-
-struct __attribute__((packed, aligned(4))) P3 {
-  float x, y, z;
-};
+using r3d_plane::P3;
+constexpr int kSumsRgb = kSums + 2;   // with the colour term: [29] the photometric pair count, [30] the sum of rI^2
 
 struct TrackParams {
   double fx, fy, cx, cy;   // the camera's doubles
@@ -107,36 +107,7 @@ __device__ __forceinline__ int32_t associate(const TrackParams& a, const double 
   return j;
 }
 
-__global__ __launch_bounds__(kThreads) void track_kernel(const float* __restrict__ src_vertex, const float* __restrict__ src_normal,
-                                                         const float* __restrict__ model_vertex,
-                                                         const float* __restrict__ model_normal, const TrackParams a,
-                                                         const double* __restrict__ state, double* __restrict__ partials,
-                                                         int32_t* __restrict__ match_out, float* __restrict__ residual_out) {
-  __shared__ double red[kThreads / 64][kSums];
-  double M[12];
-  compose_M(a, state, M);
-  double acc[kSums];
-#pragma unroll
-  for (int k = 0; k < kSums; ++k) acc[k] = 0.0;
-  const P3* SV = reinterpret_cast<const P3*>(src_vertex);
-  const P3* SN = reinterpret_cast<const P3*>(src_normal);
-  const P3* MV = reinterpret_cast<const P3*>(model_vertex);
-  const P3* MN = reinterpret_cast<const P3*>(model_normal);
-  const int base = (int)blockIdx.x * kTile + (int)threadIdx.x;   // n_px < 2^31 - kTile (checked by the host)
-  for (int k = 0; k < kPerLane; ++k) {
-    const int i = base + k * kThreads;
-    if (i >= a.n_px) break;
-    Pair o;
-    const int32_t code = associate(a, M, SV, SN, MV, MN, i, acc, o);
-    if (match_out) match_out[i] = code;
-    if (residual_out) residual_out[i] = code >= 0 ? (float)o.r : 0.0f;
-  }
-  r3d_sums::block_reduce_store<kSums>(acc, red, partials + (int64_t)blockIdx.x * kSums);
-}
-
-// ---- the same pass with a photometric term ("TSDF colour tracking") ---------------------------------------------------------------
-constexpr int kSumsRgb = kSums + 2;   // [29] the photometric pair count, [30] the sum of rI^2
-
+// ---- the photometric term ("TSDF colour tracking") ---------------------------------------------------------------------------------
 struct PhotoParams {
   double w, i_max;   // w_photo (metres^2 per intensity^2) and the residual gate
 };
@@ -172,21 +143,25 @@ __device__ __forceinline__ float photo_pair(const TrackParams& a, const PhotoPar
   return (float)rI;
 }
 
-// track_kernel's tile and order, 31 sums (62 VGPRs of accumulators); M, the poses and the intrinsics stay wave-uniform
-__global__ __launch_bounds__(kThreads) void track_rgb_kernel(const float* __restrict__ src_vertex, const float* __restrict__ src_normal,
-                                                             const float* __restrict__ model_vertex,
-                                                             const float* __restrict__ model_normal,
-                                                             const float* __restrict__ src_intensity,
-                                                             const float4* __restrict__ model_packed, const TrackParams a,
-                                                             const PhotoParams ph, const double* __restrict__ state,
-                                                             double* __restrict__ partials, int32_t* __restrict__ match_out,
-                                                             float* __restrict__ residual_out, float* __restrict__ photo_out) {
-  __shared__ double red[kThreads / 64][kSumsRgb];
+// One pass over the raster.  kRgb: with the colour term -- 31 sums per row (62 VGPRs of accumulators) instead of 29, photo_pair after
+// an accepted pair, and a third output; the tile and the order are the same, and M, the poses and the intrinsics stay wave-uniform.
+// Without it src_intensity, model_packed, ph and photo_out are never read.
+template <bool kRgb>
+__global__ __launch_bounds__(kThreads) void track_kernel(const float* __restrict__ src_vertex, const float* __restrict__ src_normal,
+                                                         const float* __restrict__ model_vertex,
+                                                         const float* __restrict__ model_normal,
+                                                         const float* __restrict__ src_intensity,
+                                                         const float4* __restrict__ model_packed, const TrackParams a,
+                                                         const PhotoParams ph, const double* __restrict__ state,
+                                                         double* __restrict__ partials, int32_t* __restrict__ match_out,
+                                                         float* __restrict__ residual_out, float* __restrict__ photo_out) {
+  constexpr int K = kRgb ? kSumsRgb : kSums;
+  __shared__ double red[kThreads / 64][K];
   double M[12];
   compose_M(a, state, M);
-  double acc[kSumsRgb];
+  double acc[K];
 #pragma unroll
-  for (int k = 0; k < kSumsRgb; ++k) acc[k] = 0.0;
+  for (int k = 0; k < K; ++k) acc[k] = 0.0;
   const P3* SV = reinterpret_cast<const P3*>(src_vertex);
   const P3* SN = reinterpret_cast<const P3*>(src_normal);
   const P3* MV = reinterpret_cast<const P3*>(model_vertex);
@@ -198,28 +173,12 @@ __global__ __launch_bounds__(kThreads) void track_rgb_kernel(const float* __rest
     Pair o;
     const int32_t code = associate(a, M, SV, SN, MV, MN, i, acc, o);
     float rI = NAN;
-    if (code >= 0) rI = photo_pair(a, ph, model_packed, src_intensity[i], o, acc);
+    if (kRgb && code >= 0) rI = photo_pair(a, ph, model_packed, src_intensity[i], o, acc);
     if (match_out) match_out[i] = code;
     if (residual_out) residual_out[i] = code >= 0 ? (float)o.r : 0.0f;
-    if (photo_out) photo_out[i] = rI;
+    if (kRgb && photo_out) photo_out[i] = rI;
   }
-  r3d_sums::block_reduce_store<kSumsRgb>(acc, red, partials + (int64_t)blockIdx.x * kSumsRgb);
-}
-
-// the finish at K = 31: the step is solved from the first 29, so the state means what track_finish_kernel's means
-__global__ __launch_bounds__(kThreads) void track_rgb_finish_kernel(const double* __restrict__ partials, int n_rows,
-                                                                    double* __restrict__ sums_out, double* __restrict__ state) {
-  r3d_sums::finish_rows<kSumsRgb>(partials, n_rows, sums_out, state,
-                                  [](const double* s, double* T, double* rms) { return r3d_plane::step_from_sums(s, T, rms); });
-}
-
-// ONE workgroup (r3d_sums::finish_rows): partial rows -> the 29 sums -> optionally the point-to-plane step and the ICP state.
-// The state update is the one every loop shares, so this loop's state means what theirs mean (a degenerate step is the
-// identity: T_total stays).
-__global__ __launch_bounds__(kThreads) void track_finish_kernel(const double* __restrict__ partials, int n_rows,
-                                                                double* __restrict__ sums_out, double* __restrict__ state) {
-  r3d_sums::finish_rows<kSums>(partials, n_rows, sums_out, state,
-                               [](const double* s, double* T, double* rms) { return r3d_plane::step_from_sums(s, T, rms); });
+  r3d_sums::block_reduce_store<K>(acc, red, partials + (int64_t)blockIdx.x * K);
 }
 
 struct Maps {
@@ -261,21 +220,21 @@ int track_checks(r3d_ctx* ctx, const r3d_camera* cam, const Maps& m, const doubl
   return R3D_OK;
 }
 
-// the caller's device outputs against the four input maps and against each other
-int output_checks(const TrackParams& p, const Maps& m, const void* const* outs, const size_t* out_bytes, int n_outs) {
+// the caller's device outputs against the input maps and against each other
+int output_checks(const TrackParams& p, const Maps& m, const r3d_range* outs, int n_outs) {
   const size_t map = (size_t)p.n_px * 12;
-  const void* in[6] = {m.src_vertex, m.src_normal, m.model_vertex, m.model_normal, m.src_intensity, m.model_packed};
-  const size_t in_bytes[6] = {map, map, map, map, (size_t)p.n_px * 4, (size_t)p.n_px * 16};
-  for (int a = 0; a < n_outs; ++a) {
-    for (int b = 0; b < 6; ++b) R3D_REQUIRE(!r3d_ranges_overlap(outs[a], out_bytes[a], in[b], in_bytes[b]), "an output overlaps an input map");
-    for (int b = a + 1; b < n_outs; ++b) R3D_REQUIRE(!r3d_ranges_overlap(outs[a], out_bytes[a], outs[b], out_bytes[b]), "outputs overlap each other");
+  const r3d_range ins[6] = {{m.src_vertex, map},   {m.src_normal, map},                   {m.model_vertex, map},
+                            {m.model_normal, map}, {m.src_intensity, (size_t)p.n_px * 4}, {m.model_packed, (size_t)p.n_px * 16}};
+  for (int a = 0; a < n_outs; ++a) {   // output by output, so that the first offender decides which of the two messages it is
+    R3D_REQUIRE(!r3d_any_overlap(outs + a, 1, ins, 6), "an output overlaps an input map");
+    R3D_REQUIRE(!r3d_any_overlap(outs + a, 1, outs + a + 1, n_outs - a - 1), "outputs overlap each other");
   }
   return R3D_OK;
 }
 
 int n_tiles(const TrackParams& p) { return (p.n_px + kTile - 1) / kTile; }
 
-// partial rows (+ one row for the one-pass form's sums) in scratch slot 4, the slot the other paths keep their partial rows in
+// partial rows (+ one row for the sums) in scratch slot 4, the slot the other paths keep their partial rows in
 int rows_workspace(r3d_ctx* ctx, int tiles, double** rows, int k_sums = kSums) {
   void* v = nullptr;
   int rc = r3d_scratch(ctx, 4, ((size_t)tiles + 2) * k_sums * sizeof(double), &v);
@@ -284,75 +243,152 @@ int rows_workspace(r3d_ctx* ctx, int tiles, double** rows, int k_sums = kSums) {
   return R3D_OK;
 }
 
-// one pass on the stream: association + sums, then the finish (and, with a state, the solve)
-void enqueue_pass(r3d_ctx* ctx, const TrackParams& p, const Maps& m, const double* d_state_in, double* rows, double* d_sums_out,
-                  double* d_state, int32_t* d_match_out, float* d_residual_out) {
+template <bool kRgb>
+void launch_pass(r3d_ctx* ctx, const TrackParams& p, const PhotoParams& ph, const Maps& m, const double* d_state_in, double* rows,
+                 double* d_sums_out, double* d_state, int32_t* d_match_out, float* d_residual_out, float* d_photo_out) {
   const int tiles = n_tiles(p);
-  hipLaunchKernelGGL(track_kernel, dim3(tiles), dim3(kThreads), 0, ctx->stream, m.src_vertex, m.src_normal, m.model_vertex,
-                     m.model_normal, p, d_state_in, rows, d_match_out, d_residual_out);
-  hipLaunchKernelGGL(track_finish_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, (const double*)rows, tiles, d_sums_out, d_state);
-}
-
-int iterate_impl(r3d_ctx* ctx, const TrackParams& p, const Maps& m, int n_iters, double* d_state) {
-  double* rows = nullptr;
-  int rc = rows_workspace(ctx, n_tiles(p), &rows);
-  if (rc) return rc;
-  for (int it = 0; it < n_iters; ++it) enqueue_pass(ctx, p, m, d_state, rows, nullptr, d_state, nullptr, nullptr);
-  R3D_HIP(hipGetLastError());
-  return R3D_OK;
-}
-
-// the same pass with the colour term: 31 sums per row
-void enqueue_pass_rgb(r3d_ctx* ctx, const TrackParams& p, const PhotoParams& ph, const Maps& m, const double* d_state_in, double* rows,
-                      double* d_sums_out, double* d_state, int32_t* d_match_out, float* d_residual_out, float* d_photo_out) {
-  const int tiles = n_tiles(p);
-  hipLaunchKernelGGL(track_rgb_kernel, dim3(tiles), dim3(kThreads), 0, ctx->stream, m.src_vertex, m.src_normal, m.model_vertex,
+  hipLaunchKernelGGL(track_kernel<kRgb>, dim3(tiles), dim3(kThreads), 0, ctx->stream, m.src_vertex, m.src_normal, m.model_vertex,
                      m.model_normal, m.src_intensity, reinterpret_cast<const float4*>(m.model_packed), p, ph, d_state_in, rows,
                      d_match_out, d_residual_out, d_photo_out);
-  hipLaunchKernelGGL(track_rgb_finish_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, (const double*)rows, tiles, d_sums_out, d_state);
+  hipLaunchKernelGGL(r3d_plane::plane_finish_kernel<kRgb ? kSumsRgb : kSums>, dim3(1), dim3(kThreads), 0, ctx->stream,
+                     (const double*)rows, tiles, d_sums_out, d_state);
 }
 
-// every pass leaves its 31 sums in the row after the partial rows: the last pass's photometric count and sum are read from there
-int iterate_rgb_impl(r3d_ctx* ctx, const TrackParams& p, const PhotoParams& ph, const Maps& m, int n_iters, double* d_state,
-                     double** d_sums_out) {
+// one pass on the stream: association + sums, then the finish (and, with a state, the solve).  ph: the colour term's parameters, or
+// NULL for the pass without it (29 sums per row instead of 31, no photo output)
+void enqueue_pass(r3d_ctx* ctx, const TrackParams& p, const PhotoParams* ph, const Maps& m, const double* d_state_in, double* rows,
+                  double* d_sums_out, double* d_state, int32_t* d_match_out, float* d_residual_out, float* d_photo_out) {
+  if (ph)
+    launch_pass<true>(ctx, p, *ph, m, d_state_in, rows, d_sums_out, d_state, d_match_out, d_residual_out, d_photo_out);
+  else
+    launch_pass<false>(ctx, p, PhotoParams{}, m, d_state_in, rows, d_sums_out, d_state, d_match_out, d_residual_out, nullptr);
+}
+
+// n_iters passes on one state.  With the colour term every pass leaves its 31 sums in the row after the partial rows: the last
+// pass's photometric count and sum are read from there (*d_sums_out); without it no pass writes its sums anywhere.
+int iterate_impl(r3d_ctx* ctx, const TrackParams& p, const PhotoParams* ph, const Maps& m, int n_iters, double* d_state,
+                 double** d_sums_out = nullptr) {
   double* rows = nullptr;
-  const int tiles = n_tiles(p);
-  int rc = rows_workspace(ctx, tiles, &rows, kSumsRgb);
+  const int tiles = n_tiles(p), k_sums = ph ? kSumsRgb : kSums;
+  int rc = rows_workspace(ctx, tiles, &rows, k_sums);
   if (rc) return rc;
-  double* d_sums = rows + (size_t)tiles * kSumsRgb;
-  for (int it = 0; it < n_iters; ++it) enqueue_pass_rgb(ctx, p, ph, m, d_state, rows, d_sums, d_state, nullptr, nullptr, nullptr);
+  double* d_sums = ph ? rows + (size_t)tiles * k_sums : nullptr;
+  for (int it = 0; it < n_iters; ++it) enqueue_pass(ctx, p, ph, m, d_state, rows, d_sums, d_state, nullptr, nullptr, nullptr);
   R3D_HIP(hipGetLastError());
   if (d_sums_out) *d_sums_out = d_sums;
   return R3D_OK;
 }
 
+// r3d_track_accumulate and _accumulate_rgb (rgb: m carries the two intensity maps): one pass from the identity, its sums to the host
+int accumulate_entry(r3d_ctx* ctx, const r3d_camera* cam, const Maps& m, const double* h_model_pose_w2c, const double* h_S, double dist_max,
+                     double cos_min, bool rgb, double w_photo, double i_max, double* h_sums, int32_t* d_match_out, float* d_residual_out,
+                     float* d_photo_out) {
+  TrackParams p;
+  PhotoParams ph;
+  int rc = track_checks(ctx, cam, m, h_model_pose_w2c, h_S, dist_max, cos_min, &p);
+  if (rc) return rc;
+  if (rgb && (rc = photo_checks(m, w_photo, i_max, &ph))) return rc;
+  R3D_REQUIRE(h_sums != nullptr, "h_sums is NULL");
+  const size_t plane = (size_t)p.n_px * 4;
+  const r3d_range outs[3] = {{d_match_out, plane}, {d_residual_out, plane}, {d_photo_out, plane}};
+  if ((rc = output_checks(p, m, outs, 3))) return rc;
+  if ((rc = r3d_ctx_enter(ctx))) return rc;
+  double* rows = nullptr;
+  const int tiles = n_tiles(p), k_sums = rgb ? kSumsRgb : kSums;
+  if ((rc = rows_workspace(ctx, tiles, &rows, k_sums))) return rc;
+  for (int a = 0; a < 3; ++a)
+    if (outs[a].p) r3d_wrote(ctx, outs[a].p, outs[a].bytes);
+  double* d_sums = rows + (size_t)tiles * k_sums;
+  enqueue_pass(ctx, p, rgb ? &ph : nullptr, m, nullptr, rows, d_sums, nullptr, d_match_out, d_residual_out, d_photo_out);
+  R3D_HIP(hipGetLastError());
+  R3D_HIP(hipMemcpyAsync(h_sums, d_sums, k_sums * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  R3D_HIP(hipStreamSynchronize(ctx->stream));
+  return R3D_OK;
+}
+
 constexpr int kMaxIters = R3D_ICP_STATE_DOUBLES - R3D_ICP_STATE_HISTORY;   // what the history holds
 
-// The whole step for one frame with the colour term, one level ("TSDF colour tracking"): track_levels' one-level case with the
-// model's colour image ray-cast next to its maps and the two intensity maps made of it and of the frame's image.
-int track_rgb(r3d_tsdf* vol, const r3d_camera* cam, const void* d_depth, int depth_dtype, double depth_scale, const uint8_t* d_rgb,
-              const double* h_pose_guess_w2c, double min_weight, double step, double t_near, double t_far, float max_jump, double dist_max,
-              double cos_min, double w_photo, double i_max, int n_iters, double* h_pose_out, double* h_info_out) {
-  int rc = r3d_tsdf_integrate_checks(vol, cam, d_depth, depth_dtype, 1, depth_scale, h_pose_guess_w2c);
+// r3d_track_iterate and _iterate_rgb: n_iters passes on the caller's state
+int iterate_entry(r3d_ctx* ctx, const r3d_camera* cam, const Maps& m, const double* h_model_pose_w2c, const double* h_S, double dist_max,
+                  double cos_min, bool rgb, double w_photo, double i_max, int n_iters, double* d_state) {
+  TrackParams p;
+  PhotoParams ph;
+  int rc = track_checks(ctx, cam, m, h_model_pose_w2c, h_S, dist_max, cos_min, &p);
   if (rc) return rc;
-  R3D_REQUIRE(d_rgb != nullptr, "d_rgb is NULL");
-  R3D_REQUIRE(h_pose_out && h_info_out, "NULL output pointer");
-  R3D_REQUIRE(!r3d_ranges_overlap(h_pose_out, 12 * sizeof(double), h_info_out, 6 * sizeof(double)) &&
-                  !r3d_ranges_overlap(h_pose_out, 12 * sizeof(double), h_pose_guess_w2c, 12 * sizeof(double)) &&
-                  !r3d_ranges_overlap(h_info_out, 6 * sizeof(double), h_pose_guess_w2c, 12 * sizeof(double)),
-              "an output overlaps the guess or the other output");
-  R3D_REQUIRE(max_jump >= 0.f, "max_jump must be >= 0");
+  if (rgb && (rc = photo_checks(m, w_photo, i_max, &ph))) return rc;
+  R3D_REQUIRE(d_state != nullptr, "d_state is NULL");
   R3D_REQUIRE(n_iters >= 0 && n_iters <= kMaxIters, "n_iters must be in [0, %d]", kMaxIters);
-  r3d_ctx* ctx = cam->ctx;
-  const double* G = h_pose_guess_w2c;
+  const r3d_range out = {d_state, R3D_ICP_STATE_DOUBLES * sizeof(double)};
+  if ((rc = output_checks(p, m, &out, 1))) return rc;
+  if ((rc = r3d_ctx_enter(ctx))) return rc;
+  if (n_iters == 0) return R3D_OK;
+  r3d_wrote(ctx, d_state, out.bytes);
+  return iterate_impl(ctx, p, rgb ? &ph : nullptr, m, n_iters, d_state);
+}
+
+// The whole-frame drivers' host arguments: the finite guess G (world -> camera, 12 doubles) and S = its inverse, in double: the
+// transposed rotation and C_k = -((R[0][k] t0 + R[1][k] t1) + R[2][k] t2)
+int guess_inverse(const double* G, double S[16]) {
   for (int k = 0; k < 12; ++k) R3D_REQUIRE(std::isfinite(G[k]), "the pose guess must be finite");
-  double S[16];   // the inverse of the guess, as in track_levels
   for (int a = 0; a < 3; ++a) {
     for (int b = 0; b < 3; ++b) S[4 * a + b] = G[3 * b + a];
     S[4 * a + 3] = -((G[a] * G[9] + G[3 + a] * G[10]) + G[6 + a] * G[11]);
     S[12 + a] = 0.0;
   }
   S[15] = 1.0;
+  return R3D_OK;
+}
+
+// ... their outputs: the pose row and the info cannot overlap each other or the guess
+int frame_output_checks(const double* G, const double* h_pose_out, const double* h_info_out, int n_info, float max_jump) {
+  R3D_REQUIRE(h_pose_out && h_info_out, "NULL output pointer");
+  const r3d_range outs[2] = {{h_pose_out, 12 * sizeof(double)}, {h_info_out, (size_t)n_info * sizeof(double)}};
+  const r3d_range in = {G, 12 * sizeof(double)};
+  R3D_REQUIRE(!r3d_any_overlap(outs, 2, &in, 1), "an output overlaps the guess or the other output");
+  R3D_REQUIRE(max_jump >= 0.f, "max_jump must be >= 0");
+  return R3D_OK;
+}
+
+// ... and what they make of the state they read back (st: its first kStatePairs + 1 doubles): T_total . S -> the world-to-camera
+// row, or the guess as it was given after a degenerate step, and info[0..3] = pairs, rms, status, iterations
+void pose_and_info(const double* st, const double* G, const double* S, double* h_pose_out, double* h_info_out) {
+  const bool bad = st[r3d_sums::kStateStatus] != 0.0;
+  if (bad) {
+    for (int k = 0; k < 12; ++k) h_pose_out[k] = G[k];
+  } else {
+    double M[16];
+    for (int r = 0; r < 4; ++r)
+      for (int cc = 0; cc < 4; ++cc) {
+        double v = 0.0;
+        for (int k = 0; k < 4; ++k) v += st[r3d_sums::kStateTTotal + 4 * r + k] * S[4 * k + cc];
+        M[4 * r + cc] = v;
+      }
+    for (int a = 0; a < 3; ++a) {
+      for (int b = 0; b < 3; ++b) h_pose_out[3 * a + b] = M[4 * b + a];
+      h_pose_out[9 + a] = -((M[a] * M[3] + M[4 + a] * M[7]) + M[8 + a] * M[11]);
+    }
+  }
+  h_info_out[0] = st[r3d_sums::kStatePairs];
+  h_info_out[1] = st[r3d_sums::kStateRms];
+  h_info_out[2] = bad ? 1.0 : 0.0;
+  h_info_out[3] = st[r3d_sums::kStateIters];
+}
+
+// The whole step for one frame with the colour term, one level ("TSDF colour tracking"): track_levels' one-level case with the
+// model's colour image ray-cast next to its maps and the two intensity maps made of it and of the frame's image.  The two stay two
+// drivers: this one's ray cast, its two intensity maps, its workspace layout and its six-entry info would each be a flag in the other.
+int track_rgb(r3d_tsdf* vol, const r3d_camera* cam, const void* d_depth, int depth_dtype, double depth_scale, const uint8_t* d_rgb,
+              const double* h_pose_guess_w2c, double min_weight, double step, double t_near, double t_far, float max_jump, double dist_max,
+              double cos_min, double w_photo, double i_max, int n_iters, double* h_pose_out, double* h_info_out) {
+  int rc = r3d_tsdf_integrate_checks(vol, cam, d_depth, depth_dtype, 1, depth_scale, h_pose_guess_w2c);
+  if (rc) return rc;
+  R3D_REQUIRE(d_rgb != nullptr, "d_rgb is NULL");
+  const double* G = h_pose_guess_w2c;
+  if ((rc = frame_output_checks(G, h_pose_out, h_info_out, 6, max_jump))) return rc;
+  R3D_REQUIRE(n_iters >= 0 && n_iters <= kMaxIters, "n_iters must be in [0, %d]", kMaxIters);
+  r3d_ctx* ctx = cam->ctx;
+  double S[16];
+  if ((rc = guess_inverse(G, S))) return rc;
   const bool gate = cos_min > -1.0;
   TrackParams p;
   PhotoParams ph;
@@ -388,31 +424,12 @@ int track_rgb(r3d_tsdf* vol, const r3d_camera* cam, const void* d_depth, int dep
   m.src_intensity = src_intensity, m.model_packed = model_packed;
   if ((rc = r3d_icp_state_reset(ctx, d_state))) return rc;
   double* d_sums = nullptr;
-  if (n_iters > 0 && (rc = iterate_rgb_impl(ctx, p, ph, m, n_iters, d_state, &d_sums))) return rc;
+  if (n_iters > 0 && (rc = iterate_impl(ctx, p, &ph, m, n_iters, d_state, &d_sums))) return rc;
   double st[r3d_sums::kStatePairs + 1], sums[kSumsRgb] = {0.0};
   R3D_HIP(hipMemcpyAsync(st, d_state, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
   if (d_sums) R3D_HIP(hipMemcpyAsync(sums, d_sums, sizeof(sums), hipMemcpyDeviceToHost, ctx->stream));
   R3D_HIP(hipStreamSynchronize(ctx->stream));
-  const bool bad = st[r3d_sums::kStateStatus] != 0.0;
-  if (bad) {
-    for (int k = 0; k < 12; ++k) h_pose_out[k] = G[k];   // a degenerate step: the guess comes back as it was given
-  } else {
-    double M[16];
-    for (int r = 0; r < 4; ++r)
-      for (int cc = 0; cc < 4; ++cc) {
-        double v = 0.0;
-        for (int k = 0; k < 4; ++k) v += st[r3d_sums::kStateTTotal + 4 * r + k] * S[4 * k + cc];
-        M[4 * r + cc] = v;
-      }
-    for (int a = 0; a < 3; ++a) {
-      for (int b = 0; b < 3; ++b) h_pose_out[3 * a + b] = M[4 * b + a];
-      h_pose_out[9 + a] = -((M[a] * M[3] + M[4 + a] * M[7]) + M[8 + a] * M[11]);
-    }
-  }
-  h_info_out[0] = st[r3d_sums::kStatePairs];
-  h_info_out[1] = st[r3d_sums::kStateRms];
-  h_info_out[2] = bad ? 1.0 : 0.0;
-  h_info_out[3] = st[r3d_sums::kStateIters];
+  pose_and_info(st, G, S, h_pose_out, h_info_out);
   h_info_out[4] = sums[kSums];
   h_info_out[5] = sums[kSums] > 0.0 ? std::sqrt(sums[kSums + 1] / sums[kSums]) : 0.0;
   return R3D_OK;
@@ -425,12 +442,8 @@ int track_levels(r3d_tsdf* vol, const r3d_camera* const* cams, int n_levels, con
                  float max_jump, double dist_max, double cos_min, double* h_pose_out, double* h_info_out, double* h_rms_out) {
   int rc = r3d_tsdf_integrate_checks(vol, cams[0], d_depth, depth_dtype, 1, depth_scale, h_pose_guess_w2c);
   if (rc) return rc;
-  R3D_REQUIRE(h_pose_out && h_info_out, "NULL output pointer");
-  R3D_REQUIRE(!r3d_ranges_overlap(h_pose_out, 12 * sizeof(double), h_info_out, 4 * sizeof(double)) &&
-                  !r3d_ranges_overlap(h_pose_out, 12 * sizeof(double), h_pose_guess_w2c, 12 * sizeof(double)) &&
-                  !r3d_ranges_overlap(h_info_out, 4 * sizeof(double), h_pose_guess_w2c, 12 * sizeof(double)),
-              "an output overlaps the guess or the other output");
-  R3D_REQUIRE(max_jump >= 0.f, "max_jump must be >= 0");
+  const double* G = h_pose_guess_w2c;
+  if ((rc = frame_output_checks(G, h_pose_out, h_info_out, 4, max_jump))) return rc;
   int64_t total = 0;
   for (int l = 0; l < n_levels; ++l) {
     R3D_REQUIRE(iters[l] >= 0, "the iteration count of level %d is negative", l);
@@ -447,16 +460,8 @@ int track_levels(r3d_tsdf* vol, const r3d_camera* const* cams, int n_levels, con
                 "h_rms_out overlaps another host argument");
   }
   r3d_ctx* ctx = cams[0]->ctx;
-  const double* G = h_pose_guess_w2c;
-  for (int k = 0; k < 12; ++k) R3D_REQUIRE(std::isfinite(G[k]), "the pose guess must be finite");
-  // S = the inverse of the guess, in double: the transposed rotation and C_k = -((R[0][k] t0 + R[1][k] t1) + R[2][k] t2)
   double S[16];
-  for (int a = 0; a < 3; ++a) {
-    for (int b = 0; b < 3; ++b) S[4 * a + b] = G[3 * b + a];
-    S[4 * a + 3] = -((G[a] * G[9] + G[3 + a] * G[10]) + G[6 + a] * G[11]);
-    S[12 + a] = 0.0;
-  }
-  S[15] = 1.0;
+  if ((rc = guess_inverse(G, S))) return rc;
   const bool gate = cos_min > -1.0;   // -1 admits every angle: the source normals are neither computed nor asked for
   TrackParams p[R3D_TRACK_MAX_LEVELS];
   for (int l = 0; l < n_levels; ++l) {   // the checks that need no buffer, before anything is enqueued
@@ -513,31 +518,12 @@ int track_levels(r3d_tsdf* vol, const r3d_camera* const* cams, int n_levels, con
   }
   if ((rc = r3d_icp_state_reset(ctx, d_state))) return rc;
   for (int l = n_levels - 1; l >= 0; --l)   // coarse to fine on the one state: T_total, the count and the rms history carry over
-    if (iters[l] > 0 && (rc = iterate_impl(ctx, p[l], m[l], iters[l], d_state))) return rc;
+    if (iters[l] > 0 && (rc = iterate_impl(ctx, p[l], nullptr, m[l], iters[l], d_state))) return rc;
   double st[R3D_ICP_STATE_DOUBLES];
   const size_t n_read = h_rms_out ? (size_t)R3D_ICP_STATE_HISTORY + (size_t)total : (size_t)r3d_sums::kStatePairs + 1;
   R3D_HIP(hipMemcpyAsync(st, d_state, n_read * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   R3D_HIP(hipStreamSynchronize(ctx->stream));
-  const bool bad = st[r3d_sums::kStateStatus] != 0.0;
-  if (bad) {
-    for (int k = 0; k < 12; ++k) h_pose_out[k] = G[k];   // a degenerate step: the guess comes back as it was given
-  } else {
-    double M[16];
-    for (int r = 0; r < 4; ++r)
-      for (int cc = 0; cc < 4; ++cc) {
-        double v = 0.0;
-        for (int k = 0; k < 4; ++k) v += st[r3d_sums::kStateTTotal + 4 * r + k] * S[4 * k + cc];
-        M[4 * r + cc] = v;
-      }
-    for (int a = 0; a < 3; ++a) {
-      for (int b = 0; b < 3; ++b) h_pose_out[3 * a + b] = M[4 * b + a];
-      h_pose_out[9 + a] = -((M[a] * M[3] + M[4 + a] * M[7]) + M[8 + a] * M[11]);
-    }
-  }
-  h_info_out[0] = st[r3d_sums::kStatePairs];
-  h_info_out[1] = st[r3d_sums::kStateRms];
-  h_info_out[2] = bad ? 1.0 : 0.0;
-  h_info_out[3] = st[r3d_sums::kStateIters];
+  pose_and_info(st, G, S, h_pose_out, h_info_out);
   for (int64_t k = 0; h_rms_out && k < total; ++k) h_rms_out[k] = st[R3D_ICP_STATE_HISTORY + k];
   return R3D_OK;
 }
@@ -549,95 +535,35 @@ extern "C" {
 int r3d_track_accumulate(r3d_ctx* ctx, const r3d_camera* cam, const float* d_src_vertex, const float* d_src_normal,
                          const float* d_model_vertex, const float* d_model_normal, const double* h_model_pose_w2c, const double* h_S,
                          double dist_max, double cos_min, double* h_sums, int32_t* d_match_out, float* d_residual_out) {
-  TrackParams p;
   const Maps m = {d_src_vertex, d_src_normal, d_model_vertex, d_model_normal};
-  int rc = track_checks(ctx, cam, m, h_model_pose_w2c, h_S, dist_max, cos_min, &p);
-  if (rc) return rc;
-  R3D_REQUIRE(h_sums != nullptr, "h_sums is NULL");
-  const void* outs[2] = {d_match_out, d_residual_out};
-  const size_t out_bytes[2] = {(size_t)p.n_px * 4, (size_t)p.n_px * 4};
-  if ((rc = output_checks(p, m, outs, out_bytes, 2))) return rc;
-  if ((rc = r3d_ctx_enter(ctx))) return rc;
-  double* rows = nullptr;
-  const int tiles = n_tiles(p);
-  if ((rc = rows_workspace(ctx, tiles, &rows))) return rc;
-  for (int a = 0; a < 2; ++a)
-    if (outs[a]) r3d_wrote(ctx, outs[a], out_bytes[a]);
-  double* d_sums = rows + (size_t)tiles * kSums;
-  enqueue_pass(ctx, p, m, nullptr, rows, d_sums, nullptr, d_match_out, d_residual_out);
-  R3D_HIP(hipGetLastError());
-  R3D_HIP(hipMemcpyAsync(h_sums, d_sums, kSums * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  R3D_HIP(hipStreamSynchronize(ctx->stream));
-  return R3D_OK;
+  return accumulate_entry(ctx, cam, m, h_model_pose_w2c, h_S, dist_max, cos_min, false, 0.0, 0.0, h_sums, d_match_out, d_residual_out,
+                          nullptr);
 }
 
 int r3d_track_iterate(r3d_ctx* ctx, const r3d_camera* cam, const float* d_src_vertex, const float* d_src_normal,
                       const float* d_model_vertex, const float* d_model_normal, const double* h_model_pose_w2c, const double* h_S,
                       double dist_max, double cos_min, int n_iters, double* d_state) {
-  TrackParams p;
   const Maps m = {d_src_vertex, d_src_normal, d_model_vertex, d_model_normal};
-  int rc = track_checks(ctx, cam, m, h_model_pose_w2c, h_S, dist_max, cos_min, &p);
-  if (rc) return rc;
-  R3D_REQUIRE(d_state != nullptr, "d_state is NULL");
-  R3D_REQUIRE(n_iters >= 0 && n_iters <= kMaxIters, "n_iters must be in [0, %d]", kMaxIters);
-  const void* outs[1] = {d_state};
-  const size_t out_bytes[1] = {R3D_ICP_STATE_DOUBLES * sizeof(double)};
-  if ((rc = output_checks(p, m, outs, out_bytes, 1))) return rc;
-  if ((rc = r3d_ctx_enter(ctx))) return rc;
-  if (n_iters == 0) return R3D_OK;
-  r3d_wrote(ctx, d_state, out_bytes[0]);
-  return iterate_impl(ctx, p, m, n_iters, d_state);
+  return iterate_entry(ctx, cam, m, h_model_pose_w2c, h_S, dist_max, cos_min, false, 0.0, 0.0, n_iters, d_state);
 }
 
 int r3d_track_accumulate_rgb(r3d_ctx* ctx, const r3d_camera* cam, const float* d_src_vertex, const float* d_src_normal,
                              const float* d_model_vertex, const float* d_model_normal, const double* h_model_pose_w2c, const double* h_S,
                              double dist_max, double cos_min, const float* d_src_intensity, const float* d_model_packed, double w_photo,
                              double i_max, double* h_sums, int32_t* d_match_out, float* d_residual_out, float* d_photo_out) {
-  TrackParams p;
-  PhotoParams ph;
   Maps m = {d_src_vertex, d_src_normal, d_model_vertex, d_model_normal};
   m.src_intensity = d_src_intensity, m.model_packed = d_model_packed;
-  int rc = track_checks(ctx, cam, m, h_model_pose_w2c, h_S, dist_max, cos_min, &p);
-  if (rc) return rc;
-  if ((rc = photo_checks(m, w_photo, i_max, &ph))) return rc;
-  R3D_REQUIRE(h_sums != nullptr, "h_sums is NULL");
-  const void* outs[3] = {d_match_out, d_residual_out, d_photo_out};
-  const size_t out_bytes[3] = {(size_t)p.n_px * 4, (size_t)p.n_px * 4, (size_t)p.n_px * 4};
-  if ((rc = output_checks(p, m, outs, out_bytes, 3))) return rc;
-  if ((rc = r3d_ctx_enter(ctx))) return rc;
-  double* rows = nullptr;
-  const int tiles = n_tiles(p);
-  if ((rc = rows_workspace(ctx, tiles, &rows, kSumsRgb))) return rc;
-  for (int a = 0; a < 3; ++a)
-    if (outs[a]) r3d_wrote(ctx, outs[a], out_bytes[a]);
-  double* d_sums = rows + (size_t)tiles * kSumsRgb;
-  enqueue_pass_rgb(ctx, p, ph, m, nullptr, rows, d_sums, nullptr, d_match_out, d_residual_out, d_photo_out);
-  R3D_HIP(hipGetLastError());
-  R3D_HIP(hipMemcpyAsync(h_sums, d_sums, kSumsRgb * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  R3D_HIP(hipStreamSynchronize(ctx->stream));
-  return R3D_OK;
+  return accumulate_entry(ctx, cam, m, h_model_pose_w2c, h_S, dist_max, cos_min, true, w_photo, i_max, h_sums, d_match_out, d_residual_out,
+                          d_photo_out);
 }
 
 int r3d_track_iterate_rgb(r3d_ctx* ctx, const r3d_camera* cam, const float* d_src_vertex, const float* d_src_normal,
                           const float* d_model_vertex, const float* d_model_normal, const double* h_model_pose_w2c, const double* h_S,
                           double dist_max, double cos_min, const float* d_src_intensity, const float* d_model_packed, double w_photo,
                           double i_max, int n_iters, double* d_state) {
-  TrackParams p;
-  PhotoParams ph;
   Maps m = {d_src_vertex, d_src_normal, d_model_vertex, d_model_normal};
   m.src_intensity = d_src_intensity, m.model_packed = d_model_packed;
-  int rc = track_checks(ctx, cam, m, h_model_pose_w2c, h_S, dist_max, cos_min, &p);
-  if (rc) return rc;
-  if ((rc = photo_checks(m, w_photo, i_max, &ph))) return rc;
-  R3D_REQUIRE(d_state != nullptr, "d_state is NULL");
-  R3D_REQUIRE(n_iters >= 0 && n_iters <= kMaxIters, "n_iters must be in [0, %d]", kMaxIters);
-  const void* outs[1] = {d_state};
-  const size_t out_bytes[1] = {R3D_ICP_STATE_DOUBLES * sizeof(double)};
-  if ((rc = output_checks(p, m, outs, out_bytes, 1))) return rc;
-  if ((rc = r3d_ctx_enter(ctx))) return rc;
-  if (n_iters == 0) return R3D_OK;
-  r3d_wrote(ctx, d_state, out_bytes[0]);
-  return iterate_rgb_impl(ctx, p, ph, m, n_iters, d_state, nullptr);
+  return iterate_entry(ctx, cam, m, h_model_pose_w2c, h_S, dist_max, cos_min, true, w_photo, i_max, n_iters, d_state);
 }
 
 int r3d_tsdf_track_rgb(r3d_tsdf* vol, const r3d_camera* cam, const void* d_depth, int depth_dtype, double depth_scale,

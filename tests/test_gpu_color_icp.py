@@ -291,6 +291,90 @@ def test_icp_colored_on_the_wall(ctx, R, CI, icp, wall):
     assert after <= 2 * REF.WALL_ERROR_AFTER
 
 
+class ColourLoop:
+    """The buffers of one r3d_icp_iterate_color loop on the wall: the source in the index's order, its intensities alongside."""
+
+    def __init__(self, ctx, L, CI, wall, src, src_I, nrm, keep_original):
+        n, m = src.shape[0], wall["tgt"].shape[0]
+        self.ctx, self.L, self.n, self.keep_original = ctx, L, n, keep_original
+        c = self.c = CI._Cloud(ctx, wall["tgt"])
+        self.d_n, self.d_i, self.d_g = c.alloc(m * 12).upload(nrm), c.alloc(m * 4).upload(wall["I"]), c.alloc(m * 12).upload(wall["grad"])
+        self.d_src, d_perm = c.alloc(n * 12).upload(src), c.alloc(n * 4)
+        c.index.sort_cloud(self.d_src.ptr, n, d_perm.ptr)
+        self.d_si = c.alloc(n * 4).upload(np.ascontiguousarray(src_I[d_perm.download(np.uint32, n)]))
+        self.d_src0 = c.alloc(n * 12)
+        L.check(ctx.lib.r3d_memcpy_d2d(ctx.handle, self.d_src0.ptr, self.d_src.ptr, n * 12))
+        self.d_idx, self.d_d2, self.d_state, self.d_sums = c.alloc(n * 4), c.alloc(n * 4), c.alloc(512 * 8), c.alloc(31 * 8)
+        L.check(ctx.lib.r3d_icp_state_reset(ctx.handle, self.d_state.ptr))
+
+    def iterate(self, iters, w_photo, i_max):
+        lib, h = self.ctx.lib, self.ctx.handle
+        self.L.check(lib.r3d_icp_iterate_color(h, self.c.index.handle, self.d_src0.ptr if self.keep_original else None, self.d_src.ptr,
+                                               self.d_si.ptr, self.n, self.d_n.ptr, self.d_i.ptr, self.d_g.ptr, self.d_idx.ptr,
+                                               self.d_d2.ptr, iters, -1.0, w_photo, i_max, self.d_state.ptr, self.d_sums.ptr))
+        return self.d_state.download(np.float64, 512)
+
+
+@pytest.mark.parametrize("keep_original", [False, True])
+def test_colour_loop_continued_with_and_without_the_original(ctx, R, L, CI, wall, keep_original):
+    """r3d_icp_iterate_color called as 1, 1, 2 iterations (max_d2 = -1) on 257 sources of the wall (two partial rows), with
+    d_src_orig and without.  After every call the state is the one before it advanced by the step and rms it stores itself
+    (icp_state_ref.check_advance), the count is the running total, and [35] is the number of sources whose match in the d_idx left
+    behind has a target normal (some normals are zeroed).  check_advance describes ONE step, and the state between the two
+    iterations of the last call is never in HBM when the host can look: a twin loop on a context of its own, called 1, 1, 1 on the
+    same inputs, supplies it (its first two states must be the loop's own, bit for bit).
+    With the original: d_src is byte for byte what r3d_apply_T_dev makes of the original and the state's T_total -- the last
+    iteration of a call moves by that very call.  Without: the last act of a call is the move by its last step, AFTER the query
+    that filled d_idx and d_d2, so those describe the cloud as it was before that move (the cloud the call began with; in the last
+    call the twin's cloud after its third iteration): they are what r3d_nn_index_query returns for THAT cloud -- both, bit for bit:
+    the warm and the cold query are exact searches over one fp32 distance expression, the lowest target index winning ties
+    (include/r3d.h, the index's contract) -- and d_src is that cloud moved by the stored step, byte for byte."""
+    import icp_state_ref as SR
+    n = 257
+    rows = np.linspace(0, wall["src"].shape[0] - 1, n).astype(np.int64)
+    src, src_I = np.ascontiguousarray(wall["src"][rows]), np.ascontiguousarray(wall["src_I"][rows])
+    nrm = wall["normals"].copy()
+    nrm[::7] = 0
+    has = (nrm != 0).any(axis=1)
+    w = CI.photo_weight(0.968)
+    twin_ctx = R.Context(0)
+    loop = twin = None
+    try:
+        loop = ColourLoop(ctx, L, CI, wall, src, src_I, nrm, keep_original)
+        twin = ColourLoop(twin_ctx, L, CI, wall, src, src_I, nrm, keep_original)
+        prev, total = loop.d_state.download(np.float64, 512), 0
+        for k, iters in enumerate((1, 1, 2)):
+            before = loop.d_src.download(np.uint8, n * 12)
+            twin_state = twin.iterate(1, w, 40.0)
+            if iters == 2:                                                  # the state and the cloud between the two iterations
+                prev, before = twin_state, twin.d_src.download(np.uint8, n * 12)
+            got = loop.iterate(iters, w, 40.0)
+            if iters == 1:
+                assert got.tobytes() == twin_state.tobytes(), (k, "the twin loop went another way")
+                assert loop.d_src.download(np.uint8, n * 12).tobytes() == twin.d_src.download(np.uint8, n * 12).tobytes(), k
+            total += iters
+            SR.check_advance(prev, got, got[16:32], got[34], 0, got[35], what=k)
+            assert got[32] == total and got[33] == 0.0
+            idx = loop.d_idx.download(np.uint32, n)
+            assert got[35] == float(has[idx].sum()) and 6 < got[35] < n, (k, got[35], has[idx].sum())
+            d_want = loop.c.alloc(n * 12)
+            if keep_original:
+                L.check(ctx.lib.r3d_apply_T_dev(ctx.handle, loop.d_src0.ptr, L.F32, n, loop.d_state.ptr, d_want.ptr, L.F32))
+            else:
+                d_before, d_i2, d_d22 = loop.c.alloc(n * 12).upload(before), loop.c.alloc(n * 4), loop.c.alloc(n * 4)
+                loop.c.index.query(d_before.ptr, n, d_i2.ptr, d_d22.ptr, presorted=True)
+                assert np.array_equal(d_i2.download(np.uint32, n), idx), k
+                assert d_d22.download(np.uint8, n * 4).tobytes() == loop.d_d2.download(np.uint8, n * 4).tobytes(), k
+                L.check(ctx.lib.r3d_apply_T_dev(ctx.handle, d_before.ptr, L.F32, n, loop.d_state.ptr + 16 * 8, d_want.ptr, L.F32))
+            assert loop.d_src.download(np.uint8, n * 12).tobytes() == d_want.download(np.uint8, n * 12).tobytes(), k
+            prev = got
+    finally:
+        for c in (loop, twin):
+            if c is not None:
+                c.c.close()
+        twin_ctx.close()
+
+
 def test_register_colored_two_scales(ctx, R, wall):
     sc = wall
     T, info = R.register_colored(sc["src"], sc["src_rgba"], sc["tgt"], sc["tgt_rgba"], voxel_sizes=(0.04, 0.005), iters=(15, 20),

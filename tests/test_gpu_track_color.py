@@ -1,4 +1,4 @@
-"""GPU: tracking with a photometric term (csrc/r3d_photo.hip, track_rgb_kernel and its drivers in csrc/r3d_track.hip) against
+"""GPU: tracking with a photometric term (csrc/r3d_photo.hip, track_kernel<true> and its drivers in csrc/r3d_track.hip) against
 tests/photo_ref.py, the NumPy restatement of include/r3d.h "TSDF colour tracking": the intensity maps and the per-pixel intensity
 differences bit for bit, match and residual against r3d_track_accumulate itself, the 31 sums at the tolerance of the 29, the
 device-resident loop against the reference loop, and the whole step in a textured corridor where depth alone cannot see along
