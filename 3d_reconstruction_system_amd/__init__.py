@@ -33,6 +33,8 @@ from .posegraph import (PoseGraph, evaluate_registration, registration_informati
 from .tsdf import TSDFVolume, poses_w2c  # noqa: F401
 from .mesh import (MeshComponents, mesh_components, mesh_components_device, remove_small_components,  # noqa: F401
                    remove_small_components_device)
+from .evaluation import (MeshIndex, cloud_to_cloud_distance, cloud_to_mesh_distance, distance_stats, distance_colors,  # noqa: F401
+                         evaluate_reconstruction, cloud_to_cloud_distance_device, distance_stats_device, distance_colors_device)
 from .tracking import TrackDevice, track_sums  # noqa: F401
 from . import cloud_io, device_text  # noqa: F401
 

@@ -206,6 +206,12 @@ SIGNATURES = {
     "r3d_color_gradient_knn": (_i, [_vp, _i, _d, _vp, _vp, _vp, _vp, _vp]),
     "r3d_icp_color_accumulate": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _f, _d, _d, _vp, _vp]),
     "r3d_icp_iterate_color": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _f, _d, _d, _vp, _vp]),
+    "r3d_mesh_index_create": (_i, [_vp, _vp, _i64, _vp, _i64, _pvp]),
+    "r3d_mesh_index_destroy": (_i, [_vp]),
+    "r3d_mesh_index_query": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp]),
+    "r3d_distance_stats": (_i, [_vp, _vp, _i64, _i, _vp, _i, _d, _i, _vp, _vp, _vp]),
+    "r3d_sqrt_f32_inplace": (_i, [_vp, _vp, _i64]),
+    "r3d_distance_colors": (_i, [_vp, _vp, _i64, _d, _vp]),
 }
 
 _lib = None

@@ -219,6 +219,7 @@ int r3d_ctx_destroy(r3d_ctx* ctx) {
   if (ctx->color_rows) (void)hipFree(ctx->color_rows);
   if (ctx->color_lists) (void)hipFree(ctx->color_lists);
   if (ctx->mesh_cc_ws) (void)hipFree(ctx->mesh_cc_ws);
+  if (ctx->meshdist_ws) (void)hipFree(ctx->meshdist_ws);
   for (int i = 0; i < r3d_ctx::kPinnedSlots; ++i)
     if (ctx->pinned[i]) (void)hipHostFree(ctx->pinned[i]);
   for (int i = 0; i < 6; ++i)

@@ -78,6 +78,10 @@ struct r3d_ctx {
   // counters, grown on demand; only r3d_mesh_components and r3d_mesh_filter_components touch it, and both are synchronous
   void* mesh_cc_ws = nullptr;
   size_t mesh_cc_ws_bytes = 0;
+  // the evaluation calls' own workspace (r3d_meshdist.hip), not a shared slot either: the sort keys of a mesh index build or query
+  // and the partial rows of r3d_distance_stats, grown on demand; only those calls touch it, in stream order
+  void* meshdist_ws = nullptr;
+  size_t meshdist_ws_bytes = 0;
   // pinned staging buffers of the host pipeline: slot = ((direction * kPipeBufs + array) * 2 + parity)
   static constexpr int kPipeBufs = 2;   // arrays per direction (depth + colour in, xyz + rgba out)
   static constexpr int kPinnedSlots = 2 * kPipeBufs * 2;

@@ -1363,6 +1363,99 @@ int r3d_icp_iterate_color(r3d_ctx* ctx, r3d_nn_index* index, const float* d_src_
                           uint32_t* d_idx, float* d_d2, int n_iters, float max_d2, double w_photo, double i_max, double* d_state,
                           double* d_sums_out);
 
+/* ---- Reconstruction evaluation (csrc/r3d_meshdist.hip; NOT IN THE REFERENCE, whose readme leaves "the accuracy comparison of the
+ * clouds" to CloudCompare; this text is the specification, tests/compare_ref.py restates it in NumPy).  Distance from every point
+ * to a triangle mesh (CloudCompare's C2M, Open3D's RaycastingScene.compute_distance; NO parity with either is claimed), fixed-order
+ * statistics of a distance field, the f32 root that turns r3d_nn_index_query's d2 into distances (cloud to cloud), and a colour
+ * ramp.  None of these kernels has been timed on a card.
+ *
+ * r3d_mesh_index_create: d_xyz [n_vertices][3] f32, d_tri [n_triangles][3] int32.  The index keeps its own copy of what it needs:
+ *   the mesh may be freed or rewritten when the call returns (it synchronises).  n_triangles == 0 and n_vertices == 0 are fine.
+ *   Validity: a triangle is valid iff its three indices lie in [0, n_vertices) -- checked before any of them is used as an address --
+ *     and its nine coordinates are finite.  An invalid triangle is never a winner.  A zero-area triangle (a repeated index,
+ *     coincident or collinear vertices) is valid and is measured as the segment or point it is; a triangle listed twice is two
+ *     triangles.
+ *   R3D_ERR_INVALID, nothing written: a NULL ctx or index_out; a negative size; a NULL d_tri with n_triangles > 0 or d_xyz with
+ *     n_vertices > 0.  n_vertices or n_triangles > 2^31 - 1: R3D_ERR_UNSUPPORTED.
+ *
+ * r3d_mesh_index_query: for every point p of d_points [n_points][3] f32 the nearest valid triangle, by this DEFINITION (brute
+ *   force over all valid triangles; culling is an implementation matter and never changes a bit).  All arithmetic is IEEE fp64 on
+ *   the f32 inputs converted exactly, products and sums in the order written, left to right, no fused multiply-add; x . y means
+ *   (x0*y0 + x1*y1) + x2*y2.  For the triangle (a, b, c):
+ *     ab = b - a, ac = c - a, bc = c - b, ap = p - a, bp = p - b, cp = p - c
+ *     d1 = ab.ap, d2 = ac.ap, d3 = ab.bp, d4 = ac.bp, d5 = ab.cp, d6 = ac.cp
+ *     vc = d1*d4 - d3*d2, vb = d5*d2 - d1*d6, va = d3*d6 - d5*d4, e43 = d4 - d3, e56 = d5 - d6
+ *     den_ab = d1 - d3, den_ac = d2 - d6, den_bc = e43 + e56   (|ab|^2, |ac|^2, |bc|^2 but for rounding)
+ *   The region is the FIRST of these that holds:
+ *     A:  d1 <= 0 and d2 <= 0                      q = a
+ *     B:  d3 >= 0 and d4 <= d3                     q = b
+ *     AB: vc <= 0, d1 >= 0, d3 <= 0, den_ab > 0    r = d1 / den_ab,              q = (a + ab*r) + ac*0
+ *     C:  d6 >= 0 and d5 <= d6                     q = c
+ *     AC: vb <= 0, d2 >= 0, d6 <= 0, den_ac > 0    r = d2 / den_ac,              q = (a + ab*0) + ac*r
+ *     BC: va <= 0, e43 >= 0, e56 >= 0, den_bc > 0  r = e43 / den_bc,             q = (b + bc*r) + ac*0
+ *     face (otherwise)                             r = 1 / ((va + vb) + vc), or 0 where that sum is not > 0,
+ *                                                  q = (a + ab*v) + ac*w  with
+ *         v = vb*r, v = v > 0 ? v : 0, v = v < 1 ? v : 1;  w = vc*r, w = w > 0 ? w : 0, w = w < 1 - v ? w : 1 - v
+ *   (q per coordinate; a vertex region returns the vertex itself).  Zero-area rule: an edge region is taken only where its
+ *   denominator is > 0 -- an edge of no length is left to the regions of its end points and of the other edges --, the face's
+ *   quotient is 0 where its denominator is not > 0, and the selects above turn a NaN into 0: no division by zero and no NaN arises
+ *   for finite input.  A triangle with a repeated index or coincident vertices has an edge vector of exact zeros, its products
+ *   are exact zeros, and it is measured exactly as its segment or point; so is a collinear triangle whose products are exact.
+ *   For other collinear triangles rounding decides the region as it does for any sliver, and q is a point of the segment.
+ *     dq = p - q,  d2(p, triangle) = (dq0*dq0 + dq1*dq1) + dq2*dq2
+ *   The triangle with the smallest d2 wins; the LOWEST triangle index wins exact ties.
+ *   d_dist_out [n_points] f32 = (float) sqrt(d2), rounded once from the correctly rounded fp64 root (+inf where d2 exceeds the f32
+ *     range).  With R3D_MESHDIST_SIGNED in flags it is negated where n . dq < 0 for n = ab x ac = (ab1*ac2 - ab2*ac1,
+ *     ab2*ac0 - ab0*ac2, ab0*ac1 - ab1*ac0) of the winning triangle; the sign is + where the product is 0.  This is the FACE-NORMAL
+ *     sign of the tie-winning triangle, not an angle-weighted pseudonormal: next to an edge or a vertex of a closed surface, where
+ *     the nearest point is shared by triangles facing differently, it may disagree with inside / outside.
+ *   d_tri_out [n_points] u32 (may be NULL): the winner.  d_closest_out [n_points][3] f32 (may be NULL): (float) q, rounded once.
+ *   A point with a non-finite coordinate, or an index without a valid triangle: distance +inf, triangle 0xFFFFFFFF, closest NaN.
+ *   h_groups_evaluated (may be NULL; the call synchronises when it is given, and is asynchronous otherwise): the number of
+ *     32-triangle groups whose triangles were measured, summed over the waves of 64 points -- waves * ceil(valid triangles / 32)
+ *     without culling.  It depends on the order the points are met in, the results do not.
+ *   n_points == 0 is fine.  R3D_ERR_INVALID, nothing written: a NULL index; a negative n_points; unknown flag bits; a NULL d_points
+ *     or d_dist_out with n_points > 0; an output overlapping the points or another output.  n_points > 2^31 - 1:
+ *     R3D_ERR_UNSUPPORTED.  Inputs are never modified.  Results do not depend on the launch geometry, on the order of the points
+ *     or on what ran before on the context (the call sorts its keys in a workspace of the context that only the evaluation calls touch, in stream order).
+ *   How: the valid triangles are sorted by the Morton code of their centroid and grouped by 32 with an f32 box per group; the
+ *     points are sorted by the same code and a wave takes 64 of them, starts at the group of its own neighbourhood, walks outwards
+ *     and skips a group only when a conservative lower bound of its box is STRICTLY above every lane's best.  No float atomics.
+ *     There is no coarser level than the group yet: every wave tests every group's box.
+ *
+ * r3d_distance_stats: d_values [n] f32 -> x = (double) v, then x = sqrt(x) (correctly rounded) when squared_input != 0.  An x that
+ *   is not finite is counted apart and takes no part in anything else.
+ *   h_stats_out [6] f64 = {n_finite, n_nonfinite, sum x, sum x*x, min, max}.  Fixed order, the same bits run to run: row r holds
+ *     elements [256 r, 256 r + 256), one per lane, a missing lane adding 0.0; a row is reduced per 64 lanes by the tree
+ *     s[i] += s[i + 32], s[i + 16], ... s[i + 1], then the four waves are added in order to 0.0; the finish gives thread t of 256 the
+ *     rows t, t + 256, ... added in order to 0.0, and reduces the 256 values the same way.  min and max have 0.0 added (a zero
+ *     is reported as +0); with no finite element they are +inf and -inf and the sums are 0.
+ *   h_count_le_out [n_thresholds] int64: the finite x with x <= h_thresholds[t]; n_thresholds <= 8.
+ *   h_hist_out [n_bins] u64: finite x counts in bin min((int64) floor(x / bin_width), n_bins - 1), a negative x in bin 0;
+ *     n_bins <= 4096 (0: no histogram, bin_width is ignored).  Integer atomics.
+ *   Synchronises.  R3D_ERR_INVALID, nothing written: a NULL ctx or h_stats_out; a negative n; a NULL d_values with n > 0;
+ *     n_thresholds outside [0, 8] or n_bins outside [0, 4096]; NULL h_thresholds or h_count_le_out with n_thresholds > 0; a NaN
+ *     threshold; NULL h_hist_out, or a bin_width that is not finite and > 0, with n_bins > 0.  n > 2^31 - 1: R3D_ERR_UNSUPPORTED.
+ * r3d_sqrt_f32_inplace: v = (float) sqrt((double) v), which is the correctly rounded f32 root (fp64 carries more than twice the
+ *   bits): r3d_nn_index_query's d2 become distances.  A negative value becomes NaN, -0 stays -0.  Asynchronous.
+ * r3d_distance_colors: CloudCompare's scalar-field view.  d_rgba_out [n] u32 = r | g << 8 | b << 16, the words r3d_write_ply_rgba
+ *   takes.  A distance that is not finite: r = g = b = 128.  Otherwise, in fp64, t = |d| / d_max, t = t < 1 ? t : 1,
+ *   q = (integer) floor(t * 765): q <= 255: (r, g, b) = (0, q, 255 - q), blue to green; q <= 510: (q - 255, 255, 0), green to
+ *   yellow; else (255, 255 - (q - 510), 0), yellow to red.  d_max must be finite and > 0.  Asynchronous.
+ *   R3D_ERR_INVALID for both, nothing written: a NULL ctx; a negative n; a NULL device pointer with n > 0; d_max as above; the
+ *     output overlapping the distances.  n > 2^31 - 1: R3D_ERR_UNSUPPORTED. */
+typedef struct r3d_mesh_index r3d_mesh_index;
+#define R3D_MESHDIST_SIGNED 1
+int r3d_mesh_index_create(r3d_ctx* ctx, const float* d_xyz, int64_t n_vertices, const int32_t* d_tri, int64_t n_triangles,
+                          r3d_mesh_index** index_out);
+int r3d_mesh_index_destroy(r3d_mesh_index* index);
+int r3d_mesh_index_query(r3d_mesh_index* index, const float* d_points, int64_t n_points, int flags, float* d_dist_out,
+                         uint32_t* d_tri_out, float* d_closest_out, int64_t* h_groups_evaluated);
+int r3d_distance_stats(r3d_ctx* ctx, const float* d_values, int64_t n, int squared_input, const double* h_thresholds, int n_thresholds,
+                       double bin_width, int n_bins, double* h_stats_out, int64_t* h_count_le_out, uint64_t* h_hist_out);
+int r3d_sqrt_f32_inplace(r3d_ctx* ctx, float* d_values, int64_t n);
+int r3d_distance_colors(r3d_ctx* ctx, const float* d_dist, int64_t n, double d_max, uint32_t* d_rgba_out);
+
 #ifdef __cplusplus
 }
 #endif
