@@ -276,8 +276,8 @@ int apply_host_common(r3d_ctx* ctx, const void* h_xyz_in, int in_dtype, int64_t 
   const size_t in_bytes = (size_t)n_points * 3 * r3d_xyz_size(in_dtype);
   const size_t out_bytes = (size_t)n_points * 3 * r3d_xyz_size(out_dtype);
   void *d_in = nullptr, *d_out = nullptr;
-  if ((rc = r3d_scratch(ctx, 0, in_bytes, &d_in))) return rc;
-  if ((rc = r3d_scratch(ctx, 1, out_bytes, &d_out))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsIn, in_bytes, &d_in))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsOut, out_bytes, &d_out))) return rc;
   // 64 Ki points per pipeline item keeps every chunk boundary on a tile (and 16-byte) boundary
   const int64_t item_pts = 65536;
   const size_t isz = 3 * r3d_xyz_size(in_dtype), osz = 3 * r3d_xyz_size(out_dtype);
@@ -339,9 +339,9 @@ int r3d_apply_T_many(r3d_ctx* ctx, const void* d_xyz_in, int in_dtype, int64_t n
   }
   if (in_dtype == R3D_F32 && out_dtype == R3D_F32 && n_transforms <= 65535) {
     r3d_wrote(ctx, d_xyz_out, block * (size_t)n_transforms);   // an ICP loop working on these points is over
-    // the table of matrices travels through a scratch slot; the copy is enqueued from a staging copy that outlives the call
+    // the table of matrices travels through kWsPartials; the copy is enqueued from a staging copy that outlives the call
     void* d_T = nullptr;
-    if ((rc = r3d_scratch(ctx, 4, (size_t)n_transforms * 16 * sizeof(double), &d_T))) return rc;
+    if ((rc = r3d_scratch(ctx, kWsPartials, (size_t)n_transforms * 16 * sizeof(double), &d_T))) return rc;
     R3D_HIP(hipMemcpyAsync(d_T, h_Ts, (size_t)n_transforms * 16 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     R3D_HIP(hipStreamSynchronize(ctx->stream));   // h_Ts is the caller's (pageable) memory
     hipLaunchKernelGGL(apply_many_kernel, dim3((unsigned)((n_points + kThreads - 1) / kThreads), (unsigned)n_transforms), dim3(kThreads),

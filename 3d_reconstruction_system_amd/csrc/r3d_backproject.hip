@@ -225,7 +225,7 @@ int r3d_project3d_grad_f32(r3d_ctx* ctx, const float* d_grad_pix, const float* d
   const int cap = ctx->num_cus * 4;   // several pixels per thread: fewer partials to add up
   if (bx > cap) bx = cap;
   void* part = nullptr;
-  if (d_grad_P && (rc = r3d_scratch(ctx, 4, (size_t)batch * bx * kProjSums * sizeof(float), &part))) return rc;
+  if (d_grad_P && (rc = r3d_scratch(ctx, kWsPartials, (size_t)batch * bx * kProjSums * sizeof(float), &part))) return rc;
   hipLaunchKernelGGL(project3d_grad_kernel, dim3(bx, batch), dim3(kThreads), 0, ctx->stream,
                      reinterpret_cast<const float2*>(d_grad_pix), d_points, d_P, hw, eps, 2.0f / (float)(width - 1),
                      2.0f / (float)(height - 1), d_grad_points, static_cast<float*>(part));

@@ -21,8 +21,7 @@ constexpr int kThreads = 256;
 constexpr int kTileW = 32, kTileH = 8;
 constexpr int kMaxR = R3D_BILATERAL_MAX_RADIUS, kBins = R3D_BILATERAL_RANGE_BINS;
 constexpr int kMaxSide = 2 * kMaxR + 1;
-constexpr int kTableFloats = kBins + kMaxSide * kMaxSide;   // the device copy: range[256], then spatial[(2r+1)^2]
-constexpr int kTableSlot = 8;                               // the ctx scratch slot that holds it (nobody else's)
+constexpr int kTableFloats = kBins + kMaxSide * kMaxSide;   // the device copy: range[256], then spatial[(2r+1)^2], in kWsBilateral
 constexpr int kMaxBlocks = 1 << 20;
 constexpr int kTrackTile = 1024;   // the raster-size limit of the tracking calls (r3d_track.hip: kTile)
 
@@ -144,7 +143,7 @@ int r3d_depth_bilateral(r3d_ctx* ctx, const float* d_in, int in_stride, int heig
   rc = r3d_ctx_enter(ctx);
   if (rc) return rc;
   void* d_tables = nullptr;
-  rc = r3d_scratch(ctx, kTableSlot, kTableFloats * sizeof(float), &d_tables);
+  rc = r3d_scratch(ctx, kWsBilateral, kTableFloats * sizeof(float), &d_tables);
   if (rc) return rc;
   if (!cached) {
     // stream-ordered behind every earlier launch that reads the old tables; the key is set only once the copy is enqueued

@@ -139,16 +139,17 @@ struct ColorPass {
   double w_photo, i_max;
 };
 
-// The partial rows, then the 31 sums (64 kB at the most), belong to this file's entry points alone and are made once per context at
-// their largest size, as r3d_registration_sums keeps its own: nothing here depends on, or disturbs, what other calls leave in the
-// context's shared scratch slots.
+// kWsColorRows: the partial rows, then the 31 sums (64 kB at the most), are this file's alone and always asked for at their largest
+// size, as r3d_registration_sums keeps its own: nothing here depends on, or disturbs, what other calls leave in the shared workspaces.
 // one sums pass: partial rows -> d_sums (the 31 doubles behind the rows when NULL is given) [-> the state]
 int color_sums_enqueue(r3d_ctx* ctx, const float* d_src, int64_t n_src, const float* d_tgt, int64_t n_tgt, const uint32_t* d_idx,
                        const float* d_d2, const ColorPass& c, double* d_sums, double* d_state, float* d_photo_out,
                        double** d_sums_used) {
   const int blocks = r3d_plane::accumulate_blocks(ctx->num_cus, n_src);
-  if (!ctx->color_rows) R3D_HIP(hipMalloc(&ctx->color_rows, ((size_t)ctx->num_cus + 1) * kSums * sizeof(double)));
-  double* rows = static_cast<double*>(ctx->color_rows);
+  void* rows_v = nullptr;
+  int rc = r3d_scratch(ctx, kWsColorRows, ((size_t)ctx->num_cus + 1) * kSums * sizeof(double), &rows_v);
+  if (rc) return rc;
+  double* rows = static_cast<double*>(rows_v);
   if (!d_sums && d_sums_used) d_sums = rows + (size_t)blocks * kSums;
   hipLaunchKernelGGL(color_accumulate_kernel, dim3(blocks), dim3(kThreads), 0, ctx->stream, d_src, c.src_I, n_src, d_tgt, c.nrm, c.tgt_I,
                      c.tgt_g, n_tgt, d_idx, d_d2, c.max_d2 >= 0.f ? c.max_d2 : -1.f, c.w_photo, c.i_max, rows, d_photo_out);
@@ -178,16 +179,10 @@ int r3d_color_gradient_knn(r3d_nn_index* index, int k, double radius, const floa
   R3D_REQUIRE(!r3d_any_overlap(outs, 3, ins, 3), "an output overlaps another output, the normals, the colours or the index's cloud");
   if ((rc = r3d_ctx_enter(ctx))) return rc;
   if (n == 0) return R3D_OK;
-  // the lists (idx | d2), stored as r3d_fpfh_knn stores them, in a grow-only buffer of this file's own
-  const size_t list_b = ((size_t)n * k * 4 + 255) & ~(size_t)255;
-  if (ctx->color_lists_bytes < 2 * list_b) {
-    if (ctx->color_lists) R3D_HIP(hipFree(ctx->color_lists));   // (waits for the device: no launch still reads the old lists)
-    ctx->color_lists = nullptr;
-    ctx->color_lists_bytes = 0;
-    R3D_HIP(hipMalloc(&ctx->color_lists, 2 * list_b));
-    ctx->color_lists_bytes = 2 * list_b;
-  }
-  void* lists = ctx->color_lists;
+  // the lists (idx | d2), stored as r3d_fpfh_knn stores them, in a workspace of this file's own
+  const size_t list_b = r3d_align_up((size_t)n * k * 4, 256);
+  void* lists = nullptr;
+  if ((rc = r3d_scratch(ctx, kWsColorLists, 2 * list_b, &lists))) return rc;
   uint32_t* idx = static_cast<uint32_t*>(lists);
   float* d2l = reinterpret_cast<float*>(static_cast<char*>(lists) + list_b);
   if ((rc = r3d_nn_index_knn_self(index, k, idx, d2l))) return rc;

@@ -14,7 +14,7 @@ namespace r3d_compact {
 constexpr int kPer = kSortTile / 256;   // consecutive items per thread
 inline int tiles_of(int64_t n) { return (int)((n + kSortTile - 1) / kSortTile); }
 
-// The counters inside a block the caller provides (a scratch slot, a workspace of its own): `rows` rows of `stride` counters,
+// The counters inside a block the caller provides (kWsCounts, kWsMisc, kWsMeshCc): `rows` rows of `stride` counters,
 // 32-byte aligned when the block is, then 64 bytes that begin with the rows' totals (a caller may keep words of its own behind
 // them).  A call without a tile still gets one tile's row, so `totals` never aliases `hist`.
 struct Counters {

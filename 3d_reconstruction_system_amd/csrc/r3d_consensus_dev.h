@@ -7,7 +7,7 @@
 //   best_kernel          one workgroup: the lowest h among the maximal counts, the number of valid hypotheses -> BestHead,
 //                        then the estimator's tail
 //   the estimator's own refit, host solve and mask
-// plan() fixes the launch geometry and layout() carves scratch slots 5 and 4 for all of it.  The two count kernels have one
+// plan() fixes the launch geometry and layout() carves kWsMisc and kWsPartials for all of it.  The two count kernels have one
 // shape (lanes own R hypotheses in registers, the chunk goes through two LDS tile buffers, every lane reads the same item) but
 // stay apart: written as one template over an item trait, the plane instantiations came out of the compiler with two more
 // VGPRs (130 at R = 2: a wave per SIMD fewer), see DESIGN 4.5h.
@@ -72,8 +72,8 @@ inline Plan plan(int64_t n_items, int H, int tile_items) {
   return p;
 }
 
-// slot 5: what the host reads (the estimator's Misc), the hypotheses, their rows, validity and counts; slot 4: the partial
-// counts, then the refit's sum rows
+// kWsMisc: what the host reads (the estimator's Misc), the hypotheses, their rows, validity and counts; kWsPartials: the
+// partial counts, then the refit's sum rows
 struct Layout {
   void* misc;
   float* hyp;
@@ -82,14 +82,14 @@ struct Layout {
 };
 
 inline int layout(r3d_ctx* ctx, const Plan& p, int params, int sums, size_t misc_bytes, Layout* out) {
-  const size_t misc_b = (misc_bytes + 255) & ~(size_t)255;
-  const size_t hyp_b = (size_t)params * p.h_pad * 4, rows_b = ((size_t)3 * p.H * 4 + 255) & ~(size_t)255;
-  const size_t hb = ((size_t)p.H * 4 + 255) & ~(size_t)255;
-  const size_t part_b = ((size_t)p.chunks * p.h_pad * 4 + 255) & ~(size_t)255;
+  const size_t misc_b = r3d_align_up(misc_bytes, 256);
+  const size_t hyp_b = (size_t)params * p.h_pad * 4, rows_b = r3d_align_up((size_t)3 * p.H * 4, 256);
+  const size_t hb = r3d_align_up((size_t)p.H * 4, 256);
+  const size_t part_b = r3d_align_up((size_t)p.chunks * p.h_pad * 4, 256);
   void *s5 = nullptr, *s4 = nullptr;
   int rc;
-  if ((rc = r3d_scratch(ctx, 5, misc_b + hyp_b + rows_b + 2 * hb, &s5))) return rc;
-  if ((rc = r3d_scratch(ctx, 4, part_b + (size_t)p.rblocks * sums * sizeof(double), &s4))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsMisc, misc_b + hyp_b + rows_b + 2 * hb, &s5))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsPartials, part_b + (size_t)p.rblocks * sums * sizeof(double), &s4))) return rc;
   char* p5 = static_cast<char*>(s5);
   out->misc = p5;
   out->hyp = reinterpret_cast<float*>(p5 + misc_b);

@@ -120,23 +120,23 @@ int r3d_inputs_tracked(r3d_ctx* ctx) {
   return r->n;
 }
 
-int r3d_scratch(r3d_ctx* ctx, int slot, size_t bytes, void** p) {
-  R3D_REQUIRE(slot >= 0 && slot < r3d_ctx::kScratchSlots, "bad scratch slot");
+int r3d_scratch(r3d_ctx* ctx, r3d_workspace which, size_t bytes, void** p) {
+  R3D_REQUIRE(which >= 0 && which < kWsEnd, "bad workspace");
   if (bytes == 0) bytes = 16;
-  if (ctx->scratch_bytes[slot] < bytes) {
-    if (ctx->scratch[slot]) {
+  if (ctx->scratch_bytes[which] < bytes) {
+    if (ctx->scratch[which]) {
       R3D_HIP(hipStreamSynchronize(ctx->stream));
       if (ctx->upload_stream) R3D_HIP(hipStreamSynchronize(ctx->upload_stream));
-      r3d_inputs_written(ctx, ctx->scratch[slot], ctx->scratch_bytes[slot]);   // the addresses may come back as anything
-      R3D_HIP(hipFree(ctx->scratch[slot]));
-      ctx->scratch[slot] = nullptr;
-      ctx->scratch_bytes[slot] = 0;
+      r3d_inputs_written(ctx, ctx->scratch[which], ctx->scratch_bytes[which]);   // the addresses may come back as anything
+      R3D_HIP(hipFree(ctx->scratch[which]));
+      ctx->scratch[which] = nullptr;
+      ctx->scratch_bytes[which] = 0;
     }
-    R3D_HIP(hipMalloc(&ctx->scratch[slot], bytes));
-    ctx->scratch_bytes[slot] = bytes;
-    if (slot == 6) ctx->select_ws = nullptr;   // fresh memory: the selection's histogram is not known to be zero (r3d_plane.hip)
+    R3D_HIP(hipMalloc(&ctx->scratch[which], bytes));
+    ctx->scratch_bytes[which] = bytes;
+    if (which == kWsSelect) ctx->select_ws = nullptr;   // fresh memory: the selection's histogram is not known to be zero (r3d_plane.hip)
   }
-  *p = ctx->scratch[slot];
+  *p = ctx->scratch[which];
   return R3D_OK;
 }
 
@@ -215,11 +215,6 @@ int r3d_ctx_destroy(r3d_ctx* ctx) {
   if (ctx->upload_stream) (void)hipStreamSynchronize(ctx->upload_stream);
   for (int i = 0; i < r3d_ctx::kScratchSlots; ++i)
     if (ctx->scratch[i]) (void)hipFree(ctx->scratch[i]);
-  if (ctx->reginfo_ws) (void)hipFree(ctx->reginfo_ws);
-  if (ctx->color_rows) (void)hipFree(ctx->color_rows);
-  if (ctx->color_lists) (void)hipFree(ctx->color_lists);
-  if (ctx->mesh_cc_ws) (void)hipFree(ctx->mesh_cc_ws);
-  if (ctx->meshdist_ws) (void)hipFree(ctx->meshdist_ws);
   for (int i = 0; i < r3d_ctx::kPinnedSlots; ++i)
     if (ctx->pinned[i]) (void)hipHostFree(ctx->pinned[i]);
   for (int i = 0; i < 6; ++i)

@@ -22,9 +22,6 @@
 
 #include "r3d_internal.h"
 
-int r3d_match_nearest(r3d_ctx* ctx, const float* d_a, int64_t na, const float* d_b, int64_t nb, uint32_t* d_idx_out, float* d_dist_out,
-                      int slot);
-
 namespace {
 
 constexpr int kThreads = 256;
@@ -253,9 +250,9 @@ __global__ __launch_bounds__(kThreads) void match_fold_kernel(const float* __res
 
 }  // namespace
 
-// idx / dist of the nearest row of b for every row of a (asynchronous); the partial minima go to scratch `slot`
+// idx / dist of the nearest row of b for every row of a (asynchronous); the partial minima go to the workspace `part`
 int r3d_match_nearest(r3d_ctx* ctx, const float* d_a, int64_t na, const float* d_b, int64_t nb, uint32_t* d_idx_out, float* d_dist_out,
-                      int slot) {
+                      r3d_workspace part) {
   const int R = na >= (int64_t)2 * kThreads * 256 ? 2 : 1;   // two rows per lane once that still leaves a block per CU
   const int64_t a_blocks = (na + kThreads * R - 1) / (kThreads * R);
   const int64_t tiles = (nb + kTileRows - 1) / kTileRows;
@@ -264,8 +261,8 @@ int r3d_match_nearest(r3d_ctx* ctx, const float* d_a, int64_t na, const float* d
   const int64_t chunk_rows = chunk_tiles * kTileRows;
   const int chunks = (int)((nb + chunk_rows - 1) / chunk_rows);
   void* ws = nullptr;
-  const size_t half = ((size_t)chunks * na * 4 + 255) & ~(size_t)255;
-  int rc = r3d_scratch(ctx, slot, 2 * half, &ws);
+  const size_t half = r3d_align_up((size_t)chunks * na * 4, 256);
+  int rc = r3d_scratch(ctx, part, 2 * half, &ws);
   if (rc) return rc;
   float* part_d = static_cast<float*>(ws);
   uint32_t* part_j = reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + half);
@@ -301,11 +298,11 @@ int r3d_fpfh_knn(r3d_nn_index* index, int k, double radius, const float* d_norma
     for (int j = i + 1; j < 3; ++j) R3D_REQUIRE(!r3d_ranges_overlap(out[i].p, out[i].bytes, out[j].p, out[j].bytes), "outputs overlap each other");
   }
   if ((rc = r3d_ctx_enter(ctx))) return rc;
-  // slot 0: the lists (idx | d2); slot 1: the 36-byte histogram rows.  The index's own search uses no scratch slot.
-  const size_t list_b = ((size_t)n * k * 4 + 255) & ~(size_t)255;
+  // kWsIn: the lists (idx | d2); kWsOut: the 36-byte histogram rows.  The index's own search takes no workspace.
+  const size_t list_b = r3d_align_up((size_t)n * k * 4, 256);
   void *lists = nullptr, *rows = nullptr;
-  if ((rc = r3d_scratch(ctx, 0, 2 * list_b, &lists))) return rc;
-  if ((rc = r3d_scratch(ctx, 1, (size_t)n * kRowBytes, &rows))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsIn, 2 * list_b, &lists))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsOut, (size_t)n * kRowBytes, &rows))) return rc;
   uint32_t* idx = static_cast<uint32_t*>(lists);
   float* d2l = reinterpret_cast<float*>(static_cast<char*>(lists) + list_b);
   if ((rc = r3d_nn_index_knn_self(index, k, idx, d2l))) return rc;

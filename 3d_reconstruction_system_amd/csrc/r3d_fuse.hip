@@ -785,10 +785,10 @@ int fuse_host_common(r3d_ctx* ctx, const r3d_camera* cam, const void* h_depth, i
   const size_t in_bytes = n * r3d_depth_size(depth_dtype);
   const size_t out_bytes = n * 3 * r3d_xyz_size(out_dtype);
   void *d_in = nullptr, *d_out = nullptr, *d_pose = nullptr;
-  if ((rc = r3d_scratch(ctx, 0, in_bytes, &d_in))) return rc;
-  if ((rc = r3d_scratch(ctx, 1, out_bytes, &d_out))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsIn, in_bytes, &d_in))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsOut, out_bytes, &d_out))) return rc;
   if (with_pose) {
-    if ((rc = r3d_scratch(ctx, 2, (size_t)n_frames * 12 * sizeof(double), &d_pose))) return rc;
+    if ((rc = r3d_scratch(ctx, kWsSpare, (size_t)n_frames * 12 * sizeof(double), &d_pose))) return rc;
     R3D_HIP(hipMemcpyAsync(d_pose, h_pose, (size_t)n_frames * 12 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   }
   // frames stream through the pinned double-buffered pipeline, a few frames per chunk
@@ -817,12 +817,12 @@ int fuse_rgb_host(r3d_ctx* ctx, const r3d_camera* cam, const void* h_depth, int 
   const size_t f_depth = px * r3d_depth_size(depth_dtype), f_rgb = px * 3, f_xyz = px * 3 * r3d_xyz_size(out_dtype),
                f_rgba = px * 4;
   void *d_depth = nullptr, *d_xyz = nullptr, *d_pose = nullptr, *d_rgb = nullptr, *d_rgba = nullptr;
-  if ((rc = r3d_scratch(ctx, 0, n * r3d_depth_size(depth_dtype), &d_depth))) return rc;
-  if ((rc = r3d_scratch(ctx, 1, n * 3 * r3d_xyz_size(out_dtype), &d_xyz))) return rc;
-  if ((rc = r3d_scratch(ctx, 3, n * 3, &d_rgb))) return rc;
-  if ((rc = r3d_scratch(ctx, 4, n * 4, &d_rgba))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsIn, n * r3d_depth_size(depth_dtype), &d_depth))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsOut, n * 3 * r3d_xyz_size(out_dtype), &d_xyz))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsCounts, n * 3, &d_rgb))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsPartials, n * 4, &d_rgba))) return rc;
   if (h_pose) {
-    if ((rc = r3d_scratch(ctx, 2, (size_t)n_frames * 12 * sizeof(double), &d_pose))) return rc;
+    if ((rc = r3d_scratch(ctx, kWsSpare, (size_t)n_frames * 12 * sizeof(double), &d_pose))) return rc;
     R3D_HIP(hipMemcpyAsync(d_pose, h_pose, (size_t)n_frames * 12 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   }
   const r3d_pipe_buf ins[2] = {{const_cast<void*>(h_depth), d_depth, f_depth}, {const_cast<unsigned char*>(h_rgb), d_rgb, f_rgb}};

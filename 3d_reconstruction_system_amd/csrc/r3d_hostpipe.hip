@@ -46,7 +46,7 @@ struct LazyCrew {
     // a member's share: ceil(bytes / n) rounded up to a page.  (Until round 4 this was floor(bytes / n) rounded up, which
     // leaves up to n - 1 bytes at the end uncopied whenever bytes / n is itself a whole number of pages and bytes is not
     // a multiple of n: e.g. 65536 k + 12 bytes over 16 threads.  tests/test_gpu_fusion.py pins such sizes now.)
-    const size_t per = (((bytes + n - 1) / n) + 4095) & ~(size_t)4095;
+    const size_t per = r3d_align_up((bytes + n - 1) / n, 4096);
     crew->run([=](unsigned t) {
       const size_t lo = (size_t)t * per;
       if (lo < bytes) memcpy(static_cast<char*>(dst) + lo, static_cast<const char*>(src) + lo, std::min(per, bytes - lo));

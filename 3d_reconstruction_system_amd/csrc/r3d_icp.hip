@@ -246,7 +246,7 @@ int r3d_icp_nn(r3d_ctx* ctx, const float* d_src, int64_t n_src, const float* d_t
   float* k_d2 = d_d2_out;
   if (n_seg > 1) {
     void* part = nullptr;
-    if ((rc = r3d_scratch(ctx, 5, (size_t)n_seg * n_src * 8, &part))) return rc;
+    if ((rc = r3d_scratch(ctx, kWsMisc, (size_t)n_seg * n_src * 8, &part))) return rc;
     k_idx = static_cast<uint32_t*>(part);
     k_d2 = reinterpret_cast<float*>(k_idx + (size_t)n_seg * n_src);
   }
@@ -281,10 +281,10 @@ int r3d_icp_nn_host(r3d_ctx* ctx, const float* h_src, int64_t n_src, const float
   R3D_REQUIRE(n_tgt >= 1, "target cloud is empty");
   R3D_REQUIRE(h_src && h_tgt && h_idx_out, "NULL host pointer");
   void *d_src = nullptr, *d_tgt = nullptr, *d_idx = nullptr, *d_d2 = nullptr;
-  if ((rc = r3d_scratch(ctx, 0, (size_t)n_src * 12, &d_src))) return rc;
-  if ((rc = r3d_scratch(ctx, 1, (size_t)n_tgt * 12, &d_tgt))) return rc;
-  if ((rc = r3d_scratch(ctx, 2, (size_t)n_src * 4, &d_idx))) return rc;
-  if ((rc = r3d_scratch(ctx, 3, (size_t)n_src * 4, &d_d2))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsIn, (size_t)n_src * 12, &d_src))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsOut, (size_t)n_tgt * 12, &d_tgt))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsSpare, (size_t)n_src * 4, &d_idx))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsCounts, (size_t)n_src * 4, &d_d2))) return rc;
   R3D_HIP(hipMemcpyAsync(d_src, h_src, (size_t)n_src * 12, hipMemcpyHostToDevice, ctx->stream));
   R3D_HIP(hipMemcpyAsync(d_tgt, h_tgt, (size_t)n_tgt * 12, hipMemcpyHostToDevice, ctx->stream));
   if ((rc = r3d_icp_nn(ctx, (const float*)d_src, n_src, (const float*)d_tgt, n_tgt, (uint32_t*)d_idx, (float*)d_d2)))
@@ -314,7 +314,7 @@ static int accumulate_impl(r3d_ctx* ctx, const float* d_src, int64_t n_src, cons
   int blocks = (int)((n_src + kThreads - 1) / kThreads);
   if (blocks > ctx->num_cus * 4) blocks = ctx->num_cus * 4;
   void* d_part_v = nullptr;
-  if ((rc = r3d_scratch(ctx, 4, ((size_t)blocks + 1) * kSums * sizeof(double), &d_part_v))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsPartials, ((size_t)blocks + 1) * kSums * sizeof(double), &d_part_v))) return rc;
   double* d_part = static_cast<double*>(d_part_v);
   hipLaunchKernelGGL(accumulate_kernel, dim3(blocks), dim3(kThreads), 0, ctx->stream, d_src, n_src, d_tgt, n_tgt, d_idx,
                      (gated || dead_zone > 0.f) ? d_d2 : nullptr, gated ? max_d2 : -1.f, dead_zone, d_part);
@@ -337,7 +337,7 @@ int r3d_icp_accumulate(r3d_ctx* ctx, const float* d_src, int64_t n_src, const fl
   R3D_REQUIRE(n_src >= 0 && n_tgt >= 0, "negative cloud size");
   if (n_src == 0) return R3D_OK;
   void* d_sums = nullptr;
-  if ((rc = r3d_scratch(ctx, 3, kSums * sizeof(double), &d_sums))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsCounts, kSums * sizeof(double), &d_sums))) return rc;
   if ((rc = r3d_icp_accumulate_dev(ctx, d_src, n_src, d_tgt, n_tgt, d_idx, d_d2, max_d2, 0.f, (double*)d_sums)))
     return rc;
   R3D_HIP(hipMemcpyAsync(h_sums, d_sums, kSums * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -383,7 +383,7 @@ int r3d_icp_iterate(r3d_ctx* ctx, r3d_nn_index* index, float* d_src, int64_t n_s
   R3D_REQUIRE(d_src && d_idx && d_d2 && d_state, "NULL device pointer");
   R3D_REQUIRE(index != nullptr || d_tgt != nullptr, "need an index or a target cloud");
   void* d_sums_v = nullptr;
-  if ((rc = r3d_scratch(ctx, 3, kSums * sizeof(double), &d_sums_v))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsCounts, kSums * sizeof(double), &d_sums_v))) return rc;
   double* d_sums = static_cast<double*>(d_sums_v);
   const bool going_on = r3d_icp_loop_going_on(ctx, index, d_state, d_src, d_idx);
   for (int it = 0; it < n_iters; ++it) {

@@ -13,6 +13,58 @@
 #include "r3d.h"
 #include "r3d_internal_api.h"
 
+// The context's grow-only device workspaces (r3d_ctx::scratch), claimed by name through r3d_scratch.  A SHARED entry is taken by
+// many entry points one after the other in stream order; nobody may expect to find in it what an earlier call left (tests/
+// test_gpu_call_order.py), and a helper takes one only if no caller above it holds data there.  A PRIVATE entry is one file's.
+//   kWsIn          shared   staged input of the *_host calls (fuse, apply, ICP source, voxel and grid points); TSDF slabs; NN sort
+//                           keys; FPFH k-NN lists; r3d_register_ransac's gathered pairs; octree records; the voxel union's list
+//   kWsOut         shared   staged output of the *_host calls (ICP: the target); the sorted voxel codes; NN query `src4` / sorted
+//                           copy; SOR scores; FPFH rows; merge remainders
+//   kWsSpare       shared   the radix sort's `tmp` where the caller has none (NN, voxel codes, r3d_sort_u64); fuse pose tables;
+//                           octree meta; merge segments; host ICP idx; feature match's b -> a partial minima
+//   kWsCounts      shared   the histogram of EVERY radix sort (r3d_radix_sort_workspace; the private files sort too); compaction
+//                           Counters of knn, tsdf, tsdf_mesh; octree tile places; host ICP d2 and sums; fuse rgb; feature match's
+//                           b -> a rows; the voxel union's counts
+//   kWsPartials    shared   partial rows of the sums passes (ICP, NN query + solve, tracking, SOR); NN bound rows; consensus
+//                           partials; r3d_apply_T_many's table; grad_P partials; fuse rgba; grid colours; a -> b partial minima
+//   kWsMisc        shared   what the host reads back: NN and knn `misc`, consensus misc | hyp | rows | counts, feature match's keep
+//                           counts, the voxel set's 64 bytes; viewpoint table; textfmt, sort-merge and brute-force ICP workspaces
+//   kWsSelect      shared   r3d_plane.hip alone: selection histogram + state, plane sums rows.  r3d_ctx::select_ws records that the
+//                           histogram is all zero; r3d_scratch forgets that when it reallocates the entry
+//   kWsTrack       shared   r3d_track.hip's maps + ICP state; r3d_plane.hip's rank-trimming residuals (never inside one call)
+//   kWsBilateral   private  r3d_bilateral.hip: the weight tables, keyed by r3d_ctx::bilateral_*; the contents outlive the call
+//   kWsRegSums     private  r3d_reginfo.hip: partial rows + 11 sums, always asked for at the largest size (never regrows)
+//   kWsColorRows   private  r3d_color_icp.hip: partial rows + 31 sums, always asked for at the largest size (never regrows)
+//   kWsColorLists  private  r3d_color_icp.hip: the k-NN lists (idx | d2) of r3d_color_gradient_knn
+//   kWsMeshCc      private  r3d_mesh_cc.hip: per-label counters, vertex flags, tile counters
+//   kWsMeshDist    private  r3d_meshdist.hip: sort keys + spare of an index build or query; r3d_distance_stats' partial rows
+// Hand-over rules between nested claims:
+//   * a sort holds kWsCounts (r3d_sort_u64 also kWsSpare) until its last pass is enqueued: its callers keep nothing of theirs
+//     there across it (the voxel code list lives in kWsOut, the NN keys in kWsIn);
+//   * r3d_voxelset_sorted_codes_device returns with the codes in kWsOut and kWsSpare / kWsCounts released: r3d_octree.hip takes
+//     those two for meta and tile places and kWsIn for the records, in stream order behind the sort;
+//   * r3d_consensus::layout takes kWsMisc and kWsPartials whole: r3d_register_ransac keeps its pairs in kWsIn, and feature
+//     matching (keep counts in kWsMisc, partial minima where r3d_match_nearest is told: kWsPartials, kWsSpare) runs no consensus;
+//   * growing frees the old block once both streams are idle: no pointer into an entry survives a larger r3d_scratch of it, so
+//     a loop reserves its largest size up front (r3d_track.hip's rows).
+enum r3d_workspace : int {
+  kWsIn = 0,
+  kWsOut,
+  kWsSpare,
+  kWsCounts,
+  kWsPartials,
+  kWsMisc,
+  kWsSelect,
+  kWsTrack,
+  kWsBilateral,
+  kWsRegSums,
+  kWsColorRows,
+  kWsColorLists,
+  kWsMeshCc,
+  kWsMeshDist,
+  kWsEnd
+};
+
 struct r3d_ctx {
   int device = -1;
   hipStream_t stream = nullptr;
@@ -56,32 +108,14 @@ struct r3d_ctx {
                           // flush barrier inside its `if` (A/B against DESIGN 4.5b's finding only)
   // HIP-event stopwatch
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-  // grow-only scratch buffers for the *_host entry points and reductions
-  static constexpr int kScratchSlots = 9;   // 6, 7: point-to-plane / selection workspace (r3d_plane.hip); 8: the bilateral
-                                            // filter's weight tables (r3d_bilateral.hip), which no other call may touch
+  // the grow-only device workspaces, one per r3d_workspace entry (the table above); r3d_scratch is their only allocator
+  static constexpr int kScratchSlots = 14;
   void* scratch[kScratchSlots] = {};
   size_t scratch_bytes[kScratchSlots] = {};
-  // the (radius, sigma_s, sigma_r) whose tables sit in slot 8: a repeated r3d_depth_bilateral uploads nothing.  radius -1 =
+  // the (radius, sigma_s, sigma_r) whose tables sit in kWsBilateral: a repeated r3d_depth_bilateral uploads nothing.  radius -1 =
   // none; the call validates its arguments before it compares them with this key, so no call matches the empty key
   int bilateral_radius = -1;
   double bilateral_sigma_s = 0, bilateral_sigma_r = 0;
-  // r3d_registration_sums' own workspace (r3d_reginfo.hip): partial rows + the 11 sums, made once at its largest size and read
-  // and written by that synchronous call alone -- not one of the shared slots above
-  void* reginfo_ws = nullptr;
-  // coloured ICP's own workspaces (r3d_color_icp.hip), not shared slots either: the partial rows + the 31 sums of its sums pass,
-  // made once at their largest size, and the grow-only k-NN lists its gradient kernel reads; only its three entry points touch
-  // them, in stream order
-  void* color_rows = nullptr;
-  void* color_lists = nullptr;
-  size_t color_lists_bytes = 0;
-  // the mesh component calls' own workspace (r3d_mesh_cc.hip), not a shared slot either: per-label counters, vertex flags and tile
-  // counters, grown on demand; only r3d_mesh_components and r3d_mesh_filter_components touch it, and both are synchronous
-  void* mesh_cc_ws = nullptr;
-  size_t mesh_cc_ws_bytes = 0;
-  // the evaluation calls' own workspace (r3d_meshdist.hip), not a shared slot either: the sort keys of a mesh index build or query
-  // and the partial rows of r3d_distance_stats, grown on demand; only those calls touch it, in stream order
-  void* meshdist_ws = nullptr;
-  size_t meshdist_ws_bytes = 0;
   // pinned staging buffers of the host pipeline: slot = ((direction * kPipeBufs + array) * 2 + parity)
   static constexpr int kPipeBufs = 2;   // arrays per direction (depth + colour in, xyz + rgba out)
   static constexpr int kPinnedSlots = 2 * kPipeBufs * 2;
@@ -90,6 +124,7 @@ struct r3d_ctx {
   hipEvent_t ev_pipe[6] = {};           // host pipeline: done[2], uploaded[2], entry, spare
   hipStream_t upload_stream = nullptr;  // H2D side of the host pipeline (full-duplex PCIe)
 };
+static_assert(kWsEnd == r3d_ctx::kScratchSlots, "one r3d_ctx::scratch entry per r3d_workspace");
 
 struct r3d_voxelset {   // r3d_voxel.hip; its fields are also read by the sort-merge insert (r3d_voxel_merge.hip)
   r3d_ctx* ctx = nullptr;
@@ -151,8 +186,11 @@ int r3d_inputs_tracked(r3d_ctx* ctx);
 // matches that describe other points).  Results never depend on either record; speed does.
 void r3d_wrote(r3d_ctx* ctx, const void* p, size_t bytes);
 
-// grow-only scratch slot (device memory); returns device pointer in *p
-int r3d_scratch(r3d_ctx* ctx, int slot, size_t bytes, void** p);
+// The one allocator of the context's workspaces (device memory, grow-only): *p = at least `bytes` bytes (16 for 0) of `which`.
+// Growing waits for both streams, drops the old range from the residency record and frees it; the contents are not kept.
+int r3d_scratch(r3d_ctx* ctx, r3d_workspace which, size_t bytes, void** p);
+// bytes rounded up to a multiple of `a`, a power of two
+constexpr size_t r3d_align_up(size_t bytes, size_t a) { return (bytes + a - 1) & ~(a - 1); }
 
 // Chunked, double-buffered host<->device pipeline (r3d_hostpipe.hip).  Items [lo, lo+n) of the batch are uploaded
 // to d_in + lo*in_item_bytes, `launch(lo, n)` enqueues the kernel for them, and d_out + lo*out_item_bytes comes back.
@@ -177,12 +215,12 @@ bool r3d_voxelset_sort_feasible(const r3d_voxelset* vs, int64_t n_points, bool f
 __attribute__((visibility("hidden"))) int r3d_voxelset_insert_sorted(r3d_voxelset* vs, const float* d_xyz, int64_t n_points);
 int r3d_voxelset_sample(r3d_voxelset* vs, const float* d_xyz, int64_t n_points, int64_t n_insert, double cas_base_ps, bool* sort_out);
 int r3d_voxelset_insert_path(r3d_voxelset* vs, const float* d_xyz, int64_t n_points, int path);
-// A table of packed keys (kEmpty = free) holding `n` keys -> their ascending Morton codes in scratch slot 1 (slot 2 is the sort's
+// A table of packed keys (kEmpty = free) holding `n` keys -> their ascending Morton codes in kWsOut (kWsSpare is the sort's
 // spare, d_counters[3] the compaction cursor); asynchronous.  Shared by the voxel set and the voxel grid (r3d_voxelgrid.hip).
 int r3d_voxel_table_sorted_codes(r3d_ctx* ctx, const uint64_t* d_table, uint64_t capacity, unsigned long long* d_counters,
                                  int64_t n, uint64_t** d_list_out);
 
-// The set's distinct voxels as ascending Morton codes in HBM (scratch slot 1 of its context, which is entered; slots 2 and 3 are
+// The set's distinct voxels as ascending Morton codes in HBM (kWsOut of its context, which is entered; kWsSpare and kWsCounts are
 // free again when this returns); an overflowed set -> R3D_ERR_NOMEM as r3d_voxelset_codes reports it.  For r3d_octree.hip.
 int r3d_voxelset_sorted_codes_device(r3d_voxelset* vs, r3d_ctx** ctx, double* resolution, uint64_t** d_list_out, int64_t* n_out);
 
@@ -197,6 +235,10 @@ int r3d_radix_sort_workspace(r3d_ctx* ctx, int64_t n, uint32_t** hist_out, int* 
 constexpr int r3d_sort_stride(int n_blocks) { return (n_blocks + 7) & ~7; }   // counters per histogram row (32-byte aligned rows)
 // hist[bin][tile] (n_bins rows of `stride` counters) -> exclusive prefixes over the tiles, in place; totals[bin] = the bin's count
 void r3d_sort_launch_scan(r3d_ctx* ctx, uint32_t* hist, int n_blocks, int stride, uint32_t* totals, int n_bins = 256);
+
+// r3d_fpfh.hip: idx / dist of the nearest 33-float row of b for every row of a; the partial minima go to the workspace `part`
+int r3d_match_nearest(r3d_ctx* ctx, const float* d_a, int64_t na, const float* d_b, int64_t nb, uint32_t* d_idx_out, float* d_dist_out,
+                      r3d_workspace part);
 
 // r3d_nnindex.hip: the index's own copy of the target cloud (original order), its size and its context
 int r3d_nn_index_target(r3d_nn_index* index, const float** d_tgt, int64_t* n_tgt, r3d_ctx** ctx);

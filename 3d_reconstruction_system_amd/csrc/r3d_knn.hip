@@ -534,7 +534,7 @@ int r3d_normals_knn(r3d_nn_index* ix, int k, double radius, const double* h_view
   if (n_views > 0) {
     // at most a few thousand rows of 24 bytes: one upload per call into the library's own buffer
     void* views = nullptr;
-    if ((rc = r3d_scratch(ctx, 5, (size_t)n_views * 24, &views))) return rc;
+    if ((rc = r3d_scratch(ctx, kWsMisc, (size_t)n_views * 24, &views))) return rc;
     R3D_HIP(hipMemcpyAsync(views, h_viewpoints, (size_t)n_views * 24, hipMemcpyHostToDevice, ctx->stream));
     a.views = static_cast<const double*>(views);
     a.n_views = divide ? (uint32_t)std::min<int64_t>(n_views, n) : 1u;
@@ -565,9 +565,9 @@ int r3d_outlier_statistical(r3d_nn_index* ix, int k, double std_ratio, uint8_t* 
   if (rc) return rc;
   const int blocks = (int)(ix->n_tiles * (kTile / kThreads)), rblocks = reduce_blocks(n);
   void *score = d_score_out, *rows = nullptr, *misc = nullptr;
-  if (!score && (rc = r3d_scratch(ctx, 1, (size_t)n * 8, &score))) return rc;
-  if ((rc = r3d_scratch(ctx, 4, (size_t)(2 * blocks + rblocks) * sizeof(double), &rows))) return rc;
-  if ((rc = r3d_scratch(ctx, 5, 64, &misc))) return rc;
+  if (!score && (rc = r3d_scratch(ctx, kWsOut, (size_t)n * 8, &score))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsPartials, (size_t)(2 * blocks + rblocks) * sizeof(double), &rows))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsMisc, 64, &misc))) return rc;
   double* stats = static_cast<double*>(misc);                                          // V, mu, sigma, T
   unsigned long long* kept = reinterpret_cast<unsigned long long*>(stats + 4);
   double* rows1 = static_cast<double*>(rows);
@@ -611,7 +611,7 @@ int r3d_outlier_radius(r3d_nn_index* ix, double radius, int64_t min_points, uint
   int rc = r3d_ctx_enter(ctx);
   if (rc) return rc;
   void* misc = nullptr;
-  if ((rc = r3d_scratch(ctx, 5, 64, &misc))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsMisc, 64, &misc))) return rc;
   unsigned long long* kept = static_cast<unsigned long long*>(misc);
   r3d_wrote(ctx, d_keep_out, (size_t)n);
   if (d_count_out) r3d_wrote(ctx, d_count_out, (size_t)n * 4);
@@ -648,7 +648,7 @@ int r3d_select_rows(r3d_ctx* ctx, const float* d_xyz, int64_t n, const uint8_t* 
   const int tiles = r3d_compact::tiles_of(n);
   r3d_compact::Counters cn(tiles, 1);
   void* ws = nullptr;
-  if ((rc = r3d_scratch(ctx, 3, cn.bytes, &ws))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsCounts, cn.bytes, &ws))) return rc;
   cn.place(ws);
   hipStream_t st = ctx->stream;
   hipLaunchKernelGGL(select_count_kernel, dim3(tiles), dim3(kThreads), 0, st, d_keep, n, cn.hist);

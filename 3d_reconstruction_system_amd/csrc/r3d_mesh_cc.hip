@@ -14,7 +14,7 @@
 //   cc_rows_*          components = roots with a triangle, compacted in ascending label (r3d_compact_dev.h)
 // r3d_mesh_filter_components -- recounts per label, picks the largest with one 64-bit atomicMax per root, marks the vertices of the
 //   kept triangles, and compacts vertices and triangles in order by the same step, both rows of counters in one scan (no cursor).
-// Workspace: owned by the context (r3d_ctx::mesh_cc_ws), grown on demand, touched by these two synchronous calls alone.
+// Workspace: kWsMeshCc of the context, grown on demand, touched by these two synchronous calls alone.
 #include "r3d_compact_dev.h"
 #include "r3d_internal.h"
 #include "r3d_unionfind_dev.h"
@@ -221,20 +221,6 @@ __global__ __launch_bounds__(kThreads) void cc_tri_write_kernel(const int32_t* _
 }
 
 inline unsigned blocks_of(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
-inline size_t align64(size_t b) { return (b + 63) & ~(size_t)63; }
-
-// the context's own workspace, grown on demand (hipFree waits for the device: no launch still uses the old one)
-int workspace(r3d_ctx* ctx, size_t bytes, char** p) {
-  if (ctx->mesh_cc_ws_bytes < bytes) {
-    if (ctx->mesh_cc_ws) R3D_HIP(hipFree(ctx->mesh_cc_ws));
-    ctx->mesh_cc_ws = nullptr;
-    ctx->mesh_cc_ws_bytes = 0;
-    R3D_HIP(hipMalloc(&ctx->mesh_cc_ws, bytes));
-    ctx->mesh_cc_ws_bytes = bytes;
-  }
-  *p = static_cast<char*>(ctx->mesh_cc_ws);
-  return R3D_OK;
-}
 
 // what both calls check of the mesh itself, before anything else; the size limit (check_size) comes after every R3D_ERR_INVALID
 int check_mesh(const r3d_ctx* ctx, const int32_t* d_tri, int64_t n_triangles, int64_t n_vertices) {
@@ -282,9 +268,10 @@ int r3d_mesh_components(r3d_ctx* ctx, const int32_t* d_tri, int64_t n_triangles,
   // workspace: cnt_v [nv] | cnt_t [nv] | the tile counters (64-byte aligned) | {n_components, n_invalid}
   const int tiles = tiles_of(nv);
   Counters cn(tiles, 1);
-  const size_t hist_at = align64((size_t)nv * 8), ws_bytes = hist_at + cn.bytes;
-  char* ws = nullptr;
-  if ((rc = workspace(ctx, ws_bytes, &ws))) return rc;
+  const size_t hist_at = r3d_align_up((size_t)nv * 8, 64), ws_bytes = hist_at + cn.bytes;
+  void* ws_v = nullptr;
+  if ((rc = r3d_scratch(ctx, kWsMeshCc, ws_bytes, &ws_v))) return rc;
+  char* ws = static_cast<char*>(ws_v);
   uint32_t* cnt_v = reinterpret_cast<uint32_t*>(ws);
   uint32_t* cnt_t = cnt_v + nv;
   cn.place(ws + hist_at);
@@ -343,9 +330,10 @@ int r3d_mesh_filter_components(r3d_ctx* ctx, const int32_t* d_tri, int64_t n_tri
   // workspace: cnt_t [nv] | vflag [nv] | the tile counters (64-byte aligned; row 0 vertices, row 1 triangles) | totals [2] | best u64
   const int tiles_v = tiles_of(nv), tiles_t = tiles_of(nt);
   Counters cn(tiles_v > tiles_t ? tiles_v : tiles_t, 2);
-  const size_t hist_at = align64((size_t)nv * 8), ws_bytes = hist_at + cn.bytes;
-  char* ws = nullptr;
-  if ((rc = workspace(ctx, ws_bytes, &ws))) return rc;
+  const size_t hist_at = r3d_align_up((size_t)nv * 8, 64), ws_bytes = hist_at + cn.bytes;
+  void* ws_v = nullptr;
+  if ((rc = r3d_scratch(ctx, kWsMeshCc, ws_bytes, &ws_v))) return rc;
+  char* ws = static_cast<char*>(ws_v);
   uint32_t* cnt_t = reinterpret_cast<uint32_t*>(ws);
   uint32_t* vflag = cnt_t + nv;
   cn.place(ws + hist_at);

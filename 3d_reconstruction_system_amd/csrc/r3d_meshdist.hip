@@ -479,19 +479,6 @@ __global__ __launch_bounds__(kThreads) void colors_kernel(const float* __restric
   out[i] = r | (g << 8) | (b << 16);
 }
 
-// the context's own workspace for these calls, grown on demand (hipFree waits for the device: no launch still uses the old one)
-int workspace(r3d_ctx* ctx, size_t bytes, void** p) {
-  if (ctx->meshdist_ws_bytes < bytes) {
-    if (ctx->meshdist_ws) R3D_HIP(hipFree(ctx->meshdist_ws));
-    ctx->meshdist_ws = nullptr;
-    ctx->meshdist_ws_bytes = 0;
-    R3D_HIP(hipMalloc(&ctx->meshdist_ws, bytes));
-    ctx->meshdist_ws_bytes = bytes;
-  }
-  *p = ctx->meshdist_ws;
-  return R3D_OK;
-}
-
 int too_large(const char* what, int64_t a, int64_t b) {
   if (a > (int64_t)INT32_MAX || b > (int64_t)INT32_MAX) {
     r3d_set_error("%s take at most 2^31 - 1 items (got %lld and %lld)", what, (long long)a, (long long)b);
@@ -536,7 +523,7 @@ int r3d_mesh_index_create(r3d_ctx* ctx, const float* d_xyz, int64_t n_vertices, 
   size_t off = 0;
   auto take = [&off](size_t bytes) {
     const size_t at = off;
-    off += (bytes + 255) & ~(size_t)255;
+    off += r3d_align_up(bytes, 256);
     return at;
   };
   const size_t o_tri = take((size_t)max_groups * kGroup * kTriFloats * sizeof(float)), o_box = take((size_t)max_groups * 6 * sizeof(float)),
@@ -564,7 +551,7 @@ int r3d_mesh_index_create(r3d_ctx* ctx, const float* d_xyz, int64_t n_vertices, 
     const uint32_t nv = (uint32_t)n_vertices;
     const int idx_bits = bits_for(nt);
     void *keys = nullptr, *tmp = nullptr;
-    if ((rc = workspace(ctx, (size_t)nt * 16, &keys))) return fail(rc);
+    if ((rc = r3d_scratch(ctx, kWsMeshDist, (size_t)nt * 16, &keys))) return fail(rc);
     tmp = static_cast<uint64_t*>(keys) + nt;
     hipLaunchKernelGGL(md_bbox_kernel, dim3(blocks_of(nt)), dim3(kThreads), 0, st, d_xyz, nv, d_tri, nt, ix->d_bounds, ix->d_counters);
     hipLaunchKernelGGL(md_frame_kernel, dim3(1), dim3(64), 0, st, (const uint32_t*)ix->d_bounds, ix->d_frame);
@@ -613,7 +600,7 @@ int r3d_mesh_index_query(r3d_mesh_index* ix, const float* d_points, int64_t n_po
   if (n > 0) {
     const int idx_bits = bits_for(n);
     void *keys = nullptr, *tmp = nullptr;
-    if ((rc = workspace(ctx, (size_t)n * 16, &keys))) return rc;
+    if ((rc = r3d_scratch(ctx, kWsMeshDist, (size_t)n * 16, &keys))) return rc;
     tmp = static_cast<uint64_t*>(keys) + n;
     hipLaunchKernelGGL(md_point_keys_kernel, dim3(blocks_of(n)), dim3(kThreads), 0, st, d_points, n, (const float*)ix->d_frame, idx_bits,
                        (uint64_t*)keys);
@@ -670,7 +657,7 @@ int r3d_distance_stats(r3d_ctx* ctx, const float* d_values, int64_t n, int squar
     const int n_counts = kMaxThresholds + n_bins;
     const size_t b_sums = (size_t)n_rows * 32, b_mm = (size_t)n_rows * 16, b_out = 64, b_counts = (size_t)n_counts * 8;
     void* ws = nullptr;
-    if ((rc = workspace(ctx, b_sums + b_mm + b_out + b_counts, &ws))) return rc;
+    if ((rc = r3d_scratch(ctx, kWsMeshDist, b_sums + b_mm + b_out + b_counts, &ws))) return rc;
     double* part_sums = static_cast<double*>(ws);
     double* part_mm = part_sums + n_rows * 4;
     double* out = part_mm + n_rows * 2;

@@ -747,13 +747,13 @@ static int nn_index_build(r3d_nn_index* ix, const float* d_tgt, int64_t n_tgt) {
   const int64_t n_pad = ix->n_tiles * kTile;
   int rc;
   void *keys = nullptr, *tmp = nullptr;
-  if ((rc = r3d_scratch(ctx, 0, (size_t)n_tgt * 8, &keys)) || (rc = r3d_scratch(ctx, 2, (size_t)n_tgt * 8, &tmp))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsIn, (size_t)n_tgt * 8, &keys)) || (rc = r3d_scratch(ctx, kWsSpare, (size_t)n_tgt * 8, &tmp))) return rc;
   hipStream_t st = ctx->stream;
   if (d_tgt != ix->d_tgt) R3D_HIP(hipMemcpyAsync(ix->d_tgt, d_tgt, (size_t)n_tgt * 12, hipMemcpyDeviceToDevice, st));
-  // 4 points per thread in flight; the rows of bounds go to a scratch slot
+  // 4 points per thread in flight; the rows of bounds go to kWsPartials
   const int blocks = (int)std::min<int64_t>((n_tgt + 4 * kThreads - 1) / (4 * kThreads), (int64_t)ctx->num_cus * 2);
   void* rows = nullptr;
-  if ((rc = r3d_scratch(ctx, 4, (size_t)blocks * 6 * sizeof(float), &rows))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsPartials, (size_t)blocks * 6 * sizeof(float), &rows))) return rc;
   hipLaunchKernelGGL(bbox_kernel, dim3(blocks), dim3(kThreads), 0, st, ix->d_tgt, n_tgt, (float*)rows);
   hipLaunchKernelGGL(frame_kernel, dim3(1), dim3(64), 0, st, (const float*)rows, blocks, ix->axis_bits, ix->d_frame);
   if ((rc = sorted_keys(ctx, ix->d_tgt, n_tgt, ix->d_frame, ix->axis_bits, ix->idx_bits, (uint64_t*)keys, (uint64_t*)tmp))) return rc;
@@ -792,7 +792,7 @@ int r3d_nn_index_create(r3d_ctx* ctx, const float* d_tgt, int64_t n_tgt, r3d_nn_
   size_t off = 0;
   auto take = [&off](size_t bytes) {
     const size_t at = off;
-    off += (bytes + 255) & ~(size_t)255;
+    off += r3d_align_up(bytes, 256);
     return at;
   };
   const size_t o_tgt4 = take((size_t)n_pad * sizeof(float4)), o_tgt = take((size_t)n_tgt * 12),
@@ -859,14 +859,14 @@ static int nn_index_query_impl(r3d_nn_index* ix, const float* d_src, int64_t n_s
     // one-off query: sort a float4 copy of the sources into index order (results are scattered back by index)
     const int src_idx_bits = bits_for(n_src);
     void *keys = nullptr, *tmp = nullptr;
-    if ((rc = r3d_scratch(ctx, 0, (size_t)n_src * 8, &keys))) return rc;
-    if ((rc = r3d_scratch(ctx, 2, (size_t)n_src * 8, &tmp))) return rc;
-    if ((rc = r3d_scratch(ctx, 1, (size_t)n_src * sizeof(float4), &src4))) return rc;
+    if ((rc = r3d_scratch(ctx, kWsIn, (size_t)n_src * 8, &keys))) return rc;
+    if ((rc = r3d_scratch(ctx, kWsSpare, (size_t)n_src * 8, &tmp))) return rc;
+    if ((rc = r3d_scratch(ctx, kWsOut, (size_t)n_src * sizeof(float4), &src4))) return rc;
     if ((rc = sorted_keys(ctx, d_src, n_src, ix->d_frame, ix->axis_bits, src_idx_bits, (uint64_t*)keys, (uint64_t*)tmp))) return rc;
     hipLaunchKernelGGL(gather4_kernel, dim3((unsigned)((n_src + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, d_src,
                        (const uint64_t*)keys, n_src, n_src, src_idx_bits, (float4*)src4);
   }
-  if ((rc = r3d_scratch(ctx, 5, 64, &misc))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsMisc, 64, &misc))) return rc;
   unsigned long long* stats = static_cast<unsigned long long*>(misc);  // [0] tile sweeps, [1] groups evaluated
   if (h_tiles_swept) R3D_HIP(hipMemsetAsync(misc, 0, 32, st));
   int S = ctx->nn_variant;
@@ -877,7 +877,7 @@ static int nn_index_query_impl(r3d_nn_index* ix, const float* d_src, int64_t n_s
   int n_rows = (int)blocks;
   if (want_sums) {
     void* pv = nullptr;
-    if ((rc = r3d_scratch(ctx, 4, (size_t)blocks * r3d_icp::kSums * sizeof(double), &pv))) return rc;
+    if ((rc = r3d_scratch(ctx, kWsPartials, (size_t)blocks * r3d_icp::kSums * sizeof(double), &pv))) return rc;
     partials = static_cast<double*>(pv);
   }
   // same sources buffer, same count, same output buffer as the last presorted query against this build of the index: the
@@ -903,7 +903,7 @@ static int nn_index_query_impl(r3d_nn_index* ix, const float* d_src, int64_t n_s
     const unsigned wblocks = (unsigned)((n_src + kThreads - 1) / kThreads);
     if (want_sums) {
       void* pv = nullptr;
-      if ((rc = r3d_scratch(ctx, 4, (size_t)wblocks * r3d_icp::kSums * sizeof(double), &pv))) return rc;
+      if ((rc = r3d_scratch(ctx, kWsPartials, (size_t)wblocks * r3d_icp::kSums * sizeof(double), &pv))) return rc;
       partials = static_cast<double*>(pv);
     }
     hipLaunchKernelGGL(nn_warm_kernel, dim3(wblocks), dim3(kThreads), 0, st, d_src, n_src, ix->d_tgt4, ix->n, ix->n_tiles,
@@ -1006,11 +1006,11 @@ static int sort_cloud_impl(r3d_nn_index* ix, float* d_xyz, int64_t n, uint32_t* 
   r3d_wrote(ctx, d_xyz, (size_t)n * 12);   // reordered in place
   const int idx_bits = bits_for(n);
   void *keys = nullptr, *tmp = nullptr, *copy = nullptr, *misc = nullptr;
-  if ((rc = r3d_scratch(ctx, 0, (size_t)n * 8, &keys))) return rc;
-  if ((rc = r3d_scratch(ctx, 2, (size_t)n * 8, &tmp))) return rc;
-  if ((rc = r3d_scratch(ctx, 1, (size_t)n * 12, &copy))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsIn, (size_t)n * 8, &keys))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsSpare, (size_t)n * 8, &tmp))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsOut, (size_t)n * 12, &copy))) return rc;
   if (h_n_valid) {
-    if ((rc = r3d_scratch(ctx, 5, 64, &misc))) return rc;
+    if ((rc = r3d_scratch(ctx, kWsMisc, 64, &misc))) return rc;
     R3D_HIP(hipMemsetAsync(misc, 0, 8, ctx->stream));
     hipLaunchKernelGGL(keys_valid_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, ctx->stream,
                        (const float*)d_xyz, n, (const float*)ix->d_frame, ix->axis_bits, idx_bits, (uint64_t*)keys,

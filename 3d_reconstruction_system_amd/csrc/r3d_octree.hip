@@ -270,9 +270,9 @@ int octree_sizes(r3d_ctx* ctx, const uint64_t* d_codes, int64_t n, Workspace& w,
   int rc;
   void *a = nullptr, *b = nullptr;
   w.tiles = (n + kOctreeTile - 1) / kOctreeTile;
-  const size_t meta_bytes = ((size_t)n + 15) & ~(size_t)15;
-  if ((rc = r3d_scratch(ctx, 2, meta_bytes + (size_t)n * 2, &a))) return rc;
-  if ((rc = r3d_scratch(ctx, 3, 64 + (size_t)w.tiles * 16, &b))) return rc;
+  const size_t meta_bytes = r3d_align_up((size_t)n, 16);
+  if ((rc = r3d_scratch(ctx, kWsSpare, meta_bytes + (size_t)n * 2, &a))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsCounts, 64 + (size_t)w.tiles * 16, &b))) return rc;
   w.meta = static_cast<uint8_t*>(a);
   w.pre = reinterpret_cast<uint16_t*>(w.meta + meta_bytes);
   w.flags = static_cast<unsigned long long*>(b);
@@ -299,10 +299,10 @@ int octree_sizes(r3d_ctx* ctx, const uint64_t* d_codes, int64_t n, Workspace& w,
   return R3D_OK;
 }
 
-// own + link into scratch slot 0 (asynchronous); *d_rec = the records
+// own + link into kWsIn (asynchronous); *d_rec = the records
 int octree_fill(r3d_ctx* ctx, const uint64_t* d_codes, int64_t n, Workspace& w, int64_t n_records, uint16_t** d_rec) {
   void* r = nullptr;
-  int rc = r3d_scratch(ctx, 0, (((size_t)n_records + 1) & ~(size_t)1) * 2, &r);
+  int rc = r3d_scratch(ctx, kWsIn, r3d_align_up((size_t)n_records, 2) * 2, &r);
   if (rc) return rc;
   hipStream_t st = ctx->stream;
   hipLaunchKernelGGL(octree_own_kernel, dim3((unsigned)w.tiles), dim3(kThreads), 0, st, d_codes, n, (const uint8_t*)w.meta,

@@ -346,7 +346,7 @@ __global__ __launch_bounds__(kThreads) void plane_accumulate_kernel(const float*
   r3d_sums::block_reduce_store<kSums>(acc, red, partials + (int64_t)blockIdx.x * kSums);
 }
 
-// workspace in scratch slot 6: [hist n_buckets x 256 u32][state n_buckets x 4 u64][SelectOut x n_buckets][pad], then the
+// workspace in kWsSelect: [hist n_buckets x 256 u32][state n_buckets x 4 u64][SelectOut x n_buckets][pad], then the
 // partial rows
 struct Workspace {
   unsigned* hist;
@@ -360,8 +360,8 @@ int workspace(r3d_ctx* ctx, int n_buckets, int n_rows, Workspace* ws) {
   void* p = nullptr;
   const size_t hist_b = (size_t)n_buckets * kBins * sizeof(unsigned), state_b = (size_t)n_buckets * 4 * sizeof(unsigned long long);
   const size_t head = hist_b + state_b + (size_t)n_buckets * sizeof(SelectOut) + 64;
-  const size_t head_al = (head + 255) & ~(size_t)255;
-  int rc = r3d_scratch(ctx, 6, head_al + (size_t)(n_rows + 1) * kSums * sizeof(double), &p);
+  const size_t head_al = r3d_align_up(head, 256);
+  int rc = r3d_scratch(ctx, kWsSelect, head_al + (size_t)(n_rows + 1) * kSums * sizeof(double), &p);
   if (rc) return rc;
   // The "histogram is known to be zero" record (select_enqueue) describes ONE layout.  A workspace laid out for another class
   // count puts its state words, picks or partial rows where that layout has its histogram -- e.g. the untrimmed sums pass
@@ -558,7 +558,7 @@ static int plane_sums_impl(r3d_ctx* ctx, const float* d_src, int64_t n_src, cons
   const SelectOut* gates = nullptr;
   if (trim) {
     void* r2 = nullptr;   // [n_src] f32 followed by [n_src] u8
-    if ((rc = r3d_scratch(ctx, 7, (size_t)n_src * 5 + 16, &r2))) return rc;
+    if ((rc = r3d_scratch(ctx, kWsTrack, (size_t)n_src * 5 + 16, &r2))) return rc;
     unsigned char* cls = reinterpret_cast<unsigned char*>(static_cast<float*>(r2) + n_src);
     if ((rc = r3d_icp_plane_residuals(ctx, d_src, n_src, d_tgt, d_nrm, n_tgt, d_idx, d_d2, gate_d2, (float*)r2, cls))) return rc;
     if ((rc = select_enqueue(ctx, (const float*)r2, cls, kNormalClasses, n_src, (double)trim_q, ws))) return rc;

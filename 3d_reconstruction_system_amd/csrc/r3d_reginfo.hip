@@ -89,11 +89,11 @@ int r3d_registration_sums(r3d_ctx* ctx, const float* d_src, int64_t n_src, const
   }
   int64_t blocks = (n_src + kThreads - 1) / kThreads;
   if (blocks > (int64_t)ctx->num_cus * 4) blocks = (int64_t)ctx->num_cus * 4;
-  // The workspace (the partial rows, then the 11 sums; 90 kB at the most) belongs to this entry point alone and is made once per
-  // context at its largest size: no other call reads or writes it, and this one is synchronous, so nothing it does depends on,
-  // or disturbs, what other calls leave in the context's shared scratch slots.
-  if (!ctx->reginfo_ws) R3D_HIP(hipMalloc(&ctx->reginfo_ws, ((size_t)ctx->num_cus * 4 + 1) * kSums * sizeof(double)));
-  return sums_pass(ctx, d_src, n_src, d_tgt, n_tgt, d_idx, d_d2, max_d2, static_cast<double*>(ctx->reginfo_ws), (int)blocks, h_sums);
+  // kWsRegSums (the partial rows, then the 11 sums; 90 kB at the most) is this synchronous entry point's alone, always asked for at
+  // its largest size: nothing here depends on, or disturbs, what other calls leave in the context's shared workspaces.
+  void* ws = nullptr;
+  if ((rc = r3d_scratch(ctx, kWsRegSums, ((size_t)ctx->num_cus * 4 + 1) * kSums * sizeof(double), &ws))) return rc;
+  return sums_pass(ctx, d_src, n_src, d_tgt, n_tgt, d_idx, d_d2, max_d2, static_cast<double*>(ws), (int)blocks, h_sums);
 }
 
 }  // extern "C"

@@ -33,9 +33,6 @@
 #include "r3d_internal.h"
 #include "r3d_sums_dev.h"
 
-int r3d_match_nearest(r3d_ctx* ctx, const float* d_a, int64_t na, const float* d_b, int64_t nb, uint32_t* d_idx_out, float* d_dist_out,
-                      int slot);
-
 namespace {
 
 using r3d_consensus::kThreads;
@@ -334,18 +331,18 @@ int r3d_feature_match(r3d_ctx* ctx, const float* d_a, int64_t na, const float* d
   }
   int rc = r3d_ctx_enter(ctx);
   if (rc) return rc;
-  // slot 4 / 2: the partial minima of a -> b / b -> a; slot 3: the b -> a rows; slot 5: the per-workgroup keep counts
+  // kWsPartials / kWsSpare: the partial minima of a -> b / b -> a; kWsCounts: the b -> a rows; kWsMisc: the per-workgroup keep counts
   const int n_blocks = (int)((na + kThreads - 1) / kThreads);
   r3d_compact::Counters cn(n_blocks, 1);
   void *idx_b_v = nullptr, *counts_v = nullptr;
-  if (mutual && (rc = r3d_scratch(ctx, 3, (size_t)nb * 4, &idx_b_v))) return rc;
-  if (d_corr_out && (rc = r3d_scratch(ctx, 5, cn.bytes, &counts_v))) return rc;
+  if (mutual && (rc = r3d_scratch(ctx, kWsCounts, (size_t)nb * 4, &idx_b_v))) return rc;
+  if (d_corr_out && (rc = r3d_scratch(ctx, kWsMisc, cn.bytes, &counts_v))) return rc;
   for (int i = 0; i < 3; ++i)
     if (out[i].p) r3d_wrote(ctx, out[i].p, out[i].bytes);
-  if ((rc = r3d_match_nearest(ctx, d_a, na, d_b, nb, d_idx_out, d_dist_out, 4))) return rc;
+  if ((rc = r3d_match_nearest(ctx, d_a, na, d_b, nb, d_idx_out, d_dist_out, kWsPartials))) return rc;
   if (!d_corr_out) return R3D_OK;
   uint32_t* idx_b = static_cast<uint32_t*>(idx_b_v);
-  if (mutual && (rc = r3d_match_nearest(ctx, d_b, nb, d_a, na, idx_b, nullptr, 2))) return rc;
+  if (mutual && (rc = r3d_match_nearest(ctx, d_b, nb, d_a, na, idx_b, nullptr, kWsSpare))) return rc;
   cn.place(counts_v);
   hipStream_t st = ctx->stream;
   hipLaunchKernelGGL(keep_count_kernel, dim3((unsigned)n_blocks), dim3(kThreads), 0, st, (const uint32_t*)d_idx_out, (const uint32_t*)idx_b,
@@ -379,10 +376,10 @@ int r3d_register_ransac(r3d_ctx* ctx, const float* d_src, int64_t ns, const floa
   R3D_REQUIRE(!r3d_ranges_overlap(d_counts_out, cb, d_inlier_out, (size_t)m), "the outputs overlap each other");
   if ((rc = r3d_ctx_enter(ctx))) return rc;
 
-  // slot 0: the gathered pairs; slots 5 and 4: the consensus layout
+  // kWsIn: the gathered pairs; kWsMisc and kWsPartials: the consensus layout
   const r3d_consensus::Plan pn = r3d_consensus::plan(m, H, kTile);
   void* s0 = nullptr;
-  if ((rc = r3d_scratch(ctx, 0, (size_t)m * 32, &s0))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsIn, (size_t)m * 32, &s0))) return rc;
   r3d_consensus::Layout lay;
   if ((rc = r3d_consensus::layout(ctx, pn, 12, kSums, sizeof(Misc), &lay))) return rc;
   float4* pairs = static_cast<float4*>(s0);

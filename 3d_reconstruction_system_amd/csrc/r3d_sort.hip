@@ -160,7 +160,7 @@ __global__ __launch_bounds__(kThreads) void digit_scatter_kernel(const uint64_t*
 // a Morton code) skips the passes over them.
 // d_tmp: scratch of n keys.  The result is in d_keys when the number of passes is even, else it is copied back -- unless the
 // caller asks where it ended up (d_result != NULL: *d_result = d_keys or d_tmp, no copy).
-// The workspace of a sort of n keys (scratch slot 3): hist[bin][r3d_sort_stride(workgroups)] + the 256 bin totals.  A producer that writes the
+// The workspace of a sort of n keys (kWsCounts): hist[bin][r3d_sort_stride(workgroups)] + the 256 bin totals.  A producer that writes the
 // keys tile by tile (kSortTile keys per workgroup, same tiling as the sort) can fill `hist` for the FIRST digit itself and
 // save the sort its first histogram pass (no producer in the library does at present: the sort-merge insert, r3d_voxel_merge.hip,
 // has passes of its own).
@@ -171,7 +171,7 @@ int r3d_radix_sort_workspace(r3d_ctx* ctx, int64_t n, uint32_t** hist_out, int* 
   R3D_REQUIRE(n_blocks64 < ((int64_t)1 << 31), "too many keys for one sort");
   void* ws = nullptr;
   const size_t hist_bytes = (size_t)kBins * r3d_sort_stride((int)n_blocks64) * sizeof(uint32_t);
-  int rc = r3d_scratch(ctx, 3, hist_bytes + kBins * sizeof(uint32_t) + 64, &ws);
+  int rc = r3d_scratch(ctx, kWsCounts, hist_bytes + kBins * sizeof(uint32_t) + 64, &ws);
   if (rc) return rc;
   *hist_out = static_cast<uint32_t*>(ws);
   *n_blocks_out = (int)n_blocks64;
@@ -197,7 +197,7 @@ int r3d_radix_sort_u64(r3d_ctx* ctx, uint64_t* d_keys, uint64_t* d_tmp, int64_t 
   if (rc) return rc;
   const int stride = r3d_sort_stride(n_blocks);
   const size_t hist_bytes = (size_t)kBins * stride * sizeof(uint32_t);
-  uint32_t* totals = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(hist) + ((hist_bytes + 15) & ~(size_t)15));
+  uint32_t* totals = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(hist) + r3d_align_up(hist_bytes, 16));
   uint64_t* src = d_keys;
   uint64_t* dst = d_tmp;
   for (int p = 0; p < passes; ++p) {
@@ -229,7 +229,7 @@ int r3d_sort_u64(r3d_ctx* ctx, uint64_t* d_keys, int64_t n_keys, int key_bits) {
   if (n_keys <= 1) return R3D_OK;
   R3D_REQUIRE(d_keys != nullptr, "NULL device pointer");
   void* tmp = nullptr;
-  if ((rc = r3d_scratch(ctx, 2, (size_t)n_keys * sizeof(uint64_t), &tmp))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsSpare, (size_t)n_keys * sizeof(uint64_t), &tmp))) return rc;
   return r3d_radix_sort_u64(ctx, d_keys, static_cast<uint64_t*>(tmp), n_keys, key_bits, 0);
 }
 
@@ -242,7 +242,7 @@ int r3d_sort_u64_bits(r3d_ctx* ctx, uint64_t* d_keys, int64_t n_keys, int first_
   if (n_keys <= 1) return R3D_OK;
   R3D_REQUIRE(d_keys != nullptr, "NULL device pointer");
   void* tmp = nullptr;
-  if ((rc = r3d_scratch(ctx, 2, (size_t)n_keys * sizeof(uint64_t), &tmp))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsSpare, (size_t)n_keys * sizeof(uint64_t), &tmp))) return rc;
   return r3d_radix_sort_u64(ctx, d_keys, static_cast<uint64_t*>(tmp), n_keys, end_bit, first_bit);
 }
 

@@ -525,7 +525,7 @@ int r3d_format_text_device(r3d_ctx* ctx, int kind, const void* d_xyz, int dtype,
   // workspace: flags (16 B) | tile_off [n_tiles + 1] u64 | tile_len [n_tiles] u32
   void* ws = nullptr;
   const size_t off_bytes = (size_t)(n_tiles + 1) * 8;
-  if ((rc = r3d_scratch(ctx, 5, 16 + off_bytes + (size_t)n_tiles * 4, &ws))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsMisc, 16 + off_bytes + (size_t)n_tiles * 4, &ws))) return rc;
   unsigned int* d_flags = static_cast<unsigned int*>(ws);
   uint64_t* d_off = reinterpret_cast<uint64_t*>(static_cast<char*>(ws) + 16);
   uint32_t* d_len = reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + 16 + off_bytes);

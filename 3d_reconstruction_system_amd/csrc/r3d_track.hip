@@ -234,10 +234,10 @@ int output_checks(const TrackParams& p, const Maps& m, const r3d_range* outs, in
 
 int n_tiles(const TrackParams& p) { return (p.n_px + kTile - 1) / kTile; }
 
-// partial rows (+ one row for the sums) in scratch slot 4, the slot the other paths keep their partial rows in
+// partial rows (+ one row for the sums) in kWsPartials, where the other paths keep their partial rows
 int rows_workspace(r3d_ctx* ctx, int tiles, double** rows, int k_sums = kSums) {
   void* v = nullptr;
-  int rc = r3d_scratch(ctx, 4, ((size_t)tiles + 2) * k_sums * sizeof(double), &v);
+  int rc = r3d_scratch(ctx, kWsPartials, ((size_t)tiles + 2) * k_sums * sizeof(double), &v);
   if (rc) return rc;
   *rows = static_cast<double*>(v);
   return R3D_OK;
@@ -401,12 +401,12 @@ int track_rgb(r3d_tsdf* vol, const r3d_camera* cam, const void* d_depth, int dep
   // the ray cast's own argument checks and the colour plane's presence: with no output it validates and does nothing else
   if ((rc = r3d_tsdf_raycast_rgb(vol, cam, 1, G, min_weight, step, t_near, t_far, nullptr, nullptr, nullptr, nullptr))) return rc;
   if ((rc = r3d_ctx_enter(ctx))) return rc;
-  // scratch slot 7, as track_levels: four maps, the model's depth, rgb and packed map, the source intensity, the state
-  const auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t n = (size_t)p.n_px, map = up(n * 12), plane = up(n * 4), img = up(n * 3), packed = up(n * 16);
+  // kWsTrack, as track_levels: four maps, the model's depth, rgb and packed map, the source intensity, the state
+  const size_t n = (size_t)p.n_px, map = r3d_align_up(n * 12, 256), plane = r3d_align_up(n * 4, 256), img = r3d_align_up(n * 3, 256);
+  const size_t packed = r3d_align_up(n * 16, 256);
   const size_t bytes = 4 * map + 2 * plane + img + packed;
   void* ws = nullptr;
-  if ((rc = r3d_scratch(ctx, 7, bytes + R3D_ICP_STATE_DOUBLES * sizeof(double), &ws))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsTrack, bytes + R3D_ICP_STATE_DOUBLES * sizeof(double), &ws))) return rc;
   char* c = static_cast<char*>(ws);
   float *model_vertex = reinterpret_cast<float*>(c), *model_normal = reinterpret_cast<float*>(c + map);
   float *src_vertex = reinterpret_cast<float*>(c + 2 * map), *src_normal = reinterpret_cast<float*>(c + 3 * map);
@@ -477,24 +477,24 @@ int track_levels(r3d_tsdf* vol, const r3d_camera* const* cams, int n_levels, con
     if ((rc = r3d_tsdf_raycast(vol, cams[l], 1, G, min_weight, step, t_near, t_far, nullptr, nullptr, nullptr))) return rc;
   }
   if ((rc = r3d_ctx_enter(ctx))) return rc;
-  // every level's four maps, the depth rasters of the levels above 0 and the state: scratch slot 7 (the rank-trimming residuals'
-  // slot; nothing of that path runs in here).  A level has a quarter of the pixels of the one below: 4/3 of level 0's maps.
+  // every level's four maps, the depth rasters of the levels above 0 and the state: kWsTrack (the rank-trimming residuals'
+  // workspace too; nothing of that path runs in here).  A level has a quarter of the pixels of the one below: 4/3 of level 0's maps.
   size_t map_at[R3D_TRACK_MAX_LEVELS], map[R3D_TRACK_MAX_LEVELS], depth_at[R3D_TRACK_MAX_LEVELS], bytes = 0;
   for (int l = 0; l < n_levels; ++l) {
-    map[l] = ((size_t)p[l].n_px * 12 + 255) & ~(size_t)255;
+    map[l] = r3d_align_up((size_t)p[l].n_px * 12, 256);
     map_at[l] = bytes;
     bytes += 4 * map[l];
   }
   for (int l = 1; l < n_levels; ++l) {
     depth_at[l] = bytes;
-    bytes += ((size_t)p[l].n_px * 4 + 255) & ~(size_t)255;
+    bytes += r3d_align_up((size_t)p[l].n_px * 4, 256);
   }
   void* ws = nullptr;
-  if ((rc = r3d_scratch(ctx, 7, bytes + R3D_ICP_STATE_DOUBLES * sizeof(double), &ws))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsTrack, bytes + R3D_ICP_STATE_DOUBLES * sizeof(double), &ws))) return rc;
   char* c = static_cast<char*>(ws);
   double* d_state = reinterpret_cast<double*>(c + bytes);
   double* rows = nullptr;
-  if ((rc = rows_workspace(ctx, n_tiles(p[0]), &rows))) return rc;   // the largest level's rows: the slot never grows mid-loop
+  if ((rc = rows_workspace(ctx, n_tiles(p[0]), &rows))) return rc;   // the largest level's rows: kWsPartials never grows mid-loop
   Maps m[R3D_TRACK_MAX_LEVELS];
   for (int l = 0; l < n_levels; ++l) {
     char* base = c + map_at[l];

@@ -313,13 +313,13 @@ int r3d_tsdf_integrate_host(r3d_tsdf* v, const r3d_camera* cam, const void* h_de
   if (rc || n_frames == 0) return rc;
   r3d_ctx* ctx = v->ctx;
   if ((rc = r3d_ctx_enter(ctx))) return rc;
-  // the batch goes up in slabs of whole frames through the context's input scratch slot; every slab is one integrate call
+  // the batch goes up in slabs of whole frames through kWsIn; every slab is one integrate call
   const size_t frame_bytes = (size_t)cam->height * cam->width * r3d_depth_size(depth_dtype);
   int slab = (int)(((size_t)256 << 20) / (frame_bytes ? frame_bytes : 1));
   if (slab < 1) slab = 1;
   if (slab > n_frames) slab = n_frames;
   void* d_in = nullptr;
-  if ((rc = r3d_scratch(ctx, 0, (size_t)slab * frame_bytes, &d_in))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsIn, (size_t)slab * frame_bytes, &d_in))) return rc;
   for (int lo = 0; lo < n_frames; lo += slab) {
     const int n = n_frames - lo < slab ? n_frames - lo : slab;
     if ((rc = r3d_memcpy_h2d(ctx, d_in, static_cast<const char*>(h_depth) + (size_t)lo * frame_bytes, (size_t)n * frame_bytes))) return rc;
@@ -340,7 +340,7 @@ int r3d_tsdf_count_points(r3d_tsdf* v, float mw, const uint32_t** d_prefix, int*
   const int tiles = r3d_compact::tiles_of(v->n);
   r3d_compact::Counters cn(tiles, 1);
   void* ws = nullptr;
-  if ((rc = r3d_scratch(ctx, 3, cn.bytes, &ws))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsCounts, cn.bytes, &ws))) return rc;
   cn.place(ws);
   hipLaunchKernelGGL(tsdf_count_kernel, dim3(tiles), dim3(kThreads), 0, ctx->stream, (const float2*)v->d_vol, v->g, v->n, mw, cn.hist);
   uint32_t m = 0;

@@ -196,16 +196,16 @@ int r3d_tsdf_integrate_rgb_host(r3d_tsdf* v, const r3d_camera* cam, const void* 
   if (rc || n_frames == 0) return rc;
   r3d_ctx* ctx = cv.ctx;
   if ((rc = r3d_ctx_enter(ctx))) return rc;
-  // the batch goes up in slabs of whole frames through the context's input scratch slot, a slab's rasters first, then its colour
+  // the batch goes up in slabs of whole frames through kWsIn, a slab's rasters first, then its colour
   // images (at a 256-byte boundary); every slab is one integrate call
   const size_t px = (size_t)cam->height * cam->width;
   const size_t depth_bytes = px * r3d_depth_size(depth_dtype), rgb_bytes = px * 3, frame_bytes = depth_bytes + rgb_bytes;
   int slab = (int)(((size_t)256 << 20) / (frame_bytes ? frame_bytes : 1));
   if (slab < 1) slab = 1;
   if (slab > n_frames) slab = n_frames;
-  const size_t rgb_at = ((size_t)slab * depth_bytes + 255) & ~(size_t)255;
+  const size_t rgb_at = r3d_align_up((size_t)slab * depth_bytes, 256);
   void* d_in = nullptr;
-  if ((rc = r3d_scratch(ctx, 0, rgb_at + (size_t)slab * rgb_bytes, &d_in))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsIn, rgb_at + (size_t)slab * rgb_bytes, &d_in))) return rc;
   uint8_t* d_rgb = static_cast<uint8_t*>(d_in) + rgb_at;
   for (int lo = 0; lo < n_frames; lo += slab) {
     const int n = n_frames - lo < slab ? n_frames - lo : slab;

@@ -213,6 +213,6 @@ int r3d_tsdf_color_plane(r3d_tsdf* vol, uint4** d_col);
 // the argument checks r3d_tsdf_integrate makes (R3D_OK with n_frames == 0 too: the caller returns then);
 int r3d_tsdf_integrate_checks(r3d_tsdf* vol, const r3d_camera* cam, const void* depth, int depth_dtype, int n_frames, double depth_scale,
                               const double* h_pose);
-// and the first half of r3d_tsdf_extract_points: tsdf_count_kernel + the tile scan into scratch slot 3, the count read back
+// and the first half of r3d_tsdf_extract_points: tsdf_count_kernel + the tile scan into kWsCounts, the count read back
 // (synchronises).  *d_prefix: the tiles' exclusive prefixes, *tiles their number, *n_points the count.
 int r3d_tsdf_count_points(r3d_tsdf* vol, float mw, const uint32_t** d_prefix, int* tiles, int64_t* n_points);

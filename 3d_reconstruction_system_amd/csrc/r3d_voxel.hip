@@ -415,7 +415,7 @@ int r3d_voxelset_sample(r3d_voxelset* vs, const float* d_xyz, int64_t n_points, 
   const int64_t n_tiles = (n_points + kThreads * 4 - 1) / (kThreads * 4);
   const int64_t samples = std::max<int64_t>(1, std::min<int64_t>(256, n_tiles / 4));
   void* ws = nullptr;
-  int rc = r3d_scratch(ctx, 5, 64, &ws);
+  int rc = r3d_scratch(ctx, kWsMisc, 64, &ws);
   if (rc) return rc;
   unsigned long long* d_sums = static_cast<unsigned long long*>(ws);
   R3D_HIP(hipMemsetAsync(d_sums, 0, 16, ctx->stream));
@@ -466,7 +466,7 @@ int r3d_voxelset_insert_host(r3d_voxelset* vs, const float* h_xyz, int64_t n_poi
   if (n_points == 0) return R3D_OK;
   R3D_REQUIRE(h_xyz != nullptr, "NULL host pointer");
   void* d = nullptr;
-  if ((rc = r3d_scratch(vs->ctx, 0, (size_t)n_points * 12, &d))) return rc;
+  if ((rc = r3d_scratch(vs->ctx, kWsIn, (size_t)n_points * 12, &d))) return rc;
   R3D_HIP(hipMemcpyAsync(d, h_xyz, (size_t)n_points * 12, hipMemcpyHostToDevice, vs->ctx->stream));
   if ((rc = r3d_voxelset_insert(vs, static_cast<const float*>(d), n_points))) return rc;
   R3D_HIP(hipStreamSynchronize(vs->ctx->stream));
@@ -502,7 +502,7 @@ int r3d_voxelset_insert_codes(r3d_voxelset* vs, const uint64_t* d_codes, int64_t
   return R3D_OK;
 }
 
-// distinct codes of the set as a sorted list in HBM (scratch slot 1); *n_out = how many
+// distinct codes of the set as a sorted list in HBM (kWsOut); *n_out = how many
 static int codes_to_device_list(r3d_voxelset* vs, uint64_t** d_list_out, int64_t* n_out) {
   int64_t n = 0, ign = 0, over = 0;
   int rc = r3d_voxelset_stats(vs, &n, &ign, &over);
@@ -531,9 +531,9 @@ int r3d_voxelset_sorted_codes_device(r3d_voxelset* vs, r3d_ctx** ctx, double* re
 int r3d_voxel_table_sorted_codes(r3d_ctx* ctx, const uint64_t* d_table, uint64_t capacity, unsigned long long* d_counters,
                                  int64_t n, uint64_t** d_list_out) {
   void *d_list = nullptr, *d_tmp = nullptr;
-  int rc = r3d_scratch(ctx, 1, (size_t)n * sizeof(uint64_t), &d_list);
+  int rc = r3d_scratch(ctx, kWsOut, (size_t)n * sizeof(uint64_t), &d_list);
   if (rc) return rc;
-  if ((rc = r3d_scratch(ctx, 2, (size_t)n * sizeof(uint64_t), &d_tmp))) return rc;
+  if ((rc = r3d_scratch(ctx, kWsSpare, (size_t)n * sizeof(uint64_t), &d_tmp))) return rc;
   R3D_HIP(hipMemsetAsync(d_counters + 3, 0, sizeof(unsigned long long), ctx->stream));
   int blocks = ctx->num_cus * 8;
   const uint64_t need = (capacity + kCompactSlots - 1) / kCompactSlots;
@@ -566,7 +566,7 @@ int r3d_voxelset_union(r3d_voxelset* vs, r3d_comm* comm) {
   // still takes part and says -1, so that EVERY rank returns the error instead of waiting for it forever.
   if (rc_mine) n_mine = -1;
   void* d_cnt = nullptr;
-  if ((rc = r3d_scratch(vs->ctx, 3, (size_t)(world + 1) * sizeof(int64_t), &d_cnt))) return rc;
+  if ((rc = r3d_scratch(vs->ctx, kWsCounts, (size_t)(world + 1) * sizeof(int64_t), &d_cnt))) return rc;
   int64_t* d_counts = static_cast<int64_t*>(d_cnt);
   R3D_HIP(hipMemcpyAsync(d_counts + world, &n_mine, sizeof(int64_t), hipMemcpyHostToDevice, vs->ctx->stream));
   std::vector<int64_t> eight((size_t)world, (int64_t)sizeof(int64_t)), counts((size_t)world), bytes((size_t)world);
@@ -585,7 +585,7 @@ int r3d_voxelset_union(r3d_voxelset* vs, r3d_comm* comm) {
   }
   if (total == 0) return R3D_OK;
   void* d_all = nullptr;
-  if ((rc = r3d_scratch(vs->ctx, 0, (size_t)total * sizeof(uint64_t), &d_all))) return rc;
+  if ((rc = r3d_scratch(vs->ctx, kWsIn, (size_t)total * sizeof(uint64_t), &d_all))) return rc;
   if ((rc = r3d_comm_allgather(comm, d_mine, bytes.data(), d_all, R3D_GATHER_AUTO))) return rc;
   return r3d_voxelset_insert_codes(vs, static_cast<const uint64_t*>(d_all), total);
 }

@@ -981,7 +981,6 @@ int r3d_voxelset_insert_sorted(r3d_voxelset* vs, const float* d_xyz, int64_t n_p
   const int sub_log2 = kPieceBits - (vs->log2cap - region_log2);                // pieces per region (log2)
   const uint32_t n_regions = (uint32_t)1 << (vs->log2cap - region_log2);
   const int64_t chunk = (int64_t)1 << 27;   // points per round: 0.5 GB of sorted remainders + 1.5 GB of segments
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
   int rc;
   for (int64_t off = 0; off < n_points; off += chunk) {
     const int64_t m = std::min(chunk, n_points - off);
@@ -992,17 +991,17 @@ int r3d_voxelset_insert_sorted(r3d_voxelset* vs, const float* d_xyz, int64_t n_p
     const int n_tiles = plan.n_tiles2, stride = r3d_sort_stride(n_tiles);   // the second pass's tiles
     const size_t seg_elems = (size_t)kSegments * plan.cap;
     void *a_v = nullptr, *b_v = nullptr, *ws = nullptr;
-    if ((rc = r3d_scratch(ctx, 1, up((size_t)m * 4), &a_v))) return rc;   // the remainders in piece order
-    if ((rc = r3d_scratch(ctx, 2, up(seg_elems * 4) + up(seg_elems), &b_v))) return rc;   // the first pass's segments: rem | hi
+    if ((rc = r3d_scratch(ctx, kWsOut, r3d_align_up((size_t)m * 4, 256), &a_v))) return rc;   // the remainders in piece order
+    if ((rc = r3d_scratch(ctx, kWsSpare, r3d_align_up(seg_elems * 4, 256) + r3d_align_up(seg_elems, 256), &b_v))) return rc;   // the first pass's segments: rem | hi
     uint32_t* rem_a = static_cast<uint32_t*>(a_v);
     uint32_t* rem_b = static_cast<uint32_t*>(b_v);
-    uint8_t* hi_b = reinterpret_cast<uint8_t*>(static_cast<char*>(b_v) + up(seg_elems * 4));
+    uint8_t* hi_b = reinterpret_cast<uint8_t*>(static_cast<char*>(b_v) + r3d_align_up(seg_elems * 4, 256));
     const unsigned merge_grid = (unsigned)ctx->num_cus * 8;   // (1536 .. 4096 workgroups measured within 3 % of each other)
-    const size_t partial_bytes = up((size_t)merge_grid * 2 * 2 * sizeof(unsigned long long));   // (the wave form's grid is twice merge_grid)
-    const size_t starts_bytes = up(((size_t)kPieces + 2) * sizeof(uint32_t));
-    const size_t hist_bytes = up((size_t)256 * stride * sizeof(uint32_t));
-    const size_t count_bytes = up((size_t)kSegments * kCursorStride * sizeof(uint32_t));   // the segments' cursors, a line each
-    if ((rc = r3d_scratch(ctx, 5, partial_bytes + starts_bytes + hist_bytes + 1024 + 256 + count_bytes + spill_cap * 8, &ws))) return rc;
+    const size_t partial_bytes = r3d_align_up((size_t)merge_grid * 2 * 2 * sizeof(unsigned long long), 256);   // (the wave form's grid is twice merge_grid)
+    const size_t starts_bytes = r3d_align_up(((size_t)kPieces + 2) * sizeof(uint32_t), 256);
+    const size_t hist_bytes = r3d_align_up((size_t)256 * stride * sizeof(uint32_t), 256);
+    const size_t count_bytes = r3d_align_up((size_t)kSegments * kCursorStride * sizeof(uint32_t), 256);   // the segments' cursors, a line each
+    if ((rc = r3d_scratch(ctx, kWsMisc, partial_bytes + starts_bytes + hist_bytes + 1024 + 256 + count_bytes + spill_cap * 8, &ws))) return rc;
     char* w = static_cast<char*>(ws);
     unsigned long long* d_partials = reinterpret_cast<unsigned long long*>(w);
     uint32_t* d_starts = reinterpret_cast<uint32_t*>(w + partial_bytes);

@@ -407,10 +407,10 @@ int r3d_voxelgrid_insert_host(r3d_voxelgrid* vg, const float* h_xyz, const uint3
   if (n_points == 0) return R3D_OK;
   R3D_REQUIRE(h_xyz != nullptr, "NULL host pointer");
   void *d = nullptr, *d_c = nullptr;
-  if ((rc = r3d_scratch(vg->ctx, 0, (size_t)n_points * 12, &d))) return rc;
+  if ((rc = r3d_scratch(vg->ctx, kWsIn, (size_t)n_points * 12, &d))) return rc;
   R3D_HIP(hipMemcpyAsync(d, h_xyz, (size_t)n_points * 12, hipMemcpyHostToDevice, vg->ctx->stream));
   if (h_rgba) {
-    if ((rc = r3d_scratch(vg->ctx, 4, (size_t)n_points * 4, &d_c))) return rc;
+    if ((rc = r3d_scratch(vg->ctx, kWsPartials, (size_t)n_points * 4, &d_c))) return rc;
     R3D_HIP(hipMemcpyAsync(d_c, h_rgba, (size_t)n_points * 4, hipMemcpyHostToDevice, vg->ctx->stream));
   }
   if ((rc = r3d_voxelgrid_insert(vg, static_cast<const float*>(d), static_cast<const uint32_t*>(d_c), n_points))) return rc;

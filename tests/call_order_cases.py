@@ -2,7 +2,7 @@
 each a function run(ctx, scale=1) -> bytes that builds its inputs from a fixed seed, runs on the context it is given, checks
 the result against the restatement that pins its module (with that module's own generators, helpers and bounds: nothing new
 is derived here) and returns every output concatenated as raw bytes.  scale = 4 gives the larger instance
-test_small_behind_large runs first so that every scratch slot has grown and holds foreign data.
+test_small_behind_large runs first so that every workspace of the context has grown and holds foreign data.
 
 Device objects that belong to a context (NN index, voxel set, voxel grid, TSDF volume) are made inside run on that context and
 closed there.  COVERS maps each case to the csrc/*.hip files whose entry points it calls; tests/test_call_order_host.py keeps
@@ -46,6 +46,7 @@ def _memo(module, *names):
 
 def _memo_all():
     import bilateral_ref, mesh_ref, normals_ref, outliers_ref, photo_ref, project_ref, pyramid_ref, raycast_color_ref, raycast_ref
+    import color_icp_ref, compare_ref, mesh_cc_ref, posegraph_ref
     import register_ref, segment_ref, sort_ref, track_ref, tsdf_color_ref, tsdf_ref
     from oracle import fusion_ref, icp_ref, octomap_ref, plane_ref
     _memo(register_ref, "ransac", "match", "nearest_rows", "fpfh")
@@ -67,6 +68,10 @@ def _memo_all():
     _memo(project_ref, "grad_points_f32", "grad_P_f64", "grad_P_bound", "dense_inputs")
     _memo(fusion_ref, "fuse_frames", "apply_T")
     _memo(sort_ref, "stable_sort_by_bits", "few_values")
+    _memo(posegraph_ref, "registration_sums")
+    _memo(color_icp_ref, "knn_lists", "nearest", "gradients", "accumulate", "loop")
+    _memo(mesh_cc_ref, "components", "filter_components")
+    _memo(compare_ref, "mesh_distance", "distance_stats")
 
 
 def _cat(*arrays):
@@ -620,6 +625,142 @@ def register_ransac(ctx, scale=1):
     return _cat(r, mask)
 
 
+# ---- the entry points with workspaces of their own --------------------------------------------------------------------------------
+def registration_sums(ctx, scale=1):
+    """r3d_registration_sums on the pairs an index query returns (the setup of test_gpu_posegraph.py, its bound)"""
+    import posegraph_ref as REF
+    from test_gpu_posegraph import N_TGT, check, sums_call
+    icp, L = _m("icp"), _m("_lib")
+    n = _n(1000, scale)
+    rng = np.random.default_rng(0)
+    tgt = (rng.uniform(-2.0, 2.0, (N_TGT, 3)) + (0.5, -1.0, 3.0)).astype(np.float32)
+    rng = np.random.default_rng(n)
+    src = (tgt[rng.integers(8, 4000, n)].astype(np.float64) + rng.normal(size=(n, 3)) * 0.02).astype(np.float32)
+    d_tgt, d_src, d_idx, d_d2 = ctx.alloc(tgt.nbytes).upload(tgt), ctx.alloc(src.nbytes).upload(src), ctx.alloc(n * 4), ctx.alloc(n * 4)
+    ix = icp.NNIndex(ctx, d_tgt.ptr, N_TGT)
+    try:
+        ix.query(d_src.ptr, n, d_idx.ptr, d_d2.ptr)
+        idx, d2 = d_idx.download(np.uint32, n), d_d2.download(np.float32, n)
+        out = []
+        for gate in (np.inf, float(np.sort(d2)[n // 2])):
+            rc, got = sums_call(ctx, d_src.ptr, n, d_tgt.ptr, N_TGT, d_idx.ptr, d_d2.ptr, gate)
+            assert rc == 0, L.last_error()
+            want = check(got, src, tgt, idx, d2, gate)
+            assert want[0] == (d2 <= gate).sum()
+            out.append(got)
+    finally:
+        ix.close()
+        for b in (d_tgt, d_src, d_idx, d_d2):
+            b.free()
+    return _cat(idx, d2, *out)
+
+
+_WALL = {}
+
+
+def _wall():
+    """the colour wall of test_gpu_color_icp.py with the restatement's intensities and gradients (its `wall` fixture)"""
+    if not _WALL:
+        import color_icp_ref as REF
+        sc = REF.wall_scene()
+        idx, d2 = REF.knn_lists(sc["tgt"], 8)
+        sc["I"], sc["grad"], _ = REF.gradients(sc["tgt"], sc["normals"], sc["tgt_rgba"], idx, d2)
+        sc["src_I"] = REF.intensity(sc["src_rgba"])
+        _WALL.update(sc)
+    return _WALL
+
+
+def color_icp(ctx, scale=1):
+    """the wall's gradients, one 31-sums pass and a two-iteration loop on 257 of its sources"""
+    import color_icp_ref as REF
+    from test_gpu_bounds import Guarded
+    from test_gpu_color_icp import ColourLoop, assert_sums, clouds, device_pass, nan_bits, pass_inputs
+    icp, L, CI = _m("icp"), _m("_lib"), _m("colored_icp")
+    wall, w = _wall(), _m("colored_icp").photo_weight(0.968)
+    made = []
+
+    def guard(nbytes, off=0, data=None, seed=0):
+        made.append(Guarded(ctx, nbytes, off, data, seed))
+        return made[-1]
+
+    loop = None
+    xyz, nrm, rgba, radius = clouds()["wall"]
+    k, rad = (32, radius) if scale > 1 else (8, None)
+    m = xyz.shape[0]
+    bufs = [ctx.alloc(a.nbytes).upload(np.ascontiguousarray(a)) for a in (xyz, nrm, rgba)] + [ctx.alloc(m * 4), ctx.alloc(m * 12), ctx.alloc(m * 4)]
+    ix = icp.NNIndex(ctx, bufs[0].ptr, m)
+    try:
+        L.check(ctx.lib.r3d_color_gradient_knn(ix.handle, k, 0.0 if rad is None else rad, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, bufs[4].ptr,
+                                               bufs[5].ptr))
+        got_I, got_g, got_c = bufs[3].download(np.float32, m), bufs[4].download(np.float32, m * 3).reshape(m, 3), bufs[5].download(np.uint32, m)
+    finally:
+        ix.close()
+        for b in bufs:
+            b.free()
+    try:
+        want_I, want_g, want_c = REF.gradients(xyz, nrm, rgba, *REF.knn_lists(xyz, k), radius=rad)
+        assert np.array_equal(got_c, want_c) and np.array_equal(got_I.view(np.uint32), want_I.view(np.uint32))
+        assert np.array_equal(nan_bits(got_g), nan_bits(want_g))
+        n = _n(257, scale)
+        src, src_I, pn, idx, d2 = pass_inputs(wall, n, 40 + n)
+        want = REF.accumulate(src, src_I, wall["tgt"], pn, wall["I"], wall["grad"], idx, d2, float(REF.WALL_MAX_D2), w, 6.0)
+        sums, photo, _ = device_pass(ctx, L, guard, wall, src, src_I, pn, idx, d2, float(REF.WALL_MAX_D2), w, 6.0)
+        assert_sums(sums, want.sums)
+        assert np.array_equal(nan_bits(photo), nan_bits(want.photo))
+        rows = np.linspace(0, wall["src"].shape[0] - 1, n).astype(np.int64)
+        lsrc, lsrc_I = np.ascontiguousarray(wall["src"][rows]), np.ascontiguousarray(wall["src_I"][rows])
+        ln = wall["normals"].copy()
+        ln[::7] = 0
+        st_want, last = REF.loop(lsrc, lsrc_I, wall["tgt"], ln, wall["I"], wall["grad"], 2, -1.0, w, 40.0)
+        loop = ColourLoop(ctx, L, CI, wall, lsrc, lsrc_I, ln, True)
+        st = loop.iterate(2, w, 40.0)
+        lsums, cloud = loop.d_sums.download(np.float64, 31), loop.d_src.download(np.float32, n * 3)
+        assert st[32] == 2.0 and st[33] == 0.0 and lsums[0] == last.sums[0] and lsums[29] == last.sums[29]
+        np.testing.assert_allclose(st[:16].reshape(4, 4), st_want[:16].reshape(4, 4), atol=2e-6, rtol=0)
+    finally:
+        if loop is not None:
+            loop.c.close()
+        for g in made:
+            g.free()
+    return _cat(got_I, got_g, got_c, sums, photo, st, lsums, cloud)
+
+
+def mesh_components(ctx, scale=1):
+    """label and filter a marching-cubes mesh with floaters and one triangle that names no vertex"""
+    import mesh_cc_ref as CC
+    from test_gpu_mesh_cc import assert_components, components, filtered
+    from test_mesh_cc_host import volume_mesh
+    L = _m("_lib")
+    xyz, _, tri = volume_mesh(((16, 16, 17), 86, 0.0) if scale > 1 else ((40, 9, 5), 3, 0.2))
+    nv = len(xyz)
+    tri = np.concatenate([tri[:len(tri) // 2], np.array([[-1, 0, 1]], np.int32), tri[len(tri) // 2:]])
+    want = CC.components(tri, nv)
+    assert want[3] == 1 and len(want[2]) > 1
+    got = components(ctx, L, tri, nv, seed=1)
+    assert_components(got, want)
+    out = [got[0], got[1], got[2]]
+    for mt, largest in ((2, False), (1, True)):
+        kept, kept_tri, n, m = filtered(ctx, L, tri, nv, got[0], mt, largest, seed=mt)
+        want_kept, want_tri = CC.filter_components(tri, nv, got[0], mt, largest)
+        assert (n, m) == (len(want_kept), len(want_tri)) and np.array_equal(kept, want_kept) and np.array_equal(kept_tri, want_tri)
+        out += [kept, kept_tri]
+    return _cat(*out)
+
+
+def mesh_distance(ctx, scale=1):
+    """index build, point-to-mesh query and the statistics of its distances"""
+    import compare_ref as CR
+    from test_gpu_compare import assert_stats, query, same_floats, sized_case, stats
+    L = _m("_lib")
+    pts, v, tri, want = sized_case(3000 if scale > 1 else 300)
+    got = query(ctx, L, pts, v, tri)
+    assert same_floats(got[0], want[0]) and np.array_equal(got[1], want[1]) and same_floats(got[2], want[2])
+    thr = (0.5, 1.0, -1.0)
+    st = stats(ctx, L, got[0], thr, 0.25, 16)
+    assert_stats(st, CR.distance_stats(got[0], thr, 0.25, 16))
+    return _cat(got[0], got[1], got[2], *st)
+
+
 def _with_memo(f):
     def run(ctx, scale=1):
         _memo_all()
@@ -631,7 +772,7 @@ def _with_memo(f):
 CASES = {f.__name__: _with_memo(f) for f in (
     fuse_host, fuse_rgb_host, apply_host, sort, nn_build_query, icp_loop, plane_icp_loop, select, knn_sor_ror_select, normals_knn, voxelset,
     voxelgrid, textfmt, segment_plane, tsdf, tsdf_rgb, track, track_pyramid_rgb, bilateral, project_grad, fpfh, feature_match,
-    register_ransac)}
+    register_ransac, registration_sums, color_icp, mesh_components, mesh_distance)}
 
 _NN = ["r3d_nnindex.hip", "r3d_sort.hip"]
 _TSDF = ["r3d_tsdf.hip", "r3d_tsdf_raycast.hip"]
@@ -659,5 +800,9 @@ COVERS = {
     "fpfh": _NN + ["r3d_knn.hip", "r3d_fpfh.hip"],
     "feature_match": ["r3d_fpfh.hip", "r3d_register.hip"],
     "register_ransac": ["r3d_register.hip"],
+    "registration_sums": _NN + ["r3d_reginfo.hip"],
+    "color_icp": _NN + ["r3d_knn.hip", "r3d_color_icp.hip", "r3d_icp.hip", "r3d_plane.hip", "r3d_apply.hip"],
+    "mesh_components": ["r3d_mesh_cc.hip"],
+    "mesh_distance": ["r3d_meshdist.hip", "r3d_sort.hip"],
     "not_covered_multi_device": ["r3d_comm.hip"],
 }

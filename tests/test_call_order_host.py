@@ -1,4 +1,4 @@
-"""No device: every csrc/*.hip file that claims a scratch slot of the shared context (a call to r3d_scratch) is named in the
+"""No device: every csrc/*.hip file that claims a workspace of the context (a call to r3d_scratch) is named in the
 catalogue's COVERS, so an entry point added later fails here until it has a case in tests/call_order_cases.py."""
 import glob
 import os
@@ -13,7 +13,7 @@ CSRC = os.path.join(ROOT, PKG, "csrc")
 def test_every_file_that_takes_a_scratch_slot_is_covered():
     takes = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "*.hip"))
                    if re.search(r"\br3d_scratch\(", open(p).read()))
-    assert len(takes) >= 20, takes
+    assert len(takes) >= 25, takes
     covered = {f for files in CAT.COVERS.values() for f in files}
     assert not [f for f in takes if f not in covered], "files with r3d_scratch( and no case in COVERS"
 

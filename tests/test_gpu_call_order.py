@@ -1,5 +1,5 @@
-"""GPU: results against call order.  One r3d_ctx carries nine grow-only scratch slots that some twenty entry points claim by
-number, and facts about what they hold (select_ws, loop_*, the bilateral table key, the per-device record of cached inputs).
+"""GPU: results against call order.  One r3d_ctx carries fourteen grow-only workspaces that some twenty-five source files claim by
+name (enum r3d_workspace), and facts about what they hold (select_ws, loop_*, the bilateral table key, the per-device record of cached inputs).
 Every case of tests/call_order_cases.py is run behind every other case, behind larger instances of all of them, interleaved
 on two contexts of one device and on a caller's stream: each result must be the BYTES the case gives on a context of its own
 (BASE).  Nothing here has a tolerance; the comparison with each module's restatement is inside the case, to that module's bound.

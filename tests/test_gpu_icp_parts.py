@@ -159,8 +159,8 @@ def test_selection_sequences_on_one_ctx(R, L):
     """24 -> 1 -> 32 -> 5 -> 24 -> 24 classes on one fresh context, twice with the entry points swapped (the hook in both class
     modes, r3d_trimmed_means_f32, r3d_select_quantile_f32 and its _dev form): every layout puts state words, picks or partial
     sums where another one keeps the histogram it presumes to be zero.  Every result against the reference, the second and
-    third 24-class result bitwise the first.  On the fresh context the 32-class call is also the first to outgrow scratch
-    slot 6; afterwards an untrimmed 29-sums call over 65536 pairs (one partial row per workgroup: ~59 KB against the 32-class
+    third 24-class result bitwise the first.  On the fresh context the 32-class call is also the first to outgrow
+    kWsSelect; afterwards an untrimmed 29-sums call over 65536 pairs (one partial row per workgroup: ~59 KB against the 32-class
     layout's 34 KB) and the largest n_classes x per_class so far make it grow again, and both rounds must repeat bit for bit."""
     c = R.Context(0)
     bufs = []
@@ -216,7 +216,7 @@ def test_selection_sequences_on_one_ctx(R, L):
                 assert r[4] == r[0] and r[5] == r[0]
             return res
         first = run()
-        # slot 6 grows: the untrimmed 29 sums keep one fp64 row per workgroup behind the 1-class head ...
+        # kWsSelect grows: the untrimmed 29 sums keep one fp64 row per workgroup behind the 1-class head ...
         n_src = 65536
         src, idx = c.alloc(n_src * 12), c.alloc(n_src * 4)
         one, sums = c.alloc(64), c.alloc(29 * 8)

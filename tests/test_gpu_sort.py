@@ -9,7 +9,7 @@ bit for bit -- there is no tolerance in this file:
   * the tile-counter scan (digit_scan_kernel) across its 1024-counter segments, with 256 rows (sort) and with one (selection);
   * the order-preserving row selection (r3d_select_rows) at the same sizes, outputs inside guarded allocations.
 
-Scratch slot 3 is shared by all of them and only ever grows: the stale-workspace tests run a small job behind a large one
+The workspace kWsCounts is shared by all of them and only ever grows: the stale-workspace tests run a small job behind a large one
 on ONE context, so the small job's padding counters hold the large job's numbers.
 
 tests/test_sort_host.py checks, without a device, that every input used here has the property it is named for.

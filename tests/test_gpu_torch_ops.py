@@ -605,7 +605,7 @@ OUTS = ("cam", "pix", "gpts", "gP", "gdep")
 
 def test_four_scales_in_turn_on_one_context_match_each_scale_alone(ctx, L, guard):
     """All forwards, then all backwards in reverse order (what autograd makes of trainer.py:387-390 over its scales), three
-    rounds without a synchronisation inside a round: the grad_P partials of all four scales pass through scratch slot 4."""
+    rounds without a synchronisation inside a round: the grad_P partials of all four scales pass through kWsPartials."""
     R = _r3d()
     inps = [PR.dense_inputs(*s, seed=8) for s in SCALES]
     alone = []

@@ -208,6 +208,8 @@ def test_header_has_the_section_and_the_signatures():
                    "ties going to the smallest label", "r3d_gather_rows", "R3D_ERR_UNSUPPORTED", "synchronises once"):
         assert phrase in section, phrase
     src = open(os.path.join(ROOT, PKG, "csrc", "r3d_mesh_cc.hip")).read()
-    assert "r3d_scratch(" not in src and '#include "r3d_unionfind_dev.h"' in src
+    claims = re.findall(r"r3d_scratch\(\s*ctx,\s*(\w+)", src)                      # its own workspace, none of the shared ones
+    assert claims and set(claims) == {"kWsMeshCc"} and src.count("r3d_scratch(") == len(claims)
+    assert '#include "r3d_unionfind_dev.h"' in src
     L = importlib.import_module(PKG + "._lib")
     assert "r3d_mesh_components" in L.SIGNATURES and "r3d_mesh_filter_components" in L.SIGNATURES
