@@ -1,13 +1,21 @@
-// Dense TSDF volume for gfx950 (MI355X): integration of depth frames and extraction of the zero level set as oriented points.
-// Semantics: include/r3d.h ("TSDF volume"); every output bit is a short chain of IEEE f32 operations in the order written there
-// (the library builds with -ffp-contract=off; hipcc's f32 division and sqrt are correctly rounded by default).
+// Dense TSDF volume for gfx950 (MI355X): the volume itself, integration of depth frames with or without colour images (all four
+// r3d_tsdf_integrate* entry points) and extraction of the zero level set as oriented points.  struct r3d_tsdf, the step through
+// its pose ring and the device pieces other files share are in r3d_tsdf_dev.h; the points' colours in r3d_tsdf_color.hip.
+// Semantics: include/r3d.h ("TSDF volume", "TSDF colour"); every output bit is a short chain of IEEE f32 operations in the order
+// written there (the library builds with -ffp-contract=off; hipcc's f32 division and sqrt are correctly rounded by default).
 //
 //   tsdf_integrate_kernel   one lane = two voxels that follow each other in x (one 16-byte access when nx is even, two 8-byte
 //                           ones otherwise: an odd nx leaves every second row 8-byte aligned only).  The frame loop is INSIDE:
 //                           a lane loads its pair once, applies the chunk's frames from registers in ascending order and stores
 //                           once -- and only if a frame touched it.  The per-frame pose (12 floats) is wave-uniform and comes
-//                           from a small device table through scalar loads; the depth read is a gather, neighbouring lanes
+//                           from the volume's pose ring through scalar loads; the depth read is a gather, neighbouring lanes
 //                           hitting neighbouring pixels.  No LDS, no atomics.
+//                           <COLOR> also loads the pair's two colour records {sum_r, sum_g, sum_b, n} (one 16-byte load each: a
+//                           record is 16-byte aligned whatever nx), adds the three bytes of the pixel an accepted frame read
+//                           (byte gathers: a colour row is 3 W bytes) and stores every record a frame touched, once.  The tsdf /
+//                           weight plane goes through the same statements either way, so it comes out bit-identical; the colour
+//                           plane holds integer sums, so it does not depend on the order of the frames or on how a batch is
+//                           split into calls.
 //   tsdf_count_kernel       extraction, the compaction step of r3d_compact_dev.h: surface points per tile of 4096 voxels, the
 //   tsdf_emit_kernel        tile scan, every tile writes its points at its start: linear voxel order, then x, y, z -- fixed by
 //                           construction, no atomics on the output cursor.
@@ -23,32 +31,35 @@ using namespace r3d_tsdf_dev;   // TsdfGrid, voxel indexing, crossings, emit_poi
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kChunk = R3D_TSDF_CHUNK;   // frames per launch = rows of one slot of the pose table
-constexpr int kSlots = 4;                // slots of the pose table: a call's chunks ride the ring without waiting for each other
+constexpr int kChunk = R3D_TSDF_CHUNK;   // frames per launch = rows of one slot of the pose ring
+constexpr int kSlots = r3d_tsdf::kSlots;
 using r3d_compact::kPer;                 // consecutive voxels per thread of the extraction kernels
 
-using TsdfFrame = TsdfPoseRow;   // world -> camera, f32: p_cam = R p_w + t (the ring's row type: r3d_tsdf_dev.h)
-
-// one frame into one voxel; returns whether the frame touched it (the rule itself: r3d_tsdf_dev.h's integrate_frame)
-template <typename D>
-__device__ __forceinline__ bool integrate_one(const TsdfFrame& fr, const TsdfCam& cam, const D* __restrict__ depth, float tr, float cx_,
-                                              float cy_, float cz_, float& tsdf, float& w) {
-  uint32_t pixel;
-  return integrate_frame(fr, cam, depth, tr, cx_, cy_, cz_, tsdf, w, pixel);
+__device__ __forceinline__ void add_pixel(uint4& c, const uint8_t* __restrict__ rgb, uint32_t pixel) {
+  const uint8_t* q = rgb + (size_t)pixel * 3;
+  c.x += q[0];
+  c.y += q[1];
+  c.z += q[2];
+  c.w += 1u;
 }
 
-// grid: ceil(rows * pairs_per_row / 256) workgroups; lane -> (row, pair) -> voxels x0 = 2 pair and x0 + 1 of row (y, z)
-template <typename D, bool VEC>
-__global__ __launch_bounds__(kThreads) void tsdf_integrate_kernel(float2* __restrict__ vol, TsdfGrid g, TsdfCam cam,
-                                                                  const D* __restrict__ depth, const TsdfFrame* __restrict__ table,
-                                                                  int n_frames, uint32_t pairs_per_row, uint32_t n_pairs) {
+// grid: ceil(rows * pairs_per_row / 256) workgroups; lane -> (row, pair) -> voxels x0 = 2 pair and x0 + 1 of row (y, z).
+// col, rgb: the colour plane and the frames' colour images when COLOR; unused, and NULL, otherwise (they come last, so the
+// depth-only variant finds its arguments where it would without them)
+template <typename D, bool VEC, bool COLOR>
+__global__ __launch_bounds__(kThreads) void tsdf_integrate_kernel(float2* __restrict__ vol, TsdfGrid g, TsdfCam cam, const D* __restrict__ depth,
+                                                                  const TsdfPoseRow* __restrict__ table, int n_frames,
+                                                                  uint32_t pairs_per_row, uint32_t n_pairs, uint4* __restrict__ col,
+                                                                  const uint8_t* __restrict__ rgb) {
   const uint32_t p = blockIdx.x * (uint32_t)kThreads + threadIdx.x;
   if (p >= n_pairs) return;
   const uint32_t row = p / pairs_per_row;
   const int x0 = (int)(p - row * pairs_per_row) * 2;
   const int z = (int)(row / (uint32_t)g.ny), y = (int)(row - (uint32_t)z * (uint32_t)g.ny);
   const bool has_b = x0 + 1 < g.nx;   // (always true when VEC: nx is even)
-  float2* at = vol + ((size_t)row * (size_t)g.nx + (size_t)x0);
+  const size_t i = (size_t)row * (size_t)g.nx + (size_t)x0;
+  float2* at = vol + i;
+  uint4* cat = col + i;
   float2 a, b = float2{0.0f, 0.0f};
   if (VEC) {
     const float4 q = *reinterpret_cast<const float4*>(at);
@@ -58,20 +69,35 @@ __global__ __launch_bounds__(kThreads) void tsdf_integrate_kernel(float2* __rest
     a = at[0];
     if (has_b) b = at[1];
   }
+  uint4 ca = uint4{0u, 0u, 0u, 0u}, cb = ca;
+  if constexpr (COLOR) {
+    ca = cat[0];
+    if (has_b) cb = cat[1];
+  }
   const float cxa = centre(g.ox, x0, g.vs), cxb = centre(g.ox, x0 + 1, g.vs);
   const float cy_ = centre(g.oy, y, g.vs), cz_ = centre(g.oz, z, g.vs);
   bool ta = false, tb = false;
   for (int f = 0; f < n_frames; ++f) {
-    const TsdfFrame fr = table[f];   // wave-uniform: scalar loads
+    const TsdfPoseRow fr = table[f];   // wave-uniform: scalar loads
     const D* frame = depth + (size_t)f * cam.frame_px;
-    ta |= integrate_one(fr, cam, frame, g.tr, cxa, cy_, cz_, a.x, a.y);
-    tb |= integrate_one(fr, cam, frame, g.tr, cxb, cy_, cz_, b.x, b.y);
+    const uint8_t* image = COLOR ? rgb + (size_t)f * cam.frame_px * 3 : nullptr;
+    uint32_t pixel;
+    const bool hit_a = integrate_frame(fr, cam, frame, g.tr, cxa, cy_, cz_, a.x, a.y, pixel);
+    ta |= hit_a;
+    if constexpr (COLOR) if (hit_a) add_pixel(ca, image, pixel);
+    const bool hit_b = integrate_frame(fr, cam, frame, g.tr, cxb, cy_, cz_, b.x, b.y, pixel);
+    tb |= hit_b;
+    if constexpr (COLOR) if (hit_b) add_pixel(cb, image, pixel);
   }
   if (VEC) {
     if (ta || tb) *reinterpret_cast<float4*>(at) = float4{a.x, a.y, b.x, b.y};
   } else {
     if (ta) at[0] = a;
     if (tb && has_b) at[1] = b;
+  }
+  if constexpr (COLOR) {
+    if (ta) cat[0] = ca;
+    if (tb && has_b) cat[1] = cb;
   }
 }
 
@@ -103,19 +129,6 @@ __global__ __launch_bounds__(kThreads) void tsdf_emit_kernel(const float2* __res
 
 }  // namespace
 
-struct r3d_tsdf {
-  r3d_ctx* ctx = nullptr;
-  int device = 0;   // for destroy, which must not dereference ctx
-  TsdfGrid g = {};
-  int64_t n = 0;    // voxels
-  float2* d_vol = nullptr;
-  uint4* d_col = nullptr;         // the colour plane {sum_r, sum_g, sum_b, n} of a volume created with colour, else NULL
-  TsdfFrame* d_table = nullptr;   // [kSlots][kChunk]
-  TsdfFrame* h_table = nullptr;   // the same, pinned: what the uploads read
-  hipEvent_t ev[kSlots] = {};     // slot s of h_table has been read by its upload
-  unsigned next_slot = 0;
-};
-
 static int create_volume(r3d_ctx* ctx, const double* h_origin, double voxel_size, int nx, int ny, int nz, double sdf_trunc, bool color,
                          r3d_tsdf** out) {
   R3D_REQUIRE(out != nullptr, "out is NULL");
@@ -141,8 +154,8 @@ static int create_volume(r3d_ctx* ctx, const double* h_origin, double voxel_size
   v->n = (int64_t)nx * ny * nz;
   hipError_t e = hipMalloc((void**)&v->d_vol, (size_t)v->n * sizeof(float2));
   if (e == hipSuccess && color) e = hipMalloc((void**)&v->d_col, (size_t)v->n * sizeof(uint4));
-  if (e == hipSuccess) e = hipMalloc((void**)&v->d_table, sizeof(TsdfFrame) * kSlots * kChunk);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&v->h_table, sizeof(TsdfFrame) * kSlots * kChunk, hipHostMallocDefault);
+  if (e == hipSuccess) e = hipMalloc((void**)&v->d_table, sizeof(TsdfPoseRow) * kSlots * kChunk);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&v->h_table, sizeof(TsdfPoseRow) * kSlots * kChunk, hipHostMallocDefault);
   for (int s = 0; s < kSlots && e == hipSuccess; ++s) e = hipEventCreateWithFlags(&v->ev[s], hipEventDisableTiming);
   if (e != hipSuccess) {
     r3d_tsdf_destroy(v);
@@ -191,54 +204,12 @@ int r3d_tsdf_reset(r3d_tsdf* v) {
   return R3D_OK;
 }
 
-int r3d_tsdf_device_view(r3d_tsdf* v, r3d_ctx** ctx, TsdfGrid* grid, const float2** d_vol, int64_t* n_voxels) {
-  R3D_REQUIRE(v != nullptr, "TSDF volume is NULL");
-  *ctx = v->ctx;
-  *grid = v->g;
-  *d_vol = v->d_vol;
-  *n_voxels = v->n;
-  return R3D_OK;
-}
-
-int r3d_tsdf_pose_slot(r3d_tsdf* v, TsdfPoseRow** h_rows, TsdfPoseRow** d_rows, hipEvent_t* ev) {
-  R3D_REQUIRE(v != nullptr, "TSDF volume is NULL");
-  const unsigned s = v->next_slot++ % kSlots;
-  *h_rows = v->h_table + (size_t)s * kChunk;
-  *d_rows = v->d_table + (size_t)s * kChunk;
-  *ev = v->ev[s];
-  return R3D_OK;
-}
-
-int r3d_tsdf_color_plane(r3d_tsdf* v, uint4** d_col) {
-  R3D_REQUIRE(v != nullptr, "TSDF volume is NULL");
-  *d_col = v->d_col;
-  return R3D_OK;
-}
-
 int r3d_tsdf_volume(r3d_tsdf* v, float** d_tsdf_weight_out, int64_t* n_voxels_out) {
   R3D_REQUIRE(v != nullptr, "TSDF volume is NULL");
   if (d_tsdf_weight_out) *d_tsdf_weight_out = reinterpret_cast<float*>(v->d_vol);
   if (n_voxels_out) *n_voxels_out = v->n;
   return R3D_OK;
 }
-
-namespace {
-
-template <typename D>
-void launch_integrate(r3d_tsdf* v, const TsdfCam& cam, const void* d_depth, const TsdfFrame* table, int n) {
-  const TsdfGrid& g = v->g;
-  const uint32_t ppr = ((uint32_t)g.nx + 1) / 2;
-  const uint32_t n_pairs = ppr * (uint32_t)((int64_t)g.ny * g.nz);   // <= nx ny nz < 2^31
-  const dim3 grid((n_pairs + kThreads - 1) / kThreads), block(kThreads);
-  if (g.nx % 2 == 0)
-    hipLaunchKernelGGL((tsdf_integrate_kernel<D, true>), grid, block, 0, v->ctx->stream, v->d_vol, g, cam, static_cast<const D*>(d_depth),
-                       table, n, ppr, n_pairs);
-  else
-    hipLaunchKernelGGL((tsdf_integrate_kernel<D, false>), grid, block, 0, v->ctx->stream, v->d_vol, g, cam, static_cast<const D*>(d_depth),
-                       table, n, ppr, n_pairs);
-}
-
-}  // namespace
 
 int r3d_tsdf_integrate_checks(r3d_tsdf* v, const r3d_camera* cam, const void* depth, int depth_dtype, int n_frames, double depth_scale,
                               const double* h_pose) {
@@ -257,76 +228,114 @@ int r3d_tsdf_integrate_checks(r3d_tsdf* v, const r3d_camera* cam, const void* de
 
 namespace {
 
-// the depth-only entry points refuse a volume with a colour plane: its n would part from its w
-int integrate_checks(r3d_tsdf* v, const r3d_camera* cam, const void* depth, int depth_dtype, int n_frames, double depth_scale,
-                     const double* h_pose) {
-  R3D_REQUIRE(v == nullptr || v->d_col == nullptr, "the volume carries colour: integrate it with r3d_tsdf_integrate_rgb");
-  return r3d_tsdf_integrate_checks(v, cam, depth, depth_dtype, n_frames, depth_scale, h_pose);
+// d_rgb: the chunk's colour images for the COLOR kernel into v->d_col, or NULL for the depth-only one (v->d_col is NULL then)
+template <typename D>
+void launch_integrate(r3d_tsdf* v, const TsdfCam& cam, const void* d_depth, const uint8_t* d_rgb, const TsdfPoseRow* table, int n) {
+  const TsdfGrid& g = v->g;
+  const uint32_t ppr = ((uint32_t)g.nx + 1) / 2;
+  const uint32_t n_pairs = ppr * (uint32_t)((int64_t)g.ny * g.nz);   // <= nx ny nz < 2^31
+  const dim3 grid((n_pairs + kThreads - 1) / kThreads), block(kThreads);
+  const bool vec = g.nx % 2 == 0;
+  const auto kernel = d_rgb ? (vec ? tsdf_integrate_kernel<D, true, true> : tsdf_integrate_kernel<D, false, true>)
+                            : (vec ? tsdf_integrate_kernel<D, true, false> : tsdf_integrate_kernel<D, false, false>);
+  hipLaunchKernelGGL(kernel, grid, block, 0, v->ctx->stream, v->d_vol, g, cam, static_cast<const D*>(d_depth), table, n, ppr, n_pairs,
+                     v->d_col, d_rgb);
 }
 
-// the launches of one batch whose rasters are in HBM; asynchronous
-int integrate_device(r3d_tsdf* v, const r3d_camera* cam, const void* d_depth, int depth_dtype, int n_frames, double depth_scale,
-                     const double* h_pose) {
-  r3d_ctx* ctx = v->ctx;
+TsdfCam tsdf_cam_of(const r3d_camera* cam, double depth_scale) {
   TsdfCam c;
   c.fx = (float)cam->fx, c.fy = (float)cam->fy, c.cx = (float)cam->cx, c.cy = (float)cam->cy;
   c.wf = (float)cam->width, c.hf = (float)cam->height, c.scale = (float)depth_scale;
   c.width = cam->width;
   c.frame_px = (uint32_t)cam->height * (uint32_t)cam->width;
+  return c;
+}
+
+// the launches of one batch whose rasters (and colour images, unless d_rgb is NULL) are in HBM; asynchronous
+int integrate_device(r3d_tsdf* v, const r3d_camera* cam, const void* d_depth, int depth_dtype, int n_frames, double depth_scale,
+                     const double* h_pose, const uint8_t* d_rgb) {
+  const TsdfCam c = tsdf_cam_of(cam, depth_scale);
   const size_t frame_bytes = (size_t)c.frame_px * r3d_depth_size(depth_dtype);
   for (int lo = 0; lo < n_frames; lo += kChunk) {
     const int n = n_frames - lo < kChunk ? n_frames - lo : kChunk;
-    const unsigned s = v->next_slot++ % kSlots;
-    R3D_HIP(hipEventSynchronize(v->ev[s]));   // the upload that read this slot of the pinned table last is done (never recorded: returns at once)
-    TsdfFrame* h = v->h_table + (size_t)s * kChunk;
-    for (int f = 0; f < n; ++f) {
-      const double* p = h_pose + (size_t)(lo + f) * 12;
-      for (int k = 0; k < 9; ++k) h[f].r[k] = (float)p[k];
-      for (int k = 0; k < 3; ++k) h[f].t[k] = (float)p[9 + k];
-      for (int k = 0; k < 4; ++k) h[f].pad[k] = 0.0f;
-    }
-    TsdfFrame* d = v->d_table + (size_t)s * kChunk;
-    R3D_HIP(hipMemcpyAsync(d, h, sizeof(TsdfFrame) * n, hipMemcpyHostToDevice, ctx->stream));
-    R3D_HIP(hipEventRecord(v->ev[s], ctx->stream));
+    const TsdfPoseRow* d = nullptr;
+    int rc = r3d_tsdf_send_rows(v, n, &d, [&](TsdfPoseRow* h) {
+      for (int f = 0; f < n; ++f) {
+        const double* p = h_pose + (size_t)(lo + f) * 12;
+        for (int k = 0; k < 9; ++k) h[f].r[k] = (float)p[k];
+        for (int k = 0; k < 3; ++k) h[f].t[k] = (float)p[9 + k];
+        for (int k = 0; k < 4; ++k) h[f].pad[k] = 0.0f;
+      }
+    });
+    if (rc) return rc;
     const void* depth = static_cast<const char*>(d_depth) + (size_t)lo * frame_bytes;
-    if (depth_dtype == R3D_DEPTH_U8) launch_integrate<uint8_t>(v, c, depth, d, n);
-    else if (depth_dtype == R3D_DEPTH_U16) launch_integrate<uint16_t>(v, c, depth, d, n);
-    else launch_integrate<float>(v, c, depth, d, n);
+    const uint8_t* rgb = d_rgb ? d_rgb + (size_t)lo * c.frame_px * 3 : nullptr;
+    if (depth_dtype == R3D_DEPTH_U8) launch_integrate<uint8_t>(v, c, depth, rgb, d, n);
+    else if (depth_dtype == R3D_DEPTH_U16) launch_integrate<uint16_t>(v, c, depth, rgb, d, n);
+    else launch_integrate<float>(v, c, depth, rgb, d, n);
     R3D_HIP(hipGetLastError());
   }
   return R3D_OK;
+}
+
+// The same for a batch in host memory: it goes up in slabs of whole frames through kWsIn, a slab's rasters first, then (unless
+// h_rgb is NULL) its colour images at a 256-byte boundary; every slab is one integrate_device call.
+int integrate_host(r3d_tsdf* v, const r3d_camera* cam, const void* h_depth, int depth_dtype, int n_frames, double depth_scale,
+                   const double* h_pose, const uint8_t* h_rgb) {
+  r3d_ctx* ctx = v->ctx;
+  const size_t px = (size_t)cam->height * cam->width;
+  const size_t depth_bytes = px * r3d_depth_size(depth_dtype), rgb_bytes = h_rgb ? px * 3 : 0, frame_bytes = depth_bytes + rgb_bytes;
+  int slab = (int)(((size_t)256 << 20) / (frame_bytes ? frame_bytes : 1));
+  if (slab < 1) slab = 1;
+  if (slab > n_frames) slab = n_frames;
+  const size_t rgb_at = h_rgb ? r3d_align_up((size_t)slab * depth_bytes, 256) : (size_t)slab * depth_bytes;
+  void* d_in = nullptr;
+  int rc = r3d_scratch(ctx, kWsIn, rgb_at + (size_t)slab * rgb_bytes, &d_in);
+  if (rc) return rc;
+  uint8_t* d_rgb = h_rgb ? static_cast<uint8_t*>(d_in) + rgb_at : nullptr;
+  for (int lo = 0; lo < n_frames; lo += slab) {
+    const int n = n_frames - lo < slab ? n_frames - lo : slab;
+    if ((rc = r3d_memcpy_h2d(ctx, d_in, static_cast<const char*>(h_depth) + (size_t)lo * depth_bytes, (size_t)n * depth_bytes))) return rc;
+    if (h_rgb && (rc = r3d_memcpy_h2d(ctx, d_rgb, h_rgb + (size_t)lo * rgb_bytes, (size_t)n * rgb_bytes))) return rc;
+    if ((rc = integrate_device(v, cam, d_in, depth_dtype, n, depth_scale, h_pose + (size_t)lo * 12, d_rgb))) return rc;
+    R3D_HIP(hipStreamSynchronize(ctx->stream));   // the next slab overwrites the scratch; the caller's memory is free at return
+  }
+  return R3D_OK;
+}
+
+// All four entry points.  rgb_call: the two that take colour images -- the volume must own the colour plane, and the depth-only
+// two refuse one that does: its n would part from its w.
+int integrate(r3d_tsdf* v, const r3d_camera* cam, const void* depth, int depth_dtype, int n_frames, double depth_scale, const double* h_pose,
+              const uint8_t* rgb, bool rgb_call, bool host) {
+  int rc = R3D_OK;
+  if (rgb_call && (rc = r3d_tsdf_require_color(v))) return rc;
+  R3D_REQUIRE(rgb_call || v == nullptr || v->d_col == nullptr, "the volume carries colour: integrate it with r3d_tsdf_integrate_rgb");
+  if ((rc = r3d_tsdf_integrate_checks(v, cam, depth, depth_dtype, n_frames, depth_scale, h_pose)) || n_frames == 0) return rc;
+  R3D_REQUIRE(!rgb_call || rgb != nullptr, "NULL colour pointer");
+  if ((rc = r3d_ctx_enter(v->ctx))) return rc;
+  return (host ? integrate_host : integrate_device)(v, cam, depth, depth_dtype, n_frames, depth_scale, h_pose, rgb);
 }
 
 }  // namespace
 
 int r3d_tsdf_integrate(r3d_tsdf* v, const r3d_camera* cam, const void* d_depth, int depth_dtype, int n_frames, double depth_scale,
                        const double* h_pose_w2c) {
-  int rc = integrate_checks(v, cam, d_depth, depth_dtype, n_frames, depth_scale, h_pose_w2c);
-  if (rc || n_frames == 0) return rc;
-  if ((rc = r3d_ctx_enter(v->ctx))) return rc;
-  return integrate_device(v, cam, d_depth, depth_dtype, n_frames, depth_scale, h_pose_w2c);
+  return integrate(v, cam, d_depth, depth_dtype, n_frames, depth_scale, h_pose_w2c, nullptr, false, false);
 }
 
 int r3d_tsdf_integrate_host(r3d_tsdf* v, const r3d_camera* cam, const void* h_depth, int depth_dtype, int n_frames, double depth_scale,
                             const double* h_pose_w2c) {
-  int rc = integrate_checks(v, cam, h_depth, depth_dtype, n_frames, depth_scale, h_pose_w2c);
-  if (rc || n_frames == 0) return rc;
-  r3d_ctx* ctx = v->ctx;
-  if ((rc = r3d_ctx_enter(ctx))) return rc;
-  // the batch goes up in slabs of whole frames through kWsIn; every slab is one integrate call
-  const size_t frame_bytes = (size_t)cam->height * cam->width * r3d_depth_size(depth_dtype);
-  int slab = (int)(((size_t)256 << 20) / (frame_bytes ? frame_bytes : 1));
-  if (slab < 1) slab = 1;
-  if (slab > n_frames) slab = n_frames;
-  void* d_in = nullptr;
-  if ((rc = r3d_scratch(ctx, kWsIn, (size_t)slab * frame_bytes, &d_in))) return rc;
-  for (int lo = 0; lo < n_frames; lo += slab) {
-    const int n = n_frames - lo < slab ? n_frames - lo : slab;
-    if ((rc = r3d_memcpy_h2d(ctx, d_in, static_cast<const char*>(h_depth) + (size_t)lo * frame_bytes, (size_t)n * frame_bytes))) return rc;
-    if ((rc = integrate_device(v, cam, d_in, depth_dtype, n, depth_scale, h_pose_w2c + (size_t)lo * 12))) return rc;
-    R3D_HIP(hipStreamSynchronize(ctx->stream));   // the next slab overwrites the scratch; the caller's memory is free at return
-  }
-  return R3D_OK;
+  return integrate(v, cam, h_depth, depth_dtype, n_frames, depth_scale, h_pose_w2c, nullptr, false, true);
+}
+
+int r3d_tsdf_integrate_rgb(r3d_tsdf* v, const r3d_camera* cam, const void* d_depth, int depth_dtype, int n_frames, double depth_scale,
+                           const double* h_pose_w2c, const uint8_t* d_rgb) {
+  return integrate(v, cam, d_depth, depth_dtype, n_frames, depth_scale, h_pose_w2c, d_rgb, true, false);
+}
+
+int r3d_tsdf_integrate_rgb_host(r3d_tsdf* v, const r3d_camera* cam, const void* h_depth, int depth_dtype, int n_frames, double depth_scale,
+                                const double* h_pose_w2c, const uint8_t* h_rgb) {
+  return integrate(v, cam, h_depth, depth_dtype, n_frames, depth_scale, h_pose_w2c, h_rgb, true, true);
 }
 
 int r3d_tsdf_count_points(r3d_tsdf* v, float mw, const uint32_t** d_prefix, int* tiles_out, int64_t* n_points) {
@@ -352,18 +361,14 @@ int r3d_tsdf_count_points(r3d_tsdf* v, float mw, const uint32_t** d_prefix, int*
 }
 
 int r3d_tsdf_extract_points(r3d_tsdf* v, double min_weight, float* d_xyz_out, float* d_normals_out, int64_t cap, int64_t* n_out) {
-  R3D_REQUIRE(v != nullptr, "TSDF volume is NULL");
-  R3D_REQUIRE(n_out != nullptr, "n_out is NULL");
-  const float mw = (float)min_weight;
-  R3D_REQUIRE(mw > 0.0f, "min_weight must be > 0 in f32");
-  R3D_REQUIRE(cap >= 0, "cap must be >= 0");
-  R3D_REQUIRE(cap == 0 || d_xyz_out != nullptr, "d_xyz_out is NULL with cap > 0");
+  float mw = 0.0f;
+  int rc = r3d_tsdf_extract_checks(v, n_out != nullptr, "n_out", min_weight, &mw, "cap", {{d_xyz_out, cap, "d_xyz_out", "cap"}});
+  if (rc) return rc;
   r3d_ctx* ctx = v->ctx;
   const uint32_t* hist = nullptr;
   int tiles = 0;
   int64_t m = 0;
-  int rc = r3d_tsdf_count_points(v, mw, &hist, &tiles, &m);
-  if (rc) return rc;
+  if ((rc = r3d_tsdf_count_points(v, mw, &hist, &tiles, &m))) return rc;
   hipStream_t st = ctx->stream;
   *n_out = m;
   const uint64_t rows = (uint64_t)(m < cap ? m : cap);

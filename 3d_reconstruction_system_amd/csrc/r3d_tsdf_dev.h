@@ -1,8 +1,10 @@
-// Device-side pieces of the TSDF volume's surface extraction that r3d_tsdf.hip (points) and r3d_tsdf_mesh.hip (indexed triangle
-// mesh) share: voxel indexing, the crossing predicate and the surface point of a crossing.  The mesh's vertices ARE the points,
-// bit for bit, so both files emit them through emit_points below.  Semantics: include/r3d.h ("TSDF volume").
-// Also the one statement of the per-frame integration rule (integrate_frame), which the depth-only kernels of r3d_tsdf.hip and the
-// colour kernel of r3d_tsdf_color.hip both apply, and the colour of a surface point (emit_colors; "TSDF colour").
+// What the TSDF volume's sources share (r3d_tsdf.hip, r3d_tsdf_color.hip, r3d_tsdf_mesh.hip, r3d_tsdf_raycast.hip, r3d_track.hip).
+// Internal to libr3d_hip.so.  Semantics: include/r3d.h ("TSDF volume", "TSDF colour").
+//   device   voxel indexing, the crossing predicate and the surface point of a crossing (emit_points: the mesh's vertices ARE the
+//            points, bit for bit), the colour of a surface point (emit_colors), the cell loads of ray casting, and the one
+//            statement of the per-frame integration rule (integrate_frame);
+//   host     struct r3d_tsdf itself, the one step through its pose ring (r3d_tsdf_send_rows), and the argument checks that more
+//            than one entry point makes.
 #pragma once
 
 #include "r3d_internal.h"
@@ -11,8 +13,7 @@
 
 #include <cmath>
 #include <cstdint>
-
-struct r3d_tsdf;
+#include <initializer_list>
 
 namespace r3d_tsdf_dev {
 
@@ -21,7 +22,7 @@ struct TsdfGrid {
   float ox, oy, oz, vs, tr;
 };
 
-// One row of the volume's pose ring (r3d_tsdf.hip), f32, 64 bytes: the world -> camera rotation, row-major, and a vector t --
+// One row of the volume's pose ring (r3d_tsdf below), f32, 64 bytes: the world -> camera rotation, row-major, and a vector t --
 // the pose's translation for integration (p_cam = R p_w + t), the camera centre in the world for ray casting.
 struct TsdfPoseRow {
   float r[9];
@@ -38,8 +39,8 @@ struct TsdfCam {
   uint32_t frame_px;   // height * width
 };
 
-// One frame into one voxel; returns whether the frame touched it, and then *pixel = vi * width + ui, the pixel it read (the
-// colour kernel gathers the same pixel of the colour image; the depth-only kernels drop it).
+// One frame into one voxel; returns whether the frame touched it, and then pixel = vi * width + ui, the pixel it read (the
+// integration kernel's colour variant gathers the same pixel of the colour image; the depth-only one drops it).
 template <typename D>
 __device__ __forceinline__ bool integrate_frame(const TsdfPoseRow& fr, const TsdfCam& cam, const D* __restrict__ depth, float tr, float cx_,
                                                 float cy_, float cz_, float& tsdf, float& w, uint32_t& pixel) {
@@ -202,15 +203,61 @@ __device__ __forceinline__ float trilinear(const float (&T)[8], const float (&f)
 
 }  // namespace r3d_tsdf_dev
 
-// r3d_tsdf.hip: what a kernel outside that file needs to read a volume (r3d_tsdf_mesh.hip)
-int r3d_tsdf_device_view(r3d_tsdf* vol, r3d_ctx** ctx, r3d_tsdf_dev::TsdfGrid* grid, const float2** d_vol, int64_t* n_voxels);
-// r3d_tsdf.hip: the next slot of the volume's pose ring for a launch outside that file (r3d_tsdf_raycast.hip).  A slot is
-// R3D_TSDF_CHUNK rows, pinned (*h_rows) and in HBM (*d_rows).  The caller keeps the integrate path's discipline:
-// hipEventSynchronize(*ev), fill the pinned rows, hipMemcpyAsync them to *d_rows on the ctx stream, hipEventRecord(*ev) there.
-int r3d_tsdf_pose_slot(r3d_tsdf* vol, r3d_tsdf_dev::TsdfPoseRow** h_rows, r3d_tsdf_dev::TsdfPoseRow** d_rows, hipEvent_t* ev);
-// r3d_tsdf.hip, for r3d_tsdf_color.hip: the colour plane ([n_voxels] uint4 {sum_r, sum_g, sum_b, n}), NULL for a volume without;
-int r3d_tsdf_color_plane(r3d_tsdf* vol, uint4** d_col);
-// the argument checks r3d_tsdf_integrate makes (R3D_OK with n_frames == 0 too: the caller returns then);
+struct r3d_tsdf {
+  static constexpr int kSlots = 4;   // slots of the pose ring: a call's chunks ride it without waiting for each other
+  r3d_ctx* ctx = nullptr;
+  int device = 0;   // for destroy, which must not dereference ctx
+  r3d_tsdf_dev::TsdfGrid g = {};
+  int64_t n = 0;    // voxels
+  float2* d_vol = nullptr;
+  uint4* d_col = nullptr;                         // the colour plane {sum_r, sum_g, sum_b, n} of a volume created with colour, else NULL
+  r3d_tsdf_dev::TsdfPoseRow* d_table = nullptr;   // the pose ring: [kSlots][R3D_TSDF_CHUNK]
+  r3d_tsdf_dev::TsdfPoseRow* h_table = nullptr;   // the same, pinned: what the uploads read
+  hipEvent_t ev[kSlots] = {};                     // slot s of h_table has been read by its upload
+  unsigned next_slot = 0;
+};
+
+// One step through the volume's pose ring, for every launch that reads poses: takes the next slot, waits until the upload that
+// read its pinned rows last is done (an event never recorded returns at once), has fill(rows) write n <= R3D_TSDF_CHUNK of them,
+// sends them on the ctx stream and records the slot's event there.  *d_rows: the rows in HBM.
+template <typename Fill>
+int r3d_tsdf_send_rows(r3d_tsdf* v, int n, const r3d_tsdf_dev::TsdfPoseRow** d_rows, Fill fill) {
+  const size_t s = v->next_slot++ % r3d_tsdf::kSlots;
+  R3D_HIP(hipEventSynchronize(v->ev[s]));
+  r3d_tsdf_dev::TsdfPoseRow *h = v->h_table + s * R3D_TSDF_CHUNK, *d = v->d_table + s * R3D_TSDF_CHUNK;
+  fill(h);
+  R3D_HIP(hipMemcpyAsync(d, h, sizeof(*h) * n, hipMemcpyHostToDevice, v->ctx->stream));
+  R3D_HIP(hipEventRecord(v->ev[s], v->ctx->stream));
+  *d_rows = d;
+  return R3D_OK;
+}
+
+// R3D_ERR_INVALID unless the volume is there and was created with the colour plane
+inline int r3d_tsdf_require_color(const r3d_tsdf* v) {
+  R3D_REQUIRE(v != nullptr, "TSDF volume is NULL");
+  R3D_REQUIRE(v->d_col != nullptr, "the volume was created without colour (r3d_tsdf_create_rgb makes one with)");
+  return R3D_OK;
+}
+
+// What r3d_tsdf_extract_points, _colors and _mesh check first, in this order: the volume, the count pointers (have_counts; counts
+// names them), min_weight (*mw: in f32), every output's cap (caps names them all), every output's pointer.
+struct r3d_tsdf_out {
+  const void* p;
+  int64_t cap;
+  const char *name, *cap_name;
+};
+inline int r3d_tsdf_extract_checks(const r3d_tsdf* v, bool have_counts, const char* counts, double min_weight, float* mw, const char* caps,
+                                   std::initializer_list<r3d_tsdf_out> outs) {
+  R3D_REQUIRE(v != nullptr, "TSDF volume is NULL");
+  R3D_REQUIRE(have_counts, "%s is NULL", counts);
+  *mw = (float)min_weight;
+  R3D_REQUIRE(*mw > 0.0f, "min_weight must be > 0 in f32");
+  for (const r3d_tsdf_out& o : outs) R3D_REQUIRE(o.cap >= 0, "%s must be >= 0", caps);
+  for (const r3d_tsdf_out& o : outs) R3D_REQUIRE(o.cap == 0 || o.p != nullptr, "%s is NULL with %s > 0", o.name, o.cap_name);
+  return R3D_OK;
+}
+
+// r3d_tsdf.hip: the argument checks r3d_tsdf_integrate makes (R3D_OK with n_frames == 0 too: the caller returns then);
 int r3d_tsdf_integrate_checks(r3d_tsdf* vol, const r3d_camera* cam, const void* depth, int depth_dtype, int n_frames, double depth_scale,
                               const double* h_pose);
 // and the first half of r3d_tsdf_extract_points: tsdf_count_kernel + the tile scan into kWsCounts, the count read back

@@ -196,17 +196,13 @@ int raycast(r3d_tsdf* v, const r3d_camera* cam, int n_views, const double* h_pos
             double t_far, float* d_depth_out, float* d_vertex_out, float* d_normal_out, uint8_t* d_rgb_out, bool rgb_call) {
   R3D_REQUIRE(v != nullptr, "TSDF volume is NULL");
   R3D_REQUIRE(cam != nullptr, "camera is NULL");
-  r3d_ctx* ctx = nullptr;
-  TsdfGrid g;
-  const float2* vol = nullptr;
-  int64_t n = 0;
-  int rc = r3d_tsdf_device_view(v, &ctx, &g, &vol, &n);
-  if (rc) return rc;
-  uint4* col = nullptr;
-  if (rgb_call) {
-    if ((rc = r3d_tsdf_color_plane(v, &col))) return rc;
-    R3D_REQUIRE(col != nullptr, "the volume was created without colour (r3d_tsdf_create_rgb makes one with)");
-  }
+  int rc = R3D_OK;
+  if (rgb_call && (rc = r3d_tsdf_require_color(v))) return rc;
+  r3d_ctx* ctx = v->ctx;
+  const TsdfGrid& g = v->g;
+  const float2* vol = v->d_vol;
+  const uint4* col = rgb_call ? v->d_col : nullptr;
+  const int64_t n = v->n;
   R3D_REQUIRE(cam->ctx == ctx, "the camera belongs to another context than the volume");
   R3D_REQUIRE(n_views >= 0, "n_views must be >= 0");
   RayMarch m;
@@ -248,29 +244,27 @@ int raycast(r3d_tsdf* v, const r3d_camera* cam, int n_views, const double* h_pos
     if (out[a].p) r3d_wrote(ctx, out[a].p, out[a].bytes);
   for (int lo = 0; lo < n_views; lo += kChunk) {
     const int nv = n_views - lo < kChunk ? n_views - lo : kChunk;
-    TsdfPoseRow *h = nullptr, *d_rows = nullptr;
-    hipEvent_t ev = nullptr;
-    if ((rc = r3d_tsdf_pose_slot(v, &h, &d_rows, &ev))) return rc;
-    R3D_HIP(hipEventSynchronize(ev));   // the upload that read this slot of the pinned ring last is done
-    for (int f = 0; f < nv; ++f) {
-      const double* R = h_pose_w2c + (size_t)(lo + f) * 12;
-      const double* t = R + 9;
-      for (int k = 0; k < 9; ++k) h[f].r[k] = (float)R[k];
-      for (int k = 0; k < 3; ++k) h[f].t[k] = (float)(-((R[k] * t[0] + R[3 + k] * t[1]) + R[6 + k] * t[2]));   // C = -R^T t, in double
-      for (int k = 0; k < 4; ++k) h[f].pad[k] = 0.0f;
-    }
-    R3D_HIP(hipMemcpyAsync(d_rows, h, sizeof(TsdfPoseRow) * nv, hipMemcpyHostToDevice, ctx->stream));
-    R3D_HIP(hipEventRecord(ev, ctx->stream));
+    const TsdfPoseRow* d_rows = nullptr;
+    rc = r3d_tsdf_send_rows(v, nv, &d_rows, [&](TsdfPoseRow* h) {
+      for (int f = 0; f < nv; ++f) {
+        const double* R = h_pose_w2c + (size_t)(lo + f) * 12;
+        const double* t = R + 9;
+        for (int k = 0; k < 9; ++k) h[f].r[k] = (float)R[k];
+        for (int k = 0; k < 3; ++k) h[f].t[k] = (float)(-((R[k] * t[0] + R[3 + k] * t[1]) + R[6 + k] * t[2]));   // C = -R^T t, in double
+        for (int k = 0; k < 4; ++k) h[f].pad[k] = 0.0f;
+      }
+    });
+    if (rc) return rc;
     const size_t at = (size_t)lo * c.frame_px;
     float* depth = d_depth_out ? d_depth_out + at : nullptr;
     float* vertex = d_vertex_out ? d_vertex_out + 3 * at : nullptr;
     float* normal = d_normal_out ? d_normal_out + 3 * at : nullptr;
     if (d_rgb_out)
-      hipLaunchKernelGGL(tsdf_raycast_kernel<true>, dim3(tiles, 1, (unsigned)nv), dim3(kThreads), 0, ctx->stream, vol, (const uint4*)col, g,
-                         c, (const TsdfPoseRow*)d_rows, m, depth, vertex, normal, d_rgb_out + 3 * at);
+      hipLaunchKernelGGL(tsdf_raycast_kernel<true>, dim3(tiles, 1, (unsigned)nv), dim3(kThreads), 0, ctx->stream, vol, col, g, c, d_rows, m,
+                         depth, vertex, normal, d_rgb_out + 3 * at);
     else
       hipLaunchKernelGGL(tsdf_raycast_kernel<false>, dim3(tiles, 1, (unsigned)nv), dim3(kThreads), 0, ctx->stream, vol, (const uint4*)nullptr, g,
-                         c, (const TsdfPoseRow*)d_rows, m, depth, vertex, normal, (uint8_t*)nullptr);
+                         c, d_rows, m, depth, vertex, normal, (uint8_t*)nullptr);
     R3D_HIP(hipGetLastError());
   }
   return R3D_OK;

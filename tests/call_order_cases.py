@@ -794,7 +794,7 @@ COVERS = {
     "tsdf": _TSDF + ["r3d_tsdf_mesh.hip"],
     "tsdf_rgb": _TSDF + ["r3d_tsdf_color.hip"],
     "track": _TSDF + ["r3d_track.hip", "r3d_backproject.hip"],
-    "track_pyramid_rgb": _TSDF + ["r3d_tsdf_color.hip", "r3d_track.hip", "r3d_pyramid.hip", "r3d_photo.hip"],
+    "track_pyramid_rgb": _TSDF + ["r3d_track.hip", "r3d_pyramid.hip", "r3d_photo.hip"],
     "bilateral": ["r3d_bilateral.hip"],
     "project_grad": ["r3d_backproject.hip"],
     "fpfh": _NN + ["r3d_knn.hip", "r3d_fpfh.hip"],

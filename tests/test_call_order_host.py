@@ -13,7 +13,7 @@ CSRC = os.path.join(ROOT, PKG, "csrc")
 def test_every_file_that_takes_a_scratch_slot_is_covered():
     takes = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "*.hip"))
                    if re.search(r"\br3d_scratch\(", open(p).read()))
-    assert len(takes) >= 25, takes
+    assert len(takes) >= 24, takes   # (25 while r3d_tsdf_color.hip had a host-slab uploader of its own: r3d_tsdf.hip's serves both now)
     covered = {f for files in CAT.COVERS.values() for f in files}
     assert not [f for f in takes if f not in covered], "files with r3d_scratch( and no case in COVERS"
 

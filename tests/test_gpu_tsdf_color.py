@@ -216,6 +216,38 @@ def test_call_forms_agree(T, L, ctx, dims, n_frames):
         v.close()
 
 
+def test_two_volumes_and_ray_casts_take_turns_on_one_context(T, ctx):
+    """The same 33 frames into a plain and a colour volume of one context in chunks of 17 and 16 -- plain, colour, plain, colour,
+    nothing waited for in between -- and one ray cast of the colour volume behind each pair: every integrate call and every ray
+    cast takes the next slot of its volume's pose ring (four slots: the colour volume uses them all), through the one driver both
+    kinds of volume share."""
+    import raycast_ref as RC
+    from test_gpu_raycast import assert_maps, cast, poses_around, raster_K
+    cut, shape = 17, (24, 32)
+    s, rgb, ref, _ = scene((33, 9, 5), 33, np.uint8, seed=31)
+    head = dict(s, depths=s["depths"][:cut], poses=s["poses"][:cut])
+    ref_head = CREF.run(head, rgb[:cut])[0]                  # the colour volume's state at the first ray cast
+    K, view = raster_K(shape), poses_around(ref, 1, 31)
+    plain = T.TSDFVolume(s["origin"], s["vs"], s["dims"], s["tr"], ctx=ctx)
+    V = color_volume(T, ctx, s)
+    cam = ctx.camera(*shape, *s["K"])
+    d_depth, d_rgb = ctx.alloc(s["depths"].nbytes).upload(s["depths"]), ctx.alloc(rgb.nbytes).upload(rgb)
+    px = shape[0] * shape[1]
+    for lo, hi, state in ((0, cut, ref_head), (cut, 33, ref)):
+        plain.integrate_device(cam, d_depth.ptr + lo * px, np.uint8, hi - lo, s["poses"][lo:hi], s["scale"])
+        V.integrate_device(cam, d_depth.ptr + lo * px, np.uint8, hi - lo, s["poses"][lo:hi], s["scale"], d_rgb=d_rgb.ptr + lo * px * 3)
+        want = RC.raycast(state, view, K, shape)
+        assert RC.hits(want[1]).any()
+        assert_maps(cast(ctx, V, view, K, shape), want)
+    assert_planes(V, ref)
+    tsdf, w = plain.volume()
+    assert np.array_equal(w, ref.w) and np.array_equal(bits(tsdf), bits(ref.tsdf))
+    for b in (d_depth, d_rgb):
+        b.free()
+    for v in (plain, V):
+        v.close()
+
+
 def test_reset_clears_both_planes(T, ctx):
     s, rgb, ref, passed = scene((33, 9, 5), 5, np.uint16, seed=11)
     V = color_volume(T, ctx, s)
