@@ -212,6 +212,9 @@ SIGNATURES = {
     "r3d_distance_stats": (_i, [_vp, _vp, _i64, _i, _vp, _i, _d, _i, _vp, _vp, _vp]),
     "r3d_sqrt_f32_inplace": (_i, [_vp, _vp, _i64]),
     "r3d_distance_colors": (_i, [_vp, _vp, _i64, _d, _vp]),
+    "r3d_depth_consistency": (_i, [_vp, _vp, _vp, _i, _i, _d, _vp, _vp, _i, _d, _i, _i, _vp, _vp, _vp]),
+    "r3d_depth_consistency_host": (_i, [_vp, _vp, _vp, _i, _i, _d, _vp, _vp, _i, _d, _i, _i, _vp, _vp, _vp]),
+    "r3d_compact_rows_by_mask": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
 }
 
 _lib = None

@@ -16,14 +16,15 @@
 // The context's grow-only device workspaces (r3d_ctx::scratch), claimed by name through r3d_scratch.  A SHARED entry is taken by
 // many entry points one after the other in stream order; nobody may expect to find in it what an earlier call left (tests/
 // test_gpu_call_order.py), and a helper takes one only if no caller above it holds data there.  A PRIVATE entry is one file's.
-//   kWsIn          shared   staged input of the *_host calls (fuse, apply, ICP source, voxel and grid points); TSDF slabs; NN sort
-//                           keys; FPFH k-NN lists; r3d_register_ransac's gathered pairs; octree records; the voxel union's list
-//   kWsOut         shared   staged output of the *_host calls (ICP: the target); the sorted voxel codes; NN query `src4` / sorted
+//   kWsIn          shared   staged input of the *_host calls (fuse, apply, ICP source, voxel and grid points, consistency rasters);
+//                           TSDF slabs; NN sort keys; FPFH k-NN lists; r3d_register_ransac's gathered pairs; octree records; the voxel union's list
+//   kWsOut         shared   staged output of the *_host calls (ICP: the target; consistency: filtered | votes | keep); the sorted voxel codes; NN query `src4` / sorted
 //                           copy; SOR scores; FPFH rows; merge remainders
 //   kWsSpare       shared   the radix sort's `tmp` where the caller has none (NN, voxel codes, r3d_sort_u64); fuse pose tables;
+//                           r3d_depth_consistency's relative pose rows ([F][S] x 64 bytes, the source index in each row's padding);
 //                           octree meta; merge segments; host ICP idx; feature match's b -> a partial minima
 //   kWsCounts      shared   the histogram of EVERY radix sort (r3d_radix_sort_workspace; the private files sort too); compaction
-//                           Counters of knn, tsdf, tsdf_mesh; octree tile places; host ICP d2 and sums; fuse rgb; feature match's
+//                           Counters of knn, tsdf, tsdf_mesh, r3d_compact_rows_by_mask; octree tile places; host ICP d2 and sums; fuse rgb; feature match's
 //                           b -> a rows; the voxel union's counts
 //   kWsPartials    shared   partial rows of the sums passes (ICP, NN query + solve, tracking, SOR); NN bound rows; consensus
 //                           partials; r3d_apply_T_many's table; grad_P partials; fuse rgba; grid colours; a -> b partial minima
@@ -239,6 +240,20 @@ void r3d_sort_launch_scan(r3d_ctx* ctx, uint32_t* hist, int n_blocks, int stride
 // r3d_fpfh.hip: idx / dist of the nearest 33-float row of b for every row of a; the partial minima go to the workspace `part`
 int r3d_match_nearest(r3d_ctx* ctx, const float* d_a, int64_t na, const float* d_b, int64_t nb, uint32_t* d_idx_out, float* d_dist_out,
                       r3d_workspace part);
+
+// r3d_consistency.hip: the launches r3d_consistency_host.cpp drives (asynchronous on the ctx stream, arguments checked by then).
+// d_rows: [n_frames][n_sources] relative pose rows shaped like r3d_tsdf_dev::TsdfPoseRow, the source index in pad[0].  The mask
+// pair is the compaction step of r3d_compact_dev.h: hist holds the tiles' counts after _count, their exclusive prefixes for _write.
+struct r3d_consistency_rule {
+  float rel_tol;
+  int min_consistent, max_violations;
+};
+void r3d_consistency_launch(r3d_ctx* ctx, const r3d_camera* cam, double depth_scale, const void* d_depth, int depth_dtype, const void* d_rows,
+                            int n_frames, int n_sources, const r3d_consistency_rule& rule, uint8_t* d_votes, uint8_t* d_keep,
+                            float* d_filtered);
+void r3d_mask_count_launch(r3d_ctx* ctx, const uint8_t* d_keep, int64_t n, int tiles, uint32_t* hist);
+void r3d_mask_write_launch(r3d_ctx* ctx, const float* d_xyz, const uint32_t* d_rgba, int64_t n, const uint8_t* d_keep, int tiles,
+                           const uint32_t* hist, float* d_xyz_out, uint32_t* d_rgba_out, uint64_t rows);
 
 // r3d_nnindex.hip: the index's own copy of the target cloud (original order), its size and its context
 int r3d_nn_index_target(r3d_nn_index* index, const float** d_tgt, int64_t* n_tgt, r3d_ctx** ctx);

@@ -242,15 +242,6 @@ void launch_integrate(r3d_tsdf* v, const TsdfCam& cam, const void* d_depth, cons
                      v->d_col, d_rgb);
 }
 
-TsdfCam tsdf_cam_of(const r3d_camera* cam, double depth_scale) {
-  TsdfCam c;
-  c.fx = (float)cam->fx, c.fy = (float)cam->fy, c.cx = (float)cam->cx, c.cy = (float)cam->cy;
-  c.wf = (float)cam->width, c.hf = (float)cam->height, c.scale = (float)depth_scale;
-  c.width = cam->width;
-  c.frame_px = (uint32_t)cam->height * (uint32_t)cam->width;
-  return c;
-}
-
 // the launches of one batch whose rasters (and colour images, unless d_rgb is NULL) are in HBM; asynchronous
 int integrate_device(r3d_tsdf* v, const r3d_camera* cam, const void* d_depth, int depth_dtype, int n_frames, double depth_scale,
                      const double* h_pose, const uint8_t* d_rgb) {

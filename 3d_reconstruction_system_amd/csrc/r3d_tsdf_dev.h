@@ -1,8 +1,9 @@
-// What the TSDF volume's sources share (r3d_tsdf.hip, r3d_tsdf_color.hip, r3d_tsdf_mesh.hip, r3d_tsdf_raycast.hip, r3d_track.hip).
+// What the TSDF volume's sources share (r3d_tsdf.hip, r3d_tsdf_color.hip, r3d_tsdf_mesh.hip, r3d_tsdf_raycast.hip, r3d_track.hip),
+// and the projection rule r3d_consistency.hip shares with them.
 // Internal to libr3d_hip.so.  Semantics: include/r3d.h ("TSDF volume", "TSDF colour").
 //   device   voxel indexing, the crossing predicate and the surface point of a crossing (emit_points: the mesh's vertices ARE the
 //            points, bit for bit), the colour of a surface point (emit_colors), the cell loads of ray casting, and the one
-//            statement of the per-frame integration rule (integrate_frame);
+//            statement of the per-frame integration rule (integrate_frame) over the one of the projection (project_to_pixel);
 //   host     struct r3d_tsdf itself, the one step through its pose ring (r3d_tsdf_send_rows), and the argument checks that more
 //            than one entry point makes.
 #pragma once
@@ -39,20 +40,40 @@ struct TsdfCam {
   uint32_t frame_px;   // height * width
 };
 
-// One frame into one voxel; returns whether the frame touched it, and then pixel = vi * width + ui, the pixel it read (the
-// integration kernel's colour variant gathers the same pixel of the colour image; the depth-only one drops it).
-template <typename D>
-__device__ __forceinline__ bool integrate_frame(const TsdfPoseRow& fr, const TsdfCam& cam, const D* __restrict__ depth, float tr, float cx_,
-                                                float cy_, float cz_, float& tsdf, float& w, uint32_t& pixel) {
-  const float px = ((fr.r[0] * cx_ + fr.r[1] * cy_) + fr.r[2] * cz_) + fr.t[0];
-  const float py = ((fr.r[3] * cx_ + fr.r[4] * cy_) + fr.r[5] * cz_) + fr.t[1];
-  const float pz = ((fr.r[6] * cx_ + fr.r[7] * cy_) + fr.r[8] * cz_) + fr.t[2];
+// the intrinsics, the raster's shape and the depth scale as the kernels take them: each rounded once to f32
+inline TsdfCam tsdf_cam_of(const r3d_camera* cam, double depth_scale) {
+  TsdfCam c;
+  c.fx = (float)cam->fx, c.fy = (float)cam->fy, c.cx = (float)cam->cx, c.cy = (float)cam->cy;
+  c.wf = (float)cam->width, c.hf = (float)cam->height, c.scale = (float)depth_scale;
+  c.width = cam->width;
+  c.frame_px = (uint32_t)cam->height * (uint32_t)cam->width;
+  return c;
+}
+
+// The projection rule, stated once (integration, r3d_consistency.hip): the point (x, y, z) of the frame fr maps from goes to
+// p = R (x, y, z) + t; false unless p.z > 0 and p falls into a pixel of the raster (nearest pixel); then pz = p.z and at =
+// vi * width + ui, that pixel.
+__device__ __forceinline__ bool project_to_pixel(const TsdfPoseRow& fr, const TsdfCam& cam, float x, float y, float z, float& pz, uint32_t& at) {
+  const float px = ((fr.r[0] * x + fr.r[1] * y) + fr.r[2] * z) + fr.t[0];
+  const float py = ((fr.r[3] * x + fr.r[4] * y) + fr.r[5] * z) + fr.t[1];
+  pz = ((fr.r[6] * x + fr.r[7] * y) + fr.r[8] * z) + fr.t[2];
   if (!(pz > 0.0f)) return false;
   const float u = cam.fx * (px / pz) + cam.cx;
   const float v = cam.fy * (py / pz) + cam.cy;
   const float ui = floorf(u + 0.5f), vi = floorf(v + 0.5f);
   if (!(ui >= 0.0f && ui < cam.wf && vi >= 0.0f && vi < cam.hf)) return false;   // NaN fails every comparison
-  const uint32_t at = (uint32_t)(int)vi * (uint32_t)cam.width + (uint32_t)(int)ui;
+  at = (uint32_t)(int)vi * (uint32_t)cam.width + (uint32_t)(int)ui;
+  return true;
+}
+
+// One frame into one voxel; returns whether the frame touched it, and then pixel = vi * width + ui, the pixel it read (the
+// integration kernel's colour variant gathers the same pixel of the colour image; the depth-only one drops it).
+template <typename D>
+__device__ __forceinline__ bool integrate_frame(const TsdfPoseRow& fr, const TsdfCam& cam, const D* __restrict__ depth, float tr, float cx_,
+                                                float cy_, float cz_, float& tsdf, float& w, uint32_t& pixel) {
+  float pz;
+  uint32_t at;
+  if (!project_to_pixel(fr, cam, cx_, cy_, cz_, pz, at)) return false;
   const float d = (float)depth[at] * cam.scale;
   if (!(d > 0.0f && d < INFINITY)) return false;
   const float sdf = d - pz;

@@ -4,6 +4,7 @@ truncated signed distance volume instead, and the volume's zero level set is wri
 
     python integrate_tsdf.py --voxel-size S --trunc T [--origin X Y Z] [--dims NX NY NZ] [--margin M] [--min-weight W]
                              [--mesh [--mesh-min-component N] [--mesh-largest]]
+                             [--consistency RADIUS,REL_TOL,MIN[,MAX_VIOL]]
                              [--raycast] [--color-dir DIR] [--raycast-color] [--track [--track-pyramid N0,N1,..] [--track-bilateral R,SIGMA_S,SIGMA_R] [--track-color [--photo-weight W] [--track-max-jump D]]]
 
 Run from a directory holding ./camera_pose/image_colmap_simi_2.txt and ./depth/ (the inputs of camera_to_world.py; the same
@@ -16,6 +17,10 @@ shades), and prints a second line "triangles M -> path".
 pieces (triangles that share a vertex) of fewer than N triangles are dropped, and with --mesh-largest all but the piece with the
 most triangles; vertices no kept triangle names go with them, so the mesh file then has fewer vertices than the surface file.
 A line "components C kept K triangles kept M dropped D" is printed in front of the "triangles" line.
+--consistency RADIUS,REL_TOL,MIN[,MAX_VIOL] (not with --track: it needs every pose) runs the multi-view depth consistency filter
+over the depth maps first and integrates the filtered rasters instead of the raw ones: a pixel stays when at least MIN of the
+RADIUS frames before and after its own see a surface within REL_TOL (relative) of where it says one is and at most MAX_VIOL
+(default 0) see past it, e.g. 2,0.01,2; a floater no longer carves the volume.  A line "consistency kept K of P pixels" is printed.
 --raycast also casts the volume from every pose of the pose file at the input rasters' size and writes the depth the model
 predicts (float32, 0 = no surface) to ./raycast/<frame name>.npy, and prints a further line "raycast F frames -> ./raycast/".
 --color-dir DIR reads the colour image DIR/<frame name> of every frame (the size of the depth maps), integrates colour with the
@@ -74,6 +79,9 @@ def parse_args(argv):
     p.add_argument("--mesh-min-component", type=int, metavar="N", default=None,
                    help="with --mesh: drop the connected pieces of the mesh that have fewer than N triangles")
     p.add_argument("--mesh-largest", action="store_true", help="with --mesh: keep only the connected piece with the most triangles")
+    p.add_argument("--consistency", metavar="RADIUS,REL_TOL,MIN[,MAX_VIOL]", default=None,
+                   help="integrate the depth maps filtered by multi-view consistency: sources RADIUS frames either side, relative "
+                        "tolerance, agreeing sources needed, sources that may see past a pixel (default 0), e.g. 2,0.01,2")
     p.add_argument("--raycast", action="store_true",
                    help="also ray-cast the volume from every pose and write the predicted depth to %s<frame name>.npy" % RAYCAST_DIR)
     p.add_argument("--color-dir", metavar="DIR", default=None,
@@ -120,6 +128,19 @@ def parse_args(argv):
             p.error("--track-bilateral takes R,SIGMA_S,SIGMA_R (an integer and two numbers), got %r" % args.track_bilateral)
         if not (0 <= args.track_bilateral[0] <= 8 and 0.0 < args.track_bilateral[1] < math.inf and 0.0 < args.track_bilateral[2] < math.inf):
             p.error("--track-bilateral takes a radius in 0..8 and two finite sigmas > 0, got %r" % (args.track_bilateral,))
+    if args.consistency is not None:
+        if args.track:
+            p.error("--consistency needs the pose of every frame (not with --track)")
+        try:
+            parts = args.consistency.split(",")
+            if len(parts) not in (3, 4):
+                raise ValueError
+            args.consistency = (int(parts[0]), float(parts[1]), int(parts[2]), int(parts[3]) if len(parts) == 4 else 0)
+        except ValueError:
+            p.error("--consistency takes RADIUS,REL_TOL,MIN[,MAX_VIOL] (an integer, a number, one or two integers), got %r" % args.consistency)
+        radius, rel_tol, min_c, max_v = args.consistency
+        if not (1 <= radius <= 8 and math.isfinite(rel_tol) and rel_tol > 0.0 and 0 <= min_c <= 255 and 0 <= max_v <= 255):
+            p.error("--consistency takes a radius in 1..8, a finite tolerance > 0 and vote thresholds in 0..255, got %r" % (args.consistency,))
     if args.track_color and not (args.track and args.color_dir is not None):
         p.error("--track-color needs --track and the colour images (--color-dir)")
     if args.track_color and args.track_pyramid is not None:
@@ -263,6 +284,12 @@ def main(argv=None):
     depths = r3d.cloud_io.read_depth_batch([os.path.join('./depth/', n) for n in names])
     rgb = read_colors(r3d, args.color_dir, names, depths.shape[-2:]) if args.color_dir is not None else None
     _common.stamp("read %d frames" % len(names))
+    if args.consistency is not None:
+        radius, rel_tol, min_c, max_v = args.consistency
+        keep, depths = r3d.depth_consistency(depths, quats, ts, intrinsics=_common.intrinsics(), radius=radius, rel_tol=rel_tol,
+                                             min_consistent=min_c, max_violations=max_v, ctx=_common.context())[2:]
+        print("consistency kept %d of %d pixels" % (int(keep.sum()), keep.size))
+        _common.stamp("consistency")
     tracked = None
     if args.track:
         vol = r3d.TSDFVolume(origin, args.voxel_size, dims, args.trunc, ctx=_common.context(), color=args.track_color)

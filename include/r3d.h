@@ -1456,6 +1456,76 @@ int r3d_distance_stats(r3d_ctx* ctx, const float* d_values, int64_t n, int squar
 int r3d_sqrt_f32_inplace(r3d_ctx* ctx, float* d_values, int64_t n);
 int r3d_distance_colors(r3d_ctx* ctx, const float* d_dist, int64_t n, double d_max, uint32_t* d_rgba_out);
 
+/* ---- Depth consistency (csrc/r3d_consistency.hip; NOT IN THE REFERENCE -- the geometric consistency check that COLMAP's fusion and
+ * MVSNet-style pipelines put between depth maps and fusion; no parity with either is claimed, this text is the specification).
+ * r3d_fuse_frames concatenates every pixel of every frame and the TSDF volume carves with every depth; the cleaning tools work on
+ * the cloud afterwards.  This filter asks the OTHER frames' depth maps: a pixel is kept when enough of them see a surface where it
+ * says one is and none (few) sees through it.  All F frames of a batch are references; frame r asks up to S sources.
+ * All device arithmetic is f32 in the order written: no fused multiply-add, correctly rounded division, f32 denormals kept.  The
+ * result of a pixel is a function of that pixel, the rasters and the poses alone -- no LDS, no atomics, independent of launch
+ * geometry.
+ * Inputs.  The rasters [F][H][W] of depth_dtype and the camera, as r3d_tsdf_integrate takes them: scale = (float) depth_scale
+ *   (finite), fx, fy, cx, cy rounded once to f32.  h_pose_w2c: F x 12 host doubles [R row-major (9), t (3)], WORLD -> CAMERA, the
+ *   layout r3d_tsdf_integrate reads.  h_sources: [F][S] host int32, S = n_sources in [1, R3D_CONSISTENCY_MAX_SOURCES]; row r lists
+ *   the sources of frame r: -1 is an empty slot, any other entry must be in [0, F), an entry equal to r is an argument error.
+ *   Repeated entries are allowed and simply vote twice.  F H W < 2^31; H, W <= 2^24.
+ * Relative pose (host, fp64, no fused multiply-add): for every filled slot (r, s = h_sources[r][k])
+ *     Rsr[i][j] = (Rs[i][0] Rr[j][0] + Rs[i][1] Rr[j][1]) + Rs[i][2] Rr[j][2]                 (R_s R_r^T)
+ *     tsr[i]    = ts[i] - ((Rsr[i][0] tr[0] + Rsr[i][1] tr[1]) + Rsr[i][2] tr[2])             (from the fp64 Rsr)
+ *   each of the twelve numbers rounded once to f32: a camera-r point p maps to camera s as Rsr p + tsr.
+ * Reference pixel (u, v) of frame r:  Z = (float) depth[r][v][u] * scale.  The pixel is valid iff Z > 0 and Z < inf.  An invalid
+ *   pixel gets votes (0, 0), keep 0 and filtered 0.0f.  For a valid pixel
+ *     x = (((float) u - cx) / fx) * Z;   y = (((float) v - cy) / fy) * Z;   z = Z
+ *   and then, for every filled slot in slot order:
+ *     1. p = ((R0 x + R1 y) + R2 z) + t  per row of the relative pose            (the parenthesisation of "TSDF volume")
+ *     2. unseen unless p.z > 0
+ *     3. u' = fx (p.x / p.z) + cx;  v' = fy (p.y / p.z) + cy;  ui = floorf(u' + 0.5f);  vi = floorf(v' + 0.5f);
+ *        unseen unless 0 <= ui < W and 0 <= vi < H (as floats; NaN fails)       (the nearest-pixel rule of "TSDF volume")
+ *     4. d = (float) depth[s][vi][ui] * scale;  unseen unless d > 0 and d < inf
+ *     5. diff = d - p.z;  tol = (float) rel_tol * p.z
+ *     6. fabsf(diff) <= tol: a CONSISTENT vote.  Otherwise diff > 0: a VIOLATION -- the source sees past the point, so the point
+ *        floats in space that camera saw as free.  Anything else: the point is occluded in s and casts no vote.
+ *   Decision: keep = consistent >= min_consistent && violations <= max_violations.
+ * Outputs (each may be NULL, at least one must be given; none may overlap the rasters or another output):
+ *     d_votes_out     [F][H][W][2] u8   {consistent, violations}; 2-byte aligned
+ *     d_keep_out      [F][H][W]    u8   0 or 1
+ *     d_filtered_out  [F][H][W]    f32  Z where kept, otherwise 0.0f: a raster r3d_tsdf_integrate takes as it stands (R3D_DEPTH_F32,
+ *                                       depth_scale 1, 0 = no measurement)
+ *   No byte outside the given outputs' extents is written.
+ * What the nearest-pixel rule costs: the source depth is read at the centre of the pixel the point falls into, up to half a pixel
+ *   away from where it falls.  On a surface slanted by an angle a to the source's image plane that is a depth difference of up to
+ *   about Z tan(a) / (2 f) (f = the focal length in pixels): 0.3 % of Z at 60 degrees and f = 300.  rel_tol has to cover it next to
+ *   the depth noise.  Bilinear sampling would not have this error on a plane, but it mixes the depths on both sides of an edge and
+ *   invents surfaces between them -- exactly where floaters sit.
+ * r3d_depth_consistency takes device rasters and is asynchronous on the ctx stream (poses and table are copied before it returns);
+ *   r3d_depth_consistency_host takes host rasters and host outputs, uploads and downloads itself and is synchronous.  One lane per
+ *   reference pixel with the source loop inside, one frame per blockIdx.y, a 32 x 2 pixel tile per wave.
+ * R3D_ERR_INVALID, nothing written, checked in this order: an unknown depth dtype; n_frames < 0; n_sources outside
+ *   [1, R3D_CONSISTENCY_MAX_SOURCES]; rel_tol not finite or not > 0 in f32; min_consistent or max_violations outside [0, 255];
+ *   depth_scale not finite in f32; with n_frames > 0 a NULL h_pose_w2c or h_sources, then a table entry outside [-1, F), then a
+ *   frame listing itself; a NULL ctx; a NULL camera; a camera of another ctx.  n_frames == 0: R3D_OK here.  Then: a raster too
+ *   large (above); a NULL raster pointer; no output given; d_votes_out at an odd address (device call); an output overlapping the
+ *   rasters or another output.
+ * r3d_compact_rows_by_mask: the filtered cloud.  d_xyz [n][3] f32, d_rgba [n] u32 colour words or NULL, d_keep [n] u8: the rows i
+ *   with d_keep[i] != 0 go, in input order and bit for bit, to d_xyz_out (and their words to d_rgba_out; given iff d_rgba is).  Fed
+ *   with r3d_fuse_frames' cloud and d_keep_out above it yields the fused cloud without the rejected pixels.  *n_out = the TRUE number
+ *   of kept rows, always; at most cap rows are written and nothing beyond them; cap < *n_out is not an error and cap == 0 with NULL
+ *   outputs asks for the count alone (the two-phase manner of r3d_tsdf_extract_points).  r3d_select_rows is its sibling for the
+ *   outlier masks: row numbers instead of colours, no cap.  Synchronises (the count is read back).
+ *   R3D_ERR_INVALID, nothing written, in this order: NULL n_out; n outside [0, 2^32); cap < 0; a NULL ctx; with n > 0 a NULL d_xyz
+ *   or d_keep; d_xyz_out NULL with cap > 0; d_rgba without d_rgba_out (cap > 0) or d_rgba_out without d_rgba; an output's written
+ *   rows overlapping an input or the other output. */
+#define R3D_CONSISTENCY_MAX_SOURCES 16
+int r3d_depth_consistency(r3d_ctx* ctx, const r3d_camera* cam, const void* d_depth, int depth_dtype, int n_frames, double depth_scale,
+                          const double* h_pose_w2c, const int32_t* h_sources, int n_sources, double rel_tol, int min_consistent,
+                          int max_violations, uint8_t* d_votes_out, uint8_t* d_keep_out, float* d_filtered_out);
+int r3d_depth_consistency_host(r3d_ctx* ctx, const r3d_camera* cam, const void* h_depth, int depth_dtype, int n_frames,
+                               double depth_scale, const double* h_pose_w2c, const int32_t* h_sources, int n_sources, double rel_tol,
+                               int min_consistent, int max_violations, uint8_t* h_votes_out, uint8_t* h_keep_out,
+                               float* h_filtered_out);
+int r3d_compact_rows_by_mask(r3d_ctx* ctx, const float* d_xyz, const uint32_t* d_rgba, int64_t n, const uint8_t* d_keep,
+                             float* d_xyz_out, uint32_t* d_rgba_out, int64_t cap, int64_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif
