@@ -34,7 +34,9 @@ from .tsdf import TSDFVolume, poses_w2c  # noqa: F401
 from .consistency import (window_sources, depth_consistency, depth_consistency_device, fuse_frames_consistent,  # noqa: F401
                           compact_rows_device)
 from .mesh import (MeshComponents, mesh_components, mesh_components_device, remove_small_components,  # noqa: F401
-                   remove_small_components_device)
+                   remove_small_components_device, mesh_adjacency, mesh_adjacency_device, smooth_mesh, smooth_mesh_device,
+                   compute_vertex_normals, vertex_normals_device, smooth_factors)
+from . import mesh  # noqa: F401
 from .evaluation import (MeshIndex, cloud_to_cloud_distance, cloud_to_mesh_distance, distance_stats, distance_colors,  # noqa: F401
                          evaluate_reconstruction, cloud_to_cloud_distance_device, distance_stats_device, distance_colors_device)
 from .tracking import TrackDevice, track_sums  # noqa: F401

@@ -181,6 +181,9 @@ SIGNATURES = {
     "r3d_tsdf_extract_mesh": (_i, [_vp, _d, _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
     "r3d_mesh_components": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
     "r3d_mesh_filter_components": (_i, [_vp, _vp, _i64, _i64, _vp, _i64, _i, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "r3d_mesh_adjacency": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "r3d_mesh_smooth": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i]),
+    "r3d_mesh_vertex_normals": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp]),
     "r3d_tsdf_raycast": (_i, [_vp, _vp, _i, _vp, _d, _d, _d, _d, _vp, _vp, _vp]),
     "r3d_tsdf_create_rgb": (_i, [_vp, _vp, _d, _i, _i, _i, _d, _pvp]),
     "r3d_tsdf_integrate_rgb": (_i, [_vp, _vp, _vp, _i, _i, _d, _vp, _vp]),

@@ -39,6 +39,8 @@
 //   kWsColorLists  private  r3d_color_icp.hip: the k-NN lists (idx | d2) of r3d_color_gradient_knn
 //   kWsMeshCc      private  r3d_mesh_cc.hip: per-label counters, vertex flags, tile counters
 //   kWsMeshDist    private  r3d_meshdist.hip: sort keys + spare of an index build or query; r3d_distance_stats' partial rows
+//   kWsMeshSmooth  private  r3d_mesh_smooth_host.cpp: adjacency side keys + spare + tile counters; the smoothing steps' two
+//                           ping-pong position arrays; the normals' corner keys + spare (one call at a time, nothing outlives it)
 // Hand-over rules between nested claims:
 //   * a sort holds kWsCounts (r3d_sort_u64 also kWsSpare) until its last pass is enqueued: its callers keep nothing of theirs
 //     there across it (the voxel code list lives in kWsOut, the NN keys in kWsIn);
@@ -63,6 +65,7 @@ enum r3d_workspace : int {
   kWsColorLists,
   kWsMeshCc,
   kWsMeshDist,
+  kWsMeshSmooth,
   kWsEnd
 };
 
@@ -110,7 +113,7 @@ struct r3d_ctx {
   // HIP-event stopwatch
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;
   // the grow-only device workspaces, one per r3d_workspace entry (the table above); r3d_scratch is their only allocator
-  static constexpr int kScratchSlots = 14;
+  static constexpr int kScratchSlots = 15;
   void* scratch[kScratchSlots] = {};
   size_t scratch_bytes[kScratchSlots] = {};
   // the (radius, sigma_s, sigma_r) whose tables sit in kWsBilateral: a repeated r3d_depth_bilateral uploads nothing.  radius -1 =
@@ -254,6 +257,23 @@ void r3d_consistency_launch(r3d_ctx* ctx, const r3d_camera* cam, double depth_sc
 void r3d_mask_count_launch(r3d_ctx* ctx, const uint8_t* d_keep, int64_t n, int tiles, uint32_t* hist);
 void r3d_mask_write_launch(r3d_ctx* ctx, const float* d_xyz, const uint32_t* d_rgba, int64_t n, const uint8_t* d_keep, int tiles,
                            const uint32_t* hist, float* d_xyz_out, uint32_t* d_rgba_out, uint64_t rows);
+
+// r3d_mesh_smooth.hip: the launches r3d_mesh_smooth_host.cpp drives (asynchronous on the ctx stream, arguments checked by then).
+// vb: the bits of a vertex index.  Side keys are (u << vb | v), 1 << 2vb for no side; corner keys (v << 32 | 3t + c), v = 1 << vb
+// for an invalid triangle.  The heads pair is the compaction step of r3d_compact_dev.h over the sorted side keys: the distinct ones
+// go to d_distinct (room for n), a run of length 1 sets d_boundary (may be NULL).  _rows: row_start[0 .. nv] by lower bound in
+// the distinct keys, and the first `rows` neighbour entries.  _step: one umbrella step, d_in != d_out.
+void r3d_mesh_side_keys_launch(r3d_ctx* ctx, const int32_t* d_tri, int64_t nt, uint32_t nv, int vb, uint64_t* d_keys);
+void r3d_mesh_heads_count_launch(r3d_ctx* ctx, const uint64_t* d_sorted, int64_t n, int vb, int tiles, uint32_t* hist);
+void r3d_mesh_heads_write_launch(r3d_ctx* ctx, const uint64_t* d_sorted, int64_t n, int vb, int tiles, const uint32_t* hist,
+                                 uint64_t* d_distinct, uint8_t* d_boundary);
+void r3d_mesh_rows_launch(r3d_ctx* ctx, const uint64_t* d_distinct, uint32_t n_distinct, uint32_t nv, int vb, uint32_t* d_row_start,
+                          uint32_t* d_neighbours, uint32_t rows);
+void r3d_mesh_step_launch(r3d_ctx* ctx, const float* d_in, float* d_out, uint32_t nv, const uint32_t* d_row_start,
+                          const uint32_t* d_neighbours, const uint8_t* d_locked, double factor);
+void r3d_mesh_corner_keys_launch(r3d_ctx* ctx, const int32_t* d_tri, int64_t nt, uint32_t nv, int vb, uint64_t* d_keys);
+void r3d_mesh_normals_launch(r3d_ctx* ctx, const float* d_xyz, uint32_t nv, const int32_t* d_tri, const uint64_t* d_sorted, uint32_t n_keys,
+                             const float* d_fallback, float* d_out);
 
 // r3d_nnindex.hip: the index's own copy of the target cloud (original order), its size and its context
 int r3d_nn_index_target(r3d_nn_index* index, const float** d_tgt, int64_t* n_tgt, r3d_ctx** ctx);

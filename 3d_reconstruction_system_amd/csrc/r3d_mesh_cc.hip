@@ -17,6 +17,7 @@
 // Workspace: kWsMeshCc of the context, grown on demand, touched by these two synchronous calls alone.
 #include "r3d_compact_dev.h"
 #include "r3d_internal.h"
+#include "r3d_mesh_dev.h"
 #include "r3d_unionfind_dev.h"
 
 using namespace r3d_compact;   // kPer consecutive items per thread of the compaction kernels
@@ -26,9 +27,7 @@ namespace {
 constexpr int kThreads = 256;
 constexpr uint32_t kNoLabel = 0xFFFFFFFFu;
 
-__device__ __forceinline__ bool tri_valid(int32_t a, int32_t b, int32_t c, uint32_t nv) {
-  return (uint32_t)a < nv && (uint32_t)b < nv && (uint32_t)c < nv;   // a negative index is >= 2^31 > nv as unsigned
-}
+using r3d_mesh::tri_valid;   // all three indices in [0, nv) (r3d_mesh_dev.h: the smoothing kernels take the same rule)
 
 // cnt[label] += 1 for the active lanes; every lane of the wave calls this.  The lanes that share the first active lane's label
 // add once, together; the others add for themselves.  Integer adds: the sums do not depend on who adds.

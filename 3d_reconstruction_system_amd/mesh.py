@@ -1,11 +1,17 @@
-"""Connected components of an indexed triangle mesh on the MI355X: label the connected pieces, count them, and drop the small
+"""Clean-up of an indexed triangle mesh on the MI355X, part one -- connected components: label the connected pieces, count them, and drop the small
 ones -- the clean-up between TSDFVolume.extract_triangle_mesh and cloud_io.write_ply_mesh, where a volume fused from noisy depth
 carries one large surface plus floaters of a few triangles each (what users of Open3D do with cluster_connected_triangles; no
 parity with Open3D is claimed: two triangles are connected here when they share a VERTEX).  Everything is integer-exact.
 Semantics: include/r3d.h ("Mesh components") and DESIGN.md section 4.5j'.
 
+Part two -- smoothing: the vertex adjacency (one-ring CSR and boundary flags), Laplacian and Taubin smoothing as a sequence of
+umbrella steps, and area-weighted vertex normals of the moved mesh (what users of Open3D do with filter_smooth_taubin and
+compute_vertex_normals; no parity is claimed).  Every bit is specified: include/r3d.h ("Mesh smoothing") and DESIGN.md section
+4.5j''.
+
 The *_device functions take raw device addresses and leave their results in HBM.
 """
+import math
 import collections
 import ctypes as C
 
@@ -161,6 +167,212 @@ def remove_small_components(xyz, normals, triangles, min_triangles=1, keep_large
         out = (download_rows(d_x, np.float32, n, 3), download_rows(d_n, np.float32, n, 3),
                download_rows(d_t, np.int32, m, 3).astype(tri_dtype, copy=False))
         return out + (colors[kept],) if colors is not None else out
+    finally:
+        for b in bufs:
+            b.free()
+
+
+# ---- smoothing (include/r3d.h "Mesh smoothing")
+
+MAX_STEPS = 4096   # umbrella steps of one smooth_mesh_device call
+METHODS = ("taubin", "laplacian")
+SMOOTH_KEYS = ("method", "iterations", "lam", "mu", "lock_boundary")   # what extract_triangle_mesh(smooth=...) takes, in this order
+
+
+def _finite(v, what):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(float(v)):
+        raise ValueError("%s must be a finite number, got %r" % (what, v))
+    return float(v)
+
+
+def smooth_factors(method="taubin", iterations=10, lam=0.5, mu=-0.53):
+    """The step factors of a filter as a list of floats: [lam] * iterations for "laplacian" (mu is ignored), [lam, mu] * iterations
+    for "taubin" (mu < 0 < lam < -mu: the second step undoes the shrinkage of the first)."""
+    if method not in METHODS:
+        raise ValueError("method must be one of %s, got %r" % (", ".join(METHODS), method))
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or int(iterations) < 0:
+        raise ValueError("iterations must be an integer >= 0, got %r" % (iterations,))
+    lam = _finite(lam, "lam")
+    if lam <= 0:
+        raise ValueError("lam must be > 0, got %r" % (lam,))
+    steps = [lam]
+    if method == "taubin":
+        mu = _finite(mu, "mu")
+        if not (mu < 0 and -mu > lam):
+            raise ValueError("mu must be negative and larger than lam in magnitude (lam %r), got %r" % (lam, mu))
+        steps = [lam, mu]
+    if len(steps) * int(iterations) > MAX_STEPS:
+        raise ValueError("iterations gives %d steps, more than %d" % (len(steps) * int(iterations), MAX_STEPS))
+    return steps * int(iterations)
+
+
+def _factors(factors):
+    f = np.ascontiguousarray(np.asarray(factors, np.float64).reshape(-1)) if len(factors) else np.zeros(0, np.float64)
+    if len(f) > MAX_STEPS:
+        raise ValueError("factors holds %d steps, more than %d" % (len(f), MAX_STEPS))
+    if not np.isfinite(f).all():
+        raise ValueError("factors must be finite, got %r" % (f[~np.isfinite(f)][0],))
+    return f
+
+
+def _positions(xyz, what="xyz"):
+    a = np.ascontiguousarray(xyz)
+    if a.ndim != 2 or a.shape[1] != 3 or a.dtype != np.float32:
+        raise ValueError("%s must be an [N,3] float32 array, got %s of shape %s" % (what, a.dtype, list(a.shape)))
+    _count(len(a), "the number of vertices")
+    return a
+
+
+def smooth_params(smooth):
+    """extract_triangle_mesh's `smooth` argument -> the dict of smooth_mesh's keywords: a dict of them, or a tuple in the order
+    (method, iterations, lam, mu, lock_boundary), both completed with smooth_mesh's defaults and checked"""
+    out = {"method": "taubin", "iterations": 10, "lam": 0.5, "mu": -0.53, "lock_boundary": True}
+    if isinstance(smooth, dict):
+        unknown = sorted(set(smooth) - set(SMOOTH_KEYS))
+        if unknown:
+            raise ValueError("smooth has unknown keys %s (it takes %s)" % (unknown, ", ".join(SMOOTH_KEYS)))
+        out.update(smooth)
+    elif isinstance(smooth, (tuple, list)):
+        if len(smooth) > len(SMOOTH_KEYS):
+            raise ValueError("smooth takes at most %d values (%s), got %d" % (len(SMOOTH_KEYS), ", ".join(SMOOTH_KEYS), len(smooth)))
+        out.update(zip(SMOOTH_KEYS, smooth))
+    else:
+        raise ValueError("smooth must be None, a dict or a tuple of (%s), got %r" % (", ".join(SMOOTH_KEYS), smooth))
+    smooth_factors(out["method"], out["iterations"], out["lam"], out["mu"])
+    out["lock_boundary"] = bool(out["lock_boundary"])
+    return out
+
+
+def mesh_adjacency_device(ctx, d_tri, n_triangles, n_vertices, d_row_start, d_neighbours=None, cap_neighbours=0, d_boundary=None):
+    """The one-ring CSR of the mesh into d_row_start ([n_vertices + 1] uint32) and d_neighbours ([cap_neighbours] uint32, optional),
+    the boundary flags into d_boundary ([n_vertices] uint8, optional) at raw device addresses; d_tri: [n_triangles][3] int32.
+    Returns the TRUE number of neighbour entries E; at most cap_neighbours were written.  Synchronises."""
+    nt, nv, cap = _count(n_triangles, "n_triangles"), _count(n_vertices, "n_vertices"), _count(cap_neighbours, "cap_neighbours")
+    e = C.c_int64()
+    L.check(ctx.lib.r3d_mesh_adjacency(ctx.handle, d_tri, nt, nv, d_row_start, d_neighbours, cap, d_boundary, C.byref(e)))
+    return e.value
+
+
+def smooth_mesh_device(ctx, d_xyz_in, d_xyz_out, n_vertices, d_row_start, d_neighbours, d_locked, factors):
+    """len(factors) umbrella steps from d_xyz_in into d_xyz_out ([n_vertices][3] float32 each, not overlapping) over the adjacency
+    mesh_adjacency_device wrote; d_locked: [n_vertices] uint8 or None.  Asynchronous."""
+    f = _factors(factors)
+    L.check(ctx.lib.r3d_mesh_smooth(ctx.handle, d_xyz_in, d_xyz_out, _count(n_vertices, "n_vertices"), d_row_start, d_neighbours, d_locked,
+                                    f.ctypes.data if len(f) else None, len(f)))
+
+
+def vertex_normals_device(ctx, d_xyz, n_vertices, d_tri, n_triangles, d_fallback, d_normals):
+    """Area-weighted vertex normals into d_normals ([n_vertices][3] float32); d_fallback: the rows of vertices without area, or
+    None for zeros.  Asynchronous."""
+    L.check(ctx.lib.r3d_mesh_vertex_normals(ctx.handle, d_xyz, _count(n_vertices, "n_vertices"), d_tri, _count(n_triangles, "n_triangles"),
+                                            d_fallback, d_normals))
+
+
+def adjacency_buffers(ctx, d_tri, n_triangles, n_vertices, bufs):
+    """(d_row_start, d_neighbours, d_boundary, E) as new DeviceBuffers (appended to bufs): the two-call round trip for the cap"""
+    nv = n_vertices
+    d_rs, d_bd = ctx.alloc(max((nv + 1) * 4, 16)), ctx.alloc(max(nv, 16))
+    bufs += [d_rs, d_bd]
+    e = mesh_adjacency_device(ctx, d_tri, n_triangles, nv, d_rs.ptr, None, 0, d_bd.ptr)
+    d_nb = ctx.alloc(max(e * 4, 16))
+    bufs.append(d_nb)
+    if e:
+        got = mesh_adjacency_device(ctx, d_tri, n_triangles, nv, d_rs.ptr, d_nb.ptr, e, d_bd.ptr)
+        assert got == e, (got, e)
+    return d_rs, d_nb, d_bd, e
+
+
+def smooth_mesh_buffers(ctx, d_xyz, d_normals, d_tri, n_vertices, n_triangles, params, bufs):
+    """The device-resident mesh (raw addresses; d_normals the fallback or None) smoothed on the device: (d_xyz, d_normals, stats)
+    with the two arrays new DeviceBuffers (appended to bufs, the caller frees them) and stats the dict {"vertices", "edges",
+    "boundary_vertices", "steps"}.  params: smooth_params' dict."""
+    nv, nt = n_vertices, n_triangles
+    factors = smooth_factors(params["method"], params["iterations"], params["lam"], params["mu"])
+    d_rs, d_nb, d_bd, e = adjacency_buffers(ctx, d_tri, nt, nv, bufs)
+    d_out, d_nrm = ctx.alloc(max(nv * 12, 16)), ctx.alloc(max(nv * 12, 16))
+    bufs += [d_out, d_nrm]
+    smooth_mesh_device(ctx, d_xyz, d_out.ptr, nv, d_rs.ptr, d_nb.ptr, d_bd.ptr if params["lock_boundary"] else None, factors)
+    vertex_normals_device(ctx, d_out.ptr, nv, d_tri, nt, d_normals, d_nrm.ptr)
+    boundary = int(np.count_nonzero(download_rows(d_bd, np.uint8, nv, 1)))
+    return d_out, d_nrm, {"vertices": nv, "edges": e // 2, "boundary_vertices": boundary, "steps": len(factors)}
+
+
+def mesh_adjacency(triangles, n_vertices, ctx=None):
+    """(row_start [N + 1] uint32, neighbours [E] uint32, boundary [N] bool) of the mesh whose [M,3] integer `triangles` index
+    n_vertices vertices: row u of the CSR holds u's distinct neighbours in ascending index; boundary[u]: u lies on an edge that
+    exactly one triangle side has."""
+    tri, nv = _triangles(triangles), _count(n_vertices, "n_vertices")
+    ctx = ctx or default_context()
+    bufs = []
+    try:
+        d_tri = ctx.alloc(max(tri.nbytes, 16))
+        bufs.append(d_tri)
+        d_tri.upload(tri)
+        d_rs, d_nb, d_bd, e = adjacency_buffers(ctx, d_tri.ptr, len(tri), nv, bufs)
+        return (d_rs.download(np.uint32, nv + 1), download_rows(d_nb, np.uint32, e, 1).reshape(-1),
+                download_rows(d_bd, np.uint8, nv, 1).reshape(-1).astype(bool))
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def _upload_mesh(ctx, xyz, tri, rows, bufs):
+    """xyz, tri and the optional [N,3] float32 `rows` in new DeviceBuffers (appended to bufs); the last is None without rows"""
+    d_xyz, d_tri = ctx.alloc(max(xyz.nbytes, 16)), ctx.alloc(max(tri.nbytes, 16))
+    bufs += [d_xyz, d_tri]
+    d_xyz.upload(xyz)
+    d_tri.upload(tri)
+    d_rows = None
+    if rows is not None:
+        d_rows = ctx.alloc(max(rows.nbytes, 16))
+        bufs.append(d_rows)
+        d_rows.upload(rows)
+    return d_xyz, d_tri, d_rows
+
+
+def _fallback(rows, nv, what):
+    if rows is None:
+        return None
+    rows = _positions(rows, what)
+    if len(rows) != nv:
+        raise ValueError("%s must have one row per vertex (%d), got %d" % (what, nv, len(rows)))
+    return rows
+
+
+def smooth_mesh(xyz, triangles, method="taubin", iterations=10, lam=0.5, mu=-0.53, lock_boundary=True, normals=None, ctx=None):
+    """(xyz, normals) of the mesh after `iterations` rounds of Taubin (a lam step, then a mu step) or Laplacian (lam steps)
+    smoothing over the one-ring of every vertex, each step moving a vertex towards (lam) or away from (mu) the mean of its
+    neighbours; with lock_boundary the vertices on an open edge stay where they are.  normals: the rows that come back for vertices
+    without area (isolated ones); the others get the area-weighted normals of the moved mesh.  The triangles are unchanged."""
+    xyz, tri = _positions(xyz), _triangles(triangles)
+    nv = len(xyz)
+    normals = _fallback(normals, nv, "normals")
+    params = smooth_params({"method": method, "iterations": iterations, "lam": lam, "mu": mu, "lock_boundary": lock_boundary})
+    ctx = ctx or default_context()
+    bufs = []
+    try:
+        d_xyz, d_tri, d_nrm = _upload_mesh(ctx, xyz, tri, normals, bufs)
+        d_out, d_n, _ = smooth_mesh_buffers(ctx, d_xyz.ptr, d_nrm.ptr if d_nrm else None, d_tri.ptr, nv, len(tri), params, bufs)
+        return download_rows(d_out, np.float32, nv, 3), download_rows(d_n, np.float32, nv, 3)
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def compute_vertex_normals(xyz, triangles, fallback=None, ctx=None):
+    """[N,3] float32 area-weighted vertex normals: the normalised sum of (b - a) x (c - a) over the triangles that name the
+    vertex; a vertex without area gets its row of `fallback`, or zeros."""
+    xyz, tri = _positions(xyz), _triangles(triangles)
+    nv = len(xyz)
+    fallback = _fallback(fallback, nv, "fallback")
+    ctx = ctx or default_context()
+    bufs = []
+    try:
+        d_xyz, d_tri, d_fb = _upload_mesh(ctx, xyz, tri, fallback, bufs)
+        d_n = ctx.alloc(max(nv * 12, 16))
+        bufs.append(d_n)
+        vertex_normals_device(ctx, d_xyz.ptr, nv, d_tri.ptr, len(tri), d_fb.ptr if d_fb else None, d_n.ptr)
+        return download_rows(d_n, np.float32, nv, 3)
     finally:
         for b in bufs:
             b.free()

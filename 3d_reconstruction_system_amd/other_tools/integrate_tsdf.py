@@ -3,7 +3,8 @@
 truncated signed distance volume instead, and the volume's zero level set is written as oriented surface points.
 
     python integrate_tsdf.py --voxel-size S --trunc T [--origin X Y Z] [--dims NX NY NZ] [--margin M] [--min-weight W]
-                             [--mesh [--mesh-min-component N] [--mesh-largest]]
+                             [--mesh [--mesh-min-component N] [--mesh-largest]
+                                     [--mesh-smooth METHOD,ITERATIONS[,LAM[,MU]] [--mesh-smooth-free-boundary]]]
                              [--consistency RADIUS,REL_TOL,MIN[,MAX_VIOL]]
                              [--raycast] [--color-dir DIR] [--raycast-color] [--track [--track-pyramid N0,N1,..] [--track-bilateral R,SIGMA_S,SIGMA_R] [--track-color [--photo-weight W] [--track-max-jump D]]]
 
@@ -17,6 +18,12 @@ shades), and prints a second line "triangles M -> path".
 pieces (triangles that share a vertex) of fewer than N triangles are dropped, and with --mesh-largest all but the piece with the
 most triangles; vertices no kept triangle names go with them, so the mesh file then has fewer vertices than the surface file.
 A line "components C kept K triangles kept M dropped D" is printed in front of the "triangles" line.
+--mesh-smooth METHOD,ITERATIONS[,LAM[,MU]] (with --mesh) smooths the mesh on the device, behind the component filter, before it
+is written: METHOD taubin (ITERATIONS times a LAM step then a MU step; defaults 0.5 and -0.53; the surface does not shrink) or
+laplacian (ITERATIONS LAM steps), e.g. taubin,10.  Every step moves a vertex towards (or, for MU, away from) the mean of its
+neighbours; the vertices on an open edge stay where they are unless --mesh-smooth-free-boundary is given.  The normals of the mesh
+file are then the area-weighted vertex normals of the moved mesh; faces, colours and counts are as without the flag.  A line
+"smoothed vertices N edges E boundary B steps S" is printed in front of the "triangles" line.
 --consistency RADIUS,REL_TOL,MIN[,MAX_VIOL] (not with --track: it needs every pose) runs the multi-view depth consistency filter
 over the depth maps first and integrates the filtered rasters instead of the raw ones: a pixel stays when at least MIN of the
 RADIUS frames before and after its own see a surface within REL_TOL (relative) of where it says one is and at most MAX_VIOL
@@ -79,6 +86,10 @@ def parse_args(argv):
     p.add_argument("--mesh-min-component", type=int, metavar="N", default=None,
                    help="with --mesh: drop the connected pieces of the mesh that have fewer than N triangles")
     p.add_argument("--mesh-largest", action="store_true", help="with --mesh: keep only the connected piece with the most triangles")
+    p.add_argument("--mesh-smooth", metavar="METHOD,ITERATIONS[,LAM[,MU]]", default=None,
+                   help="with --mesh: smooth the mesh (taubin or laplacian) and recompute its vertex normals, e.g. taubin,10")
+    p.add_argument("--mesh-smooth-free-boundary", action="store_true",
+                   help="with --mesh-smooth: move the vertices on open edges too (default: they stay)")
     p.add_argument("--consistency", metavar="RADIUS,REL_TOL,MIN[,MAX_VIOL]", default=None,
                    help="integrate the depth maps filtered by multi-view consistency: sources RADIUS frames either side, relative "
                         "tolerance, agreeing sources needed, sources that may see past a pixel (default 0), e.g. 2,0.01,2")
@@ -107,6 +118,24 @@ def parse_args(argv):
         p.error("--mesh-min-component and --mesh-largest need --mesh")
     if args.mesh_min_component is not None and args.mesh_min_component < 1:
         p.error("--mesh-min-component must be >= 1, got %r" % args.mesh_min_component)
+    if args.mesh_smooth is not None and not args.mesh:
+        p.error("--mesh-smooth needs --mesh")
+    if args.mesh_smooth_free_boundary and args.mesh_smooth is None:
+        p.error("--mesh-smooth-free-boundary needs --mesh-smooth")
+    if args.mesh_smooth is not None:
+        try:
+            parts = args.mesh_smooth.split(",")
+            if len(parts) not in (2, 3, 4):
+                raise ValueError
+            smooth = {"method": parts[0], "iterations": int(parts[1])}
+            smooth.update(zip(("lam", "mu"), (float(v) for v in parts[2:])))
+        except ValueError:
+            p.error("--mesh-smooth takes METHOD,ITERATIONS[,LAM[,MU]] (a name, an integer, up to two numbers), got %r" % args.mesh_smooth)
+        smooth["lock_boundary"] = not args.mesh_smooth_free_boundary
+        try:
+            args.mesh_smooth = _common.package().mesh.smooth_params(smooth)
+        except ValueError as e:
+            p.error("--mesh-smooth: %s" % e)
     if (args.photo_weight is not None or args.track_max_jump is not None) and not args.track_color:
         p.error("--photo-weight and --track-max-jump need --track-color")
     if args.track_pyramid is not None:
@@ -312,15 +341,16 @@ def main(argv=None):
     _common.stamp("integrate")
     colors, mesh_stats = None, None
     clean = args.mesh and (args.mesh_min_component is not None or args.mesh_largest)
+    smooth = args.mesh_smooth if args.mesh else None
     if rgb is None:
         xyz, normals = vol.extract_point_cloud(args.min_weight)
-        mesh = vol.extract_triangle_mesh(args.min_weight) if args.mesh and not clean else None
+        mesh = vol.extract_triangle_mesh(args.min_weight, smooth=smooth) if args.mesh and not clean else None
     else:
         xyz, normals, colors = vol.extract_point_cloud(args.min_weight, with_colors=True)
-        mesh = vol.extract_triangle_mesh(args.min_weight)[:3] + (colors,) if args.mesh and not clean else None   # the vertices are the points
+        mesh = vol.extract_triangle_mesh(args.min_weight, smooth=smooth)[:3] + (colors,) if args.mesh and not clean else None   # the vertices are the points
     if clean:
         got = vol.extract_triangle_mesh(args.min_weight, with_colors=rgb is not None, min_component_triangles=args.mesh_min_component,
-                                        keep_largest=args.mesh_largest, with_stats=True)
+                                        keep_largest=args.mesh_largest, with_stats=True, smooth=smooth)
         mesh, mesh_stats = got[:-1], got[-1]
     cast = raycast_depth(r3d, vol, quats, ts, depths.shape[-2:], args.min_weight) if args.raycast else None
     cast_rgb = raycast_color(r3d, vol, quats, ts, depths.shape[-2:], args.min_weight) if args.raycast_color else None
@@ -336,6 +366,8 @@ def main(argv=None):
             print("components %d kept %d triangles kept %d dropped %d" % (mesh_stats["components"], mesh_stats["components_kept"],
                                                                           mesh_stats["triangles_kept"],
                                                                           mesh_stats["triangles"] - mesh_stats["triangles_kept"]))
+        if smooth is not None:
+            print("smoothed vertices %(vertices)d edges %(edges)d boundary %(boundary_vertices)d steps %(steps)d" % vol.last_smooth)
         print("triangles %d -> %s" % (len(mesh[2]), MESH_FILE))
     if cast is not None:
         import numpy as np

@@ -107,6 +107,7 @@ class TSDFVolume:
         self.origin, self.voxel_size, self.sdf_trunc, self.dims = o, vs, tr, (nx, ny, nz)
         self.n_voxels = nx * ny * nz
         self.color = bool(color)
+        self.last_smooth = None       # what the last extract_triangle_mesh(smooth=...) did: vertices, edges, boundary vertices, steps
         h = C.c_void_p()
         create = self.ctx.lib.r3d_tsdf_create_rgb if self.color else self.ctx.lib.r3d_tsdf_create
         L.check(create(self.ctx.handle, o.ctypes.data, vs, nx, ny, nz, tr, C.byref(h)))
@@ -267,7 +268,7 @@ class TSDFVolume:
         return nv.value, nt.value
 
     def extract_triangle_mesh(self, min_weight=1.0, with_colors=False, min_component_triangles=None, keep_largest=False,
-                              with_stats=False):
+                              with_stats=False, smooth=None):
         """(xyz [N,3] float32, normals [N,3] float32, triangles [M,3] int32): marching cubes over the cells whose eight voxels
         have at least min_weight frames each.  The vertices are extract_point_cloud's rows (one per crossing volume edge, so the
         mesh is welded by construction); a triangle (a, b, c) winds so that (b - a) x (c - a) points towards the cameras, like the
@@ -277,7 +278,11 @@ class TSDFVolume:
         keep_largest all but the component with the most triangles; vertices no kept triangle names go with them, and the order of
         what stays is kept (mesh.remove_small_components; include/r3d.h "Mesh components").  With neither, the call is what it was.
         with_stats (with either of the two): a last element, the dict {"components", "components_kept", "triangles",
-        "triangles_kept"}."""
+        "triangles_kept"}.  smooth: None, or a dict / tuple of mesh.smooth_mesh's keywords (method, iterations, lam, mu,
+        lock_boundary): the vertices are smoothed on the device behind the component filter and the normals become the area-weighted
+        vertex normals of the moved mesh, the TSDF normals staying where a vertex has no area (include/r3d.h "Mesh smoothing");
+        colours, triangles, counts and stats are untouched, and self.last_smooth is the dict {"vertices", "edges",
+        "boundary_vertices", "steps"} of the run.  With smooth=None the call is what it was."""
         mw = _positive_f32(min_weight, "min_weight")
         if with_colors and not self.color:
             raise ValueError("with_colors needs a volume created with color=True")
@@ -287,6 +292,12 @@ class TSDFVolume:
         if filtered:
             from .mesh import _min_triangles
             min_tris = _min_triangles(1 if min_component_triangles is None else min_component_triangles)
+        params = None
+        if smooth is not None:
+            from .mesh import smooth_factors, smooth_params
+            params = smooth_params(smooth)
+            self.last_smooth = {"vertices": 0, "edges": 0, "boundary_vertices": 0,
+                                "steps": len(smooth_factors(params["method"], params["iterations"], params["lam"], params["mu"]))}
         n, m = self.extract_mesh_device(mw, None, None, 0, None, 0)
         if n == 0:
             empty = (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32))
@@ -297,7 +308,9 @@ class TSDFVolume:
             got = self.extract_mesh_device(mw, d_xyz.ptr, d_nrm.ptr, n, d_tri.ptr if m else None, m)
             assert got == (n, m), (got, n, m)
             if filtered:
-                return self._filtered_mesh(mw, d_xyz, d_nrm, d_tri, n, m, min_tris, bool(keep_largest), with_colors, with_stats)
+                return self._filtered_mesh(mw, d_xyz, d_nrm, d_tri, n, m, min_tris, bool(keep_largest), with_colors, with_stats, params)
+            if params is not None:
+                return self._smoothed_mesh(mw, d_xyz, d_nrm, d_tri, n, m, with_colors, params)
             tri = d_tri.download(np.int32, 3 * m).reshape(m, 3) if m else np.zeros((0, 3), np.int32)
             out = (d_xyz.download(np.float32, 3 * n).reshape(n, 3), d_nrm.download(np.float32, 3 * n).reshape(n, 3), tri)
             return out + (self._extract_colors(mw, n),) if with_colors else out
@@ -305,13 +318,28 @@ class TSDFVolume:
             for b in (d_xyz, d_nrm, d_tri):
                 b.free()
 
-    def _filtered_mesh(self, mw, d_xyz, d_nrm, d_tri, n, m, min_tris, keep_largest, with_colors, with_stats):
-        """extract_triangle_mesh's result from the n vertices and m triangles in HBM, filtered there (mesh.filter_mesh_device)"""
-        from .mesh import download_rows, filter_mesh_device, mesh_components_device
+    def _smoothed_mesh(self, mw, d_xyz, d_nrm, d_tri, n, m, with_colors, params):
+        """extract_triangle_mesh's result from the n vertices and m triangles in HBM, smoothed there (mesh.smooth_mesh_buffers)"""
+        from .mesh import download_rows, smooth_mesh_buffers
+        bufs = []
+        try:
+            d_x, d_n, self.last_smooth = smooth_mesh_buffers(self.ctx, d_xyz.ptr, d_nrm.ptr, d_tri.ptr, n, m, params, bufs)
+            out = (download_rows(d_x, np.float32, n, 3), download_rows(d_n, np.float32, n, 3), download_rows(d_tri, np.int32, m, 3))
+            return out + (self._extract_colors(mw, n),) if with_colors else out
+        finally:
+            for b in bufs:
+                b.free()
+
+    def _filtered_mesh(self, mw, d_xyz, d_nrm, d_tri, n, m, min_tris, keep_largest, with_colors, with_stats, params=None):
+        """extract_triangle_mesh's result from the n vertices and m triangles in HBM, filtered there (mesh.filter_mesh_device) and,
+        with params, smoothed behind the filter"""
+        from .mesh import download_rows, filter_mesh_device, mesh_components_device, smooth_mesh_buffers
         bufs = []
         try:
             d_x, d_n, d_t, kept, nk, mk, comps = filter_mesh_device(self.ctx, d_xyz.ptr, d_nrm.ptr, d_tri.ptr, n, m, min_tris, keep_largest,
                                                                     bufs)
+            if params is not None:
+                d_x, d_n, self.last_smooth = smooth_mesh_buffers(self.ctx, d_x.ptr, d_n.ptr, d_t.ptr, nk, mk, params, bufs)
             out = (download_rows(d_x, np.float32, nk, 3), download_rows(d_n, np.float32, nk, 3), download_rows(d_t, np.int32, mk, 3))
             if with_colors:
                 out += (self._extract_colors(mw, n)[kept],)

@@ -855,6 +855,80 @@ int r3d_mesh_filter_components(r3d_ctx* ctx, const int32_t* d_tri, int64_t n_tri
                                uint32_t* d_kept_vertices_out, int64_t cap_vertices, int32_t* d_tri_out, int64_t cap_triangles,
                                int64_t* n_vertices_out, int64_t* n_triangles_out);
 
+/* ---- Mesh smoothing (csrc/r3d_mesh_smooth.hip, csrc/r3d_mesh_smooth_host.cpp; NOT IN THE REFERENCE, this text is the
+ * specification).  Component removal takes the floaters away; the surface that stays is bumpy and terraced where the depth was
+ * noisy.  These three calls build the vertex adjacency of an indexed triangle mesh, move the vertices by a sequence of umbrella
+ * steps (Laplacian and Taubin smoothing), and recompute the vertex normals of the moved mesh, on the device, between
+ * r3d_tsdf_extract_mesh (or r3d_mesh_filter_components) and the download.  Users know the steps as Open3D's filter_smooth_taubin
+ * and compute_vertex_normals; NO parity with Open3D or MeshLab is claimed.  tests/mesh_smooth_ref.py restates this text in NumPy and
+ * the device matches it bit for bit: no result depends on the launch geometry, the scheduling or the order of the triangles.
+ * Timed once, without a gate: DESIGN.md 4.5j''.
+ * The mesh: d_tri [n_triangles][3] int32 vertex indices into n_vertices vertices; positions [n_vertices][3] f32, packed.
+ * A triangle is VALID iff its three indices lie in [0, n_vertices) (the rule of "Mesh components"); an invalid triangle
+ * contributes nothing anywhere below, and no index is used as an address before it is checked.
+ *
+ * r3d_mesh_adjacency: the one-ring of every vertex as a CSR, and the boundary flags.
+ *   Sides: a valid triangle (a, b, c) has the sides (a, b), (b, c), (c, a).  A side with u == v is dropped; the other sides of a
+ *     degenerate triangle still count.
+ *   Neighbours: v is a neighbour of u iff some side joins them, in either direction.  Row u of the CSR holds its distinct
+ *     neighbours in ASCENDING INDEX: d_neighbours_out[d_row_start_out[u] .. d_row_start_out[u + 1]).  d_row_start_out
+ *     [n_vertices + 1] u32 is always written whole; row_start[u + 1] - row_start[u] is the degree and row_start[n_vertices] the
+ *     total E.  The adjacency is symmetric by construction, so E is even.
+ *   Boundary: d_boundary_out [n_vertices] u8 (may be NULL): 1 iff the vertex lies on an undirected edge {u, v} that exactly one
+ *     side has, counted with multiplicity over all valid triangles and both directions; else 0.  A triangle listed twice
+ *     therefore makes its edges non-boundary, and a vertex without neighbours is not boundary.
+ *   Caps: *n_neighbours_out is the true E, always; at most cap_neighbours entries of d_neighbours_out are written and nothing
+ *     beyond them (call with cap 0 for the count, then with room); d_neighbours_out may be NULL with cap_neighbours == 0.
+ *   n_triangles == 0 gives an all-zero row_start and boundary; n_vertices == 0 (every triangle is then invalid) is legal and
+ *     writes the one word row_start[0] = 0.
+ *   R3D_ERR_INVALID, nothing written: a NULL ctx, d_row_start_out or n_neighbours_out; a negative size or cap; a NULL d_tri with
+ *     n_triangles > 0 or d_neighbours_out with cap_neighbours > 0; any overlap between d_tri and an output or between two
+ *     outputs.  6 * n_triangles >= 2^32 (the prefixes are 32-bit) or n_vertices > 2^31 - 1: R3D_ERR_UNSUPPORTED.
+ *   How: both directions of every side as a key (u << vb | v), vb = the bits of a vertex index, radix-sorted over the 2 vb + 1
+ *     bits in use; the run heads are the distinct neighbours, compacted in order; a run of length 1 is a boundary edge; row_start
+ *     is a lower bound per vertex.  The call synchronises (twice: for E, and before it returns).
+ *
+ * r3d_mesh_smooth: n_factors umbrella steps, `factors` (host, fp64) one per step.  Laplacian smoothing with `it` iterations is
+ *   [lambda] * it; Taubin smoothing is [lambda, mu] * it with mu < 0 and |mu| > lambda (e.g. 0.5 and -0.53).
+ *   d_row_start, d_neighbours: what r3d_mesh_adjacency wrote for this mesh (all E entries).  d_locked [n_vertices] u8 or NULL.
+ *   One step with factor f, for every vertex i with degree d > 0 and (d_locked == NULL or d_locked[i] == 0), per component, in
+ *   fp64 from the f32 positions widened first, the neighbours j0, j1, ... in row order (ascending index):
+ *       s  = (((double)p[j0] + (double)p[j1]) + (double)p[j2]) + ...
+ *       m  = s / (double)d
+ *       p' = (float)((double)p[i] + f * (m - (double)p[i]))          no fused multiply-add, correctly rounded division
+ *   Every other vertex keeps its bits.  Positions are rounded to f32 once per step, and every vertex of a step reads the previous
+ *   step's positions (Jacobi, never in place).  NaN and infinities propagate as the arithmetic says; there is no special case.
+ *   n_factors == 0 copies d_xyz_in to d_xyz_out.  n_vertices == 0 does nothing.  d_neighbours is read only for vertices with a
+ *   degree > 0 (it may be NULL for a mesh without edges).  d_xyz_in is not modified.
+ *   R3D_ERR_INVALID, nothing written: a NULL ctx; n_vertices < 0; n_factors outside [0, 4096]; NULL factors with n_factors > 0; a
+ *     factor that is not finite; a NULL position pointer with n_vertices > 0; a NULL d_row_start with steps to do; d_xyz_out
+ *     overlapping d_xyz_in, d_row_start, d_neighbours or d_locked.  n_vertices > 2^31 - 1: R3D_ERR_UNSUPPORTED.
+ *   How: one lane per vertex, one launch per step, no atomics, vector stores; the intermediate positions ping-pong between two
+ *     arrays of the context's workspace: only the first step reads d_xyz_in and only the last writes d_xyz_out.  ASYNCHRONOUS on
+ *     the context's stream (`factors` has been read when the call returns).
+ *
+ * r3d_mesh_vertex_normals: area-weighted vertex normals of the mesh as it stands.
+ *   For vertex i, s starts at (+0, +0, +0); every valid triangle t in ASCENDING t, and in it every corner c = 0, 1, 2 that names
+ *   i, adds the unnormalised face normal of t = (a, b, c) in fp64 from the f32 positions widened first, without fused multiply-add:
+ *       e1 = p[b] - p[a],  e2 = p[c] - p[a]
+ *       s.x += e1.y * e2.z - e1.z * e2.y;   s.y += e1.z * e2.x - e1.x * e2.z;   s.z += e1.x * e2.y - e1.y * e2.x
+ *   (a triangle that names i twice adds twice; a degenerate triangle adds exactly zero).  len = sqrt((s.x^2 + s.y^2) + s.z^2),
+ *   correctly rounded.  If 0 < len < inf the row is (float)(s / len) per component; otherwise it is row i of d_fallback, bits
+ *   kept, or (0, 0, 0) with d_fallback == NULL.  The winding of r3d_tsdf_extract_mesh faces the cameras, so these normals agree
+ *   in sign with the TSDF normals they replace.
+ *   R3D_ERR_INVALID, nothing written: a NULL ctx; a negative size; a NULL d_tri with n_triangles > 0, d_xyz or d_normals_out with
+ *     n_vertices > 0; d_normals_out overlapping an input.  The size limits of r3d_mesh_adjacency: R3D_ERR_UNSUPPORTED.
+ *   How: the incidence list (v << 32 | 3 t + c), sorted on the v bits alone by the stable radix sort, keeps t ascending; a lane per
+ *     vertex finds its run by lower bound.  No count comes back: ASYNCHRONOUS on the context's stream.
+ * The three calls keep their workspace (16 bytes per side or corner key, 24 per vertex) in the context, apart from the scratch
+ *   other calls share: results do not depend on what ran before on the context. */
+int r3d_mesh_adjacency(r3d_ctx* ctx, const int32_t* d_tri, int64_t n_triangles, int64_t n_vertices, uint32_t* d_row_start_out,
+                       uint32_t* d_neighbours_out, int64_t cap_neighbours, uint8_t* d_boundary_out, int64_t* n_neighbours_out);
+int r3d_mesh_smooth(r3d_ctx* ctx, const float* d_xyz_in, float* d_xyz_out, int64_t n_vertices, const uint32_t* d_row_start,
+                    const uint32_t* d_neighbours, const uint8_t* d_locked, const double* factors, int n_factors);
+int r3d_mesh_vertex_normals(r3d_ctx* ctx, const float* d_xyz, int64_t n_vertices, const int32_t* d_tri, int64_t n_triangles,
+                            const float* d_fallback, float* d_normals_out);
+
 /* ---- TSDF ray casting (csrc/r3d_tsdf_raycast.hip; the volume above seen from a camera: the depth, surface-point and normal image
  * the model predicts for a pose -- the third leg of integrate / ray cast / register; this text is the specification).  A ray-cast
  * vertex and normal map is a target cloud with normals for r3d's point-to-plane ICP (frame-to-model registration), and the depth
