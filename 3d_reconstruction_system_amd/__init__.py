@@ -31,6 +31,7 @@ from .colored_icp import ColourGradients, colour_gradients, colour_gradients_dev
 from .posegraph import (PoseGraph, evaluate_registration, registration_information, registration_sums_device,  # noqa: F401
                         register_multiway)
 from .tsdf import TSDFVolume, poses_w2c  # noqa: F401
+from .surface import volume_for_cloud, reconstruct_surface  # noqa: F401
 from .consistency import (window_sources, depth_consistency, depth_consistency_device, fuse_frames_consistent,  # noqa: F401
                           compact_rows_device)
 from .mesh import (MeshComponents, mesh_components, mesh_components_device, remove_small_components,  # noqa: F401

@@ -190,6 +190,8 @@ SIGNATURES = {
     "r3d_tsdf_integrate_rgb_host": (_i, [_vp, _vp, _vp, _i, _i, _d, _vp, _vp]),
     "r3d_tsdf_colors": (_i, [_vp, _pvp, _vp]),
     "r3d_tsdf_extract_colors": (_i, [_vp, _d, _vp, _i64, _vp]),
+    "r3d_tsdf_integrate_cloud": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "r3d_tsdf_integrate_cloud_host": (_i, [_vp, _vp, _vp, _vp, _i64, _vp]),
     "r3d_tsdf_raycast_rgb": (_i, [_vp, _vp, _i, _vp, _d, _d, _d, _d, _vp, _vp, _vp, _vp]),
     "r3d_track_accumulate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _vp, _vp, _vp]),
     "r3d_track_iterate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _i, _vp]),

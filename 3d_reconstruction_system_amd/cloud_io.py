@@ -423,9 +423,10 @@ def write_ply_normals(path, xyz, normals, rgb=None):
         f.write(rows.tobytes())
 
 
-def read_ply_normals(path):
+def read_ply_normals(path, with_colors=False):
     """(xyz [N,3] float32, normals [N,3] float32) of a binary little-endian PLY whose vertex properties start with float
-    x y z nx ny nz (write_ply_normals' layout, with or without its colour bytes)."""
+    x y z nx ny nz (write_ply_normals' layout, with or without its colour bytes).  with_colors: a third value, the [N,3] uint8
+    colours of uchar red green blue right behind the normals, or None for a file without."""
     with open(path, 'rb') as f:
         data = f.read()
     end = data.find(b'end_header\n')
@@ -455,7 +456,11 @@ def read_ply_normals(path):
         raise ValueError("%s: %d vertices of %d bytes announced, file is too short" % (path, n, stride))
     rows = np.frombuffer(data, dtype=np.uint8, count=n * stride, offset=start).reshape(n, stride)
     six = np.ascontiguousarray(rows[:, :24]).view('<f4').reshape(n, 6).astype(np.float32)
-    return np.ascontiguousarray(six[:, :3]), np.ascontiguousarray(six[:, 3:])
+    out = (np.ascontiguousarray(six[:, :3]), np.ascontiguousarray(six[:, 3:]))
+    if with_colors:
+        has_rgb = [(name, sizes[t]) for name, t in props[6:9]] == [('red', 1), ('green', 1), ('blue', 1)]
+        out += (np.ascontiguousarray(rows[:, 24:27]) if has_rgb else None,)
+    return out
 
 
 def _mesh_triangles(triangles, n_vertices, what):

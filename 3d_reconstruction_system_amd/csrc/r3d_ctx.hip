@@ -260,6 +260,7 @@ static int* tuning_slot(r3d_ctx* ctx, const char* key) {
   if (!strcmp(key, "octree_scan_us")) return &ctx->octree_us[1];
   if (!strcmp(key, "octree_own_us")) return &ctx->octree_us[2];
   if (!strcmp(key, "octree_link_us")) return &ctx->octree_us[3];
+  if (!strcmp(key, "tsdf_cloud_chunk")) return &ctx->tsdf_cloud_chunk;
   return nullptr;
 }
 

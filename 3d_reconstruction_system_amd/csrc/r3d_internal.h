@@ -22,9 +22,10 @@
 //                           copy; SOR scores; FPFH rows; merge remainders
 //   kWsSpare       shared   the radix sort's `tmp` where the caller has none (NN, voxel codes, r3d_sort_u64); fuse pose tables;
 //                           r3d_depth_consistency's relative pose rows ([F][S] x 64 bytes, the source index in each row's padding);
-//                           octree meta; merge segments; host ICP idx; feature match's b -> a partial minima
+//                           octree meta; merge segments; host ICP idx; feature match's b -> a partial minima; the block bitmap of
+//                           r3d_tsdf_integrate_cloud (dead before its first NN query)
 //   kWsCounts      shared   the histogram of EVERY radix sort (r3d_radix_sort_workspace; the private files sort too); compaction
-//                           Counters of knn, tsdf, tsdf_mesh, r3d_compact_rows_by_mask; octree tile places; host ICP d2 and sums; fuse rgb; feature match's
+//                           Counters of knn, tsdf, tsdf_mesh, tsdf_cloud, r3d_compact_rows_by_mask; octree tile places; host ICP d2 and sums; fuse rgb; feature match's
 //                           b -> a rows; the voxel union's counts
 //   kWsPartials    shared   partial rows of the sums passes (ICP, NN query + solve, tracking, SOR); NN bound rows; consensus
 //                           partials; r3d_apply_T_many's table; grad_P partials; fuse rgba; grid colours; a -> b partial minima
@@ -108,6 +109,7 @@ struct r3d_ctx {
   int voxel_last_path = 0; // read-only: the path the last r3d_voxelset_insert took (1 / 2)
   int octree_timing = 0;  // 1: the device octree serialiser puts HIP events around its four launches and waits for them ...
   int octree_us[4] = {};  // ... read-only: microseconds of count, scan, own, link of the last such call (r3d_octree.hip)
+  int tsdf_cloud_chunk = 0;  // 4 x 4 x 4 voxel blocks per chunk of r3d_tsdf_integrate_cloud's band (0 auto: 16384); results never depend on it
   int voxel_dedupe = 0;   // 0 auto (on), 1 off, 2 on: per-workgroup LDS dedupe in front of the global hash set; 3: on, with the
                           // flush barrier inside its `if` (A/B against DESIGN 4.5b's finding only)
   // HIP-event stopwatch

@@ -189,6 +189,8 @@ int r3d_tsdf_destroy(r3d_tsdf* v) {
   if (v->d_col) (void)hipFree(v->d_col);
   if (v->d_table) (void)hipFree(v->d_table);
   if (v->h_table) (void)hipHostFree(v->h_table);
+  for (void* p : v->cloud_buf)
+    if (p) (void)hipFree(p);
   for (int s = 0; s < kSlots; ++s)
     if (v->ev[s]) (void)hipEventDestroy(v->ev[s]);
   delete v;

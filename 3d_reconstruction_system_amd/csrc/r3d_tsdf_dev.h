@@ -236,6 +236,11 @@ struct r3d_tsdf {
   r3d_tsdf_dev::TsdfPoseRow* h_table = nullptr;   // the same, pinned: what the uploads read
   hipEvent_t ev[kSlots] = {};                     // slot s of h_table has been read by its upload
   unsigned next_slot = 0;
+  // r3d_tsdf_cloud.hip's grow-only device buffers (block list, one chunk's queries and matches, the host entry's upload): the NN
+  // query in the middle of a cloud call takes the context's shared workspaces, so what lives across it belongs to the volume
+  static constexpr int kCloudBufs = 3;
+  void* cloud_buf[kCloudBufs] = {};
+  size_t cloud_bytes[kCloudBufs] = {};
 };
 
 // One step through the volume's pose ring, for every launch that reads poses: takes the next slot, waits until the upload that
@@ -277,6 +282,23 @@ inline int r3d_tsdf_extract_checks(const r3d_tsdf* v, bool have_counts, const ch
   for (const r3d_tsdf_out& o : outs) R3D_REQUIRE(o.cap == 0 || o.p != nullptr, "%s is NULL with %s > 0", o.name, o.cap_name);
   return R3D_OK;
 }
+
+// r3d_tsdf_cloud.hip: the launches r3d_tsdf_cloud_host.cpp drives (asynchronous on the ctx stream, arguments checked by then).  The
+// band is made of blocks of 4 x 4 x 4 voxels, numbered (bz by + by) bx + bx with b* = ceil(n* / 4): _blocks is their number.  _mark:
+// the bit of every block that the sdf_trunc box of one of the n points at d_tgt overlaps is set in d_bitmap (zeroed by the caller,
+// ceil(blocks / 32) words).  _count / _list: the compaction step of r3d_compact_dev.h over those words -- hist holds the tiles'
+// counts after _count, their exclusive prefixes for _list, which writes the marked blocks' numbers in ascending order.  _centres:
+// the 64 voxel centres of each of n_blocks listed blocks as query points d_q [n_blocks * 64][3] (NaN where a block hangs over the
+// volume).  _apply: the rule for the same voxels from their matches d_idx / d_d2; d_rgba != NULL: into d_col too; *d_touched
+// grows by the number of voxels updated.
+int64_t r3d_tsdf_cloud_blocks(const r3d_tsdf_dev::TsdfGrid& g);
+void r3d_tsdf_cloud_mark_launch(r3d_ctx* ctx, const float* d_tgt, int64_t n, const r3d_tsdf_dev::TsdfGrid& g, uint32_t* d_bitmap);
+void r3d_tsdf_cloud_count_launch(r3d_ctx* ctx, const uint32_t* d_bitmap, int64_t n_words, int tiles, uint32_t* hist);
+void r3d_tsdf_cloud_list_launch(r3d_ctx* ctx, const uint32_t* d_bitmap, int64_t n_words, int tiles, const uint32_t* hist, uint32_t* d_list);
+void r3d_tsdf_cloud_centres_launch(r3d_ctx* ctx, const uint32_t* d_list, uint32_t n_blocks, const r3d_tsdf_dev::TsdfGrid& g, float* d_q);
+void r3d_tsdf_cloud_apply_launch(r3d_ctx* ctx, const uint32_t* d_list, uint32_t n_blocks, const r3d_tsdf_dev::TsdfGrid& g,
+                                 const uint32_t* d_idx, const float* d_d2, const float* d_tgt, const float* d_normals, const uint32_t* d_rgba,
+                                 uint32_t n_points, float2* d_vol, uint4* d_col, unsigned long long* d_touched);
 
 // r3d_tsdf.hip: the argument checks r3d_tsdf_integrate makes (R3D_OK with n_frames == 0 too: the caller returns then);
 int r3d_tsdf_integrate_checks(r3d_tsdf* vol, const r3d_camera* cam, const void* depth, int depth_dtype, int n_frames, double depth_scale,

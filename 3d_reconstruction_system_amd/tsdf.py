@@ -79,6 +79,14 @@ def _unpack_rgba(words):
     return np.stack([w & 0xff, (w >> 8) & 0xff, (w >> 16) & 0xff], axis=1).astype(np.uint8)
 
 
+def _cloud_rows(a, what):
+    """a as a contiguous [N,3] float32 array"""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.ndim != 2 or a.shape[1] != 3 or a.shape[0] >= 1 << 32:
+        raise ValueError("%s must be [N,3] with N < 2^32, got shape %s" % (what, list(a.shape)))
+    return a
+
+
 def _pose_rows(poses, n_frames):
     p = np.ascontiguousarray(poses, dtype=np.float64)
     if p.ndim != 2 or p.shape != (n_frames, 12):
@@ -174,6 +182,37 @@ class TSDFVolume:
             return
         L.check(self.ctx.lib.r3d_tsdf_integrate(self.handle, cam.handle, d_depth, depth_code(depth_dtype), n_frames, float(depth_scale),
                                                 table.ctypes.data))
+
+    def integrate_cloud(self, xyz, normals, rgb=None):
+        """Integrate an oriented cloud as ONE frame: every voxel within sdf_trunc of its nearest point takes the signed distance
+        to that point's tangent plane, truncated like a depth frame's (include/r3d.h "TSDF from an oriented cloud"; Hoppe et
+        al.).  xyz, normals: [N,3] float32 (normals as estimate_normals orients them, pointing out of the surface; zero or
+        non-finite rows contribute nothing, and neither do non-finite points); a volume with colour takes rgb too: [N,3] uint8.
+        Composes with integrate() and with itself as running averages.  Returns the number of voxels updated.  Synchronous."""
+        self._check_color(rgb is not None, "rgb")
+        p, nrm = _cloud_rows(xyz, "xyz"), _cloud_rows(normals, "normals")
+        if nrm.shape != p.shape:
+            raise ValueError("normals must be [N,3] like the cloud, got %s for %s" % (list(nrm.shape), list(p.shape)))
+        words = None
+        if rgb is not None:
+            c = np.asarray(rgb)
+            if c.dtype != np.uint8 or c.shape != p.shape:
+                raise ValueError("rgb must be [N,3] uint8 like the cloud, got %s of shape %s" % (c.dtype, list(c.shape)))
+            c = c.astype(np.uint32)
+            words = np.ascontiguousarray(c[:, 0] | c[:, 1] << 8 | c[:, 2] << 16)
+        n = C.c_int64()
+        L.check(self.ctx.lib.r3d_tsdf_integrate_cloud_host(self.handle, p.ctypes.data, nrm.ctypes.data,
+                                                           None if words is None else words.ctypes.data, p.shape[0], C.byref(n)))
+        return n.value
+
+    def integrate_cloud_device(self, index, d_normals, d_rgba=None, want_count=False):
+        """The same from a cloud in HBM: index is an NNIndex over it (same context), d_normals its [n][3] float32 normals in the
+        cloud's row order and d_rgba (a volume with colour) its [n] uint32 words r | g << 8 | b << 16, at raw device addresses.
+        Asynchronous on the context's stream; want_count: synchronises and returns the number of voxels updated."""
+        self._check_color(d_rgba is not None, "d_rgba")
+        n = C.c_int64()
+        L.check(self.ctx.lib.r3d_tsdf_integrate_cloud(self.handle, index.handle, d_normals, d_rgba, C.byref(n) if want_count else None))
+        return n.value if want_count else None
 
     def device_view(self):
         """(raw device address of the [n_voxels][2] float32 {tsdf, weight} array, n_voxels)."""

@@ -1012,6 +1012,42 @@ int r3d_tsdf_integrate_rgb_host(r3d_tsdf* vol, const r3d_camera* cam, const void
 int r3d_tsdf_colors(r3d_tsdf* vol, uint32_t** d_sums_out, int64_t* n_voxels_out);
 int r3d_tsdf_extract_colors(r3d_tsdf* vol, double min_weight, uint32_t* d_rgba_out, int64_t cap, int64_t* n_out);
 
+/* ---- TSDF from an oriented cloud (csrc/r3d_tsdf_cloud.hip; NOT IN THE REFERENCE -- the way from a fused, cleaned cloud with
+ * oriented normals (r3d_normals_knn) to a surface: the volume above is filled with the signed distance to the tangent plane of
+ * the NEAREST cloud point (Hoppe et al. 1992), after which the mesh, the surface points, ray casting and colour work unchanged;
+ * this text is the specification).  Every output bit is a chain of IEEE f32 operations in the order written here: no contraction
+ * except where fmaf is written, correctly rounded division, f32 denormals kept.
+ * Inputs: a volume; an r3d_nn_index built over the cloud's n points (same ctx as the volume); d_normals [n][3] f32 in the cloud's
+ *   ORIGINAL row order; d_rgba [n] u32 words r | g << 8 | b << 16, for a volume created with colour and only for one.
+ * For every voxel (x, y, z):
+ *     c    = o + ((float) idx + 0.5f) * vs                                 per axis (the volume's own centre rule)
+ *     j,d2 = the nearest cloud point of c under r3d_icp_nn's rule          d2 = fmaf(dz,dz, fmaf(dy,dy, dx*dx)) with dx = c.x - p.x ...;
+ *                                                                          lowest index wins exact ties; non-finite pairs never win
+ *     skip unless d2 <= tr * tr                                            (an f32 product; a voxel without a finite pair has d2 = +inf)
+ *     n    = normals[j];  skip unless all three are finite and not all are zero
+ *     s    = ((c.x - p.x) * n.x + (c.y - p.y) * n.y) + (c.z - p.z) * n.z   p = points[j]
+ *     tn   = fmaxf(-1.0f, fminf(1.0f, s / tr))                             (fminf / fmaxf return the other operand of a NaN: an s that
+ *                                                                          overflowed to NaN gives 1)
+ *     w1   = w + 1.0f;  tsdf = (tsdf * w + tn) / w1;  w = w1               the update of "TSDF volume": a cloud counts as ONE frame
+ *     colour (with d_rgba): r, g, b of rgba[j] are added to sum_r, sum_g, sum_b and 1 to n, as r3d_tsdf_integrate_rgb adds a pixel
+ *   The normals are used as given: unit length is the caller's business (a longer normal clamps earlier).  The winner alone decides:
+ *   a voxel whose nearest point has a zero or non-finite normal is skipped, not handed to the runner-up.  A skipped voxel keeps
+ *   every bit it had.  The result is DEFINED by brute force over all voxels and all points: it does not depend on launch geometry,
+ *   on how the implementation limits the work to the band of voxels within tr of the cloud, or on its chunking (tuning key
+ *   "tsdf_cloud_chunk": blocks of 4 x 4 x 4 voxels per chunk, 0 = default).  Calls compose with each other and with
+ *   r3d_tsdf_integrate*: a cloud on top of depth frames, or two clouds, are the running averages written above.
+ * r3d_tsdf_integrate_cloud is asynchronous on the ctx stream unless n_touched_out != NULL: then it synchronises and reports the
+ *   number of voxels updated.  (Sizing the band costs one small read-back either way.)  r3d_tsdf_integrate_cloud_host uploads
+ *   h_xyz [n][3], h_normals [n][3] (and h_rgba [n]), builds and destroys an index of its own and is synchronous; n == 0 -> R3D_OK,
+ *   nothing written.  The work buffers belong to the volume and go with r3d_tsdf_destroy.
+ * R3D_ERR_INVALID, nothing written: NULL volume, index or normals (NULL h_xyz / h_normals with n > 0; n < 0); an index of another
+ *   ctx than the volume's; d_rgba on a volume without colour; NO d_rgba on a volume WITH colour (n and w would part, as in "TSDF
+ *   colour"). */
+int r3d_tsdf_integrate_cloud(r3d_tsdf* vol, r3d_nn_index* index, const float* d_normals, const uint32_t* d_rgba,
+                             int64_t* n_touched_out);
+int r3d_tsdf_integrate_cloud_host(r3d_tsdf* vol, const float* h_xyz, const float* h_normals, const uint32_t* h_rgba, int64_t n,
+                                  int64_t* n_touched_out);
+
 /* ---- TSDF ray-cast colour (csrc/r3d_tsdf_raycast.hip; the colour image a volume with colour predicts for a pose, next to the three
  * maps of "TSDF ray casting"; this text is the specification).  r3d_tsdf_raycast_rgb is r3d_tsdf_raycast with a fourth output: the
  * ray, the slab test, the march, the hit and the hit-point sample are the ones specified there, word for word, and d_depth_out,
