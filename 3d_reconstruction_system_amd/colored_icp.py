@@ -13,10 +13,13 @@ import math
 import numpy as np
 
 from . import _lib as L
+from ._args import colour_words as _words, positive as _positive
 from .device import default_context
 from .icp import NNIndex, STATE_DOUBLES
 from .normals import _check_k, _check_radius
-from .outliers import _Cloud, _cloud
+from .outliers import Cloud, _cloud
+
+_Cloud = Cloud            # the name this class had while it was private: callers written against it keep working
 
 COLOR_SUMS = 31            # R3D_COLOR_ICP_SUMS: the 29 plane sums, the photometric pair count, the sum of rI^2
 # defaults from the sweep of DESIGN.md section 4.5t (one scene: a starting point, not a law)
@@ -29,29 +32,11 @@ ColourGradients.__doc__ = ("Intensity [N] float32 in 0..255, its tangent-plane g
                            "gradient), neighbours used [N] uint32.")
 
 
-def _words(rgba, n, what):
-    w = np.asarray(rgba)
-    if w.dtype != np.uint32 or w.ndim != 1 or w.shape[0] != n:
-        raise ValueError("%s must be [N] uint32 colour words (r | g << 8 | b << 16), one per point: got %s %s for %d points"
-                         % (what, w.dtype, w.shape, n))
-    return np.ascontiguousarray(w)
-
-
 def _normals(normals, n):
     nrm = np.asarray(normals)
     if nrm.dtype.kind != "f" or nrm.shape != (n, 3):
         raise ValueError("normals must be a float [%d,3] array, got %s %r" % (n, nrm.dtype, nrm.shape))
     return np.ascontiguousarray(nrm, dtype=np.float32)
-
-
-def _positive(v, what):
-    try:
-        v = float(v)
-    except (TypeError, ValueError):
-        raise ValueError("%s must be a finite number > 0, got %r" % (what, v))
-    if not (math.isfinite(v) and v > 0.0):
-        raise ValueError("%s must be a finite number > 0, got %r" % (what, v))
-    return v
 
 
 def photo_weight(lambda_geometric):
@@ -89,14 +74,11 @@ def colour_gradients(tgt, tgt_rgba, normals, k=K, radius=None, ctx=None):
     rgba, nrm = _words(tgt_rgba, n, "tgt_rgba"), _normals(normals, n)
     if n == 0:
         return ColourGradients(np.zeros(0, np.float32), np.zeros((0, 3), np.float32), np.zeros(0, np.uint32))
-    c = _Cloud(ctx or default_context(), xyz)
-    try:
-        d_n, d_w = c.alloc(n * 12).upload(nrm), c.alloc(n * 4).upload(rgba)
+    with Cloud(ctx or default_context(), xyz) as c:
+        d_n, d_w = c.upload(nrm), c.upload(rgba)
         d_i, d_g, d_c = c.alloc(n * 4), c.alloc(n * 12), c.alloc(n * 4)
         L.check(c.ctx.lib.r3d_color_gradient_knn(c.index.handle, k, r, d_n.ptr, d_w.ptr, d_i.ptr, d_g.ptr, d_c.ptr))
-        return ColourGradients(d_i.download(np.float32, n), d_g.download(np.float32, 3 * n).reshape(n, 3), d_c.download(np.uint32, n))
-    finally:
-        c.close()
+        return ColourGradients(d_i.download(np.float32, n), d_g.download_array(np.float32, (n, 3)), d_c.download(np.uint32, n))
 
 
 def icp_colored(src, src_rgba, tgt, tgt_rgba, tgt_normals=None, init=None, max_iter=30, max_dist=None, lambda_geometric=LAMBDA_GEOMETRIC,
@@ -132,20 +114,19 @@ def icp_colored(src, src_rgba, tgt, tgt_rgba, tgt_normals=None, init=None, max_i
     if nrm is None:
         from .normals import estimate_normals
         nrm = estimate_normals(tgt, k, ctx=ctx).normals
-    c = _Cloud(ctx, tgt)
-    try:
+    with Cloud(ctx, tgt) as c:
         lib, h = ctx.lib, ctx.handle
-        d_n, d_w = c.alloc(m * 12).upload(nrm), c.alloc(m * 4).upload(tgt_w)
+        d_n, d_w = c.upload(nrm), c.upload(tgt_w)
         d_i, d_g = c.alloc(m * 4), c.alloc(m * 12)
         L.check(lib.r3d_color_gradient_knn(c.index.handle, k, 0.0, d_n.ptr, d_w.ptr, d_i.ptr, d_g.ptr, None))
         # the source: moved by init, put into the index's order where it lies then (rigid moves preserve the order), its
         # intensities permuted alongside
-        d_src, d_src0, d_perm = c.alloc(n * 12).upload(src), c.alloc(n * 12), c.alloc(n * 4)
+        d_src, d_src0, d_perm = c.upload(src), c.alloc(n * 12), c.alloc(n * 4)
         if init is not None:
             L.check(lib.r3d_apply_T(h, d_src.ptr, L.F32, n, np.ascontiguousarray(T0).ctypes.data, d_src.ptr, L.F32))
         c.index.sort_cloud(d_src.ptr, n, d_perm.ptr)
         perm = d_perm.download(np.uint32, n)
-        d_si = c.alloc(n * 4).upload(np.ascontiguousarray(intensity(src_w)[perm]))
+        d_si = c.upload(intensity(src_w)[perm])
         d_idx, d_d2 = c.alloc(n * 4), c.alloc(n * 4)
         d_state, d_sums = c.alloc(STATE_DOUBLES * 8), c.alloc(COLOR_SUMS * 8)
         L.check(lib.r3d_icp_state_reset(h, d_state.ptr))
@@ -153,8 +134,6 @@ def icp_colored(src, src_rgba, tgt, tgt_rgba, tgt_normals=None, init=None, max_i
         L.check(lib.r3d_icp_iterate_color(h, c.index.handle, d_src0.ptr, d_src.ptr, d_si.ptr, n, d_n.ptr, d_i.ptr, d_g.ptr, d_idx.ptr,
                                           d_d2.ptr, int(max_iter), max_d2, w, i_max, d_state.ptr, d_sums.ptr))
         st, s = d_state.download(np.float64, STATE_DOUBLES), d_sums.download(np.float64, COLOR_SUMS)
-    finally:
-        c.close()
     it = int(st[32])
     info = {"pairs": float(st[35]), "rms": float(st[34]), "photo_pairs": float(s[29]),
             "photo_rms": float(np.sqrt(s[30] / s[29])) if s[29] > 0 else 0.0, "status": int(st[33]), "iterations": it,

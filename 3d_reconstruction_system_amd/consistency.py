@@ -144,13 +144,11 @@ def fuse_frames_consistent(depths, quats_xyzw, ts, intrinsics=REF_INTRINSICS, ra
     ctx = ctx or default_context()
     cam = ctx.camera(h, w, *intrinsics)
     tab = pose_table(quats_xyzw, ts)
-    bufs = [ctx.alloc(d.nbytes).upload(d), ctx.alloc(tab.nbytes).upload(tab), ctx.alloc(n), ctx.alloc(n * 12)]
-    try:
-        d_depth, d_pose, d_keep, d_xyz = bufs
+    with ctx.buffers() as B:
+        d_depth, d_pose, d_keep, d_xyz = B.upload(d), B.upload(tab), B.alloc(n), B.alloc(n * 12)
         d_rgb = d_rgba = None
         if rgb is not None:
-            bufs += [ctx.alloc(rgb.nbytes).upload(rgb), ctx.alloc(n * 4)]
-            d_rgb, d_rgba = bufs[4:]
+            d_rgb, d_rgba = B.upload(rgb), B.alloc(n * 4)
         depth_consistency_device(ctx, cam, d_depth.ptr, d.dtype, f, w2c, src, d_keep=d_keep.ptr, rel_tol=rel_tol,
                                  min_consistent=min_consistent, max_violations=max_violations, depth_scale=depth_scale)
         if rgb is None:
@@ -161,16 +159,12 @@ def fuse_frames_consistent(depths, quats_xyzw, ts, intrinsics=REF_INTRINSICS, ra
         m = int(keep.sum())
         out_xyz, out_rgba = np.zeros((m, 3), np.float32), np.zeros(m, np.uint32)
         if m:
-            bufs.append(ctx.alloc(m * 12))
-            if rgb is not None:
-                bufs.append(ctx.alloc(m * 4))
-            got = compact_rows_device(ctx, d_xyz.ptr, None if rgb is None else d_rgba.ptr, n, d_keep.ptr, bufs[-2 if rgb is not None else -1].ptr,
-                                      None if rgb is None else bufs[-1].ptr, m)
+            d_out = B.alloc(m * 12)
+            d_out_rgba = None if rgb is None else B.alloc(m * 4)
+            got = compact_rows_device(ctx, d_xyz.ptr, None if rgb is None else d_rgba.ptr, n, d_keep.ptr, d_out.ptr,
+                                      None if rgb is None else d_out_rgba.ptr, m)
             assert got == m, (got, m)
-            out_xyz = bufs[-2 if rgb is not None else -1].download(np.float32, 3 * m).reshape(m, 3)
+            out_xyz = d_out.download_array(np.float32, (m, 3))
             if rgb is not None:
-                out_rgba = bufs[-1].download(np.uint32, m)
-    finally:
-        for b in bufs:
-            b.free()
+                out_rgba = d_out_rgba.download(np.uint32, m)
     return (out_xyz, keep) if rgb is None else (out_xyz, out_rgba, keep)

@@ -69,6 +69,11 @@ class DeviceBuffer:
         L.check(self.ctx.lib.r3d_download(self.ctx.handle, out.ctypes.data, self.ptr, out.nbytes))   # synchronous
         return out
 
+    def download_array(self, dtype, shape):
+        """The buffer's first prod(shape) elements as an array of that shape; nothing is read for a shape with a zero extent."""
+        n = int(np.prod(shape))
+        return self.download(dtype, n).reshape(shape) if n else np.zeros(shape, dtype)
+
     def free(self):
         if self.ptr:
             L.check(self.ctx.lib.r3d_dev_free(self.ctx.handle, self.ptr))
@@ -80,6 +85,51 @@ class DeviceBuffer:
                 self.ctx.lib.r3d_dev_free(self.ctx.handle, self.ptr)
         except Exception:
             pass
+
+
+class BufferScope:
+    """The device memory of one call (Context.buffers()): DeviceBuffers and the objects built over them, released together in
+    reverse order of creation by close().  A context manager.  Sizes go to the library as they are: it rounds 0 bytes up."""
+
+    def __init__(self, ctx):
+        self.ctx, self._owned = ctx, []
+
+    def alloc(self, nbytes):
+        self._owned.append(self.ctx.alloc(nbytes))
+        return self._owned[-1]
+
+    def upload(self, array):
+        """A new buffer holding `array` (nothing is copied, and nothing waited for, for 0 bytes)"""
+        array = np.ascontiguousarray(array)
+        b = self.alloc(array.nbytes)
+        return b.upload(array) if array.nbytes else b
+
+    def adopt(self, obj):
+        """Take over an object with a close() or free() method (an NNIndex, a MeshIndex); returns it."""
+        self._owned.append(obj)
+        return obj
+
+    def close(self):
+        """Release everything, the newest first.  All of it is tried; the first failure is raised at the end."""
+        failed = None
+        while self._owned:
+            obj = self._owned.pop()
+            try:
+                (obj.close if hasattr(obj, "close") else obj.free)()
+            except Exception as e:
+                failed = failed or e
+        if failed is not None:
+            raise failed
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        try:
+            self.close()
+        except Exception:
+            if exc_type is None:
+                raise
 
 
 class Context:
@@ -158,6 +208,10 @@ class Context:
 
     def alloc(self, nbytes):
         return DeviceBuffer(self, nbytes)
+
+    def buffers(self):
+        """A BufferScope: `with ctx.buffers() as B:` owns the device memory of one call."""
+        return BufferScope(self)
 
     def pinned_empty(self, shape, dtype):
         """NumPy array backed by page-locked host memory (r3d_host_alloc): the *_host entry points DMA

@@ -127,7 +127,7 @@ class TextWriter:
         total = sum(j[7] for j in self._jobs)
         raw_total = sum(r[3] for r in self._raw)
         files, keep = [], []
-        buf = ctx.alloc(max(total, 16)) if self._jobs else None
+        buf = ctx.alloc(total) if self._jobs else None
         try:
             _common.stamp("text buffer allocated (%d bytes)" % total)
             at = 0

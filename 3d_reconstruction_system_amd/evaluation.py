@@ -12,19 +12,13 @@ import math
 import numpy as np
 
 from . import _lib as L
+from ._args import MAX_ITEMS, count as _count
 from .device import default_context
 from .icp import NNIndex
 
 NO_TRIANGLE = 0xFFFFFFFF     # the winner of a point without a nearest triangle
 SIGNED = 1                   # R3D_MESHDIST_SIGNED
 MAX_THRESHOLDS, MAX_BINS = 8, 4096
-MAX_ITEMS = 2 ** 31 - 1
-
-
-def _count(v, what):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= MAX_ITEMS:
-        raise ValueError("%s must be an integer in [0, 2^31 - 1], got %r" % (what, v))
-    return int(v)
 
 
 def _points(xyz, what):
@@ -139,48 +133,17 @@ def distance_colors_device(ctx, d_dist, n, d_max, d_rgba):
     L.check(ctx.lib.r3d_distance_colors(ctx.handle, d_dist, _count(n, "n"), float(d_max), d_rgba))
 
 
-class _Buffers:
-    """device allocations freed together"""
-
-    def __init__(self, ctx):
-        self.ctx, self.bufs = ctx, []
-
-    def alloc(self, nbytes):
-        b = self.ctx.alloc(max(int(nbytes), 16))
-        self.bufs.append(b)
-        return b
-
-    def upload(self, array):
-        b = self.alloc(array.nbytes)
-        if array.nbytes:
-            b.upload(array)
-        return b
-
-    def free(self):
-        for b in self.bufs:
-            b.free()
-        self.bufs = []
-
-
-def _download(buf, dtype, shape):
-    n = int(np.prod(shape))
-    return buf.download(dtype, n).reshape(shape) if n else np.zeros(shape, dtype)
-
-
 def cloud_to_cloud_distance(src, tgt, ctx=None):
     """(distances [N] float32, indices [N] uint32): from every point of src to its exact nearest point of tgt (at least one)."""
     src, tgt = _points(src, "src"), _points(tgt, "tgt")
     if len(tgt) == 0:
         raise ValueError("the target cloud is empty")
     ctx = ctx or default_context()
-    B = _Buffers(ctx)
-    try:
+    with ctx.buffers() as B:
         d_src, d_tgt = B.upload(src), B.upload(tgt)
         d_dist, d_idx = B.alloc(len(src) * 4), B.alloc(len(src) * 4)
         cloud_to_cloud_distance_device(ctx, d_src.ptr, len(src), d_tgt.ptr, len(tgt), d_dist.ptr, d_idx.ptr)
-        return _download(d_dist, np.float32, (len(src),)), _download(d_idx, np.uint32, (len(src),))
-    finally:
-        B.free()
+        return d_dist.download_array(np.float32, (len(src),)), d_idx.download_array(np.uint32, (len(src),))
 
 
 def cloud_to_mesh_distance(points, vertices, triangles, signed=False, return_closest=False, ctx=None):
@@ -189,18 +152,15 @@ def cloud_to_mesh_distance(points, vertices, triangles, signed=False, return_clo
     triangle's face.  A point with a non-finite coordinate, or a mesh without a valid triangle: +inf, 0xFFFFFFFF, NaN."""
     pts, v, t = _points(points, "points"), _points(vertices, "vertices"), _triangles(triangles)
     ctx = ctx or default_context()
-    B = _Buffers(ctx)
-    try:
+    with ctx.buffers() as B:
         d_pts, d_v, d_t = B.upload(pts), B.upload(v), B.upload(t)
         n = len(pts)
         d_dist, d_win = B.alloc(n * 4), B.alloc(n * 4)
         d_q = B.alloc(n * 12) if return_closest else None
-        with MeshIndex(ctx, d_v.ptr, len(v), d_t.ptr, len(t)) as index:
-            index.query(d_pts.ptr, n, d_dist.ptr, d_win.ptr, d_q.ptr if d_q else None, signed=signed)
-            out = (_download(d_dist, np.float32, (n,)), _download(d_win, np.uint32, (n,)))
-            return out + (_download(d_q, np.float32, (n, 3)),) if return_closest else out
-    finally:
-        B.free()
+        index = B.adopt(MeshIndex(ctx, d_v.ptr, len(v), d_t.ptr, len(t)))
+        index.query(d_pts.ptr, n, d_dist.ptr, d_win.ptr, d_q.ptr if d_q else None, signed=signed)
+        out = (d_dist.download_array(np.float32, (n,)), d_win.download_array(np.uint32, (n,)))
+        return out + (d_q.download_array(np.float32, (n, 3)),) if return_closest else out
 
 
 def distance_stats(d, thresholds=(), bin_width=None, n_bins=0, squared=False, ctx=None):
@@ -209,24 +169,18 @@ def distance_stats(d, thresholds=(), bin_width=None, n_bins=0, squared=False, ct
     values are counted apart.  Fixed-order device sums: the same bits run to run."""
     d = np.ascontiguousarray(np.asarray(d, np.float32).reshape(-1))
     ctx = ctx or default_context()
-    B = _Buffers(ctx)
-    try:
+    with ctx.buffers() as B:
         return distance_stats_device(ctx, B.upload(d).ptr, len(d), thresholds, bin_width, n_bins, squared)
-    finally:
-        B.free()
 
 
 def distance_colors(d, d_max, ctx=None):
     """[N] uint32 colour words (r | g << 8 | b << 16, what cloud_io.write_ply_rgb takes) of the distances d."""
     d = np.ascontiguousarray(np.asarray(d, np.float32).reshape(-1))
     ctx = ctx or default_context()
-    B = _Buffers(ctx)
-    try:
+    with ctx.buffers() as B:
         d_rgba = B.alloc(len(d) * 4)
         distance_colors_device(ctx, B.upload(d).ptr, len(d), d_max, d_rgba.ptr)
-        return _download(d_rgba, np.uint32, (len(d),))
-    finally:
-        B.free()
+        return d_rgba.download_array(np.uint32, (len(d),))
 
 
 def _side(x, what):
@@ -280,15 +234,12 @@ def evaluate_reconstruction(recon, truth, threshold, ctx=None, return_distances=
         raise ValueError("threshold must be >= 0, got %r" % threshold)
     rec, tru = _side(recon, "recon"), _side(truth, "truth")
     ctx = ctx or default_context()
-    B = _Buffers(ctx)
-    try:
+    with ctx.buffers() as B:
         d_rec = [B.upload(rec[0])] + ([B.upload(rec[1])] if rec[1] is not None else [])
         d_tru = [B.upload(tru[0])] + ([B.upload(tru[1])] if tru[1] is not None else [])
         acc, d_acc = _directed(ctx, B, d_rec[0].ptr, len(rec[0]), tru, d_tru, threshold)
         com, d_com = _directed(ctx, B, d_tru[0].ptr, len(tru[0]), rec, d_rec, threshold)
         out = combine(acc, com, threshold)
         if return_distances:
-            return out, _download(d_acc, np.float32, (len(rec[0]),)), _download(d_com, np.float32, (len(tru[0]),))
+            return out, d_acc.download_array(np.float32, (len(rec[0]),)), d_com.download_array(np.float32, (len(tru[0]),))
         return out
-    finally:
-        B.free()

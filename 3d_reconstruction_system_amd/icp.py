@@ -738,19 +738,14 @@ def organized_normals(xyz, height, width, max_jump=0.05, viewpoint=None, ctx=Non
     n = xyz.shape[0]
     if n % (height * width) != 0:
         raise ValueError("cloud of %d points is not a whole number of %dx%d rasters" % (n, height, width))
-    out = np.zeros((n, 3), dtype=np.float32)
     if n == 0:
-        return out
-    d_in, d_out = ctx.alloc(xyz.nbytes).upload(xyz), ctx.alloc(xyz.nbytes)
-    try:
+        return np.zeros((0, 3), dtype=np.float32)
+    with ctx.buffers() as B:
+        d_in, d_out = B.upload(xyz), B.alloc(xyz.nbytes)
         vp = None if viewpoint is None else np.ascontiguousarray(viewpoint, dtype=np.float64)
         L.check(ctx.lib.r3d_normals_organized(ctx.handle, d_in.ptr, n // (height * width), int(height), int(width),
                                               float(max_jump), None if vp is None else vp.ctypes.data, d_out.ptr))
-        out = d_out.download(np.float32, n * 3).reshape(-1, 3)
-    finally:
-        d_in.free()
-        d_out.free()
-    return out
+        return d_out.download_array(np.float32, (n, 3))
 
 
 def select_quantile(d_values_ptr, n, q, ctx=None):

@@ -18,22 +18,16 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from ._args import MAX_ITEMS, count as _count
 from .device import default_context
 
 NO_LABEL = 0xFFFFFFFF   # the triangle label of an invalid triangle
-MAX_ITEMS = 2 ** 31 - 1
 
 MeshComponents = collections.namedtuple("MeshComponents", ["vertex_labels", "triangle_labels", "components", "n_invalid"])
 MeshComponents.__doc__ = ("vertex_labels [N] uint32 (the smallest vertex index of the vertex's component), triangle_labels [M] uint32 "
                           "(the label of the triangle's first index; 0xFFFFFFFF for a triangle with an index outside [0, N)), "
                           "components [K,3] uint32 rows (label, vertices, triangles) in ascending label -- the components that have "
                           "a triangle --, n_invalid: the number of invalid triangles.")
-
-
-def _count(v, what, lo=0):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= MAX_ITEMS:
-        raise ValueError("%s must be an integer in [%d, 2^31 - 1], got %r" % (what, lo, v))
-    return int(v)
 
 
 def _triangles(triangles):
@@ -55,13 +49,6 @@ def _min_triangles(v):
     if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) < 2 ** 63:
         raise ValueError("min_triangles must be an integer >= 1, got %r" % (v,))
     return int(v)
-
-
-def download_rows(buf, dtype, rows, width):
-    """[rows, width] of dtype from a DeviceBuffer (nothing is read for 0 rows)"""
-    if rows == 0:
-        return np.zeros((0, width), dtype)
-    return buf.download(dtype, rows * width).reshape(rows, width)
 
 
 def mesh_components_device(ctx, d_tri, n_triangles, n_vertices, d_vertex_labels, d_triangle_labels=None, d_components=None,
@@ -100,41 +87,31 @@ def mesh_components(triangles, n_vertices, ctx=None):
     tri, nv = _triangles(triangles), _count(n_vertices, "n_vertices")
     nt = len(tri)
     ctx = ctx or default_context()
-    bufs = []
-    try:
-        d_tri, d_vl, d_tl = ctx.alloc(max(tri.nbytes, 16)), ctx.alloc(max(nv * 4, 16)), ctx.alloc(max(nt * 4, 16))
-        bufs += [d_tri, d_vl, d_tl]
-        d_tri.upload(tri)
+    with ctx.buffers() as B:
+        d_tri, d_vl, d_tl = B.upload(tri), B.alloc(nv * 4), B.alloc(nt * 4)
         k, bad = mesh_components_device(ctx, d_tri.ptr, nt, nv, d_vl.ptr, d_tl.ptr)
         rows = np.zeros((0, 3), np.uint32)
         if k:
-            d_rows = ctx.alloc(k * 12)
-            bufs.append(d_rows)
+            d_rows = B.alloc(k * 12)
             got = mesh_components_device(ctx, d_tri.ptr, nt, nv, d_vl.ptr, d_tl.ptr, d_rows.ptr, k)
             assert got == (k, bad), (got, k, bad)
-            rows = d_rows.download(np.uint32, 3 * k).reshape(k, 3)
-        return MeshComponents(download_rows(d_vl, np.uint32, nv, 1).reshape(-1), download_rows(d_tl, np.uint32, nt, 1).reshape(-1), rows, bad)
-    finally:
-        for b in bufs:
-            b.free()
+            rows = d_rows.download_array(np.uint32, (k, 3))
+        return MeshComponents(d_vl.download_array(np.uint32, (nv,)), d_tl.download_array(np.uint32, (nt,)), rows, bad)
 
 
-def filter_mesh_device(ctx, d_xyz, d_normals, d_tri, n_vertices, n_triangles, min_triangles, keep_largest, bufs):
+def filter_mesh_device(ctx, d_xyz, d_normals, d_tri, n_vertices, n_triangles, min_triangles, keep_largest, B):
     """The device-resident mesh (raw addresses) filtered on the device: (d_xyz, d_normals, d_tri, kept [n] uint32 on the host,
-    n, m, n_components) with the three arrays new DeviceBuffers (appended to bufs, the caller frees them).  Positions and normals go
-    through r3d_gather_rows."""
+    n, m, n_components) with the three arrays new DeviceBuffers of the caller's buffer scope B.  Positions and normals go through
+    r3d_gather_rows."""
     nv, nt = n_vertices, n_triangles
-    d_vl, d_kept, d_out = ctx.alloc(max(nv * 4, 16)), ctx.alloc(max(nv * 4, 16)), ctx.alloc(max(nt * 12, 16))
-    bufs += [d_vl, d_kept, d_out]
+    d_vl, d_kept, d_out = B.alloc(nv * 4), B.alloc(nv * 4), B.alloc(nt * 12)
     k, _ = mesh_components_device(ctx, d_tri, nt, nv, d_vl.ptr)
     n, m = remove_small_components_device(ctx, d_tri, nt, nv, d_vl.ptr, min_triangles, keep_largest, d_kept.ptr, nv, d_out.ptr, nt)
-    d_xyz_out, d_nrm_out = ctx.alloc(max(n * 12, 16)), ctx.alloc(max(n * 12, 16))
-    bufs += [d_xyz_out, d_nrm_out]
+    d_xyz_out, d_nrm_out = B.alloc(n * 12), B.alloc(n * 12)
     if n:
         gather_rows_device(ctx, d_xyz, nv, d_kept.ptr, n, d_xyz_out.ptr)
         gather_rows_device(ctx, d_normals, nv, d_kept.ptr, n, d_nrm_out.ptr)
-    kept = download_rows(d_kept, np.uint32, n, 1).reshape(-1)
-    return d_xyz_out, d_nrm_out, d_out, kept, n, m, k
+    return d_xyz_out, d_nrm_out, d_out, d_kept.download_array(np.uint32, (n,)), n, m, k
 
 
 def remove_small_components(xyz, normals, triangles, min_triangles=1, keep_largest=False, colors=None, ctx=None):
@@ -155,21 +132,13 @@ def remove_small_components(xyz, normals, triangles, min_triangles=1, keep_large
         if colors.ndim < 1 or len(colors) != nv:
             raise ValueError("colors must have one row per vertex (%d), got shape %s" % (nv, list(colors.shape)))
     ctx = ctx or default_context()
-    bufs = []
-    try:
-        d_xyz, d_nrm, d_tri = ctx.alloc(max(xyz.nbytes, 16)), ctx.alloc(max(normals.nbytes, 16)), ctx.alloc(max(tri.nbytes, 16))
-        bufs += [d_xyz, d_nrm, d_tri]
-        d_xyz.upload(xyz)
-        d_nrm.upload(normals)
-        d_tri.upload(tri)
-        d_x, d_n, d_t, kept, n, m, _ = filter_mesh_device(ctx, d_xyz.ptr, d_nrm.ptr, d_tri.ptr, nv, nt, mt, keep_largest, bufs)
+    with ctx.buffers() as B:
+        d_xyz, d_nrm, d_tri = B.upload(xyz), B.upload(normals), B.upload(tri)
+        d_x, d_n, d_t, kept, n, m, _ = filter_mesh_device(ctx, d_xyz.ptr, d_nrm.ptr, d_tri.ptr, nv, nt, mt, keep_largest, B)
         tri_dtype = tri_in.dtype if tri_in.size else np.int32
-        out = (download_rows(d_x, np.float32, n, 3), download_rows(d_n, np.float32, n, 3),
-               download_rows(d_t, np.int32, m, 3).astype(tri_dtype, copy=False))
+        out = (d_x.download_array(np.float32, (n, 3)), d_n.download_array(np.float32, (n, 3)),
+               d_t.download_array(np.int32, (m, 3)).astype(tri_dtype, copy=False))
         return out + (colors[kept],) if colors is not None else out
-    finally:
-        for b in bufs:
-            b.free()
 
 
 # ---- smoothing (include/r3d.h "Mesh smoothing")
@@ -268,32 +237,29 @@ def vertex_normals_device(ctx, d_xyz, n_vertices, d_tri, n_triangles, d_fallback
                                             d_fallback, d_normals))
 
 
-def adjacency_buffers(ctx, d_tri, n_triangles, n_vertices, bufs):
-    """(d_row_start, d_neighbours, d_boundary, E) as new DeviceBuffers (appended to bufs): the two-call round trip for the cap"""
+def adjacency_buffers(ctx, d_tri, n_triangles, n_vertices, B):
+    """(d_row_start, d_neighbours, d_boundary, E) as new DeviceBuffers of the buffer scope B: the two-call round trip for the cap"""
     nv = n_vertices
-    d_rs, d_bd = ctx.alloc(max((nv + 1) * 4, 16)), ctx.alloc(max(nv, 16))
-    bufs += [d_rs, d_bd]
+    d_rs, d_bd = B.alloc((nv + 1) * 4), B.alloc(nv)
     e = mesh_adjacency_device(ctx, d_tri, n_triangles, nv, d_rs.ptr, None, 0, d_bd.ptr)
-    d_nb = ctx.alloc(max(e * 4, 16))
-    bufs.append(d_nb)
+    d_nb = B.alloc(e * 4)
     if e:
         got = mesh_adjacency_device(ctx, d_tri, n_triangles, nv, d_rs.ptr, d_nb.ptr, e, d_bd.ptr)
         assert got == e, (got, e)
     return d_rs, d_nb, d_bd, e
 
 
-def smooth_mesh_buffers(ctx, d_xyz, d_normals, d_tri, n_vertices, n_triangles, params, bufs):
+def smooth_mesh_buffers(ctx, d_xyz, d_normals, d_tri, n_vertices, n_triangles, params, B):
     """The device-resident mesh (raw addresses; d_normals the fallback or None) smoothed on the device: (d_xyz, d_normals, stats)
-    with the two arrays new DeviceBuffers (appended to bufs, the caller frees them) and stats the dict {"vertices", "edges",
+    with the two arrays new DeviceBuffers of the caller's buffer scope B and stats the dict {"vertices", "edges",
     "boundary_vertices", "steps"}.  params: smooth_params' dict."""
     nv, nt = n_vertices, n_triangles
     factors = smooth_factors(params["method"], params["iterations"], params["lam"], params["mu"])
-    d_rs, d_nb, d_bd, e = adjacency_buffers(ctx, d_tri, nt, nv, bufs)
-    d_out, d_nrm = ctx.alloc(max(nv * 12, 16)), ctx.alloc(max(nv * 12, 16))
-    bufs += [d_out, d_nrm]
+    d_rs, d_nb, d_bd, e = adjacency_buffers(ctx, d_tri, nt, nv, B)
+    d_out, d_nrm = B.alloc(nv * 12), B.alloc(nv * 12)
     smooth_mesh_device(ctx, d_xyz, d_out.ptr, nv, d_rs.ptr, d_nb.ptr, d_bd.ptr if params["lock_boundary"] else None, factors)
     vertex_normals_device(ctx, d_out.ptr, nv, d_tri, nt, d_normals, d_nrm.ptr)
-    boundary = int(np.count_nonzero(download_rows(d_bd, np.uint8, nv, 1)))
+    boundary = int(np.count_nonzero(d_bd.download_array(np.uint8, (nv,))))
     return d_out, d_nrm, {"vertices": nv, "edges": e // 2, "boundary_vertices": boundary, "steps": len(factors)}
 
 
@@ -303,31 +269,14 @@ def mesh_adjacency(triangles, n_vertices, ctx=None):
     exactly one triangle side has."""
     tri, nv = _triangles(triangles), _count(n_vertices, "n_vertices")
     ctx = ctx or default_context()
-    bufs = []
-    try:
-        d_tri = ctx.alloc(max(tri.nbytes, 16))
-        bufs.append(d_tri)
-        d_tri.upload(tri)
-        d_rs, d_nb, d_bd, e = adjacency_buffers(ctx, d_tri.ptr, len(tri), nv, bufs)
-        return (d_rs.download(np.uint32, nv + 1), download_rows(d_nb, np.uint32, e, 1).reshape(-1),
-                download_rows(d_bd, np.uint8, nv, 1).reshape(-1).astype(bool))
-    finally:
-        for b in bufs:
-            b.free()
+    with ctx.buffers() as B:
+        d_rs, d_nb, d_bd, e = adjacency_buffers(ctx, B.upload(tri).ptr, len(tri), nv, B)
+        return (d_rs.download(np.uint32, nv + 1), d_nb.download_array(np.uint32, (e,)), d_bd.download_array(np.uint8, (nv,)).astype(bool))
 
 
-def _upload_mesh(ctx, xyz, tri, rows, bufs):
-    """xyz, tri and the optional [N,3] float32 `rows` in new DeviceBuffers (appended to bufs); the last is None without rows"""
-    d_xyz, d_tri = ctx.alloc(max(xyz.nbytes, 16)), ctx.alloc(max(tri.nbytes, 16))
-    bufs += [d_xyz, d_tri]
-    d_xyz.upload(xyz)
-    d_tri.upload(tri)
-    d_rows = None
-    if rows is not None:
-        d_rows = ctx.alloc(max(rows.nbytes, 16))
-        bufs.append(d_rows)
-        d_rows.upload(rows)
-    return d_xyz, d_tri, d_rows
+def _upload_mesh(B, xyz, tri, rows):
+    """xyz, tri and the optional [N,3] float32 `rows` in new DeviceBuffers of the buffer scope B; the last is None without rows"""
+    return B.upload(xyz), B.upload(tri), None if rows is None else B.upload(rows)
 
 
 def _fallback(rows, nv, what):
@@ -349,14 +298,10 @@ def smooth_mesh(xyz, triangles, method="taubin", iterations=10, lam=0.5, mu=-0.5
     normals = _fallback(normals, nv, "normals")
     params = smooth_params({"method": method, "iterations": iterations, "lam": lam, "mu": mu, "lock_boundary": lock_boundary})
     ctx = ctx or default_context()
-    bufs = []
-    try:
-        d_xyz, d_tri, d_nrm = _upload_mesh(ctx, xyz, tri, normals, bufs)
-        d_out, d_n, _ = smooth_mesh_buffers(ctx, d_xyz.ptr, d_nrm.ptr if d_nrm else None, d_tri.ptr, nv, len(tri), params, bufs)
-        return download_rows(d_out, np.float32, nv, 3), download_rows(d_n, np.float32, nv, 3)
-    finally:
-        for b in bufs:
-            b.free()
+    with ctx.buffers() as B:
+        d_xyz, d_tri, d_nrm = _upload_mesh(B, xyz, tri, normals)
+        d_out, d_n, _ = smooth_mesh_buffers(ctx, d_xyz.ptr, d_nrm.ptr if d_nrm else None, d_tri.ptr, nv, len(tri), params, B)
+        return d_out.download_array(np.float32, (nv, 3)), d_n.download_array(np.float32, (nv, 3))
 
 
 def compute_vertex_normals(xyz, triangles, fallback=None, ctx=None):
@@ -366,13 +311,8 @@ def compute_vertex_normals(xyz, triangles, fallback=None, ctx=None):
     nv = len(xyz)
     fallback = _fallback(fallback, nv, "fallback")
     ctx = ctx or default_context()
-    bufs = []
-    try:
-        d_xyz, d_tri, d_fb = _upload_mesh(ctx, xyz, tri, fallback, bufs)
-        d_n = ctx.alloc(max(nv * 12, 16))
-        bufs.append(d_n)
+    with ctx.buffers() as B:
+        d_xyz, d_tri, d_fb = _upload_mesh(B, xyz, tri, fallback)
+        d_n = B.alloc(nv * 12)
         vertex_normals_device(ctx, d_xyz.ptr, nv, d_tri.ptr, len(tri), d_fb.ptr if d_fb else None, d_n.ptr)
-        return download_rows(d_n, np.float32, nv, 3)
-    finally:
-        for b in bufs:
-            b.free()
+        return d_n.download_array(np.float32, (nv, 3))

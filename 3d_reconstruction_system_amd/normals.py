@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib as L
 from .device import default_context
-from .outliers import _Cloud, _cloud
+from .outliers import Cloud, _cloud
 from .poses import pose_table
 
 Normals = collections.namedtuple("Normals", ["normals", "curvature", "count"])
@@ -91,13 +91,10 @@ def estimate_normals(xyz, k=20, radius=None, viewpoint=None, viewpoints=None, po
     n = xyz.shape[0]
     if n == 0:
         return Normals(np.zeros((0, 3), np.float32), np.zeros(0, np.float32), np.zeros(0, np.uint32))
-    c = _Cloud(ctx or default_context(), xyz)
-    try:
+    with Cloud(ctx or default_context(), xyz) as c:
         d_n, d_c, d_m = c.alloc(n * 12), c.alloc(n * 4), c.alloc(n * 4)
         c.index.normals_knn(k, r, views, ppv, d_n.ptr, d_c.ptr, None, d_m.ptr)
-        return Normals(d_n.download(np.float32, 3 * n).reshape(n, 3), d_c.download(np.float32, n), d_m.download(np.uint32, n))
-    finally:
-        c.close()
+        return Normals(d_n.download_array(np.float32, (n, 3)), d_c.download(np.float32, n), d_m.download(np.uint32, n))
 
 
 def estimate_covariances(xyz, k, radius=None, ctx=None):
@@ -106,10 +103,7 @@ def estimate_covariances(xyz, k, radius=None, ctx=None):
     n = xyz.shape[0]
     if n == 0:
         return np.zeros((0, 6))
-    c = _Cloud(ctx or default_context(), xyz)
-    try:
+    with Cloud(ctx or default_context(), xyz) as c:
         d_n, d_cov = c.alloc(n * 12), c.alloc(n * 48)
         c.index.normals_knn(k, r, None, 1, d_n.ptr, None, d_cov.ptr, None)
-        return d_cov.download(np.float64, 6 * n).reshape(n, 6)
-    finally:
-        c.close()
+        return d_cov.download_array(np.float64, (n, 6))

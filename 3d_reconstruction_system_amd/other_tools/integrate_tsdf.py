@@ -210,14 +210,12 @@ def raycast_depth(r3d, vol, quats, ts, shape, min_weight):
     cam = vol.ctx.camera(h, w, *_common.intrinsics())
     out = np.empty((len(table), h, w), np.float32)
     chunk = 32
-    buf = vol.ctx.alloc(max(min(chunk, len(table)) * h * w * 4, 16))
-    try:
+    with vol.ctx.buffers() as B:
+        buf = B.alloc(min(chunk, len(table)) * h * w * 4)
         for lo in range(0, len(table), chunk):
             n = min(chunk, len(table) - lo)
             vol.raycast_device(cam, n, table[lo:lo + n], buf.ptr, None, None, min_weight=min_weight)
-            out[lo:lo + n] = buf.download(np.float32, n * h * w).reshape(n, h, w)
-    finally:
-        buf.free()
+            out[lo:lo + n] = buf.download_array(np.float32, (n, h, w))
     return out
 
 
@@ -230,14 +228,12 @@ def raycast_color(r3d, vol, quats, ts, shape, min_weight):
     cam = vol.ctx.camera(h, w, *_common.intrinsics())
     out = np.empty((len(table), h, w, 3), np.uint8)
     chunk = 32
-    buf = vol.ctx.alloc(max(min(chunk, len(table)) * h * w * 3, 16))
-    try:
+    with vol.ctx.buffers() as B:
+        buf = B.alloc(min(chunk, len(table)) * h * w * 3)
         for lo in range(0, len(table), chunk):
             n = min(chunk, len(table) - lo)
             vol.raycast_device(cam, n, table[lo:lo + n], None, None, None, min_weight=min_weight, d_rgb=buf.ptr)
-            out[lo:lo + n] = buf.download(np.uint8, n * h * w * 3).reshape(n, h, w, 3)
-    finally:
-        buf.free()
+            out[lo:lo + n] = buf.download_array(np.uint8, (n, h, w, 3))
     return out
 
 

@@ -8,12 +8,12 @@ data with) and the per-point score or count.  The *_device functions take an NNI
 """
 import collections
 import ctypes as C
-import math
 
 import numpy as np
 
 from . import _lib as L
-from .device import default_context
+from ._args import positive as _check_positive
+from .device import BufferScope, default_context
 from .icp import NNIndex
 
 SORStats = collections.namedtuple("SORStats", ["V", "mu", "sigma", "T"])
@@ -39,16 +39,6 @@ def _check_k(k, what="k"):
     if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 32:
         raise ValueError("%s must be an integer in [1, 32], got %r" % (what, k))
     return int(k)
-
-
-def _check_positive(v, what):
-    try:
-        v = float(v)
-    except (TypeError, ValueError):
-        raise ValueError("%s must be a finite number > 0, got %r" % (what, v))
-    if not (math.isfinite(v) and v > 0.0):
-        raise ValueError("%s must be a finite number > 0, got %r" % (what, v))
-    return v
 
 
 def _check_min_points(n):
@@ -90,18 +80,19 @@ def select_rows_device(ctx, d_xyz, n, d_keep, d_xyz_out, d_rows_out=None):
 
 # ---- host arrays ---------------------------------------------------------------------------------------------------------
 
-class _Cloud:
-    """The cloud in HBM, its index and the buffers of one call; everything goes at close()."""
+class Cloud(BufferScope):
+    """The buffer scope of one call over a cloud: the cloud in HBM (d_xyz) and its NNIndex (index) are its first two members, the
+    call's other buffers follow; everything goes at close()."""
 
     def __init__(self, ctx, xyz):
-        self.ctx, self.n, self.bufs, self.index = ctx, xyz.shape[0], [], None
-        self.d_xyz = self.alloc(xyz.nbytes).upload(xyz)
-        self.index = NNIndex(ctx, self.d_xyz.ptr, self.n)
-
-    def alloc(self, nbytes):
-        b = self.ctx.alloc(max(int(nbytes), 16))
-        self.bufs.append(b)
-        return b
+        super().__init__(ctx)
+        self.n = xyz.shape[0]
+        try:
+            self.d_xyz = self.upload(xyz)
+            self.index = self.adopt(NNIndex(ctx, self.d_xyz.ptr, self.n))
+        except BaseException:
+            self.close()
+            raise
 
     def select(self, d_keep, m):
         """(xyz [m,3], rows [m]) of the kept rows."""
@@ -110,13 +101,7 @@ class _Cloud:
         d_out, d_rows = self.alloc(m * 12), self.alloc(m * 4)
         got = select_rows_device(self.ctx, self.d_xyz.ptr, self.n, d_keep.ptr, d_out.ptr, d_rows.ptr)
         assert got == m, (got, m)
-        return d_out.download(np.float32, 3 * m).reshape(-1, 3), d_rows.download(np.uint32, m)
-
-    def close(self):
-        if self.index is not None:
-            self.index.close()
-        for b in self.bufs:
-            b.free()
+        return d_out.download_array(np.float32, (m, 3)), d_rows.download(np.uint32, m)
 
 
 def knn(xyz, k, ctx=None):
@@ -127,13 +112,10 @@ def knn(xyz, k, ctx=None):
     n = xyz.shape[0]
     if n == 0:
         return np.zeros((0, k), np.uint32), np.zeros((0, k), np.float32)
-    c = _Cloud(ctx, xyz)
-    try:
+    with Cloud(ctx, xyz) as c:
         d_idx, d_d2 = c.alloc(n * k * 4), c.alloc(n * k * 4)
         knn_device(c.index, k, d_idx.ptr, d_d2.ptr)
-        return d_idx.download(np.uint32, n * k).reshape(n, k), d_d2.download(np.float32, n * k).reshape(n, k)
-    finally:
-        c.close()
+        return d_idx.download_array(np.uint32, (n, k)), d_d2.download_array(np.float32, (n, k))
 
 
 def remove_statistical_outlier(xyz, nb_neighbors=20, std_ratio=2.0, ctx=None):
@@ -145,14 +127,11 @@ def remove_statistical_outlier(xyz, nb_neighbors=20, std_ratio=2.0, ctx=None):
     if n == 0:
         return StatisticalOutliers(np.zeros((0, 3), np.float32), np.zeros(0, np.uint32), np.zeros(0),
                                    SORStats(0, float("nan"), 0.0, float("nan")))
-    c = _Cloud(ctx, xyz)
-    try:
+    with Cloud(ctx, xyz) as c:
         d_keep, d_score = c.alloc(n), c.alloc(n * 8)
         m, stats = statistical_outlier_device(c.index, k, ratio, d_keep.ptr, d_score.ptr)
         kept, rows = c.select(d_keep, m)
         return StatisticalOutliers(kept, rows, d_score.download(np.float64, n), stats)
-    finally:
-        c.close()
 
 
 def remove_radius_outlier(xyz, nb_points, radius, ctx=None):
@@ -162,11 +141,8 @@ def remove_radius_outlier(xyz, nb_points, radius, ctx=None):
     n = xyz.shape[0]
     if n == 0:
         return RadiusOutliers(np.zeros((0, 3), np.float32), np.zeros(0, np.uint32), np.zeros(0, np.uint32))
-    c = _Cloud(ctx, xyz)
-    try:
+    with Cloud(ctx, xyz) as c:
         d_keep, d_count = c.alloc(n), c.alloc(n * 4)
         m = radius_outlier_device(c.index, m_pts, r, d_keep.ptr, d_count.ptr)
         kept, rows = c.select(d_keep, m)
         return RadiusOutliers(kept, rows, d_count.download(np.uint32, n))
-    finally:
-        c.close()

@@ -14,9 +14,10 @@ import math
 import numpy as np
 
 from . import _lib as L
+from ._args import positive as _check_positive
 from .device import default_context
 from .icp import NNIndex
-from .outliers import _check_positive, _cloud
+from .outliers import _cloud
 
 SUMS = 11             # R3D_REGISTRATION_SUMS
 MAX_NODES = 512       # R3D_POSEGRAPH_MAX_NODES
@@ -68,22 +69,13 @@ def _pair_sums(src, tgt, T, max_dist, ctx):
     if n == 0:
         return np.zeros(SUMS, np.float64), 0
     ctx = index.ctx if index is not None else (ctx or default_context())
-    bufs, own = [], None
-    try:
+    with ctx.buffers() as B:
         if index is None:
-            d_tgt = ctx.alloc(tgt.nbytes).upload(tgt)
-            bufs.append(d_tgt)
-            index = own = NNIndex(ctx, d_tgt.ptr, tgt.shape[0])
-        d_src, d_idx, d_d2 = ctx.alloc(max(src.nbytes, 16)).upload(src), ctx.alloc(max(n * 4, 16)), ctx.alloc(max(n * 4, 16))
-        bufs += [d_src, d_idx, d_d2]
+            index = B.adopt(NNIndex(ctx, B.upload(tgt).ptr, tgt.shape[0]))
+        d_src, d_idx, d_d2 = B.upload(src), B.alloc(n * 4), B.alloc(n * 4)
         L.check(ctx.lib.r3d_apply_T(ctx.handle, d_src.ptr, L.F32, n, T.ctypes.data, d_src.ptr, L.F32))
         index.query(d_src.ptr, n, d_idx.ptr, d_d2.ptr)
         return registration_sums_device(ctx, d_src.ptr, n, index.d_tgt, index.n, d_idx.ptr, d_d2.ptr, max_dist), n
-    finally:
-        if own is not None:
-            own.close()
-        for b in bufs:
-            b.free()
 
 
 def evaluate_registration(src, tgt, T, max_dist, ctx=None):

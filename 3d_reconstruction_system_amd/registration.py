@@ -12,9 +12,10 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from ._args import colour_words, positive as _check_positive
 from .device import default_context
 from .normals import _check_k, _check_radius
-from .outliers import _Cloud, _check_positive, _cloud
+from .outliers import Cloud, _cloud
 from .segmentation import MAX_HYPOTHESES, _check_hypotheses, _check_seed
 
 FPFH_DIM = 33
@@ -112,8 +113,7 @@ def compute_fpfh(xyz, normals=None, k=32, radius=None, ctx=None):
     nrm = None if normals is None else _normals(normals, n)
     if n == 0:
         return Fpfh(np.zeros((0, FPFH_DIM), np.float32), np.zeros((0, FPFH_DIM), np.uint8), np.zeros(0, np.uint32))
-    c = _Cloud(ctx or default_context(), xyz)
-    try:
+    with Cloud(ctx or default_context(), xyz) as c:
         d_n = c.alloc(n * 12)
         if nrm is None:
             c.index.normals_knn(k, r, None, 1, d_n.ptr)
@@ -121,10 +121,7 @@ def compute_fpfh(xyz, normals=None, k=32, radius=None, ctx=None):
             d_n.upload(nrm)
         d_f, d_s, d_c = c.alloc(n * FPFH_DIM * 4), c.alloc(n * FPFH_DIM), c.alloc(n * 4)
         L.check(c.ctx.lib.r3d_fpfh_knn(c.index.handle, k, r, d_n.ptr, d_f.ptr, d_s.ptr, d_c.ptr))
-        return Fpfh(d_f.download(np.float32, n * FPFH_DIM).reshape(n, FPFH_DIM), d_s.download(np.uint8, n * FPFH_DIM).reshape(n, FPFH_DIM),
-                    d_c.download(np.uint32, n))
-    finally:
-        c.close()
+        return Fpfh(d_f.download_array(np.float32, (n, FPFH_DIM)), d_s.download_array(np.uint8, (n, FPFH_DIM)), d_c.download(np.uint32, n))
 
 
 def match_features(fa, fb, mutual=True, ctx=None):
@@ -133,18 +130,11 @@ def match_features(fa, fb, mutual=True, ctx=None):
     fa, fb, mutual = _features(fa, "fa"), _features(fb, "fb"), _check_bool(mutual, "mutual")
     ctx = ctx or default_context()
     na, nb = fa.shape[0], fb.shape[0]
-    bufs = []
-    try:
-        d_a, d_b = ctx.alloc(fa.nbytes).upload(fa), ctx.alloc(fb.nbytes).upload(fb)
-        bufs += [d_a, d_b]
-        d_idx, d_dist, d_corr = ctx.alloc(max(na * 4, 16)), ctx.alloc(max(na * 4, 16)), ctx.alloc(max(na * 8, 16))
-        bufs += [d_idx, d_dist, d_corr]
+    with ctx.buffers() as B:
+        d_a, d_b = B.upload(fa), B.upload(fb)
+        d_idx, d_dist, d_corr = B.alloc(na * 4), B.alloc(na * 4), B.alloc(na * 8)
         m = match_features_device(ctx, d_a.ptr, na, d_b.ptr, nb, d_idx.ptr, d_dist.ptr, d_corr.ptr, mutual)
-        corr = d_corr.download(np.uint32, 2 * m).reshape(m, 2) if m else np.zeros((0, 2), np.uint32)
-        return Matches(corr, d_idx.download(np.uint32, na), d_dist.download(np.float32, na))
-    finally:
-        for b in bufs:
-            b.free()
+        return Matches(d_corr.download_array(np.uint32, (m, 2)), d_idx.download(np.uint32, na), d_dist.download(np.float32, na))
 
 
 def _result(r, inliers, counts):
@@ -161,21 +151,12 @@ def registration_ransac(src, tgt, corr, distance_threshold, num_hypotheses=4096,
         raise ValueError("both clouds need at least one point")
     ctx = ctx or default_context()
     m = corr.shape[0]
-    bufs = []
-    try:
-        d_src, d_tgt, d_corr = ctx.alloc(src.nbytes).upload(src), ctx.alloc(tgt.nbytes).upload(tgt), ctx.alloc(corr.nbytes).upload(corr)
-        bufs += [d_src, d_tgt, d_corr]
-        d_in = ctx.alloc(max(m, 16))
-        bufs.append(d_in)
-        d_cnt = ctx.alloc(hyp * 4) if want_counts else None
-        if d_cnt:
-            bufs.append(d_cnt)
+    with ctx.buffers() as B:
+        d_src, d_tgt, d_corr, d_in = B.upload(src), B.upload(tgt), B.upload(corr), B.alloc(m)
+        d_cnt = B.alloc(hyp * 4) if want_counts else None
         r = registration_ransac_device(ctx, d_src.ptr, src.shape[0], d_tgt.ptr, tgt.shape[0], d_corr.ptr, m, thr, hyp, seed, d_in.ptr,
                                        d_cnt.ptr if d_cnt else None)
         return _result(r, d_in.download(np.uint8, m) != 0, d_cnt.download(np.uint32, hyp) if d_cnt else None)
-    finally:
-        for b in bufs:
-            b.free()
 
 
 def _viewpoint(v, what):
@@ -252,7 +233,7 @@ def register_colored(src, src_rgba, tgt, tgt_rgba, voxel_sizes=(0.04, 0.02, 0.01
     from . import colored_icp as CI, voxelmap
     from .normals import estimate_normals
     src, tgt = _cloud(src), _cloud(tgt)
-    src_w, tgt_w = CI._words(src_rgba, src.shape[0], "src_rgba"), CI._words(tgt_rgba, tgt.shape[0], "tgt_rgba")
+    src_w, tgt_w = colour_words(src_rgba, src.shape[0], "src_rgba"), colour_words(tgt_rgba, tgt.shape[0], "tgt_rgba")
     try:
         sizes, its = [float(v) for v in voxel_sizes], [int(v) for v in iters]
     except (TypeError, ValueError):

@@ -11,8 +11,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from ._args import positive as _check_positive, whole as _check_count
 from .device import default_context
-from .outliers import _check_positive, _cloud, select_rows_device
+from .outliers import _cloud, select_rows_device
 
 MAX_HYPOTHESES = 65536
 
@@ -38,12 +39,6 @@ def _check_seed(seed):
     return int(seed)
 
 
-def _check_count(v, what, lo):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < lo:
-        raise ValueError("%s must be an integer >= %d, got %r" % (what, lo, v))
-    return int(v)
-
-
 def ransac_rows(seed, h, n):
     """The three rows hypothesis h samples from a cloud of n rows (host only, no GPU)."""
     seed = _check_seed(seed)
@@ -67,10 +62,9 @@ def segment_plane_device(ctx, d_xyz, n, distance_threshold, num_hypotheses, seed
                        m.value)
 
 
-def _rows_of(ctx, d_xyz, n, d_keep, m, bufs):
-    """Row numbers (uint32 [m]) and the device copy of the rows with d_keep != 0."""
-    d_out, d_rows = ctx.alloc(max(m * 12, 16)), ctx.alloc(max(m * 4, 16))
-    bufs += [d_out, d_rows]
+def _rows_of(ctx, d_xyz, n, d_keep, m, B):
+    """Row numbers (uint32 [m]) and the device copy (in the buffer scope B) of the rows with d_keep != 0."""
+    d_out, d_rows = B.alloc(m * 12), B.alloc(m * 4)
     if m == 0:
         return np.zeros(0, np.uint32), d_out
     got = select_rows_device(ctx, d_xyz.ptr, n, d_keep.ptr, d_out.ptr, d_rows.ptr)
@@ -87,16 +81,11 @@ def segment_plane(xyz, distance_threshold=0.01, num_hypotheses=1024, seed=0, ctx
     if n < 3:
         raise ValueError("a plane needs at least 3 points, got %d" % n)
     ctx = ctx or default_context()
-    bufs = []
-    try:
-        d_xyz, d_keep = ctx.alloc(xyz.nbytes).upload(xyz), ctx.alloc(max(n, 16))
-        bufs += [d_xyz, d_keep]
+    with ctx.buffers() as B:
+        d_xyz, d_keep = B.upload(xyz), B.alloc(n)
         p = segment_plane_device(ctx, d_xyz.ptr, n, thr, hyp, seed, d_keep.ptr)
-        rows, _ = _rows_of(ctx, d_xyz, n, d_keep, p.n_inliers, bufs)
+        rows, _ = _rows_of(ctx, d_xyz, n, d_keep, p.n_inliers, B)
         return PlaneSegment(p.plane, rows, p.centroid, p.eigenvalues, p.best_hypothesis, p.best_count, p.n_valid)
-    finally:
-        for b in bufs:
-            b.free()
 
 
 def segment_planes(xyz, distance_threshold=0.01, num_hypotheses=1024, max_planes=6, min_inliers=100, seed=0, ctx=None):
@@ -112,11 +101,8 @@ def segment_planes(xyz, distance_threshold=0.01, num_hypotheses=1024, max_planes
     if n < 3 or max_planes == 0:
         return np.zeros((0, 4)), labels, np.zeros(0, np.int64)
     ctx = ctx or default_context()
-    bufs = []
-    try:
-        d_cur = ctx.alloc(xyz.nbytes).upload(xyz)
-        d_keep = ctx.alloc(max(n, 16))
-        bufs += [d_cur, d_keep]
+    with ctx.buffers() as B:
+        d_cur, d_keep = B.upload(xyz), B.alloc(n)
         rows_cur, m = np.arange(n, dtype=np.int64), n       # original row of every remaining row
         for r in range(max_planes):
             if m < 3:
@@ -131,9 +117,6 @@ def segment_planes(xyz, distance_threshold=0.01, num_hypotheses=1024, max_planes
             # the rest, compacted on the device: flip the mask and select
             d_keep.upload((~keep).astype(np.uint8))
             rest = m - p.n_inliers
-            _, d_next = _rows_of(ctx, d_cur, m, d_keep, rest, bufs)
+            _, d_next = _rows_of(ctx, d_cur, m, d_keep, rest, B)
             rows_cur, d_cur, m = rows_cur[~keep], d_next, rest
         return np.array(planes, np.float64).reshape(-1, 4), labels, np.array(counts, np.int64)
-    finally:
-        for b in bufs:
-            b.free()

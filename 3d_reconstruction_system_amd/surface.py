@@ -7,15 +7,10 @@ volume_for_cloud sizes a volume around a cloud; reconstruct_surface is cloud -> 
 """
 import numpy as np
 
+from ._args import whole as _whole
 from .tsdf import TSDFVolume, _cloud_rows, _positive_f32
 
 MAX_MESH_VOXELS = ((1 << 32) + 4) // 5 - 1   # r3d_tsdf_extract_mesh takes volumes of fewer than 2^32 / 5 voxels
-
-
-def _whole(v, what, least):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < least:
-        raise ValueError("%s must be an integer >= %d, got %r" % (what, least, v))
-    return int(v)
 
 
 def cloud_volume_geometry(xyz, voxel_size, trunc_voxels=4, margin_voxels=None):

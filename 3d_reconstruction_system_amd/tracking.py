@@ -88,13 +88,10 @@ def depth_half(depth, max_jump, ctx=None):
     c = ctx or default_context()
     h, w = d.shape
     oh, ow = pyramid_shape(h, w, 1)
-    d_in, d_out = c.alloc(d.nbytes).upload(d), c.alloc(oh * ow * 4)
-    try:
+    with c.buffers() as B:
+        d_in, d_out = B.upload(d), B.alloc(oh * ow * 4)
         L.check(c.lib.r3d_depth_half(c.handle, d_in.ptr, 1, h, w, mj, d_out.ptr))
-        return d_out.download(np.float32, oh * ow).reshape(oh, ow)
-    finally:
-        d_in.free()
-        d_out.free()
+        return d_out.download_array(np.float32, (oh, ow))
 
 
 MAX_BILATERAL_RADIUS = 8                    # R3D_BILATERAL_MAX_RADIUS
@@ -145,13 +142,10 @@ def depth_bilateral(depth, radius, sigma_s, sigma_r, ctx=None):
     d = np.ascontiguousarray(d)
     c = ctx or default_context()
     h, w = d.shape
-    d_in, d_out = c.alloc(d.nbytes).upload(d), c.alloc(d.nbytes)
-    try:
+    with c.buffers() as B:
+        d_in, d_out = B.upload(d), B.alloc(d.nbytes)
         L.check(c.lib.r3d_depth_bilateral(c.handle, d_in.ptr, 1, h, w, r, ss, sr, d_out.ptr))
-        return d_out.download(np.float32, h * w).reshape(h, w)
-    finally:
-        d_in.free()
-        d_out.free()
+        return d_out.download_array(np.float32, (h, w))
 
 
 def photo_args(photo_weight, i_max):
@@ -187,13 +181,10 @@ def intensity_map(rgb, valid, max_jump, ctx=None):
     c_img, d = np.ascontiguousarray(c_img), np.ascontiguousarray(d)
     c = ctx or default_context()
     h, w = d.shape
-    bufs = [c.alloc(c_img.nbytes).upload(c_img), c.alloc(d.nbytes).upload(d), c.alloc(h * w * 4), c.alloc(h * w * 16)]
-    try:
-        L.check(c.lib.r3d_intensity_map(c.handle, bufs[0].ptr, bufs[1].ptr, 1, h, w, mj, bufs[2].ptr, bufs[3].ptr))
-        return bufs[2].download(np.float32, h * w).reshape(h, w), bufs[3].download(np.float32, h * w * 4).reshape(h, w, 4)
-    finally:
-        for b in bufs:
-            b.free()
+    with c.buffers() as B:
+        d_rgb, d_valid, d_i, d_packed = B.upload(c_img), B.upload(d), B.alloc(h * w * 4), B.alloc(h * w * 16)
+        L.check(c.lib.r3d_intensity_map(c.handle, d_rgb.ptr, d_valid.ptr, 1, h, w, mj, d_i.ptr, d_packed.ptr))
+        return d_i.download_array(np.float32, (h, w)), d_packed.download_array(np.float32, (h, w, 4))
 
 
 def inverse_pose(pose_w2c):
@@ -302,22 +293,19 @@ class TrackDevice:
         self.h, self.w = sv.shape[:2]
         self.n = self.h * self.w
         self.cam = c.camera(self.h, self.w, *K)
-        self._bufs = []
-
-        def put(a):
-            b = c.alloc(a.nbytes).upload(a)
-            self._bufs.append(b)
-            return b
-        self.d_src_vertex, self.d_model_vertex, self.d_model_normal = put(sv), put(mv), put(mn)
-        self.d_src_normal = None if sn is None else put(sn)
-        self.d_src_intensity = self.d_model_packed = self.d_photo = None
-        if src_intensity is not None:
-            self.d_src_intensity, self.d_model_packed, self.d_photo = put(si), put(mp), c.alloc(self.n * 4)
-            self._bufs.append(self.d_photo)
-        self.d_match, self.d_residual = c.alloc(self.n * 4), c.alloc(self.n * 4)
-        self.d_state = c.alloc(STATE_DOUBLES * 8)
-        self._bufs += [self.d_match, self.d_residual, self.d_state]
-        self.state_reset()
+        self._buffers = B = c.buffers()   # everything below, until free()
+        try:
+            self.d_src_vertex, self.d_model_vertex, self.d_model_normal = B.upload(sv), B.upload(mv), B.upload(mn)
+            self.d_src_normal = None if sn is None else B.upload(sn)
+            self.d_src_intensity = self.d_model_packed = self.d_photo = None
+            if src_intensity is not None:
+                self.d_src_intensity, self.d_model_packed, self.d_photo = B.upload(si), B.upload(mp), B.alloc(self.n * 4)
+            self.d_match, self.d_residual = B.alloc(self.n * 4), B.alloc(self.n * 4)
+            self.d_state = B.alloc(STATE_DOUBLES * 8)
+            self.state_reset()
+        except BaseException:
+            B.close()
+            raise
 
     def _maps(self):
         return (self.d_src_vertex.ptr, None if self.d_src_normal is None else self.d_src_normal.ptr, self.d_model_vertex.ptr,
@@ -384,9 +372,7 @@ class TrackDevice:
 
     def free(self):
         self.ctx.sync()
-        for b in self._bufs:
-            b.free()
-        self._bufs = []
+        self._buffers.close()
 
 
 def track_sums(src_vertex, model_vertex, model_normal, model_pose_w2c, S, intrinsics, dist_max, cos_min=-1.0, src_normal=None,

@@ -292,22 +292,18 @@ def get_file_name(qt_path):
     n = n_frames * per
     cam = ctx.camera(depths.shape[1], depths.shape[2], *_common.intrinsics())
     table = r3d.pose_table(quats, ts * _common.pose_scale())       # 1 unless R3D_POSE_SCALE says otherwise
-    bufs = []
-    try:
-        d_depth, d_pose, d_world = ctx.alloc(depths.nbytes).upload(depths), ctx.alloc(table.nbytes).upload(table), ctx.alloc(n * 24)
-        bufs += [d_depth, d_pose, d_world]
+    with ctx.buffers() as B:
+        d_depth, d_pose, d_world = B.upload(depths), B.upload(table), B.alloc(n * 24)
         r3d.fuse_frames_device(ctx, cam, d_depth.ptr, depths.dtype, n_frames, d_pose.ptr, d_world.ptr, np.float64)
         text = r3d.device_text.TextWriter(ctx)
         if _common.ply_binary():      # f1's optional flag (R3D_PLY_BINARY=1): a standard binary PLY of the f32 cloud, NOT the reference's text
-            d_world32 = ctx.alloc(n * 12)
-            bufs.append(d_world32)
+            d_world32 = B.alloc(n * 12)
             r3d.fuse_frames_device(ctx, cam, d_depth.ptr, depths.dtype, n_frames, d_pose.ptr, d_world32.ptr, np.float32)
             text.add_ply_binary('./ply/small_035_p8.ply', d_world32.ptr, n)
         else:
             text.add_ply('./ply/small_035_p8.ply', d_world.ptr, np.float64, n)     # the same bytes genply(world, ...) writes
         if not _common.skip_intermediate():
-            d_cam = ctx.alloc(n * 24)
-            bufs.append(d_cam)
+            d_cam = B.alloc(n * 24)
             r3d.unproject_device(ctx, cam, d_depth.ptr, depths.dtype, n_frames, d_cam.ptr, np.float64)
             integral = depths.dtype in (np.uint8, np.uint16)
             # the per-frame camera txt the reference leaves in ./point/ (third column: the raster's own integers)
@@ -318,9 +314,6 @@ def get_file_name(qt_path):
         _common.stamp("fused launches + text sizes (device)")
         written = text.write()
         _common.stamp("%d bytes of text formatted on the GPU and written" % written)
-    finally:
-        for b in bufs:
-            b.free()
     t2 = time.time()
     print('##################')
     print("%d frames cost ." % n_frames, t2 - t1)

@@ -120,7 +120,8 @@ class TSDFVolume:
         create = self.ctx.lib.r3d_tsdf_create_rgb if self.color else self.ctx.lib.r3d_tsdf_create
         L.check(create(self.ctx.handle, o.ctypes.data, vs, nx, ny, nz, tr, C.byref(h)))
         self.handle = h.value
-        self._bilateral_bufs = None   # (pixels, vertex map, filtered raster) of track(bilateral=): _bilateral_raster
+        self._bilateral = self.ctx.buffers()   # owns the two buffers of track(bilateral=): _bilateral_raster
+        self._bilateral_bufs = None            # (pixels, vertex map, filtered raster) while they exist
         self.ctx.adopt(self)
 
     def close(self):
@@ -257,13 +258,11 @@ class TSDFVolume:
         """[n,3] uint8: the colours of the n surface points"""
         if n == 0:
             return np.zeros((0, 3), np.uint8)
-        d_rgba = self.ctx.alloc(n * 4)
-        try:
+        with self.ctx.buffers() as B:
+            d_rgba = B.alloc(n * 4)
             got = self.extract_colors_device(mw, d_rgba.ptr, n)
             assert got == n, (got, n)
             return _unpack_rgba(d_rgba.download(np.uint32, n))
-        finally:
-            d_rgba.free()
 
     def extract_points_device(self, min_weight, d_xyz, d_normals, cap):
         """Surface points into d_xyz / d_normals ([cap][3] float32 device addresses; d_normals may be None); returns the TRUE
@@ -285,15 +284,12 @@ class TSDFVolume:
         if n == 0:
             empty = (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32))
             return empty + (np.zeros((0, 3), np.uint8),) if with_colors else empty
-        d_xyz, d_nrm = self.ctx.alloc(n * 12), self.ctx.alloc(n * 12)
-        try:
+        with self.ctx.buffers() as B:
+            d_xyz, d_nrm = B.alloc(n * 12), B.alloc(n * 12)
             got = self.extract_points_device(mw, d_xyz.ptr, d_nrm.ptr, n)
             assert got == n, (got, n)
-            out = (d_xyz.download(np.float32, 3 * n).reshape(n, 3), d_nrm.download(np.float32, 3 * n).reshape(n, 3))
+            out = (d_xyz.download_array(np.float32, (n, 3)), d_nrm.download_array(np.float32, (n, 3)))
             return out + (self._extract_colors(mw, n),) if with_colors else out
-        finally:
-            d_xyz.free()
-            d_nrm.free()
 
     def extract_mesh_device(self, min_weight, d_xyz, d_normals, cap_vertices, d_tri, cap_triangles):
         """The indexed triangle mesh into d_xyz / d_normals ([cap_vertices][3] float32) and d_tri ([cap_triangles][3] int32) at raw
@@ -333,7 +329,7 @@ class TSDFVolume:
             min_tris = _min_triangles(1 if min_component_triangles is None else min_component_triangles)
         params = None
         if smooth is not None:
-            from .mesh import smooth_factors, smooth_params
+            from .mesh import smooth_factors, smooth_mesh_buffers, smooth_params
             params = smooth_params(smooth)
             self.last_smooth = {"vertices": 0, "edges": 0, "boundary_vertices": 0,
                                 "steps": len(smooth_factors(params["method"], params["iterations"], params["lam"], params["mu"]))}
@@ -342,55 +338,31 @@ class TSDFVolume:
             empty = (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32))
             empty = empty + (np.zeros((0, 3), np.uint8),) if with_colors else empty
             return empty + ({"components": 0, "components_kept": 0, "triangles": 0, "triangles_kept": 0},) if with_stats else empty
-        d_xyz, d_nrm, d_tri = self.ctx.alloc(n * 12), self.ctx.alloc(n * 12), self.ctx.alloc(max(m, 1) * 12)
-        try:
+        with self.ctx.buffers() as B:
+            d_xyz, d_nrm, d_tri = B.alloc(n * 12), B.alloc(n * 12), B.alloc(max(m, 1) * 12)
             got = self.extract_mesh_device(mw, d_xyz.ptr, d_nrm.ptr, n, d_tri.ptr if m else None, m)
             assert got == (n, m), (got, n, m)
             if filtered:
-                return self._filtered_mesh(mw, d_xyz, d_nrm, d_tri, n, m, min_tris, bool(keep_largest), with_colors, with_stats, params)
+                return self._filtered_mesh(B, mw, d_xyz, d_nrm, d_tri, n, m, min_tris, bool(keep_largest), with_colors, with_stats, params)
             if params is not None:
-                return self._smoothed_mesh(mw, d_xyz, d_nrm, d_tri, n, m, with_colors, params)
-            tri = d_tri.download(np.int32, 3 * m).reshape(m, 3) if m else np.zeros((0, 3), np.int32)
-            out = (d_xyz.download(np.float32, 3 * n).reshape(n, 3), d_nrm.download(np.float32, 3 * n).reshape(n, 3), tri)
+                d_xyz, d_nrm, self.last_smooth = smooth_mesh_buffers(self.ctx, d_xyz.ptr, d_nrm.ptr, d_tri.ptr, n, m, params, B)
+            out = (d_xyz.download_array(np.float32, (n, 3)), d_nrm.download_array(np.float32, (n, 3)), d_tri.download_array(np.int32, (m, 3)))
             return out + (self._extract_colors(mw, n),) if with_colors else out
-        finally:
-            for b in (d_xyz, d_nrm, d_tri):
-                b.free()
 
-    def _smoothed_mesh(self, mw, d_xyz, d_nrm, d_tri, n, m, with_colors, params):
-        """extract_triangle_mesh's result from the n vertices and m triangles in HBM, smoothed there (mesh.smooth_mesh_buffers)"""
-        from .mesh import download_rows, smooth_mesh_buffers
-        bufs = []
-        try:
-            d_x, d_n, self.last_smooth = smooth_mesh_buffers(self.ctx, d_xyz.ptr, d_nrm.ptr, d_tri.ptr, n, m, params, bufs)
-            out = (download_rows(d_x, np.float32, n, 3), download_rows(d_n, np.float32, n, 3), download_rows(d_tri, np.int32, m, 3))
-            return out + (self._extract_colors(mw, n),) if with_colors else out
-        finally:
-            for b in bufs:
-                b.free()
-
-    def _filtered_mesh(self, mw, d_xyz, d_nrm, d_tri, n, m, min_tris, keep_largest, with_colors, with_stats, params=None):
+    def _filtered_mesh(self, B, mw, d_xyz, d_nrm, d_tri, n, m, min_tris, keep_largest, with_colors, with_stats, params=None):
         """extract_triangle_mesh's result from the n vertices and m triangles in HBM, filtered there (mesh.filter_mesh_device) and,
-        with params, smoothed behind the filter"""
-        from .mesh import download_rows, filter_mesh_device, mesh_components_device, smooth_mesh_buffers
-        bufs = []
-        try:
-            d_x, d_n, d_t, kept, nk, mk, comps = filter_mesh_device(self.ctx, d_xyz.ptr, d_nrm.ptr, d_tri.ptr, n, m, min_tris, keep_largest,
-                                                                    bufs)
-            if params is not None:
-                d_x, d_n, self.last_smooth = smooth_mesh_buffers(self.ctx, d_x.ptr, d_n.ptr, d_t.ptr, nk, mk, params, bufs)
-            out = (download_rows(d_x, np.float32, nk, 3), download_rows(d_n, np.float32, nk, 3), download_rows(d_t, np.int32, mk, 3))
-            if with_colors:
-                out += (self._extract_colors(mw, n)[kept],)
-            if with_stats:
-                d_lab = self.ctx.alloc(max(nk * 4, 16))
-                bufs.append(d_lab)
-                kept_comps, _ = mesh_components_device(self.ctx, d_t.ptr, mk, nk, d_lab.ptr)
-                out += ({"components": comps, "components_kept": kept_comps, "triangles": m, "triangles_kept": mk},)
-            return out
-        finally:
-            for b in bufs:
-                b.free()
+        with params, smoothed behind the filter; B: the call's buffer scope"""
+        from .mesh import filter_mesh_device, mesh_components_device, smooth_mesh_buffers
+        d_x, d_n, d_t, kept, nk, mk, comps = filter_mesh_device(self.ctx, d_xyz.ptr, d_nrm.ptr, d_tri.ptr, n, m, min_tris, keep_largest, B)
+        if params is not None:
+            d_x, d_n, self.last_smooth = smooth_mesh_buffers(self.ctx, d_x.ptr, d_n.ptr, d_t.ptr, nk, mk, params, B)
+        out = (d_x.download_array(np.float32, (nk, 3)), d_n.download_array(np.float32, (nk, 3)), d_t.download_array(np.int32, (mk, 3)))
+        if with_colors:
+            out += (self._extract_colors(mw, n)[kept],)
+        if with_stats:
+            kept_comps, _ = mesh_components_device(self.ctx, d_t.ptr, mk, nk, B.alloc(nk * 4).ptr)
+            out += ({"components": comps, "components_kept": kept_comps, "triangles": m, "triangles_kept": mk},)
+        return out
 
     def raycast_device(self, cam, n_views, poses_w2c, d_depth, d_vertex, d_normal, min_weight=1.0, step=None, t_near=0.0,
                        t_far=math.inf, d_rgb=None):
@@ -443,19 +415,14 @@ class TSDFVolume:
             return empty + (np.zeros((0, h, w, 3), np.uint8),) if with_colors else empty
         cam = self.ctx.camera(h, w, *intrinsics)
         n = f * h * w
-        bufs = [self.ctx.alloc(n * 4), self.ctx.alloc(n * 12), self.ctx.alloc(n * 12)]
-        try:
-            if with_colors:
-                bufs.append(self.ctx.alloc(n * 3))
-            d_depth, d_vtx, d_nrm = bufs[:3]
+        with self.ctx.buffers() as B:
+            d_depth, d_vtx, d_nrm = B.alloc(n * 4), B.alloc(n * 12), B.alloc(n * 12)
+            d_rgb = B.alloc(n * 3) if with_colors else None
             self.raycast_device(cam, f, table, d_depth.ptr, d_vtx.ptr, d_nrm.ptr, mw, step, t_near, t_far,
-                                d_rgb=bufs[3].ptr if with_colors else None)
-            out = (d_depth.download(np.float32, n).reshape(f, h, w), d_vtx.download(np.float32, 3 * n).reshape(f, h, w, 3),
-                   d_nrm.download(np.float32, 3 * n).reshape(f, h, w, 3))
-            return out + (bufs[3].download(np.uint8, 3 * n).reshape(f, h, w, 3),) if with_colors else out
-        finally:
-            for b in bufs:
-                b.free()
+                                d_rgb=d_rgb.ptr if with_colors else None)
+            out = (d_depth.download_array(np.float32, (f, h, w)), d_vtx.download_array(np.float32, (f, h, w, 3)),
+                   d_nrm.download_array(np.float32, (f, h, w, 3)))
+            return out + (d_rgb.download_array(np.uint8, (f, h, w, 3)),) if with_colors else out
 
     def _track_args(self, n_iters, dist_max, max_angle_deg, max_jump, min_weight, step, t_near, t_far):
         """(n_iters, dist_max, cos_min, max_jump, min_weight, step, t_near, t_far) as the library takes them; ValueError otherwise"""
@@ -546,7 +513,7 @@ class TSDFVolume:
         n = cam.height * cam.width
         if self._bilateral_bufs is None or self._bilateral_bufs[0] != n:
             self._free_bilateral()
-            self._bilateral_bufs = (n, self.ctx.alloc(n * 12), self.ctx.alloc(n * 4))
+            self._bilateral_bufs = (n, self._bilateral.alloc(n * 12), self._bilateral.alloc(n * 4))
         _, vertex, raster = self._bilateral_bufs
         L.check(self.ctx.lib.r3d_unproject(self.ctx.handle, cam.handle, d_depth, depth_code(depth_dtype), 1, float(depth_scale),
                                            vertex.ptr, L.F32))
@@ -556,9 +523,8 @@ class TSDFVolume:
     def _free_bilateral(self):
         if self._bilateral_bufs is not None:
             self.ctx.sync()
-            for b in self._bilateral_bufs[1:]:
-                b.free()
             self._bilateral_bufs = None
+        self._bilateral.close()
 
     def track(self, depth, pose_guess_w2c, intrinsics=REF_INTRINSICS, n_iters=10, dist_max=None, max_angle_deg=None, depth_scale=1.0,
               max_jump=0.05, min_weight=1.0, step=None, t_near=0.0, t_far=math.inf, pyramid_iters=None, rgb=None, photo_weight=None,
@@ -609,16 +575,12 @@ class TSDFVolume:
         if guess.size != 12 or not np.isfinite(guess).all():
             raise ValueError("pose_guess_w2c must be 12 finite numbers (R row-major, t), got shape %s" % (list(guess.shape),))
         cam = self.ctx.camera(d.shape[0], d.shape[1], *intrinsics)
-        buf = self.ctx.alloc(d.nbytes).upload(d)
-        cbuf = None if rgb is None else self.ctx.alloc(img.nbytes).upload(img)
-        try:
+        with self.ctx.buffers() as B:
+            buf = B.upload(d)
+            cbuf = None if rgb is None else B.upload(img)
             return self.track_device(cam, buf.ptr, d.dtype, guess, n_iters, dist_max, max_angle_deg, depth_scale, max_jump, min_weight,
                                      step, t_near, t_far, pyramid_iters, None if cbuf is None else cbuf.ptr, photo_weight, i_max,
                                      bilateral)
-        finally:
-            buf.free()
-            if cbuf is not None:
-                cbuf.free()
 
     def track_and_integrate(self, depths, first_pose_w2c, intrinsics=REF_INTRINSICS, depth_scale=1.0, rgbs=None, **track_args):
         """Reconstruct from depth rasters [F,H,W] and ONE pose: frame 0 is integrated at first_pose_w2c (12 doubles, world ->
@@ -654,9 +616,9 @@ class TSDFVolume:
         if f * h * w == 0:
             return poses
         cam = self.ctx.camera(h, w, *intrinsics)
-        buf = self.ctx.alloc(d[0].nbytes)
-        cbuf = None if img is None else self.ctx.alloc(img[0].nbytes)
-        try:
+        with self.ctx.buffers() as B:
+            buf = B.alloc(d[0].nbytes)
+            cbuf = None if img is None else B.alloc(img[0].nbytes)
             for k in range(f):
                 buf.upload(d[k])
                 if cbuf is not None:
@@ -671,8 +633,4 @@ class TSDFVolume:
                                            % (k, int(info["pairs"])))
                 self.integrate_device(cam, buf.ptr, d.dtype, 1, poses[k:k + 1], depth_scale, d_rgb=None if cbuf is None else cbuf.ptr)
             self.ctx.sync()
-        finally:
-            buf.free()
-            if cbuf is not None:
-                cbuf.free()
         return poses

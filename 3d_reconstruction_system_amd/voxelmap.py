@@ -14,6 +14,7 @@ import os
 import numpy as np
 
 from . import _lib as L
+from ._args import colour_words as _colour_words
 from .device import default_context
 
 
@@ -108,13 +109,11 @@ def octree_records_device(d_codes, n, ctx=None):
     L.check(ctx.lib.r3d_octree_records_device(ctx.handle, d_codes, int(n), None, 0, C.byref(n_rec), C.byref(nodes)))
     if n_rec.value == 0:
         return np.zeros(0, np.uint16), nodes.value
-    d_rec = ctx.alloc(n_rec.value * 2)
-    try:
+    with ctx.buffers() as B:
+        d_rec = B.alloc(n_rec.value * 2)
         L.check(ctx.lib.r3d_octree_records_device(ctx.handle, d_codes, int(n), d_rec.ptr, n_rec.value, C.byref(n_rec),
                                                   C.byref(nodes)))
         return d_rec.download(np.uint16, n_rec.value), nodes.value
-    finally:
-        d_rec.free()
 
 
 def _voxelize_set(xyz, resolution=0.1, ctx=None, capacity=None):
@@ -157,14 +156,6 @@ def _cloud_f32(xyz):
     if xyz.ndim != 2 or xyz.shape[1] != 3:
         raise ValueError("cloud must be [N,3]")
     return xyz
-
-
-def _colour_words(rgba, n):
-    rgba = np.asarray(rgba)
-    if rgba.dtype != np.uint32 or rgba.ndim != 1 or rgba.shape[0] != n:
-        raise ValueError("rgba must be [N] uint32 colour words (r | g << 8 | b << 16), one per point: got %s %s for %d points"
-                         % (rgba.dtype, rgba.shape, n))
-    return np.ascontiguousarray(rgba)
 
 
 class VoxelGrid:
@@ -239,18 +230,12 @@ class VoxelGrid:
         if m == 0:
             return DownSampled(np.zeros((0, 3), np.float32), np.zeros(0, np.uint32) if self.colour else None,
                                np.zeros(0, np.uint32), np.zeros(0, np.uint64))
-        d_xyz, d_cnt, d_codes = self.ctx.alloc(m * 12), self.ctx.alloc(m * 4), self.ctx.alloc(m * 8)
-        d_rgba = self.ctx.alloc(m * 4) if self.colour else None
-        try:
+        with self.ctx.buffers() as B:
+            d_xyz, d_cnt, d_codes = B.alloc(m * 12), B.alloc(m * 4), B.alloc(m * 8)
+            d_rgba = B.alloc(m * 4) if self.colour else None
             self.extract_device(d_xyz.ptr, d_rgba.ptr if d_rgba else None, d_cnt.ptr, d_codes.ptr, m)
-            xyz = d_xyz.download(np.float32, 3 * m).reshape(-1, 3)
-            rgba = d_rgba.download(np.uint32, m) if d_rgba else None
-            counts, codes = d_cnt.download(np.uint32, m), d_codes.download(np.uint64, m)
-        finally:
-            for b in (d_xyz, d_cnt, d_codes, d_rgba):
-                if b is not None:
-                    b.free()
-        return DownSampled(xyz, rgba, counts, codes)
+            return DownSampled(d_xyz.download_array(np.float32, (m, 3)), d_rgba.download(np.uint32, m) if d_rgba else None,
+                               d_cnt.download(np.uint32, m), d_codes.download(np.uint64, m))
 
 
 def voxel_down_sample(xyz, voxel_size, rgba=None, ctx=None):

@@ -297,7 +297,7 @@ class ColourLoop:
     def __init__(self, ctx, L, CI, wall, src, src_I, nrm, keep_original):
         n, m = src.shape[0], wall["tgt"].shape[0]
         self.ctx, self.L, self.n, self.keep_original = ctx, L, n, keep_original
-        c = self.c = CI._Cloud(ctx, wall["tgt"])
+        c = self.c = CI.Cloud(ctx, wall["tgt"])
         self.d_n, self.d_i, self.d_g = c.alloc(m * 12).upload(nrm), c.alloc(m * 4).upload(wall["I"]), c.alloc(m * 12).upload(wall["grad"])
         self.d_src, d_perm = c.alloc(n * 12).upload(src), c.alloc(n * 4)
         c.index.sort_cloud(self.d_src.ptr, n, d_perm.ptr)

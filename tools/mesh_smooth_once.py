@@ -40,8 +40,7 @@ ctx.sync()
 nv, nt = vol.extract_mesh_device(1.0, None, None, 0, None, 0)
 d_xyz, d_nrm, d_tri = ctx.alloc(nv * 12), ctx.alloc(nv * 12), ctx.alloc(nt * 12)
 assert vol.extract_mesh_device(1.0, d_xyz.ptr, d_nrm.ptr, nv, d_tri.ptr, nt) == (nv, nt)
-bufs = []
-d_rs, d_nb, d_bd, e = M.adjacency_buffers(ctx, d_tri.ptr, nt, nv, bufs)
+d_rs, d_nb, d_bd, e = M.adjacency_buffers(ctx, d_tri.ptr, nt, nv, ctx.buffers())
 d_out, d_n = ctx.alloc(nv * 12), ctx.alloc(nv * 12)
 
 
