@@ -180,11 +180,12 @@ int r3d_color_gradient_knn(r3d_nn_index* index, int k, double radius, const floa
   if ((rc = r3d_ctx_enter(ctx))) return rc;
   if (n == 0) return R3D_OK;
   // the lists (idx | d2), stored as r3d_fpfh_knn stores them, in a workspace of this file's own
-  const size_t list_b = r3d_align_up((size_t)n * k * 4, 256);
-  void* lists = nullptr;
-  if ((rc = r3d_scratch(ctx, kWsColorLists, 2 * list_b, &lists))) return rc;
-  uint32_t* idx = static_cast<uint32_t*>(lists);
-  float* d2l = reinterpret_cast<float*>(static_cast<char*>(lists) + list_b);
+  r3d_carve lists;
+  const auto idx_h = lists.take<uint32_t>((size_t)n * k);
+  const auto d2l_h = lists.take<float>((size_t)n * k);
+  if ((rc = r3d_scratch(ctx, kWsColorLists, lists))) return rc;
+  uint32_t* idx = lists.at(idx_h);
+  float* d2l = lists.at(d2l_h);
   if ((rc = r3d_nn_index_knn_self(index, k, idx, d2l))) return rc;
   for (int i = 0; i < 3; ++i)
     if (outs[i].p) r3d_wrote(ctx, outs[i].p, outs[i].bytes);

@@ -82,22 +82,15 @@ struct Layout {
 };
 
 inline int layout(r3d_ctx* ctx, const Plan& p, int params, int sums, size_t misc_bytes, Layout* out) {
-  const size_t misc_b = r3d_align_up(misc_bytes, 256);
-  const size_t hyp_b = (size_t)params * p.h_pad * 4, rows_b = r3d_align_up((size_t)3 * p.H * 4, 256);
-  const size_t hb = r3d_align_up((size_t)p.H * 4, 256);
-  const size_t part_b = r3d_align_up((size_t)p.chunks * p.h_pad * 4, 256);
-  void *s5 = nullptr, *s4 = nullptr;
+  r3d_carve s5, s4;
+  const auto misc = s5.take<char>(misc_bytes);   // one piece: the estimator's Misc struct, read back in one copy
+  const auto hyp = s5.take<float>((size_t)params * p.h_pad);
+  const auto rows = s5.take<uint32_t>((size_t)3 * p.H), valid = s5.take<uint32_t>(p.H), counts = s5.take<uint32_t>(p.H);
+  const auto partial = s4.take<uint32_t>((size_t)p.chunks * p.h_pad);
+  const auto part = s4.take<double>((size_t)p.rblocks * sums);
   int rc;
-  if ((rc = r3d_scratch(ctx, kWsMisc, misc_b + hyp_b + rows_b + 2 * hb, &s5))) return rc;
-  if ((rc = r3d_scratch(ctx, kWsPartials, part_b + (size_t)p.rblocks * sums * sizeof(double), &s4))) return rc;
-  char* p5 = static_cast<char*>(s5);
-  out->misc = p5;
-  out->hyp = reinterpret_cast<float*>(p5 + misc_b);
-  out->rows = reinterpret_cast<uint32_t*>(p5 + misc_b + hyp_b);
-  out->valid = reinterpret_cast<uint32_t*>(p5 + misc_b + hyp_b + rows_b);
-  out->counts = reinterpret_cast<uint32_t*>(p5 + misc_b + hyp_b + rows_b + hb);
-  out->partial = static_cast<uint32_t*>(s4);
-  out->part = reinterpret_cast<double*>(static_cast<char*>(s4) + part_b);
+  if ((rc = r3d_scratch(ctx, kWsMisc, s5)) || (rc = r3d_scratch(ctx, kWsPartials, s4))) return rc;
+  *out = {s5.at(misc), s5.at(hyp), s5.at(rows), s5.at(valid), s5.at(counts), s4.at(partial), s4.at(part)};
   return R3D_OK;
 }
 

@@ -126,13 +126,14 @@ int r3d_depth_consistency_host(r3d_ctx* ctx, const r3d_camera* cam, const void* 
   if ((rc = r3d_ctx_enter(ctx))) return rc;
   // the rasters through kWsIn; the requested outputs through kWsOut: filtered | votes | keep, so each is aligned for its type
   const size_t filtered_bytes = h_filtered_out ? n * 4 : 0, votes_bytes = h_votes_out ? n * 2 : 0, keep_bytes = h_keep_out ? n : 0;
-  void *d_in = nullptr, *d_out = nullptr;
-  if ((rc = r3d_scratch(ctx, kWsIn, in_bytes, &d_in))) return rc;
-  if ((rc = r3d_scratch(ctx, kWsOut, filtered_bytes + votes_bytes + keep_bytes, &d_out))) return rc;
-  char* o = static_cast<char*>(d_out);
-  float* d_filtered = h_filtered_out ? reinterpret_cast<float*>(o) : nullptr;
-  uint8_t* d_votes = h_votes_out ? reinterpret_cast<uint8_t*>(o + filtered_bytes) : nullptr;
-  uint8_t* d_keep = h_keep_out ? reinterpret_cast<uint8_t*>(o + filtered_bytes + votes_bytes) : nullptr;
+  void* d_in = nullptr;
+  r3d_carve out;
+  const auto filtered_h = out.take<float>(filtered_bytes / 4);
+  const auto votes_h = out.take<uint8_t>(votes_bytes), keep_h = out.take<uint8_t>(keep_bytes);
+  if ((rc = r3d_scratch(ctx, kWsIn, in_bytes, &d_in)) || (rc = r3d_scratch(ctx, kWsOut, out))) return rc;
+  float* d_filtered = h_filtered_out ? out.at(filtered_h) : nullptr;
+  uint8_t* d_votes = h_votes_out ? out.at(votes_h) : nullptr;
+  uint8_t* d_keep = h_keep_out ? out.at(keep_h) : nullptr;
   if ((rc = r3d_memcpy_h2d(ctx, d_in, h_depth, in_bytes))) return rc;
   if ((rc = consistency_device(ctx, cam, d_in, depth_dtype, n_frames, depth_scale, h_pose_w2c, h_sources, n_sources,
                                Rule{(float)rel_tol, min_consistent, max_violations}, d_votes, d_keep, d_filtered)))

@@ -260,12 +260,13 @@ int r3d_match_nearest(r3d_ctx* ctx, const float* d_a, int64_t na, const float* d
   const int64_t chunk_tiles = (tiles + std::min(tiles, want) - 1) / std::min(tiles, want);
   const int64_t chunk_rows = chunk_tiles * kTileRows;
   const int chunks = (int)((nb + chunk_rows - 1) / chunk_rows);
-  void* ws = nullptr;
-  const size_t half = r3d_align_up((size_t)chunks * na * 4, 256);
-  int rc = r3d_scratch(ctx, part, 2 * half, &ws);
+  r3d_carve ws;
+  const auto part_d_h = ws.take<float>((size_t)chunks * na);
+  const auto part_j_h = ws.take<uint32_t>((size_t)chunks * na);
+  int rc = r3d_scratch(ctx, part, ws);
   if (rc) return rc;
-  float* part_d = static_cast<float*>(ws);
-  uint32_t* part_j = reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + half);
+  float* part_d = ws.at(part_d_h);
+  uint32_t* part_j = ws.at(part_j_h);
   const dim3 grid((unsigned)a_blocks, (unsigned)chunks);
   if (R == 2) hipLaunchKernelGGL((match_kernel<2>), grid, dim3(kThreads), 0, ctx->stream, d_a, na, d_b, nb, chunk_rows, part_d, part_j);
   else hipLaunchKernelGGL((match_kernel<1>), grid, dim3(kThreads), 0, ctx->stream, d_a, na, d_b, nb, chunk_rows, part_d, part_j);
@@ -299,12 +300,14 @@ int r3d_fpfh_knn(r3d_nn_index* index, int k, double radius, const float* d_norma
   }
   if ((rc = r3d_ctx_enter(ctx))) return rc;
   // kWsIn: the lists (idx | d2); kWsOut: the 36-byte histogram rows.  The index's own search takes no workspace.
-  const size_t list_b = r3d_align_up((size_t)n * k * 4, 256);
-  void *lists = nullptr, *rows = nullptr;
-  if ((rc = r3d_scratch(ctx, kWsIn, 2 * list_b, &lists))) return rc;
+  r3d_carve lists;
+  const auto idx_h = lists.take<uint32_t>((size_t)n * k);
+  const auto d2l_h = lists.take<float>((size_t)n * k);
+  void* rows = nullptr;
+  if ((rc = r3d_scratch(ctx, kWsIn, lists))) return rc;
   if ((rc = r3d_scratch(ctx, kWsOut, (size_t)n * kRowBytes, &rows))) return rc;
-  uint32_t* idx = static_cast<uint32_t*>(lists);
-  float* d2l = reinterpret_cast<float*>(static_cast<char*>(lists) + list_b);
+  uint32_t* idx = lists.at(idx_h);
+  float* d2l = lists.at(d2l_h);
   if ((rc = r3d_nn_index_knn_self(index, k, idx, d2l))) return rc;
   for (int i = 0; i < 3; ++i)
     if (out[i].p) r3d_wrote(ctx, out[i].p, out[i].bytes);

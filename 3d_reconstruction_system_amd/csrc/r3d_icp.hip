@@ -245,10 +245,11 @@ int r3d_icp_nn(r3d_ctx* ctx, const float* d_src, int64_t n_src, const float* d_t
   uint32_t* k_idx = d_idx_out;
   float* k_d2 = d_d2_out;
   if (n_seg > 1) {
-    void* part = nullptr;
-    if ((rc = r3d_scratch(ctx, kWsMisc, (size_t)n_seg * n_src * 8, &part))) return rc;
-    k_idx = static_cast<uint32_t*>(part);
-    k_d2 = reinterpret_cast<float*>(k_idx + (size_t)n_seg * n_src);
+    r3d_carve part;
+    const auto idx_h = part.take<uint32_t>((size_t)n_seg * n_src);
+    const auto d2_h = part.take<float>((size_t)n_seg * n_src);
+    if ((rc = r3d_scratch(ctx, kWsMisc, part))) return rc;
+    k_idx = part.at(idx_h), k_d2 = part.at(d2_h);
   }
   const dim3 grid((unsigned)src_blocks, (unsigned)n_seg);
   switch (S) {

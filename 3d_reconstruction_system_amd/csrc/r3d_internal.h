@@ -11,37 +11,45 @@
 #include <functional>
 
 #include "r3d.h"
+#include "r3d_carve.h"
 #include "r3d_internal_api.h"
 
 // The context's grow-only device workspaces (r3d_ctx::scratch), claimed by name through r3d_scratch.  A SHARED entry is taken by
 // many entry points one after the other in stream order; nobody may expect to find in it what an earlier call left (tests/
 // test_gpu_call_order.py), and a helper takes one only if no caller above it holds data there.  A PRIVATE entry is one file's.
+// A claim that holds more than one array is an r3d_carve (r3d_carve.h): the claimant take()s its pieces in the order given below
+// ("a | b": b behind a), r3d_scratch(ctx, which, carve) asks for their sum, and carve.at(piece) is the only pointer arithmetic.
 //   kWsIn          shared   staged input of the *_host calls (fuse, apply, ICP source, voxel and grid points, consistency rasters);
-//                           TSDF slabs; NN sort keys; FPFH k-NN lists; r3d_register_ransac's gathered pairs; octree records; the voxel union's list
+//                           TSDF slabs (depth | rgb); NN sort keys; FPFH k-NN lists (idx | d2); r3d_register_ransac's gathered pairs; octree
+//                           records; the voxel union's list
 //   kWsOut         shared   staged output of the *_host calls (ICP: the target; consistency: filtered | votes | keep); the sorted voxel codes; NN query `src4` / sorted
 //                           copy; SOR scores; FPFH rows; merge remainders
 //   kWsSpare       shared   the radix sort's `tmp` where the caller has none (NN, voxel codes, r3d_sort_u64); fuse pose tables;
 //                           r3d_depth_consistency's relative pose rows ([F][S] x 64 bytes, the source index in each row's padding);
-//                           octree meta; merge segments; host ICP idx; feature match's b -> a partial minima; the block bitmap of
+//                           octree meta | pre; merge segments (rem | hi); host ICP idx; feature match's b -> a partial minima (dist | idx); the block bitmap of
 //                           r3d_tsdf_integrate_cloud (dead before its first NN query)
-//   kWsCounts      shared   the histogram of EVERY radix sort (r3d_radix_sort_workspace; the private files sort too); compaction
-//                           Counters of knn, tsdf, tsdf_mesh, tsdf_cloud, r3d_compact_rows_by_mask; octree tile places; host ICP d2 and sums; fuse rgb; feature match's
-//                           b -> a rows; the voxel union's counts
+//   kWsCounts      shared   hist | totals of EVERY radix sort (r3d_radix_sort_workspace; the private files sort too); compaction
+//                           Counters of knn, tsdf, tsdf_mesh (masks | group_first | Counters), tsdf_cloud, r3d_compact_rows_by_mask; the octree's
+//                           flags | tile_base | tile_cnt | tile_leaf; host ICP d2 and sums; fuse rgb; feature match's b -> a rows; the voxel union's counts
 //   kWsPartials    shared   partial rows of the sums passes (ICP, NN query + solve, tracking, SOR); NN bound rows; consensus
-//                           partials; r3d_apply_T_many's table; grad_P partials; fuse rgba; grid colours; a -> b partial minima
-//   kWsMisc        shared   what the host reads back: NN and knn `misc`, consensus misc | hyp | rows | counts, feature match's keep
-//                           counts, the voxel set's 64 bytes; viewpoint table; textfmt, sort-merge and brute-force ICP workspaces
-//   kWsSelect      shared   r3d_plane.hip alone: selection histogram + state, plane sums rows.  r3d_ctx::select_ws records that the
-//                           histogram is all zero; r3d_scratch forgets that when it reallocates the entry
-//   kWsTrack       shared   r3d_track.hip's maps + ICP state; r3d_plane.hip's rank-trimming residuals (never inside one call)
+//                           partial | part; r3d_apply_T_many's table; grad_P partials; fuse rgba; grid colours; a -> b partial minima (dist | idx);
+//                           SOR rows1 | rows2
+//   kWsMisc        shared   what the host reads back: NN `misc`, SOR stats | kept (one copy), consensus misc | hyp | rows | valid | counts, feature
+//                           match's keep counts, the voxel set's 64 bytes; viewpoint table; textfmt flags | off | len (flags | off: one copy);
+//                           sort-merge partials | starts | hist | totals | spill count | flags | cursors | spill (count .. cursors: one memset);
+//                           brute-force ICP idx | d2
+//   kWsSelect      shared   r3d_plane.hip alone: hist | state | out | rows (hist | state: one memset).  r3d_ctx::select_ws records that the
+//                           histogram, the block's first piece, is all zero; r3d_scratch forgets that when it reallocates the entry
+//   kWsTrack       shared   r3d_track.hip: every level's four maps | the upper levels' depth | ICP state, or (colour) four maps | model packed |
+//                           model depth | source intensity | model rgb | state; r3d_plane.hip's rank-trimming r2 | class (never inside one call)
 //   kWsBilateral   private  r3d_bilateral.hip: the weight tables, keyed by r3d_ctx::bilateral_*; the contents outlive the call
 //   kWsRegSums     private  r3d_reginfo.hip: partial rows + 11 sums, always asked for at the largest size (never regrows)
 //   kWsColorRows   private  r3d_color_icp.hip: partial rows + 31 sums, always asked for at the largest size (never regrows)
 //   kWsColorLists  private  r3d_color_icp.hip: the k-NN lists (idx | d2) of r3d_color_gradient_knn
-//   kWsMeshCc      private  r3d_mesh_cc.hip: per-label counters, vertex flags, tile counters
-//   kWsMeshDist    private  r3d_meshdist.hip: sort keys + spare of an index build or query; r3d_distance_stats' partial rows
-//   kWsMeshSmooth  private  r3d_mesh_smooth_host.cpp: adjacency side keys + spare + tile counters; the smoothing steps' two
-//                           ping-pong position arrays; the normals' corner keys + spare (one call at a time, nothing outlives it)
+//   kWsMeshCc      private  r3d_mesh_cc.hip: two per-vertex arrays | Counters (its 64-byte tail: totals, then `best`); cleared whole by one memset
+//   kWsMeshDist    private  r3d_meshdist.hip: keys | tmp of an index build or query; r3d_distance_stats' sums | min-max | out | counts
+//   kWsMeshSmooth  private  r3d_mesh_smooth_host.cpp: adjacency keys | tmp | Counters; the smoothing steps' two ping-pong position
+//                           arrays; the normals' keys | tmp (one call at a time, nothing outlives it)
 // Hand-over rules between nested claims:
 //   * a sort holds kWsCounts (r3d_sort_u64 also kWsSpare) until its last pass is enqueued: its callers keep nothing of theirs
 //     there across it (the voxel code list lives in kWsOut, the NN keys in kWsIn);
@@ -50,7 +58,9 @@
 //   * r3d_consensus::layout takes kWsMisc and kWsPartials whole: r3d_register_ransac keeps its pairs in kWsIn, and feature
 //     matching (keep counts in kWsMisc, partial minima where r3d_match_nearest is told: kWsPartials, kWsSpare) runs no consensus;
 //   * growing frees the old block once both streams are idle: no pointer into an entry survives a larger r3d_scratch of it, so
-//     a loop reserves its largest size up front (r3d_track.hip's rows).
+//     a loop reserves its largest size up front (r3d_track.hip's rows) and a carve is claimed once, before its first at();
+//   * pieces that one copy or one memset spans are taken next to each other and the length is the distance between two pieces'
+//     offsets (or the comment at the take() says why they touch); a Counters block is one piece (cn.bytes), its tail included.
 enum r3d_workspace : int {
   kWsIn = 0,
   kWsOut,
@@ -195,8 +205,19 @@ void r3d_wrote(r3d_ctx* ctx, const void* p, size_t bytes);
 // The one allocator of the context's workspaces (device memory, grow-only): *p = at least `bytes` bytes (16 for 0) of `which`.
 // Growing waits for both streams, drops the old range from the residency record and frees it; the contents are not kept.
 int r3d_scratch(r3d_ctx* ctx, r3d_workspace which, size_t bytes, void** p);
-// bytes rounded up to a multiple of `a`, a power of two
-constexpr size_t r3d_align_up(size_t bytes, size_t a) { return (bytes + a - 1) & ~(a - 1); }
+// ... and of a block that is divided (r3d_carve.h): `which` holds c.bytes and c is placed there.  carve.at() is the only way in.
+inline int r3d_scratch(r3d_ctx* ctx, r3d_workspace which, r3d_carve& c) {
+  void* p = nullptr;
+  const int rc = r3d_scratch(ctx, which, c.bytes, &p);
+  c.place(p);
+  return rc;
+}
+// The same for a slab an object owns for its lifetime (the NN index, the mesh index): *slab = hipMalloc(c.bytes), c placed there.
+inline hipError_t r3d_carve_malloc(r3d_carve& c, void** slab) {
+  const hipError_t e = hipMalloc(slab, c.bytes);
+  c.place(e == hipSuccess ? *slab : nullptr);
+  return e;
+}
 
 // Chunked, double-buffered host<->device pipeline (r3d_hostpipe.hip).  Items [lo, lo+n) of the batch are uploaded
 // to d_in + lo*in_item_bytes, `launch(lo, n)` enqueues the kernel for them, and d_out + lo*out_item_bytes comes back.
@@ -237,7 +258,7 @@ int r3d_download_pageable(r3d_ctx* ctx, void* h_dst, const void* d_src, size_t b
 int r3d_radix_sort_u64(r3d_ctx* ctx, uint64_t* d_keys, uint64_t* d_tmp, int64_t n, int bits, int first_bit = 0,
                        uint64_t** d_result = nullptr, bool first_hist_done = false);
 constexpr int kSortTile = 4096;   // keys per workgroup of every sort kernel
-int r3d_radix_sort_workspace(r3d_ctx* ctx, int64_t n, uint32_t** hist_out, int* n_blocks_out);
+int r3d_radix_sort_workspace(r3d_ctx* ctx, int64_t n, uint32_t** hist_out, uint32_t** totals_out, int* n_blocks_out);
 constexpr int r3d_sort_stride(int n_blocks) { return (n_blocks + 7) & ~7; }   // counters per histogram row (32-byte aligned rows)
 // hist[bin][tile] (n_bins rows of `stride` counters) -> exclusive prefixes over the tiles, in place; totals[bin] = the bin's count
 void r3d_sort_launch_scan(r3d_ctx* ctx, uint32_t* hist, int n_blocks, int stride, uint32_t* totals, int n_bins = 256);

@@ -564,14 +564,17 @@ int r3d_outlier_statistical(r3d_nn_index* ix, int k, double std_ratio, uint8_t* 
   int rc = r3d_ctx_enter(ctx);
   if (rc) return rc;
   const int blocks = (int)(ix->n_tiles * (kTile / kThreads)), rblocks = reduce_blocks(n);
-  void *score = d_score_out, *rows = nullptr, *misc = nullptr;
+  void* score = d_score_out;
   if (!score && (rc = r3d_scratch(ctx, kWsOut, (size_t)n * 8, &score))) return rc;
-  if ((rc = r3d_scratch(ctx, kWsPartials, (size_t)(2 * blocks + rblocks) * sizeof(double), &rows))) return rc;
-  if ((rc = r3d_scratch(ctx, kWsMisc, 64, &misc))) return rc;
-  double* stats = static_cast<double*>(misc);                                          // V, mu, sigma, T
-  unsigned long long* kept = reinterpret_cast<unsigned long long*>(stats + 4);
-  double* rows1 = static_cast<double*>(rows);
-  double* rows2 = rows1 + 2 * blocks;
+  r3d_carve rows, misc;
+  const auto rows1_h = rows.take<double>((size_t)2 * blocks), rows2_h = rows.take<double>(rblocks);
+  // the four statistics fill their 32 bytes, so the kept count, taken at the same alignment, lies right behind them: one copy of
+  // five words reads both
+  const auto stats_h = misc.take<double>(4, 32);   // V, mu, sigma, T
+  const auto kept_h = misc.take<unsigned long long>(1, 32);
+  if ((rc = r3d_scratch(ctx, kWsPartials, rows)) || (rc = r3d_scratch(ctx, kWsMisc, misc))) return rc;
+  double *stats = misc.at(stats_h), *rows1 = rows.at(rows1_h), *rows2 = rows.at(rows2_h);
+  unsigned long long* kept = misc.at(kept_h);
   r3d_wrote(ctx, d_keep_out, (size_t)n);
   if (d_score_out) r3d_wrote(ctx, d_score_out, (size_t)n * 8);
   hipStream_t st = ctx->stream;
@@ -588,7 +591,7 @@ int r3d_outlier_statistical(r3d_nn_index* ix, int k, double std_ratio, uint8_t* 
                      kept);
   R3D_HIP(hipGetLastError());
   double h[5];
-  R3D_HIP(hipMemcpyAsync(h, misc, sizeof(h), hipMemcpyDeviceToHost, st));
+  R3D_HIP(hipMemcpyAsync(h, stats, sizeof(h), hipMemcpyDeviceToHost, st));
   R3D_HIP(hipStreamSynchronize(st));
   if (h_stats_out) memcpy(h_stats_out, h, 4 * sizeof(double));
   if (h_n_kept) {

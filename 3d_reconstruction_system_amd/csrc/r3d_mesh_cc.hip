@@ -267,16 +267,15 @@ int r3d_mesh_components(r3d_ctx* ctx, const int32_t* d_tri, int64_t n_triangles,
   // workspace: cnt_v [nv] | cnt_t [nv] | the tile counters (64-byte aligned) | {n_components, n_invalid}
   const int tiles = tiles_of(nv);
   Counters cn(tiles, 1);
-  const size_t hist_at = r3d_align_up((size_t)nv * 8, 64), ws_bytes = hist_at + cn.bytes;
-  void* ws_v = nullptr;
-  if ((rc = r3d_scratch(ctx, kWsMeshCc, ws_bytes, &ws_v))) return rc;
-  char* ws = static_cast<char*>(ws_v);
-  uint32_t* cnt_v = reinterpret_cast<uint32_t*>(ws);
-  uint32_t* cnt_t = cnt_v + nv;
-  cn.place(ws + hist_at);
+  r3d_carve ws;
+  const auto cnt_v_h = ws.take<uint32_t>(nv, 64), cnt_t_h = ws.take<uint32_t>(nv, 64);
+  const auto cn_h = ws.take<char>(cn.bytes, 64);
+  if ((rc = r3d_scratch(ctx, kWsMeshCc, ws))) return rc;
+  uint32_t *cnt_v = ws.at(cnt_v_h), *cnt_t = ws.at(cnt_t_h);
+  cn.place(ws.at(cn_h));
   uint32_t *hist = cn.hist, *totals = cn.totals;
   hipStream_t st = ctx->stream;
-  R3D_HIP(hipMemsetAsync(ws, 0, ws_bytes, st));
+  R3D_HIP(hipMemsetAsync(ws.block, 0, ws.bytes, st));   // every piece
   uint32_t* label = d_vertex_label_out;
   if (nv) {
     r3d_wrote(ctx, label, vl_b);
@@ -329,17 +328,16 @@ int r3d_mesh_filter_components(r3d_ctx* ctx, const int32_t* d_tri, int64_t n_tri
   // workspace: cnt_t [nv] | vflag [nv] | the tile counters (64-byte aligned; row 0 vertices, row 1 triangles) | totals [2] | best u64
   const int tiles_v = tiles_of(nv), tiles_t = tiles_of(nt);
   Counters cn(tiles_v > tiles_t ? tiles_v : tiles_t, 2);
-  const size_t hist_at = r3d_align_up((size_t)nv * 8, 64), ws_bytes = hist_at + cn.bytes;
-  void* ws_v = nullptr;
-  if ((rc = r3d_scratch(ctx, kWsMeshCc, ws_bytes, &ws_v))) return rc;
-  char* ws = static_cast<char*>(ws_v);
-  uint32_t* cnt_t = reinterpret_cast<uint32_t*>(ws);
-  uint32_t* vflag = cnt_t + nv;
-  cn.place(ws + hist_at);
+  r3d_carve ws;
+  const auto cnt_t_h = ws.take<uint32_t>(nv, 64), vflag_h = ws.take<uint32_t>(nv, 64);
+  const auto cn_h = ws.take<char>(cn.bytes, 64);   // one piece: the counters' 64-byte tail holds the totals and, behind them, `best`
+  if ((rc = r3d_scratch(ctx, kWsMeshCc, ws))) return rc;
+  uint32_t *cnt_t = ws.at(cnt_t_h), *vflag = ws.at(vflag_h);
+  cn.place(ws.at(cn_h));
   uint32_t* totals = cn.totals;
   unsigned long long* best = reinterpret_cast<unsigned long long*>(totals + 2);   // 8-byte aligned: stride is a multiple of 8 words
   hipStream_t st = ctx->stream;
-  R3D_HIP(hipMemsetAsync(ws, 0, ws_bytes, st));   // (the tile counters beyond either row's own tiles must read 0 in the scan)
+  R3D_HIP(hipMemsetAsync(ws.block, 0, ws.bytes, st));   // every piece (the tile counters beyond either row's own tiles must read 0 in the scan)
   const Keep keep{min_triangles, keep_largest != 0 ? 1 : 0};
   if (nt && nv) {
     hipLaunchKernelGGL(cc_count_kernel, dim3(blocks_of(nt)), dim3(kThreads), 0, st, d_tri, nt, (uint32_t)nv, d_vertex_label,

@@ -72,12 +72,12 @@ int r3d_mesh_adjacency(r3d_ctx* ctx, const int32_t* d_tri, int64_t n_triangles, 
   }
   const int vb = vertex_bits(nv), tiles = r3d_compact::tiles_of(n_keys);
   r3d_compact::Counters cn(tiles, 1);
-  const size_t keys_b = r3d_align_up((size_t)n_keys * 8, 64);
-  void* ws_v = nullptr;
-  if ((rc = r3d_scratch(ctx, kWsMeshSmooth, 2 * keys_b + cn.bytes, &ws_v))) return rc;
-  char* ws = static_cast<char*>(ws_v);
-  uint64_t *keys = reinterpret_cast<uint64_t*>(ws), *tmp = reinterpret_cast<uint64_t*>(ws + keys_b), *sorted = nullptr;
-  cn.place(ws + 2 * keys_b);
+  r3d_carve ws;
+  const auto keys_h = ws.take<uint64_t>(n_keys, 64), tmp_h = ws.take<uint64_t>(n_keys, 64);
+  const auto cn_h = ws.take<char>(cn.bytes, 64);
+  if ((rc = r3d_scratch(ctx, kWsMeshSmooth, ws))) return rc;
+  uint64_t *keys = ws.at(keys_h), *tmp = ws.at(tmp_h), *sorted = nullptr;
+  cn.place(ws.at(cn_h));
   r3d_mesh_side_keys_launch(ctx, d_tri, nt, (uint32_t)nv, vb, keys);
   R3D_HIP(hipGetLastError());
   if ((rc = r3d_radix_sort_u64(ctx, keys, tmp, n_keys, 2 * vb + 1, 0, &sorted))) return rc;
@@ -123,13 +123,12 @@ int r3d_mesh_smooth(r3d_ctx* ctx, const float* d_xyz_in, float* d_xyz_out, int64
     return R3D_OK;
   }
   // step k reads what step k - 1 wrote: in -> ws[0] -> ws[1] -> ws[0] ... -> out
-  const size_t buf_b = r3d_align_up(xyz_b, 64);
   float* pp[2] = {nullptr, nullptr};
   if (n_factors > 1) {
-    void* ws = nullptr;
-    if ((rc = r3d_scratch(ctx, kWsMeshSmooth, (n_factors > 2 ? 2 : 1) * buf_b, &ws))) return rc;
-    pp[0] = static_cast<float*>(ws);
-    pp[1] = reinterpret_cast<float*>(static_cast<char*>(ws) + buf_b);
+    r3d_carve ws;
+    const auto p0 = ws.take<float>((size_t)nv * 3, 64), p1 = ws.take<float>(n_factors > 2 ? (size_t)nv * 3 : 0, 64);   // two steps need one
+    if ((rc = r3d_scratch(ctx, kWsMeshSmooth, ws))) return rc;
+    pp[0] = ws.at(p0), pp[1] = ws.at(p1);
   }
   const float* src = d_xyz_in;
   for (int k = 0; k < n_factors; ++k) {
@@ -158,11 +157,10 @@ int r3d_mesh_vertex_normals(r3d_ctx* ctx, const float* d_xyz, int64_t n_vertices
   uint64_t* sorted = nullptr;
   if (nt > 0) {
     const int vb = vertex_bits(nv);
-    const size_t keys_b = r3d_align_up((size_t)n_keys * 8, 64);
-    void* ws_v = nullptr;
-    if ((rc = r3d_scratch(ctx, kWsMeshSmooth, 2 * keys_b, &ws_v))) return rc;
-    uint64_t* keys = static_cast<uint64_t*>(ws_v);
-    uint64_t* tmp = reinterpret_cast<uint64_t*>(static_cast<char*>(ws_v) + keys_b);
+    r3d_carve ws;
+    const auto keys_h = ws.take<uint64_t>(n_keys, 64), tmp_h = ws.take<uint64_t>(n_keys, 64);
+    if ((rc = r3d_scratch(ctx, kWsMeshSmooth, ws))) return rc;
+    uint64_t *keys = ws.at(keys_h), *tmp = ws.at(tmp_h);
     r3d_mesh_corner_keys_launch(ctx, d_tri, nt, (uint32_t)nv, vb, keys);
     R3D_HIP(hipGetLastError());
     // (the low 32 bits hold 3t + c, which already ascends: the stable sort skips those digits)

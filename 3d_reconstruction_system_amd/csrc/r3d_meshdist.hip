@@ -520,27 +520,19 @@ int r3d_mesh_index_create(r3d_ctx* ctx, const float* d_xyz, int64_t n_vertices, 
   ix->ctx = ctx;
   ix->device = ctx->device;
   const int64_t nt = n_triangles, max_groups = (nt + kGroup - 1) / kGroup;
-  size_t off = 0;
-  auto take = [&off](size_t bytes) {
-    const size_t at = off;
-    off += r3d_align_up(bytes, 256);
-    return at;
-  };
-  const size_t o_tri = take((size_t)max_groups * kGroup * kTriFloats * sizeof(float)), o_box = take((size_t)max_groups * 6 * sizeof(float)),
-               o_code = take((size_t)max_groups * sizeof(uint64_t)), o_frame = take(8 * sizeof(float)), o_bounds = take(6 * sizeof(uint32_t)),
-               o_cnt = take(2 * sizeof(unsigned long long));
-  hipError_t e = hipMalloc(&ix->d_slab, off);
+  r3d_carve slab;
+  const auto tri = slab.take<float>((size_t)max_groups * kGroup * kTriFloats), box = slab.take<float>((size_t)max_groups * 6);
+  const auto code = slab.take<uint64_t>(max_groups);
+  const auto frame = slab.take<float>(8);
+  const auto bounds = slab.take<uint32_t>(6);
+  const auto cnt = slab.take<unsigned long long>(2);
+  hipError_t e = r3d_carve_malloc(slab, &ix->d_slab);
   if (e != hipSuccess) {
     r3d_mesh_index_destroy(ix);
     return r3d_fail_hip(e, "mesh index allocation", __FILE__, __LINE__);
   }
-  char* slab = static_cast<char*>(ix->d_slab);
-  ix->d_tri = reinterpret_cast<float*>(slab + o_tri);
-  ix->d_group_box = reinterpret_cast<float*>(slab + o_box);
-  ix->d_group_code = reinterpret_cast<uint64_t*>(slab + o_code);
-  ix->d_frame = reinterpret_cast<float*>(slab + o_frame);
-  ix->d_bounds = reinterpret_cast<uint32_t*>(slab + o_bounds);
-  ix->d_counters = reinterpret_cast<unsigned long long*>(slab + o_cnt);
+  ix->d_tri = slab.at(tri), ix->d_group_box = slab.at(box), ix->d_group_code = slab.at(code);
+  ix->d_frame = slab.at(frame), ix->d_bounds = slab.at(bounds), ix->d_counters = slab.at(cnt);
   auto fail = [ix](int code) {
     r3d_mesh_index_destroy(ix);
     return code;
@@ -550,16 +542,17 @@ int r3d_mesh_index_create(r3d_ctx* ctx, const float* d_xyz, int64_t n_vertices, 
   if (nt > 0) {
     const uint32_t nv = (uint32_t)n_vertices;
     const int idx_bits = bits_for(nt);
-    void *keys = nullptr, *tmp = nullptr;
-    if ((rc = r3d_scratch(ctx, kWsMeshDist, (size_t)nt * 16, &keys))) return fail(rc);
-    tmp = static_cast<uint64_t*>(keys) + nt;
+    r3d_carve ws;
+    const auto keys_h = ws.take<uint64_t>(nt), tmp_h = ws.take<uint64_t>(nt);
+    if ((rc = r3d_scratch(ctx, kWsMeshDist, ws))) return fail(rc);
+    uint64_t *keys = ws.at(keys_h), *tmp = ws.at(tmp_h);
     hipLaunchKernelGGL(md_bbox_kernel, dim3(blocks_of(nt)), dim3(kThreads), 0, st, d_xyz, nv, d_tri, nt, ix->d_bounds, ix->d_counters);
     hipLaunchKernelGGL(md_frame_kernel, dim3(1), dim3(64), 0, st, (const uint32_t*)ix->d_bounds, ix->d_frame);
     hipLaunchKernelGGL(md_keys_kernel, dim3(blocks_of(nt)), dim3(kThreads), 0, st, d_xyz, nv, d_tri, nt, (const float*)ix->d_frame, idx_bits,
-                       (uint64_t*)keys);
+                       keys);
     if ((e = hipGetLastError()) != hipSuccess) return fail(r3d_fail_hip(e, "mesh index build", __FILE__, __LINE__));
     // (the low idx_bits hold the triangle number, which already ascends: the stable sort skips those digits)
-    if ((rc = r3d_radix_sort_u64(ctx, (uint64_t*)keys, (uint64_t*)tmp, nt, 3 * kAxisBits + 1 + idx_bits, idx_bits))) return fail(rc);
+    if ((rc = r3d_radix_sort_u64(ctx, keys, tmp, nt, 3 * kAxisBits + 1 + idx_bits, idx_bits))) return fail(rc);
     unsigned long long n_valid = 0;
     if ((e = hipMemcpyAsync(&n_valid, ix->d_counters, sizeof n_valid, hipMemcpyDeviceToHost, st)) != hipSuccess ||
         (e = hipStreamSynchronize(st)) != hipSuccess)
@@ -599,13 +592,14 @@ int r3d_mesh_index_query(r3d_mesh_index* ix, const float* d_points, int64_t n_po
   hipStream_t st = ctx->stream;
   if (n > 0) {
     const int idx_bits = bits_for(n);
-    void *keys = nullptr, *tmp = nullptr;
-    if ((rc = r3d_scratch(ctx, kWsMeshDist, (size_t)n * 16, &keys))) return rc;
-    tmp = static_cast<uint64_t*>(keys) + n;
+    r3d_carve ws;
+    const auto keys_h = ws.take<uint64_t>(n), tmp_h = ws.take<uint64_t>(n);
+    if ((rc = r3d_scratch(ctx, kWsMeshDist, ws))) return rc;
+    uint64_t *keys = ws.at(keys_h), *tmp = ws.at(tmp_h);
     hipLaunchKernelGGL(md_point_keys_kernel, dim3(blocks_of(n)), dim3(kThreads), 0, st, d_points, n, (const float*)ix->d_frame, idx_bits,
-                       (uint64_t*)keys);
+                       keys);
     R3D_HIP(hipGetLastError());
-    if ((rc = r3d_radix_sort_u64(ctx, (uint64_t*)keys, (uint64_t*)tmp, n, 3 * kAxisBits + 1 + idx_bits, idx_bits))) return rc;
+    if ((rc = r3d_radix_sort_u64(ctx, keys, tmp, n, 3 * kAxisBits + 1 + idx_bits, idx_bits))) return rc;
     unsigned long long* counter = h_groups_evaluated ? ix->d_counters + 1 : nullptr;
     if (counter) R3D_HIP(hipMemsetAsync(counter, 0, sizeof *counter, st));
     r3d_wrote(ctx, d_dist_out, (size_t)n * 4);
@@ -655,13 +649,13 @@ int r3d_distance_stats(r3d_ctx* ctx, const float* d_values, int64_t n, int squar
   if (n > 0) {
     const int64_t n_rows = (n + kStatsRow - 1) / kStatsRow;
     const int n_counts = kMaxThresholds + n_bins;
-    const size_t b_sums = (size_t)n_rows * 32, b_mm = (size_t)n_rows * 16, b_out = 64, b_counts = (size_t)n_counts * 8;
-    void* ws = nullptr;
-    if ((rc = r3d_scratch(ctx, kWsMeshDist, b_sums + b_mm + b_out + b_counts, &ws))) return rc;
-    double* part_sums = static_cast<double*>(ws);
-    double* part_mm = part_sums + n_rows * 4;
-    double* out = part_mm + n_rows * 2;
-    unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(out + 8);
+    const size_t b_counts = (size_t)n_counts * 8;
+    r3d_carve ws;
+    const auto sums_h = ws.take<double>((size_t)n_rows * 4), mm_h = ws.take<double>((size_t)n_rows * 2), out_h = ws.take<double>(8);
+    const auto counts_h = ws.take<unsigned long long>(n_counts);   // read back by a copy of its own
+    if ((rc = r3d_scratch(ctx, kWsMeshDist, ws))) return rc;
+    double *part_sums = ws.at(sums_h), *part_mm = ws.at(mm_h), *out = ws.at(out_h);
+    unsigned long long* d_counts = ws.at(counts_h);
     hipStream_t st = ctx->stream;
     R3D_HIP(hipMemsetAsync(d_counts, 0, b_counts, st));
     const int64_t max_blocks = (int64_t)ctx->num_cus * 4;

@@ -789,33 +789,23 @@ int r3d_nn_index_create(r3d_ctx* ctx, const float* d_tgt, int64_t n_tgt, r3d_nn_
   ix->capacity = n_tgt;
   const int64_t n_tiles = (n_tgt + kTile - 1) / kTile, n_pad = n_tiles * kTile;
   // one slab, every table at a 256-byte boundary
-  size_t off = 0;
-  auto take = [&off](size_t bytes) {
-    const size_t at = off;
-    off += r3d_align_up(bytes, 256);
-    return at;
-  };
-  const size_t o_tgt4 = take((size_t)n_pad * sizeof(float4)), o_tgt = take((size_t)n_tgt * 12),
-               o_tile = take((size_t)n_tiles * 6 * sizeof(float)), o_sub = take((size_t)n_tiles * (kTile / kSub) * 6 * sizeof(float)),
-               o_group = take((size_t)n_tiles * (kTile / kGroup) * 6 * sizeof(float)),
-               o_super = take((size_t)((n_tiles + kSuper - 1) / kSuper) * 6 * sizeof(float)),
-               o_code = take((size_t)n_tiles * sizeof(uint64_t)), o_frame = take(16 * sizeof(float)),
-               o_knn = take(sizeof(unsigned long long));
-  hipError_t e = hipMalloc(&ix->d_slab, off);
+  r3d_carve slab;
+  const auto tgt4 = slab.take<float4>(n_pad);
+  const auto tgt = slab.take<float>((size_t)n_tgt * 3);
+  const auto tile = slab.take<float>((size_t)n_tiles * 6), sub = slab.take<float>((size_t)n_tiles * (kTile / kSub) * 6);
+  const auto group = slab.take<float>((size_t)n_tiles * (kTile / kGroup) * 6);
+  const auto super = slab.take<float>((size_t)((n_tiles + kSuper - 1) / kSuper) * 6);
+  const auto code = slab.take<uint64_t>(n_tiles);
+  const auto frame = slab.take<float>(16);
+  const auto knn = slab.take<unsigned long long>(1);
+  const hipError_t e = r3d_carve_malloc(slab, &ix->d_slab);
   if (e != hipSuccess) {
     r3d_nn_index_destroy(ix);
     return r3d_fail_hip(e, "nn index allocation", __FILE__, __LINE__);
   }
-  char* slab = static_cast<char*>(ix->d_slab);
-  ix->d_tgt4 = reinterpret_cast<float4*>(slab + o_tgt4);
-  ix->d_tgt = reinterpret_cast<float*>(slab + o_tgt);
-  ix->d_tile_box = reinterpret_cast<float*>(slab + o_tile);
-  ix->d_sub_box = reinterpret_cast<float*>(slab + o_sub);
-  ix->d_group_box = reinterpret_cast<float*>(slab + o_group);
-  ix->d_super_box = reinterpret_cast<float*>(slab + o_super);
-  ix->d_tile_code = reinterpret_cast<uint64_t*>(slab + o_code);
-  ix->d_frame = reinterpret_cast<float*>(slab + o_frame);
-  ix->d_knn_groups = reinterpret_cast<unsigned long long*>(slab + o_knn);
+  ix->d_tgt4 = slab.at(tgt4), ix->d_tgt = slab.at(tgt);
+  ix->d_tile_box = slab.at(tile), ix->d_sub_box = slab.at(sub), ix->d_group_box = slab.at(group), ix->d_super_box = slab.at(super);
+  ix->d_tile_code = slab.at(code), ix->d_frame = slab.at(frame), ix->d_knn_groups = slab.at(knn);
   if ((rc = nn_index_build(ix, d_tgt, n_tgt))) {
     r3d_nn_index_destroy(ix);
     return rc;

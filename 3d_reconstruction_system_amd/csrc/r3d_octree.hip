@@ -268,17 +268,16 @@ void timing_finish(r3d_ctx* ctx, Workspace& w, bool filled) {
 // count + scan; waits for the sizes; refuses bad codes.  Nothing a caller can see has been written when this returns.
 int octree_sizes(r3d_ctx* ctx, const uint64_t* d_codes, int64_t n, Workspace& w, int64_t* n_records, int64_t* n_leaves) {
   int rc;
-  void *a = nullptr, *b = nullptr;
   w.tiles = (n + kOctreeTile - 1) / kOctreeTile;
-  const size_t meta_bytes = r3d_align_up((size_t)n, 16);
-  if ((rc = r3d_scratch(ctx, kWsSpare, meta_bytes + (size_t)n * 2, &a))) return rc;
-  if ((rc = r3d_scratch(ctx, kWsCounts, 64 + (size_t)w.tiles * 16, &b))) return rc;
-  w.meta = static_cast<uint8_t*>(a);
-  w.pre = reinterpret_cast<uint16_t*>(w.meta + meta_bytes);
-  w.flags = static_cast<unsigned long long*>(b);
-  w.tile_base = reinterpret_cast<uint64_t*>(static_cast<char*>(b) + 64);
-  w.tile_cnt = reinterpret_cast<uint32_t*>(w.tile_base + w.tiles);
-  w.tile_leaf = w.tile_cnt + w.tiles;
+  r3d_carve a, b;
+  const auto meta = a.take<uint8_t>(n, 16);
+  const auto pre = a.take<uint16_t>(n, 16);
+  const auto flags = b.take<unsigned long long>(kFlags, 64);
+  const auto tile_base = b.take<uint64_t>(w.tiles, 64);
+  const auto tile_cnt = b.take<uint32_t>(w.tiles, 16), tile_leaf = b.take<uint32_t>(w.tiles, 16);
+  if ((rc = r3d_scratch(ctx, kWsSpare, a)) || (rc = r3d_scratch(ctx, kWsCounts, b))) return rc;
+  w.meta = a.at(meta), w.pre = a.at(pre);
+  w.flags = b.at(flags), w.tile_base = b.at(tile_base), w.tile_cnt = b.at(tile_cnt), w.tile_leaf = b.at(tile_leaf);
   hipStream_t st = ctx->stream;
   static const unsigned long long init[kFlags] = {~0ull, 0, 0, 0};
   R3D_HIP(hipMemcpyAsync(w.flags, init, sizeof(init), hipMemcpyHostToDevice, st));

@@ -346,34 +346,32 @@ __global__ __launch_bounds__(kThreads) void plane_accumulate_kernel(const float*
   r3d_sums::block_reduce_store<kSums>(acc, red, partials + (int64_t)blockIdx.x * kSums);
 }
 
-// workspace in kWsSelect: [hist n_buckets x 256 u32][state n_buckets x 4 u64][SelectOut x n_buckets][pad], then the
-// partial rows
+// the pieces of kWsSelect, as workspace() carves them: the histogram (n_buckets x 256), the state (n_buckets x 4), a SelectOut
+// per class, then the partial rows
 struct Workspace {
   unsigned* hist;
   unsigned long long* state;
   SelectOut* out;
   double* rows;
-  size_t clear_bytes;   // hist + state
+  size_t clear_bytes;   // hist + state, up to where `out` begins
 };
 
 int workspace(r3d_ctx* ctx, int n_buckets, int n_rows, Workspace* ws) {
-  void* p = nullptr;
-  const size_t hist_b = (size_t)n_buckets * kBins * sizeof(unsigned), state_b = (size_t)n_buckets * 4 * sizeof(unsigned long long);
-  const size_t head = hist_b + state_b + (size_t)n_buckets * sizeof(SelectOut) + 64;
-  const size_t head_al = r3d_align_up(head, 256);
-  int rc = r3d_scratch(ctx, kWsSelect, head_al + (size_t)(n_rows + 1) * kSums * sizeof(double), &p);
+  r3d_carve c;
+  // hist is the block's first piece (select_ws records its address) and a whole number of KiB, so the state lies right behind
+  // it: one memset of clear_bytes clears both
+  const auto hist = c.take<unsigned>((size_t)n_buckets * kBins);
+  const auto state = c.take<unsigned long long>((size_t)n_buckets * 4);
+  const auto out = c.take<SelectOut>(n_buckets);
+  const auto rows = c.take<double>((size_t)(n_rows + 1) * kSums);
+  int rc = r3d_scratch(ctx, kWsSelect, c);
   if (rc) return rc;
   // The "histogram is known to be zero" record (select_enqueue) describes ONE layout.  A workspace laid out for another class
   // count puts its state words, picks or partial rows where that layout has its histogram -- e.g. the untrimmed sums pass
-  // (1 class) writes fp64 rows at byte 1280, inside the 24-class histogram -- so the record dies here, whether or not a
+  // (1 class) writes fp64 rows at byte 1536, inside the 24-class histogram -- so the record dies here, whether or not a
   // selection follows (round-3 advisor finding: trim -> no trim -> trim on one ctx ranked against leftover rows).
   if (ctx->select_ws_buckets != n_buckets) ctx->select_ws = nullptr;
-  char* c = static_cast<char*>(p);
-  ws->hist = reinterpret_cast<unsigned*>(c);
-  ws->state = reinterpret_cast<unsigned long long*>(c + hist_b);
-  ws->out = reinterpret_cast<SelectOut*>(c + hist_b + state_b);
-  ws->rows = reinterpret_cast<double*>(c + head_al);
-  ws->clear_bytes = hist_b + state_b;
+  *ws = {c.at(hist), c.at(state), c.at(out), c.at(rows), out.at - hist.at};
   return R3D_OK;
 }
 
@@ -557,11 +555,14 @@ static int plane_sums_impl(r3d_ctx* ctx, const float* d_src, int64_t n_src, cons
   const float gate_d2 = max_d2 >= 0.f ? max_d2 : -1.f;
   const SelectOut* gates = nullptr;
   if (trim) {
-    void* r2 = nullptr;   // [n_src] f32 followed by [n_src] u8
-    if ((rc = r3d_scratch(ctx, kWsTrack, (size_t)n_src * 5 + 16, &r2))) return rc;
-    unsigned char* cls = reinterpret_cast<unsigned char*>(static_cast<float*>(r2) + n_src);
-    if ((rc = r3d_icp_plane_residuals(ctx, d_src, n_src, d_tgt, d_nrm, n_tgt, d_idx, d_d2, gate_d2, (float*)r2, cls))) return rc;
-    if ((rc = select_enqueue(ctx, (const float*)r2, cls, kNormalClasses, n_src, (double)trim_q, ws))) return rc;
+    r3d_carve c;
+    const auto r2_h = c.take<float>(n_src, 16);
+    const auto cls_h = c.take<unsigned char>(n_src, 16);
+    if ((rc = r3d_scratch(ctx, kWsTrack, c))) return rc;
+    float* r2 = c.at(r2_h);
+    unsigned char* cls = c.at(cls_h);
+    if ((rc = r3d_icp_plane_residuals(ctx, d_src, n_src, d_tgt, d_nrm, n_tgt, d_idx, d_d2, gate_d2, r2, cls))) return rc;
+    if ((rc = select_enqueue(ctx, r2, cls, kNormalClasses, n_src, (double)trim_q, ws))) return rc;
     gates = ws.out;
   }
   hipLaunchKernelGGL(plane_accumulate_kernel, dim3(blocks), dim3(kThreads), 0, ctx->stream, d_src, n_src, d_tgt, d_nrm, n_tgt,

@@ -166,14 +166,14 @@ __global__ __launch_bounds__(kThreads) void digit_scatter_kernel(const uint64_t*
 // has passes of its own).
 // Limit: the bin totals and the tiles' prefixes are uint32, so one sort takes fewer than 2^32 keys; nothing in the library
 // reaches that size, and the check below (tiles < 2^31) does not enforce it.
-int r3d_radix_sort_workspace(r3d_ctx* ctx, int64_t n, uint32_t** hist_out, int* n_blocks_out) {
+int r3d_radix_sort_workspace(r3d_ctx* ctx, int64_t n, uint32_t** hist_out, uint32_t** totals_out, int* n_blocks_out) {
   const int64_t n_blocks64 = (n + kTile - 1) / kTile;
   R3D_REQUIRE(n_blocks64 < ((int64_t)1 << 31), "too many keys for one sort");
-  void* ws = nullptr;
-  const size_t hist_bytes = (size_t)kBins * r3d_sort_stride((int)n_blocks64) * sizeof(uint32_t);
-  int rc = r3d_scratch(ctx, kWsCounts, hist_bytes + kBins * sizeof(uint32_t) + 64, &ws);
+  r3d_carve ws;
+  const auto hist = ws.take<uint32_t>((size_t)kBins * r3d_sort_stride((int)n_blocks64), 32), totals = ws.take<uint32_t>(kBins, 16);
+  int rc = r3d_scratch(ctx, kWsCounts, ws);
   if (rc) return rc;
-  *hist_out = static_cast<uint32_t*>(ws);
+  *hist_out = ws.at(hist), *totals_out = ws.at(totals);
   *n_blocks_out = (int)n_blocks64;
   return R3D_OK;
 }
@@ -191,13 +191,11 @@ int r3d_radix_sort_u64(r3d_ctx* ctx, uint64_t* d_keys, uint64_t* d_tmp, int64_t 
   if (n <= 1) return R3D_OK;
   if (first_bit < 0 || first_bit >= bits) first_bit = 0;
   const int passes = (bits - first_bit + 7) / 8;
-  uint32_t* hist = nullptr;
+  uint32_t *hist = nullptr, *totals = nullptr;
   int n_blocks = 0;
-  int rc = r3d_radix_sort_workspace(ctx, n, &hist, &n_blocks);
+  int rc = r3d_radix_sort_workspace(ctx, n, &hist, &totals, &n_blocks);
   if (rc) return rc;
   const int stride = r3d_sort_stride(n_blocks);
-  const size_t hist_bytes = (size_t)kBins * stride * sizeof(uint32_t);
-  uint32_t* totals = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(hist) + r3d_align_up(hist_bytes, 16));
   uint64_t* src = d_keys;
   uint64_t* dst = d_tmp;
   for (int p = 0; p < passes; ++p) {

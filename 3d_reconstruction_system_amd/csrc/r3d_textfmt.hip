@@ -522,13 +522,16 @@ int r3d_format_text_device(r3d_ctx* ctx, int kind, const void* d_xyz, int dtype,
   R3D_REQUIRE(tps <= 0x7fffffff && n_seg * tps <= 0x7fffffff, "too many tiles for one launch (%lld points)", (long long)n_points);
   const int64_t n_tiles = n_seg * tps;
   if ((rc = upload_table(ctx))) return rc;
-  // workspace: flags (16 B) | tile_off [n_tiles + 1] u64 | tile_len [n_tiles] u32
-  void* ws = nullptr;
+  // the flags fill their 16 bytes, so the tiles' offsets, taken at the same alignment, lie right behind them: one copy reads both
+  r3d_carve ws;
   const size_t off_bytes = (size_t)(n_tiles + 1) * 8;
-  if ((rc = r3d_scratch(ctx, kWsMisc, 16 + off_bytes + (size_t)n_tiles * 4, &ws))) return rc;
-  unsigned int* d_flags = static_cast<unsigned int*>(ws);
-  uint64_t* d_off = reinterpret_cast<uint64_t*>(static_cast<char*>(ws) + 16);
-  uint32_t* d_len = reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + 16 + off_bytes);
+  const auto flags_h = ws.take<unsigned int>(4, 16);
+  const auto off_h = ws.take<uint64_t>((size_t)n_tiles + 1, 16);
+  const auto len_h = ws.take<uint32_t>(n_tiles, 16);
+  if ((rc = r3d_scratch(ctx, kWsMisc, ws))) return rc;
+  unsigned int* d_flags = ws.at(flags_h);
+  uint64_t* d_off = ws.at(off_h);
+  uint32_t* d_len = ws.at(len_h);
   R3D_HIP(hipMemsetAsync(d_flags, 0, 16, ctx->stream));
   TextJob job{d_xyz, d_aux, n_points, seg, (int)tps, kind, dtype == R3D_F64, aux_stride};
   if (dtype == R3D_F64)
@@ -539,7 +542,7 @@ int r3d_format_text_device(r3d_ctx* ctx, int kind, const void* d_xyz, int dtype,
   R3D_HIP(hipGetLastError());
   // the offsets come to the host: the size, the segment starts (and the flag word in front of them)
   std::vector<uint64_t> h((size_t)n_tiles + 3);
-  R3D_HIP(hipMemcpyAsync(h.data(), ws, 16 + off_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  R3D_HIP(hipMemcpyAsync(h.data(), d_flags, 16 + off_bytes, hipMemcpyDeviceToHost, ctx->stream));
   R3D_HIP(hipStreamSynchronize(ctx->stream));
   const unsigned int flags = (unsigned int)(h[0] & 0xffffffffu);
   const uint64_t* off = h.data() + 2;

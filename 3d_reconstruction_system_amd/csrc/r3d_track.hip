@@ -401,19 +401,21 @@ int track_rgb(r3d_tsdf* vol, const r3d_camera* cam, const void* d_depth, int dep
   // the ray cast's own argument checks and the colour plane's presence: with no output it validates and does nothing else
   if ((rc = r3d_tsdf_raycast_rgb(vol, cam, 1, G, min_weight, step, t_near, t_far, nullptr, nullptr, nullptr, nullptr))) return rc;
   if ((rc = r3d_ctx_enter(ctx))) return rc;
-  // kWsTrack, as track_levels: four maps, the model's depth, rgb and packed map, the source intensity, the state
-  const size_t n = (size_t)p.n_px, map = r3d_align_up(n * 12, 256), plane = r3d_align_up(n * 4, 256), img = r3d_align_up(n * 3, 256);
-  const size_t packed = r3d_align_up(n * 16, 256);
-  const size_t bytes = 4 * map + 2 * plane + img + packed;
-  void* ws = nullptr;
-  if ((rc = r3d_scratch(ctx, kWsTrack, bytes + R3D_ICP_STATE_DOUBLES * sizeof(double), &ws))) return rc;
-  char* c = static_cast<char*>(ws);
-  float *model_vertex = reinterpret_cast<float*>(c), *model_normal = reinterpret_cast<float*>(c + map);
-  float *src_vertex = reinterpret_cast<float*>(c + 2 * map), *src_normal = reinterpret_cast<float*>(c + 3 * map);
-  float* model_packed = reinterpret_cast<float*>(c + 4 * map);
-  float *model_depth = reinterpret_cast<float*>(c + 4 * map + packed), *src_intensity = reinterpret_cast<float*>(c + 4 * map + packed + plane);
-  uint8_t* model_rgb = reinterpret_cast<uint8_t*>(c + 4 * map + packed + 2 * plane);
-  double* d_state = reinterpret_cast<double*>(c + bytes);
+  // kWsTrack: four vertex / normal maps, the model's packed intensity map (float4 loads), its depth, the source intensity,
+  // the model's colour image and the ICP state
+  const size_t n = (size_t)p.n_px;
+  r3d_carve ws;
+  const auto model_vertex_h = ws.take<float>(n * 3), model_normal_h = ws.take<float>(n * 3);
+  const auto src_vertex_h = ws.take<float>(n * 3), src_normal_h = ws.take<float>(n * 3);
+  const auto model_packed_h = ws.take<float>(n * 4), model_depth_h = ws.take<float>(n), src_intensity_h = ws.take<float>(n);
+  const auto model_rgb_h = ws.take<uint8_t>(n * 3);
+  const auto state_h = ws.take<double>(R3D_ICP_STATE_DOUBLES);
+  if ((rc = r3d_scratch(ctx, kWsTrack, ws))) return rc;
+  float *model_vertex = ws.at(model_vertex_h), *model_normal = ws.at(model_normal_h);
+  float *src_vertex = ws.at(src_vertex_h), *src_normal = ws.at(src_normal_h);
+  float *model_packed = ws.at(model_packed_h), *model_depth = ws.at(model_depth_h), *src_intensity = ws.at(src_intensity_h);
+  uint8_t* model_rgb = ws.at(model_rgb_h);
+  double* d_state = ws.at(state_h);
   if ((rc = r3d_tsdf_raycast_rgb(vol, cam, 1, G, min_weight, step, t_near, t_far, model_depth, model_vertex, model_normal, model_rgb)))
     return rc;
   if ((rc = r3d_intensity_map(ctx, model_rgb, model_depth, 1, cam->height, cam->width, max_jump, nullptr, model_packed))) return rc;
@@ -479,27 +481,20 @@ int track_levels(r3d_tsdf* vol, const r3d_camera* const* cams, int n_levels, con
   if ((rc = r3d_ctx_enter(ctx))) return rc;
   // every level's four maps, the depth rasters of the levels above 0 and the state: kWsTrack (the rank-trimming residuals'
   // workspace too; nothing of that path runs in here).  A level has a quarter of the pixels of the one below: 4/3 of level 0's maps.
-  size_t map_at[R3D_TRACK_MAX_LEVELS], map[R3D_TRACK_MAX_LEVELS], depth_at[R3D_TRACK_MAX_LEVELS], bytes = 0;
-  for (int l = 0; l < n_levels; ++l) {
-    map[l] = r3d_align_up((size_t)p[l].n_px * 12, 256);
-    map_at[l] = bytes;
-    bytes += 4 * map[l];
-  }
-  for (int l = 1; l < n_levels; ++l) {
-    depth_at[l] = bytes;
-    bytes += r3d_align_up((size_t)p[l].n_px * 4, 256);
-  }
-  void* ws = nullptr;
-  if ((rc = r3d_scratch(ctx, kWsTrack, bytes + R3D_ICP_STATE_DOUBLES * sizeof(double), &ws))) return rc;
-  char* c = static_cast<char*>(ws);
-  double* d_state = reinterpret_cast<double*>(c + bytes);
+  r3d_carve ws;
+  r3d_carve::piece<float> maps[R3D_TRACK_MAX_LEVELS][4], depth[R3D_TRACK_MAX_LEVELS];   // model vertex, model normal, source vertex, source normal
+  for (int l = 0; l < n_levels; ++l)
+    for (auto& map : maps[l]) map = ws.take<float>((size_t)p[l].n_px * 3);
+  for (int l = 1; l < n_levels; ++l) depth[l] = ws.take<float>((size_t)p[l].n_px);
+  const auto state_h = ws.take<double>(R3D_ICP_STATE_DOUBLES);
+  if ((rc = r3d_scratch(ctx, kWsTrack, ws))) return rc;
+  double* d_state = ws.at(state_h);
   double* rows = nullptr;
   if ((rc = rows_workspace(ctx, n_tiles(p[0]), &rows))) return rc;   // the largest level's rows: kWsPartials never grows mid-loop
   Maps m[R3D_TRACK_MAX_LEVELS];
   for (int l = 0; l < n_levels; ++l) {
-    char* base = c + map_at[l];
-    float *model_vertex = reinterpret_cast<float*>(base), *model_normal = reinterpret_cast<float*>(base + map[l]);
-    float *src_vertex = reinterpret_cast<float*>(base + 2 * map[l]), *src_normal = reinterpret_cast<float*>(base + 3 * map[l]);
+    float *model_vertex = ws.at(maps[l][0]), *model_normal = ws.at(maps[l][1]);
+    float *src_vertex = ws.at(maps[l][2]), *src_normal = ws.at(maps[l][3]);
     const bool used = iters[l] > 0;
     if (used && (rc = r3d_tsdf_raycast(vol, cams[l], 1, G, min_weight, step, t_near, t_far, nullptr, model_vertex, model_normal)))
       return rc;
@@ -507,10 +502,10 @@ int track_levels(r3d_tsdf* vol, const r3d_camera* const* cams, int n_levels, con
       if ((rc = r3d_unproject(ctx, cams[0], d_depth, depth_dtype, 1, depth_scale, src_vertex, R3D_F32))) return rc;
     } else {
       // the depth of the level below: level 0's is the z column of its vertex map, whatever dtype the frame came in
-      float* depth = reinterpret_cast<float*>(c + depth_at[l]);
-      const float* below = l == 1 ? m[0].src_vertex + 2 : reinterpret_cast<const float*>(c + depth_at[l - 1]);
-      if ((rc = r3d_depth_half(ctx, below, l == 1 ? 3 : 1, cams[l - 1]->height, cams[l - 1]->width, max_jump, depth))) return rc;
-      if (used && (rc = r3d_unproject(ctx, cams[l], depth, R3D_DEPTH_F32, 1, 1.0, src_vertex, R3D_F32))) return rc;
+      float* d = ws.at(depth[l]);
+      const float* below = l == 1 ? m[0].src_vertex + 2 : ws.at(depth[l - 1]);
+      if ((rc = r3d_depth_half(ctx, below, l == 1 ? 3 : 1, cams[l - 1]->height, cams[l - 1]->width, max_jump, d))) return rc;
+      if (used && (rc = r3d_unproject(ctx, cams[l], d, R3D_DEPTH_F32, 1, 1.0, src_vertex, R3D_F32))) return rc;
     }
     if (used && gate && (rc = r3d_normals_organized(ctx, src_vertex, 1, cams[l]->height, cams[l]->width, max_jump, nullptr, src_normal)))
       return rc;

@@ -281,11 +281,13 @@ int integrate_host(r3d_tsdf* v, const r3d_camera* cam, const void* h_depth, int 
   int slab = (int)(((size_t)256 << 20) / (frame_bytes ? frame_bytes : 1));
   if (slab < 1) slab = 1;
   if (slab > n_frames) slab = n_frames;
-  const size_t rgb_at = h_rgb ? r3d_align_up((size_t)slab * depth_bytes, 256) : (size_t)slab * depth_bytes;
-  void* d_in = nullptr;
-  int rc = r3d_scratch(ctx, kWsIn, rgb_at + (size_t)slab * rgb_bytes, &d_in);
+  r3d_carve in;
+  const auto depth_h = in.take<char>((size_t)slab * depth_bytes);
+  const auto rgb_h = in.take<uint8_t>((size_t)slab * rgb_bytes);
+  int rc = r3d_scratch(ctx, kWsIn, in);
   if (rc) return rc;
-  uint8_t* d_rgb = h_rgb ? static_cast<uint8_t*>(d_in) + rgb_at : nullptr;
+  void* d_in = in.at(depth_h);
+  uint8_t* d_rgb = h_rgb ? in.at(rgb_h) : nullptr;
   for (int lo = 0; lo < n_frames; lo += slab) {
     const int n = n_frames - lo < slab ? n_frames - lo : slab;
     if ((rc = r3d_memcpy_h2d(ctx, d_in, static_cast<const char*>(h_depth) + (size_t)lo * depth_bytes, (size_t)n * depth_bytes))) return rc;

@@ -20,7 +20,6 @@ namespace {
 
 constexpr int kChunkBlocks = 16384;           // blocks per chunk unless "tsdf_cloud_chunk" says otherwise: 2^20 queries, 20 MiB
 enum { kBufList = 0, kBufChunk, kBufHost };   // r3d_tsdf::cloud_buf
-constexpr size_t kListHeader = 256;           // in front of the block list: the touched-voxel counter
 static_assert(kBufHost + 1 == r3d_tsdf::kCloudBufs, "one r3d_tsdf::cloud_buf entry per buffer");
 
 // *p = at least `bytes` bytes of the volume's own buffer `which` (grow-only; the contents are not kept across growing)
@@ -40,6 +39,12 @@ int cloud_buffer(r3d_tsdf* v, int which, size_t bytes, void** p) {
   }
   *p = v->cloud_buf[which];
   return R3D_OK;
+}
+int cloud_buffer(r3d_tsdf* v, int which, r3d_carve& c) {   // ... holding c.bytes, c placed there
+  void* p = nullptr;
+  const int rc = cloud_buffer(v, which, c.bytes, &p);
+  c.place(p);
+  return rc;
 }
 
 // what both entry points check about the colours of a volume that is there: rgba goes with the colour plane and only with it (a
@@ -84,10 +89,12 @@ int r3d_tsdf_integrate_cloud(r3d_tsdf* v, r3d_nn_index* ix, const float* d_norma
   if (n_marked == 0) return R3D_OK;
 
   // the list of marked blocks, behind the counter of touched voxels
-  void* lb = nullptr;
-  if ((rc = cloud_buffer(v, kBufList, kListHeader + (size_t)n_marked * 4, &lb))) return rc;
-  unsigned long long* touched = static_cast<unsigned long long*>(lb);
-  uint32_t* list = reinterpret_cast<uint32_t*>(static_cast<char*>(lb) + kListHeader);
+  r3d_carve lb;
+  const auto touched_h = lb.take<unsigned long long>(1);
+  const auto list_h = lb.take<uint32_t>(n_marked);
+  if ((rc = cloud_buffer(v, kBufList, lb))) return rc;
+  unsigned long long* touched = lb.at(touched_h);
+  uint32_t* list = lb.at(list_h);
   R3D_HIP(hipMemsetAsync(touched, 0, sizeof(*touched), st));
   r3d_tsdf_cloud_list_launch(ctx, bitmap, n_words, tiles, cn.hist, list);
   R3D_HIP(hipGetLastError());
@@ -97,12 +104,13 @@ int r3d_tsdf_integrate_cloud(r3d_tsdf* v, r3d_nn_index* ix, const float* d_norma
   if (chunk > (1u << 24)) chunk = 1u << 24;   // the lanes of a chunk fit 32 bits
   if (chunk > n_marked) chunk = n_marked;
   const size_t lanes_max = (size_t)chunk * 64;
-  const size_t o_idx = r3d_align_up(lanes_max * 12, 256), o_d2 = o_idx + r3d_align_up(lanes_max * 4, 256);
-  void* cb = nullptr;
-  if ((rc = cloud_buffer(v, kBufChunk, o_d2 + lanes_max * 4, &cb))) return rc;
-  float* q = static_cast<float*>(cb);
-  uint32_t* idx = reinterpret_cast<uint32_t*>(static_cast<char*>(cb) + o_idx);
-  float* d2 = reinterpret_cast<float*>(static_cast<char*>(cb) + o_d2);
+  r3d_carve cb;
+  const auto q_h = cb.take<float>(lanes_max * 3);
+  const auto idx_h = cb.take<uint32_t>(lanes_max);
+  const auto d2_h = cb.take<float>(lanes_max);
+  if ((rc = cloud_buffer(v, kBufChunk, cb))) return rc;
+  float *q = cb.at(q_h), *d2 = cb.at(d2_h);
+  uint32_t* idx = cb.at(idx_h);
   for (uint32_t lo = 0; lo < n_marked; lo += chunk) {
     const uint32_t nb = n_marked - lo < chunk ? n_marked - lo : chunk;
     r3d_tsdf_cloud_centres_launch(ctx, list + lo, nb, g, q);
@@ -132,12 +140,12 @@ int r3d_tsdf_integrate_cloud_host(r3d_tsdf* v, const float* h_xyz, const float* 
   if (n == 0) return R3D_OK;
   r3d_ctx* ctx = v->ctx;
   if ((rc = r3d_ctx_enter(ctx))) return rc;
-  const size_t rows = r3d_align_up((size_t)n * 12, 256);
-  void* in = nullptr;
-  if ((rc = cloud_buffer(v, kBufHost, 2 * rows + (h_rgba ? (size_t)n * 4 : 0), &in))) return rc;
-  float* d_xyz = static_cast<float*>(in);
-  float* d_normals = reinterpret_cast<float*>(static_cast<char*>(in) + rows);
-  uint32_t* d_rgba = h_rgba ? reinterpret_cast<uint32_t*>(static_cast<char*>(in) + 2 * rows) : nullptr;
+  r3d_carve in;
+  const auto xyz_h = in.take<float>((size_t)n * 3), normals_h = in.take<float>((size_t)n * 3);
+  const auto rgba_h = in.take<uint32_t>(h_rgba ? (size_t)n : 0);
+  if ((rc = cloud_buffer(v, kBufHost, in))) return rc;
+  float *d_xyz = in.at(xyz_h), *d_normals = in.at(normals_h);
+  uint32_t* d_rgba = h_rgba ? in.at(rgba_h) : nullptr;
   if ((rc = r3d_memcpy_h2d(ctx, d_xyz, h_xyz, (size_t)n * 12)) || (rc = r3d_memcpy_h2d(ctx, d_normals, h_normals, (size_t)n * 12))) return rc;
   if (h_rgba && (rc = r3d_memcpy_h2d(ctx, d_rgba, h_rgba, (size_t)n * 4))) return rc;
   r3d_nn_index* ix = nullptr;

@@ -990,29 +990,28 @@ int r3d_voxelset_insert_sorted(r3d_voxelset* vs, const float* d_xyz, int64_t n_p
     const int64_t n_tiles1 = (m + kSortTile - 1) / kSortTile;   // the first pass's tiles
     const int n_tiles = plan.n_tiles2, stride = r3d_sort_stride(n_tiles);   // the second pass's tiles
     const size_t seg_elems = (size_t)kSegments * plan.cap;
-    void *a_v = nullptr, *b_v = nullptr, *ws = nullptr;
-    if ((rc = r3d_scratch(ctx, kWsOut, r3d_align_up((size_t)m * 4, 256), &a_v))) return rc;   // the remainders in piece order
-    if ((rc = r3d_scratch(ctx, kWsSpare, r3d_align_up(seg_elems * 4, 256) + r3d_align_up(seg_elems, 256), &b_v))) return rc;   // the first pass's segments: rem | hi
-    uint32_t* rem_a = static_cast<uint32_t*>(a_v);
-    uint32_t* rem_b = static_cast<uint32_t*>(b_v);
-    uint8_t* hi_b = reinterpret_cast<uint8_t*>(static_cast<char*>(b_v) + r3d_align_up(seg_elems * 4, 256));
     const unsigned merge_grid = (unsigned)ctx->num_cus * 8;   // (1536 .. 4096 workgroups measured within 3 % of each other)
-    const size_t partial_bytes = r3d_align_up((size_t)merge_grid * 2 * 2 * sizeof(unsigned long long), 256);   // (the wave form's grid is twice merge_grid)
-    const size_t starts_bytes = r3d_align_up(((size_t)kPieces + 2) * sizeof(uint32_t), 256);
-    const size_t hist_bytes = r3d_align_up((size_t)256 * stride * sizeof(uint32_t), 256);
-    const size_t count_bytes = r3d_align_up((size_t)kSegments * kCursorStride * sizeof(uint32_t), 256);   // the segments' cursors, a line each
-    if ((rc = r3d_scratch(ctx, kWsMisc, partial_bytes + starts_bytes + hist_bytes + 1024 + 256 + count_bytes + spill_cap * 8, &ws))) return rc;
-    char* w = static_cast<char*>(ws);
-    unsigned long long* d_partials = reinterpret_cast<unsigned long long*>(w);
-    uint32_t* d_starts = reinterpret_cast<uint32_t*>(w + partial_bytes);
-    uint32_t* hist_hi = reinterpret_cast<uint32_t*>(w + partial_bytes + starts_bytes);
-    uint32_t* totals_hi = reinterpret_cast<uint32_t*>(w + partial_bytes + starts_bytes + hist_bytes);
-    char* zeroed = w + partial_bytes + starts_bytes + hist_bytes + 1024;   // one memset: the deferred keys' count, the flags, the cursors
-    unsigned long long* d_spill_count = reinterpret_cast<unsigned long long*>(zeroed);
-    uint32_t* d_flags = reinterpret_cast<uint32_t*>(zeroed + 64);   // [2..3] points without a key
-    uint32_t* d_cursors = reinterpret_cast<uint32_t*>(zeroed + 256);
-    uint64_t* d_spill = reinterpret_cast<uint64_t*>(zeroed + 256 + count_bytes);
-    R3D_HIP(hipMemsetAsync(zeroed, 0, 256 + count_bytes, ctx->stream));
+    r3d_carve a, b, ws;
+    const auto rem_a_h = a.take<uint32_t>(m);   // the remainders in piece order
+    const auto rem_b_h = b.take<uint32_t>(seg_elems);   // the first pass's segments: rem | hi
+    const auto hi_b_h = b.take<uint8_t>(seg_elems);
+    const auto partials_h = ws.take<unsigned long long>((size_t)merge_grid * 2 * 2);   // (the wave form's grid is twice merge_grid)
+    const auto starts_h = ws.take<uint32_t>((size_t)kPieces + 2);
+    const auto hist_h = ws.take<uint32_t>((size_t)256 * stride), totals_h = ws.take<uint32_t>(256);
+    // taken one after the other: one memset from the deferred keys' count up to where the spill list begins clears the count,
+    // the flags and the cursors (a line per segment), with whatever padding lies between them
+    const auto spill_count_h = ws.take<unsigned long long>(1, 64);
+    const auto flags_h = ws.take<uint32_t>(4, 64);   // flags [2..3]: points without a key
+    const auto cursors_h = ws.take<uint32_t>((size_t)kSegments * kCursorStride);
+    const auto spill_h = ws.take<uint64_t>(spill_cap);
+    if ((rc = r3d_scratch(ctx, kWsOut, a)) || (rc = r3d_scratch(ctx, kWsSpare, b)) || (rc = r3d_scratch(ctx, kWsMisc, ws))) return rc;
+    uint32_t *rem_a = a.at(rem_a_h), *rem_b = b.at(rem_b_h);
+    uint8_t* hi_b = b.at(hi_b_h);
+    unsigned long long *d_partials = ws.at(partials_h), *d_spill_count = ws.at(spill_count_h);
+    uint32_t *d_starts = ws.at(starts_h), *hist_hi = ws.at(hist_h), *totals_hi = ws.at(totals_h);
+    uint32_t *d_flags = ws.at(flags_h), *d_cursors = ws.at(cursors_h);
+    uint64_t* d_spill = ws.at(spill_h);
+    R3D_HIP(hipMemsetAsync(d_spill_count, 0, spill_h.at - spill_count_h.at, ctx->stream));
     // |x| < safe_abs  =>  |factor x| < 32767: every key in range whatever the rounding of the fp64 product (a bound strictly
     // inside the map's edge 32768 / factor, rounded towards zero and shrunk by 2^-20 on top)
     const float safe_abs = nextafterf((float)((32767.0 / vs->factor) * (1.0 - 1.0 / 1048576.0)), 0.0f);

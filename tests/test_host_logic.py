@@ -1085,3 +1085,24 @@ def test_compaction_counters_layout(tmp_path):
         assert at[rows] == 4 * stride * rows                                # the totals lie right behind the last row
         assert nbytes >= at[rows] + 4 * rows and nbytes == 4 * stride * rows + 64
     assert seen == {(t, r) for t in (0, 1, 7, 8, 9) for r in (1, 2)}
+
+
+def test_carve_layout(tmp_path):
+    """csrc/r3d_carve.h, which lays the pieces of every divided device block end to end, through tests/c/carve_check.cpp (a
+    stand-alone program of plain C++, under AddressSanitizer and UndefinedBehaviorSanitizer): for lists over element counts 0, 1,
+    255, 256, 257, element sizes 1, 4, 8, 12, 16 and alignments 16, 64, 256 the program itself asserts ascending, aligned, pairwise
+    disjoint pieces and `bytes` = the rounded end of the last one, writes every byte of every piece into a block of exactly
+    `bytes` bytes, and does the arithmetic of one list past 2^32 bytes."""
+    import subprocess
+    csrc = os.path.join(ROOT, PKG, "csrc")
+    exe = str(tmp_path / "carve_check")
+    build = subprocess.run(["/opt/rocm/bin/hipcc", "-O1", "-g", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
+                            "-I" + csrc, "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined",
+                            "-x", "hip", os.path.join(ROOT, "tests", "c", "carve_check.cpp"), "-fsanitize=address,undefined",
+                            "-o", exe], capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr[-2000:]
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0 and "carve check OK" in run.stdout, run.stdout[-2000:] + run.stderr[-2000:]
+    assert "FAILED" not in run.stdout, run.stdout[-2000:]
+    assert "Sanitizer" not in run.stderr and "runtime error" not in run.stderr, run.stderr[-2000:]
+    assert "32 lists" in run.stdout   # 15 mixed + 15 uniform + the empty piece between two + the one past 2^32
